@@ -26,6 +26,8 @@ torch.distributed.run on 127.0.0.1, before this process has imported torch or to
 
 Prints ONE JSON line on rank 0 with the driver's fields plus `roofline` (dominant kernel vs HBM peak) and
 `cpu_baseline` (the C oracle = CPU restatement of the reference path, timed on this box's host cores).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (see dump_outputs): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -63,7 +65,13 @@ def parse_args():
                     help="no GPU: every rank joins a gloo group, runs the barrier / MAX / SUM protocol of the timed region on "
                          "dummy numbers and rank 0 prints the JSON line (tests the N-rank launch path on CPU)")
     ap.add_argument("--selftest-fail-rank", type=int, default=-1, help="with --launcher-selftest: this rank exits non-zero")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (at most 64 MB: "
+                         "a fixed, seeded sample of the rows when the output is larger)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(n_ranks, argv):
@@ -294,7 +302,7 @@ def extra_lines(chq, torch, dev, ctx, n):
             o.release()
         run_config5_steps(chq, ctx, grp, pred, 1)
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        rows_out, kernel_ns, alg = run_config5_steps(chq, ctx, grp, pred, 3)
+        rows_out, kernel_ns, alg, _ = run_config5_steps(chq, ctx, grp, pred, 3)
         torch.cuda.synchronize(); secs = (time.perf_counter() - t0) / 3
         kms = kernel_ns / 3 / 1e6
         out["config5_shard"] = {
@@ -351,15 +359,18 @@ def make_config2_columns(torch, dev, n, rank):
     return cols
 
 
-def time_config2(chq, torch, dist, world, ctx, cols, n, expr, aliases, steps, warmup):
-    """W untimed steps, then exactly K timed steps between barrier + synchronize on both sides -> (elapsed s, kernel ns, stats)"""
+def time_config2(chq, torch, dist, world, ctx, cols, n, expr, aliases, steps, warmup, keep_last=False):
+    """W untimed steps, then exactly K timed steps between barrier + synchronize on both sides -> (elapsed s, kernel ns, stats,
+    the last step's output batch when keep_last, else None; the caller releases it)"""
     rec = chq.DeviceRecordBatch.from_device_pointers([(f"value{c}", "f", cols[c].data_ptr()) for c in range(3)], n, ctx=ctx, keepalive=cols)
 
-    def step():
+    def step(keep=False):
         out = chq.filter_record(rec, aliases, expr, ctx=ctx)   # result stays in HBM
         st = ctx.last_stats()
-        out.release()
-        return st
+        if not keep:
+            out.release()
+            out = None
+        return st, out
 
     for _ in range(warmup):
         step()
@@ -368,9 +379,9 @@ def time_config2(chq, torch, dist, world, ctx, cols, n, expr, aliases, steps, wa
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    kernel_ns, stats = 0, None
-    for _ in range(steps):
-        stats = step()
+    kernel_ns, stats, last = 0, None, None
+    for i in range(steps):
+        stats, last = step(keep_last and i == steps - 1)
         kernel_ns += stats["kernel_ns"]
     torch.cuda.synchronize()
     if world > 1:
@@ -378,7 +389,63 @@ def time_config2(chq, torch, dist, world, ctx, cols, n, expr, aliases, steps, wa
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     rec.release()
-    return elapsed, kernel_ns, stats
+    return elapsed, kernel_ns, stats, last
+
+
+# ---- --dump-outputs: what the timed path returned, for comparing two builds output for output ---------------------------
+DUMP_BYTES = 64_000_000   # all ranks together
+DUMP_SEED = 0xD0
+DUMP_UTF8_BYTES = 16      # leading bytes kept of every sampled string
+
+
+def dump_outputs(torch, outs, out_dir, prefix="", budget=DUMP_BYTES):
+    """Write the output batches `outs` of one step as out_dir/<prefix><name>.npy: `num_rows` (rows of every batch),
+    `row_index` (the rows written, counted over the batches in order) and one array per column at those rows --
+    float32 / float64 columns as they are, integer columns as float64 (exact below 2^53), a Utf8 column as <name>_length
+    and <name>_bytes (its first DUMP_UTF8_BYTES bytes, zero-padded, as float32).  Rows that do not all fit `budget` bytes
+    are sampled: one row from each of k equal strata of the output, drawn by a generator seeded with DUMP_SEED, so the
+    same output always gives the same sample."""
+    import numpy as np
+    counts = np.array([o.num_rows for o in outs], dtype=np.int64)
+    names, fmts = outs[0].column_names, outs[0].column_formats
+    row_bytes = 8 + sum(8 + 4 * DUMP_UTF8_BYTES if f == "u" else 8 if f in "cCsilg" else 4 for f in fmts)
+    total = int(counts.sum())
+    k = min(total, (budget - 8 * len(outs) - 4096) // row_bytes)   # 4096: the .npy headers
+    lo = np.arange(k, dtype=np.int64) * total // k
+    hi = np.arange(1, k + 1, dtype=np.int64) * total // k
+    idx = lo + np.random.default_rng(DUMP_SEED).integers(0, hi - lo)
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    batch = np.searchsorted(starts, idx, side="right") - 1
+    local = idx - starts[batch]
+    assert ((local >= 0) & (local < counts[batch])).all()   # every gathered row lies inside its batch
+    arrays = {"num_rows": counts.astype(np.float64), "row_index": idx.astype(np.float64)}
+    for c, (name, fmt) in enumerate(zip(names, fmts)):
+        parts = []
+        for b, o in enumerate(outs):
+            sel = local[batch == b]
+            if not len(sel):
+                continue
+            dev = torch.device("cuda", o.ctx.device_id)
+            ti = torch.from_numpy(sel).to(dev)
+            if fmt == "u":
+                offs, data = o.utf8_tensors(c, torch)
+                start, length = offs[ti].long(), (offs[ti + 1] - offs[ti]).long()
+                pos = start[:, None] + torch.arange(DUMP_UTF8_BYTES, device=dev)
+                inside = pos < (start + length)[:, None]
+                got = data[torch.where(inside, pos, 0)].masked_fill(~inside, 0) if data.numel() else torch.zeros(pos.shape, dtype=torch.uint8, device=dev)
+                parts.append((length.cpu().numpy(), got.cpu().numpy()))
+            else:
+                parts.append(o.column_tensor(c, torch)[ti].cpu().numpy())
+        if fmt == "u":
+            arrays[name + "_length"] = np.concatenate([p[0] for p in parts] or [np.zeros(0)]).astype(np.float64)
+            arrays[name + "_bytes"] = np.concatenate([p[1] for p in parts] or [np.zeros((0, DUMP_UTF8_BYTES))]).astype(np.float32)
+        else:
+            v = np.concatenate(parts) if parts else np.zeros(0, dtype=np.float32)
+            arrays[name] = v.astype(np.float64 if v.dtype.kind in "iu" or v.dtype.itemsize == 8 else np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= budget - 4096
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
 
 
 # ---- config 5: the huge_simple.sql shape --------------------------------------------------------------------------------
@@ -410,19 +477,23 @@ def build_config5_shard(chq, torch, dev, ctx, rows, batch_rows, rank=0):
     return batches, keep
 
 
-def run_config5_steps(chq, ctx, grp, expr, steps):
+def run_config5_steps(chq, ctx, grp, expr, steps, keep_last=False):
     """`steps` passes over the shard: ONE chq_filter_records call per pass (the caller's loop of filter_task.rs:86-125 hoisted
-    below the boundary, one output per input record id) -> (rows out of the last pass, kernel ns, alg. bytes of one pass)"""
-    kernel_ns, rows_out, alg = 0, 0, 0
-    for _ in range(steps):
+    below the boundary, one output per input record id) -> (rows out of the last pass, kernel ns, alg. bytes of one pass,
+    the last pass's output batches when keep_last, else None; the caller releases them)"""
+    kernel_ns, rows_out, alg, last = 0, 0, 0, None
+    for i in range(steps):
         outs = chq.filter_records(grp, [[], [], []], expr, ctx=ctx)
         st = ctx.last_stats()
         kernel_ns += st["kernel_ns"]
         alg = st["bytes_read_alg"] + st["bytes_written_alg"]
         rows_out = sum(o.num_rows for o in outs)
-        for o in outs:
-            o.release()
-    return rows_out, kernel_ns, alg
+        if keep_last and i == steps - 1:
+            last = outs
+        else:
+            for o in outs:
+                o.release()
+    return rows_out, kernel_ns, alg, last
 
 
 def check_config5_outputs(torch, keep, outs, batch_index=0):
@@ -480,12 +551,16 @@ def config5_main(args, chq, torch, dist, rank, local_rank, world, dev, ctx, comm
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    rows_out, kernel_ns, alg = run_config5_steps(chq, ctx, grp, expr, args.steps)
+    rows_out, kernel_ns, alg, last = run_config5_steps(chq, ctx, grp, expr, args.steps, keep_last=args.dump_outputs is not None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if last is not None:
+        dump_outputs(torch, last, args.dump_outputs, f"rank{rank}_" if world > 1 else "", DUMP_BYTES // world)
+        for o in last:
+            o.release()
     elapsed, per_gpu, (rows_out_total, kernel_ns_sum, alg_sum) = reduce_timing(dist, torch, world, comm_dev, elapsed, rows, args.steps, [rows_out, kernel_ns, alg])
     gathered = None
     if args.gathered and world > 1:
@@ -623,7 +698,11 @@ def main():
         if not validated:
             raise SystemExit("bench: GPU result differs from the oracle on the validation prefix")
 
-    elapsed, kernel_ns, stats = time_config2(chq, torch, dist, world, ctx, cols, n, expr, aliases, args.steps, args.warmup)
+    elapsed, kernel_ns, stats, last = time_config2(chq, torch, dist, world, ctx, cols, n, expr, aliases, args.steps, args.warmup,
+                                                   keep_last=args.dump_outputs is not None)
+    if last is not None:
+        dump_outputs(torch, [last], args.dump_outputs, f"rank{rank}_" if world > 1 else "", DUMP_BYTES // world)
+        last.release()
     rows_out = stats["rows_out"]
     elapsed, per_gpu, (rows_out_total, kernel_ns_sum) = reduce_timing(dist, torch, world, comm_dev, elapsed, n, args.steps, [rows_out, kernel_ns])
     kernel_ns = kernel_ns_sum // world
@@ -634,7 +713,7 @@ def main():
         del cols
         torch.cuda.empty_cache()
         wcols = make_config2_columns(torch, dev, total_rows, rank)
-        w_elapsed, w_kns, w_stats = time_config2(chq, torch, dist, world, ctx, wcols, total_rows, expr, aliases, args.steps, args.warmup)
+        w_elapsed, w_kns, w_stats, _ = time_config2(chq, torch, dist, world, ctx, wcols, total_rows, expr, aliases, args.steps, args.warmup)
         w_elapsed, w_per_gpu, (w_rows_out, w_kns_sum) = reduce_timing(dist, torch, world, comm_dev, w_elapsed, total_rows, args.steps, [w_stats["rows_out"], w_kns])
         w_alg = w_stats["bytes_read_alg"] + w_stats["bytes_written_alg"]
         w_kms = w_kns_sum / world / args.steps / 1e6

@@ -243,3 +243,57 @@ def test_bench_n_rank_path_rehearsed_on_one_gpu(extra, rows_per_gpu):
         assert j["extra"]["weak"]["rows_per_gpu"] == 120_000_001 and j["extra"]["weak"]["value"] > 0
         assert 0.89 < j["config"]["rows_out_total"] / 120_000_001 < 0.91     # value2 > 10.0 keeps ~90 %
         assert j["roofline"]["traffic"] is None                              # (the PMC file was measured on 1e9 rows per GPU)
+
+
+@pytest.mark.parametrize("extra", [["--rows", "5000001"], ["--config", "5", "--rows", "1000001", "--batch-rows", "300000"]])
+def test_bench_dump_outputs_are_the_last_step_and_repeat(tmp_path, extra):
+    """`bench.py --dump-outputs DIR`: the last timed step's output within 64 MB (config 2 at 5 M rows does not fit and is
+    sampled, config 5 at 1 M rows in four batches fits whole), the same files from a second run, and every dumped value
+    the one the seeded inputs give at its row."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import torch
+
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+               "--validate-rows", "200000", "--dump-outputs", str(d)] + extra
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        j = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")][0]
+        assert j["steps"] == 3 and j["ms_per_step"] > 0
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64_000_000
+        dumps.append({f.stem: np.load(f) for f in d.iterdir()})
+    a, b = dumps
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["row_index"].astype(np.int64)
+    assert (np.diff(idx) > 0).all() and idx[-1] < a["num_rows"].sum()
+    assert all(a[k].dtype in (np.float32, np.float64) for k in a)
+    dev = torch.device("cuda", 0)
+    if "--config" not in extra:
+        cols = [c.cpu().numpy() for c in bench.make_config2_columns(torch, dev, 5_000_001, 0)]
+        keep = cols[2] > 10.0
+        assert a["num_rows"].tolist() == [keep.sum()] and len(idx) < keep.sum()     # sampled
+        for c in range(3):
+            assert np.array_equal(a[f"value{c}"].view(np.uint32), cols[c][keep][idx].view(np.uint32))
+    else:
+        ctx = chq.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+        batches, shard = bench.build_config5_shard(chq, torch, dev, ctx, 1_000_001, 300_000)
+        chars = torch.cat(shard[1::4]).cpu().numpy().reshape(-1, bench.C5_STRLEN)
+        v2 = torch.cat(shard[3::4]).cpu().numpy()
+        assert a["num_rows"].tolist() == [150_000, 150_000, 150_000, 50_001] and len(idx) == 500_001   # whole
+        ids = 2 * idx                                      # the even ids, batch after batch
+        assert np.array_equal(a["id"], ids.astype(np.float64))
+        assert np.array_equal(a["value2"].view(np.uint32), v2[ids].view(np.uint32))
+        assert (a["value1_length"] == bench.C5_STRLEN).all()
+        assert np.array_equal(a["value1_bytes"][:, :bench.C5_STRLEN], chars[ids].astype(np.float32))
+        assert not a["value1_bytes"][:, bench.C5_STRLEN:].any()
+        for x in batches:
+            x.release()
+        ctx.close()
