@@ -596,6 +596,8 @@ chq_status chq_record_to_ipc(chq_ctx* ctx, const ArrowDeviceArray* rec, const Ar
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     Batch in = import_batch(rec, schema);
     Batch dev = to_device(ctx->c, in);   // (a host batch is staged: the body is assembled by the device either way)
+    // an unknown null count (-1, a view) stays unknown: the encoder counts it; to_device's "may have nulls" 1 would be written
+    for (size_t i = 0; i < dev.cols.size(); ++i) if (in.on_device && in.cols[i].validity && in.cols[i].null_count < 0) dev.cols[i].null_count = -1;
     auto* h = new IpcHolder();
     try {
       h->msg = record_to_ipc(ctx->c, dev, body_device == ARROW_DEVICE_ROCM);

@@ -2251,8 +2251,13 @@ std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const
   if (fold && lite && !host_in && (sliced || co) && ctx.opt_uniform_utf8_rows > 0 && total_rows >= ctx.opt_uniform_utf8_rows) {
     bool pred_reads_utf8 = false;
     for (int r : lw.refs) pred_reads_utf8 |= recs[0].cols[(size_t)r].type == T_UTF8;
+    // a Utf8 column with a bitmap in any batch keeps the string path, as in filter_record: the conversion below zeroes the
+    // Arrow offset the bitmap is read at, and the coalesced form rebuilds the column without its validity
+    bool utf8_bitmap = false;
+    for (int i : fold_utf8)
+      for (size_t b = 0; b < nb && !utf8_bitmap; ++b) utf8_bitmap = lite->validity[b * ncols + (size_t)i] != nullptr;
     // (a group whose joined strings do not fit ONE output column is cut into sub-groups first: each comes back here)
-    if (!pred_reads_utf8 && finish_fold_sizes()) {
+    if (!pred_reads_utf8 && !utf8_bitmap && finish_fold_sizes()) {
       const size_t nu = fold_utf8.size();
       std::vector<unsigned long long> h_in((nu + 1) * nb);
       for (size_t b = 0; b < nb; ++b) h_in[b] = (unsigned long long)lite->rows[b];
@@ -2940,6 +2945,7 @@ Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, c
   out.on_device = true; out.device_id = ctx.device;
   std::vector<Evaluated> evs;            // computed items, evaluated together after the walk
   std::vector<int> computed_slot;        // output column index of each computed item
+  std::vector<size_t> passthrough_slot;  // output column index of each identifier item
   size_t unnamed_idx = 0;
   for (const chq_select_item& f : fields) {
     switch (f.kind) {
@@ -2975,7 +2981,7 @@ Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, c
         else name = "unnamed_" + std::to_string(unnamed_idx);          // :49-53
         if (f.kind == CHQ_ITEM_UNNAMED_EXPR) ++unnamed_idx;           // :58, counts identifiers too
         Column col;
-        if (ev.kind == Evaluated::PASSTHROUGH) col = clone_device_column(ctx, rec.cols[ev.col]);
+        if (ev.kind == Evaluated::PASSTHROUGH) { col = clone_device_column(ctx, rec.cols[ev.col]); passthrough_slot.push_back(out.cols.size()); }
         else if (ev.kind == Evaluated::SCALAR) col = scalar_column(ctx, ev.value, name);
         else { computed_slot.push_back((int)out.cols.size()); evs.push_back(std::move(ev)); }
         col.name = name;
@@ -2994,7 +3000,31 @@ Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, c
       out.cols[computed_slot[i]].name = name;
     }
   }
+  // an identifier over a view keeps the view's bitmap with its null count unknown (imported as "may have nulls"): count the
+  // window's nulls, so that its nullability is the reference's null_count > 0 below
+  std::vector<size_t> counted;
+  for (size_t k : passthrough_slot) {
+    Column& c = out.cols[k];
+    if (c.validity && c.null_count != 0 && c.length == 0) { c.null_count = 0; c.validity = nullptr; }
+    else if (c.validity && c.null_count != 0) counted.push_back(k);
+  }
+  BufferPtr d_valid;
+  std::vector<unsigned long long> h_valid(counted.size(), 0);
+  if (!counted.empty()) {
+    d_valid = make_device_buffer(counted.size() * 8 + 16, ctx.device);
+    check_hip(hipMemsetAsync(d_valid->ptr, 0, counted.size() * 8, ctx.stream), "memset");
+    for (size_t j = 0; j < counted.size(); ++j) {
+      const Column& c = out.cols[counted[j]];
+      check_hip(launch_count_bits(c.validity, c.offset, c.length, (unsigned long long*)d_valid->ptr + j, ctx.stream), "launch count_bits_kernel");
+    }
+    check_hip(hipMemcpyAsync(h_valid.data(), d_valid->ptr, counted.size() * 8, hipMemcpyDeviceToHost, ctx.stream), "read back");
+  }
   check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  for (size_t j = 0; j < counted.size(); ++j) {
+    Column& c = out.cols[counted[j]];
+    c.null_count = c.length - (int64_t)h_valid[j];
+    if (c.null_count == 0) c.validity = nullptr;
+  }
   // Field nullability: wildcard fields keep the schema flag; computed / identifier fields use
   // Array::is_nullable() = null_count > 0 (RU/record_projection.rs:45-47, 51-53, 62-66)
   {

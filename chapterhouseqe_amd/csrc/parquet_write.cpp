@@ -184,6 +184,7 @@ RowGroupPlan plan_row_group(Context& ctx, const Batch& in, int64_t& at) {
     const Column& c = rec.cols[ci];
     ColumnPlan& pl = plan[ci];
     const long long mn = h_stats[3 * ci], mx = h_stats[3 * ci + 1], cnt = h_stats[3 * ci + 2];
+    if (pl.string && pl.enc.validity) pl.null_count = rows > 0 ? rows - cnt : 0;   // a Utf8 slice's null count may be unknown (imported as 1): the valid rows the statistics counted
     if (rows == 0 || cnt == 0) continue;   // all null (or all NaN): no min / max
     auto raw = [](const void* v, size_t n) { return std::string((const char*)v, n); };
     if (pl.string) {
