@@ -55,8 +55,8 @@ void for_each_parallel(int n, F&& f) {
   pool_ranges((size_t)n, 1024, [&](size_t i0, size_t i1) { for (size_t i = i0; i < i1; ++i) f((int)i); });
 }
 
-// ---- the outputs of a one-launch group call, exported from ONE block ---------------------------------------------------
-// Every output batch of such a call is a slice of the same dense buffers (engine.hpp: GroupSliced).  Exporting them one by
+// ---- the outputs of a joined group call, exported from ONE block --------------------------------------------------------
+// Every output batch of such a call is a slice of the same joined buffers (engine.hpp: JoinedGroup).  Exporting them one by
 // one (export_batch) costs ~20 allocations per batch and, worse, an atomic reference-count increment per column and batch
 // on the SAME few shared buffers from sixteen threads -- 7.5 ms for 12 500 batches, far more than the kernel.  Here the
 // Arrow structs of all batches live in a handful of arrays inside one reference-counted block that also holds the buffers:
@@ -103,70 +103,73 @@ void group_release_schema(ArrowSchema* s) {
   group_drop(blk);
 }
 
-void export_group(GroupSliced&& g, int device_type, ArrowDeviceArray* outs, ArrowSchema* out_schemas) {
-  const size_t nb = g.ends.size(), C = g.proto.size();
-  auto* blk = new GroupBlock();
-  for (size_t i = 0; i < C; ++i) {
-    blk->names.push_back(g.proto[i].name); blk->formats.push_back(g.proto[i].format);
-    blk->buffers.push_back(g.values[i]);
-    if (g.data[i]) blk->buffers.push_back(g.data[i]);
-  }
-  const size_t cells = std::max<size_t>(1, nb * C);
-  blk->child_arrays.reset(new ArrowArray[cells]); blk->child_ptrs.reset(new ArrowArray*[cells]); blk->bufs.reset(new const void*[cells * 3]);
-  blk->parent_bufs.reset(new const void*[std::max<size_t>(1, nb)]); blk->child_schemas.reset(new ArrowSchema[cells]); blk->schild_ptrs.reset(new ArrowSchema*[cells]);
-  blk->live.store((int64_t)(nb * (2 + 2 * C)));
-  std::vector<const uint8_t*> vbase(C), dbase(C), nbase(C);
-  for (size_t i = 0; i < C; ++i) {
-    vbase[i] = (const uint8_t*)g.values[i]->ptr; dbase[i] = g.data[i] ? (const uint8_t*)g.data[i]->ptr : nullptr;
-    nbase[i] = (i < g.validity.size() && g.validity[i]) ? (const uint8_t*)g.validity[i]->ptr : nullptr;
-    if (nbase[i]) blk->buffers.push_back(g.validity[i]);
-  }
-  const bool host_out = device_type != ARROW_DEVICE_ROCM;
-  pool_ranges(nb, 1024, [&](size_t b0, size_t b1) {
-    for (size_t b = b0; b < b1; ++b) {
-      const int64_t begin = b ? g.ends[b - 1] : 0, rows = g.ends[b] - begin;
-      for (size_t i = 0; i < C; ++i) {
-        const Column& pc = g.proto[i];
-        ArrowArray& ca = blk->child_arrays[b * C + i];
-        const void** cb = &blk->bufs[(b * C + i) * 3];
-        memset(&ca, 0, sizeof ca);
-        cb[0] = nullptr; cb[2] = nullptr;
-        ca.null_count = 0;
-        if (pc.type == T_UTF8) { cb[1] = vbase[i]; cb[2] = dbase[i]; ca.offset = begin; ca.n_buffers = 3; }   // a slice of the joined column
-        else if (pc.type == T_BOOL || nbase[i]) { cb[1] = vbase[i]; ca.offset = begin; ca.n_buffers = 2; }    // (one Arrow offset serves values and validity)
-        else { cb[1] = vbase[i] + begin * pc.width; ca.offset = 0; ca.n_buffers = 2; }
-        if (nbase[i]) {   // nulls of the slice: unknown on the device (-1), counted for a host result; an all-valid slice drops the bitmap
-          cb[0] = nbase[i];
-          if (!host_out) ca.null_count = -1;
-          else {
-            int64_t nulls = 0;
-            for (int64_t r = begin; r < begin + rows; ++r) nulls += !((nbase[i][r >> 3] >> (r & 7)) & 1);
-            ca.null_count = nulls;
-            if (nulls == 0) cb[0] = nullptr;
-          }
-        }
-        ca.length = rows; ca.buffers = cb; ca.release = group_release_child_array; ca.private_data = blk;
-        blk->child_ptrs[b * C + i] = &ca;
-        ArrowSchema& cs = blk->child_schemas[b * C + i];
-        memset(&cs, 0, sizeof cs);
-        cs.format = blk->formats[i].c_str(); cs.name = blk->names[i].c_str(); cs.flags = pc.nullable ? ARROW_FLAG_NULLABLE : 0;
-        cs.release = group_release_child_schema; cs.private_data = blk;
-        blk->schild_ptrs[b * C + i] = &cs;
-      }
-      ArrowDeviceArray& o = outs[b];
-      memset(&o, 0, sizeof o);
-      blk->parent_bufs[b] = nullptr;
-      o.array.length = rows; o.array.n_buffers = 1; o.array.buffers = &blk->parent_bufs[b];
-      o.array.n_children = (int64_t)C; o.array.children = C ? &blk->child_ptrs[b * C] : nullptr;
-      o.array.release = group_release_array; o.array.private_data = blk;
-      o.device_id = device_type == ARROW_DEVICE_ROCM ? g.device_id : -1; o.device_type = device_type; o.sync_event = nullptr;
-      ArrowSchema& os = out_schemas[b];
-      memset(&os, 0, sizeof os);
-      os.format = blk->struct_format.c_str(); os.name = blk->empty.c_str();
-      os.n_children = (int64_t)C; os.children = C ? &blk->schild_ptrs[b * C] : nullptr;
-      os.release = group_release_schema; os.private_data = blk;
+// `outs` / `out_schemas`: one per batch the part covers.  The block goes to the exported structs only once every one of them
+// is written; a failure before that frees it and leaves the structs released.
+void export_group(JoinedGroup&& g, int device_type, ArrowDeviceArray* outs, ArrowSchema* out_schemas) {
+  const size_t nb = g.ends.size(), C = g.joined.cols.size();
+  std::unique_ptr<GroupBlock> blk(new GroupBlock());
+  try {
+    for (Column& c : g.joined.cols) {
+      blk->names.push_back(c.name); blk->formats.push_back(c.format);
+      for (BufferPtr& b : c.owned) blk->buffers.push_back(std::move(b));
     }
-  });
+    const size_t cells = std::max<size_t>(1, nb * C);
+    blk->child_arrays.reset(new ArrowArray[cells]); blk->child_ptrs.reset(new ArrowArray*[cells]); blk->bufs.reset(new const void*[cells * 3]);
+    blk->parent_bufs.reset(new const void*[std::max<size_t>(1, nb)]); blk->child_schemas.reset(new ArrowSchema[cells]); blk->schild_ptrs.reset(new ArrowSchema*[cells]);
+    const bool host_out = device_type != ARROW_DEVICE_ROCM;
+    GroupBlock* pb = blk.get();
+    pool_ranges(nb, 1024, [&](size_t b0, size_t b1) {
+      for (size_t b = b0; b < b1; ++b) {
+        const int64_t begin = b ? g.ends[b - 1] : 0, rows = g.ends[b] - begin;
+        for (size_t i = 0; i < C; ++i) {
+          const Column& c = g.joined.cols[i];
+          const int64_t at = c.offset + begin;   // the slice's first row in the joined buffers
+          ArrowArray& ca = pb->child_arrays[b * C + i];
+          const void** cb = &pb->bufs[(b * C + i) * 3];
+          memset(&ca, 0, sizeof ca);
+          cb[0] = nullptr; cb[2] = nullptr;
+          ca.null_count = 0;
+          if (c.type == T_UTF8) { cb[1] = c.values; cb[2] = c.data; ca.offset = at; ca.n_buffers = 3; }   // a slice of the joined column
+          else if (c.type == T_BOOL || c.validity) { cb[1] = c.values; ca.offset = at; ca.n_buffers = 2; }   // (one Arrow offset serves values and validity)
+          else { cb[1] = c.values + at * c.width; ca.offset = 0; ca.n_buffers = 2; }
+          if (c.validity) {   // nulls of the slice: unknown on the device (-1), counted for a host result; an all-valid slice drops the bitmap
+            cb[0] = c.validity;
+            if (!host_out) ca.null_count = -1;
+            else {
+              int64_t nulls = 0;
+              for (int64_t r = at; r < at + rows; ++r) nulls += !((c.validity[r >> 3] >> (r & 7)) & 1);
+              ca.null_count = nulls;
+              if (nulls == 0) cb[0] = nullptr;
+            }
+          }
+          ca.length = rows; ca.buffers = cb; ca.release = group_release_child_array; ca.private_data = pb;
+          pb->child_ptrs[b * C + i] = &ca;
+          ArrowSchema& cs = pb->child_schemas[b * C + i];
+          memset(&cs, 0, sizeof cs);
+          cs.format = pb->formats[i].c_str(); cs.name = pb->names[i].c_str(); cs.flags = c.nullable ? ARROW_FLAG_NULLABLE : 0;
+          cs.release = group_release_child_schema; cs.private_data = pb;
+          pb->schild_ptrs[b * C + i] = &cs;
+        }
+        ArrowDeviceArray& o = outs[b];
+        memset(&o, 0, sizeof o);
+        pb->parent_bufs[b] = nullptr;
+        o.array.length = rows; o.array.n_buffers = 1; o.array.buffers = &pb->parent_bufs[b];
+        o.array.n_children = (int64_t)C; o.array.children = C ? &pb->child_ptrs[b * C] : nullptr;
+        o.array.release = group_release_array; o.array.private_data = pb;
+        o.device_id = device_type == ARROW_DEVICE_ROCM ? g.joined.device_id : -1; o.device_type = device_type; o.sync_event = nullptr;
+        ArrowSchema& os = out_schemas[b];
+        memset(&os, 0, sizeof os);
+        os.format = pb->struct_format.c_str(); os.name = pb->empty.c_str();
+        os.n_children = (int64_t)C; os.children = C ? &pb->schild_ptrs[b * C] : nullptr;
+        os.release = group_release_schema; os.private_data = pb;
+      }
+    });
+  } catch (...) {
+    for (size_t b = 0; b < nb; ++b) mark_released(&outs[b], &out_schemas[b]);
+    throw;
+  }
+  blk->live.store((int64_t)(nb * (2 + 2 * C)));
+  (void)blk.release();
 }
 
 // Import of a group.  Batch 0 is imported in full.  A DEVICE-resident group then only gathers its GroupLite -- the checks of
@@ -419,26 +422,26 @@ chq_status chq_filter_records(chq_ctx* ctx, int n_records, const ArrowDeviceArra
     for (int i = 0; i < n_records; ++i) require(recs[i], "record");
     import_group(n_records, recs, schema, ctx->c.device, in, lite, gi);
     pt.mark("import");
-    GroupSliced sliced;
-    std::vector<Batch> res = filter_records(ctx->c, gi, table_aliases, expr->e, out_device == ARROW_DEVICE_ROCM, &sliced);
+    GroupResult res = filter_records(ctx->c, gi, table_aliases, expr->e, out_device == ARROW_DEVICE_ROCM);
     pt.mark("filter");
-    if (sliced.filled) {
-      std::vector<GroupSliced> more = std::move(sliced.more);
-      size_t at = sliced.ends.size();
-      export_group(std::move(sliced), out_device, outs, out_schemas);
-      for (GroupSliced& m : more) { const size_t n = m.ends.size(); export_group(std::move(m), out_device, outs + at, out_schemas + at); at += n; }
-      pt.mark("export");
-      return;
-    }
-    try {
-      for_each_parallel(n_records, [&](int i) { export_batch(std::move(res[(size_t)i]), out_device, &outs[i], &out_schemas[i]); });
-    } catch (...) {   // no partial output
+    if (res.batches() != (size_t)n_records)
+      throw ChqError{CHQ_ERR_DEVICE, "internal error: the group result covers " + std::to_string(res.batches()) + " of " + std::to_string(n_records) + " batches"};
+    try {   // every output or none
+      size_t at = 0;
+      for (JoinedGroup& part : res.parts) {
+        const size_t n = part.ends.size();
+        export_group(std::move(part), out_device, outs + at, out_schemas + at);
+        at += n;
+      }
+      if (res.parts.empty()) for_each_parallel(n_records, [&](int i) { export_batch(std::move(res.per_batch[(size_t)i]), out_device, &outs[i], &out_schemas[i]); });
+    } catch (...) {
       for (int i = 0; i < n_records; ++i) {
         if (outs[i].array.release) outs[i].array.release(&outs[i].array);
         if (out_schemas[i].release) out_schemas[i].release(&out_schemas[i]);
       }
       throw;
     }
+    pt.mark("export");
   });
 }
 
@@ -464,6 +467,8 @@ chq_status chq_filter_records_coalesced(chq_ctx* ctx, int n_records, const Arrow
     std::vector<int64_t> rows;
     Batch res = filter_records_coalesced(ctx->c, gi, table_aliases, expr->e, out_device == ARROW_DEVICE_ROCM, &rows);
     pt.mark("filter");
+    if (rows.size() != (size_t)n_records)
+      throw ChqError{CHQ_ERR_DEVICE, "internal error: the coalesced result covers " + std::to_string(rows.size()) + " of " + std::to_string(n_records) + " batches"};
     if (rows_per_record) for (int i = 0; i < n_records; ++i) rows_per_record[i] = rows[(size_t)i];
     export_batch(std::move(res), out_device, out, out_schema);
     pt.mark("export");

@@ -495,6 +495,18 @@ void GroupLite::set(size_t b, const Batch& r, const Batch& first, int device) {
   flags[b] = f;
 }
 
+GroupLite GroupLite::slice(size_t b0, size_t b1) const {
+  GroupLite s;
+  s.ncols = ncols;
+  s.rows.assign(rows.begin() + b0, rows.begin() + b1);
+  s.flags.assign(flags.begin() + b0, flags.begin() + b1);
+  s.values0.assign(values0.begin() + b0 * ncols, values0.begin() + b1 * ncols);
+  s.data.assign(data.begin() + b0 * ncols, data.begin() + b1 * ncols);
+  s.validity.assign(validity.begin() + b0 * ncols, validity.begin() + b1 * ncols);
+  s.offset.assign(offset.begin() + b0 * ncols, offset.begin() + b1 * ncols);
+  return s;
+}
+
 std::vector<PlanColumn> plan_columns(const Batch& b, const chq_table_aliases* aliases) {
   std::vector<PlanColumn> out;
   for (size_t i = 0; i < b.cols.size(); ++i) {
@@ -961,6 +973,36 @@ Column empty_like(const Column& c) {
   return o;
 }
 
+// ---- the uniform-length Utf8 rewrite (filter_record and the group path) -------------------------------------------------
+// A Utf8 column qualifies when it has no bitmap that may hold nulls (the rewrite zeroes the Arrow offset a bitmap is read
+// at), all its values have one length L in {1, 2, 4, 8, 16} (whole values per lane) and rows x L fits int32 offsets.
+// Asked with L = 1 before the lengths are known.
+bool uniform_utf8_ok(bool may_hold_nulls, int64_t rows, int64_t L) {
+  return !may_hold_nulls && (L == 1 || L == 2 || L == 4 || L == 8 || L == 16) && rows * L < (1ll << 31) - 64;
+}
+// The rebuild: the fixed-width (w:L) output of such a column back to Utf8 with the schema of `like` -- its values become
+// the bytes, and the offsets 0, L, 2 L, ... are written where the column lives
+Column uniform_to_utf8(Context& ctx, Column&& fixed, const Column& like, int64_t rows, bool on_device) {
+  const int32_t L = fixed.width;
+  BufferPtr ob;
+  if (on_device) {
+    ob = make_device_buffer((size_t)(rows + 1) * 4 + 16, ctx.device);
+    IotaOffsetsParams ip{(int32_t*)ob->ptr, rows + 1, L, 0};
+    check_hip(launch_iota_offsets(ip, ctx.stream), "launch iota_offsets_kernel");
+  } else {
+    ob = make_host_buffer((size_t)(rows + 1) * 4 + 16);
+    int32_t* o = (int32_t*)ob->ptr;
+    for (int64_t r = 0; r <= rows; ++r) o[r] = (int32_t)(r * L);
+  }
+  Column u = empty_like(like);
+  u.length = rows; u.null_count = 0; u.offset = 0;
+  u.data = (const uint8_t*)fixed.values0(); u.data_bytes = rows * (int64_t)L;
+  u.values = (const uint8_t*)ob->ptr;
+  u.owned = std::move(fixed.owned); u.owned.push_back(ob);
+  ctx.stats.bytes_written_alg += (rows + 1) * 4;
+  return u;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -1007,7 +1049,7 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
     std::vector<int> cand;
     for (size_t i = 0; i < rec.cols.size(); ++i) {
       const Column& c = rec.cols[i];
-      if (c.type != T_UTF8 || !c.values || !c.data || (c.validity && c.null_count != 0)) continue;
+      if (c.type != T_UTF8 || !c.values || !c.data || !uniform_utf8_ok(c.validity && c.null_count != 0, nrows, 1)) continue;
       if (std::find(lw.refs.begin(), lw.refs.end(), (int)i) != lw.refs.end()) continue;
       cand.push_back((int)i);
     }
@@ -1033,7 +1075,7 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
       std::vector<int> turned;
       for (size_t k = 0; k < cand.size(); ++k) {
         const int32_t differs = h_chk[4 * k], len = h_chk[4 * k + 1], first = h_chk[4 * k + 2];
-        if (differs || !(len == 1 || len == 2 || len == 4 || len == 8 || len == 16) || nrows * (int64_t)len >= (1ll << 31) - 64 || first < 0) continue;
+        if (differs || first < 0 || !uniform_utf8_ok(false, nrows, len)) continue;
         Column& v = view.cols[(size_t)cand[k]];
         v.type = T_FIXED_OPAQUE; v.format = "w:" + std::to_string(len); v.width = len;
         v.values = v.data + first; v.data = nullptr; v.data_bytes = -1; v.offset = 0; v.validity = nullptr; v.null_count = 0;
@@ -1046,19 +1088,8 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
         if (tev[2]) check_hip(hipEventRecord(tev[2], ctx.stream), "hipEventRecord");
         for (int ci : turned) {
           Column& o = res.cols[(size_t)ci];
-          const Column& c = rec.cols[(size_t)ci];
-          const int32_t len = o.width;
-          auto ob = make_device_buffer((size_t)(res.nrows + 1) * 4 + 16, ctx.device);
-          IotaOffsetsParams ip{(int32_t*)ob->ptr, res.nrows + 1, len, 0};
-          check_hip(launch_iota_offsets(ip, ctx.stream), "launch iota_offsets_kernel");
-          Column u = empty_like(c);
-          u.length = res.nrows; u.null_count = 0; u.offset = 0;
-          u.data = o.values; u.data_bytes = res.nrows * (int64_t)len;
-          u.values = (const uint8_t*)ob->ptr;
-          u.owned = std::move(o.owned); u.owned.push_back(ob);
-          o = std::move(u);
-          ctx.stats.bytes_read_alg += (nrows + 1) * 4;             // the offsets were read (by the check) ...
-          ctx.stats.bytes_written_alg += (res.nrows + 1) * 4;      // ... and written
+          o = uniform_to_utf8(ctx, std::move(o), rec.cols[(size_t)ci], res.nrows, true);   // (counts the offsets written)
+          ctx.stats.bytes_read_alg += (nrows + 1) * 4;   // the offsets were read by the check
         }
         if (tev[3]) check_hip(hipEventRecord(tev[3], ctx.stream), "hipEventRecord");
         check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
@@ -1932,453 +1963,332 @@ std::vector<std::vector<int64_t>> device_utf8_bytes(Context& ctx, const std::vec
 }  // namespace
 
 namespace {
-// `co` != nullptr asks for ONE output batch (all surviving rows, input order) + rows per input batch; the one-launch
-// path fills it directly and sets co->done, every other path returns per-batch outputs for the caller to join
-struct Coalesced { Batch out; std::vector<int64_t> rows; bool done = false; };
-std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const chq_table_aliases* aliases,
-                                       const Expr& expr, bool out_on_device, Coalesced* co, GroupSliced* sliced);
-}  // namespace
-
-std::vector<Batch> filter_records(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases,
-                                  const Expr& expr, bool out_on_device, GroupSliced* sliced) {
-  return filter_records_impl(ctx, in, aliases, expr, out_on_device, nullptr, sliced);
+// ---- the pieces of a group call ------------------------------------------------------------------------------------------
+// Chunks [cuts[k], cuts[k+1]) of a group: a cut before the batch at which the rows would pass 2^30 or the bytes of any Utf8
+// column would pass `limit` (int32 offsets of the joined output; a batch over the limit on its own is a chunk of its own).
+// `bytes[k][b]`: data bytes of the k-th Utf8 column of batch b.
+std::vector<size_t> chunk_cuts(const std::vector<int64_t>& rows, const std::vector<std::vector<int64_t>>& bytes, int64_t limit) {
+  std::vector<size_t> cuts{0};
+  std::vector<int64_t> sum(bytes.size(), 0);
+  int64_t at = 0;
+  for (size_t b = 0; b < rows.size(); ++b) {
+    bool over = at + rows[b] > (1ll << 30);
+    for (size_t k = 0; k < bytes.size(); ++k) over |= sum[k] + bytes[k][b] > limit;
+    if (over && b > cuts.back()) { cuts.push_back(b); std::fill(sum.begin(), sum.end(), 0); at = 0; }
+    for (size_t k = 0; k < bytes.size(); ++k) sum[k] += bytes[k][b];
+    at += rows[b];
+  }
+  cuts.push_back(rows.size());
+  return cuts;
 }
 
-Batch filter_records_coalesced(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases,
-                               const Expr& expr, bool out_on_device, std::vector<int64_t>* rows_per_record) {
-  if (!in.batches || in.batches->empty()) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "no record batches to coalesce"};
-  Coalesced co;
-  std::vector<Batch> outs = filter_records_impl(ctx, in, aliases, expr, out_on_device, &co, nullptr);
-  if (!co.done) {   // join the per-batch results on the host (general column kinds), then move them where they are wanted
-    const chq_call_stats st = ctx.stats;
-    std::vector<Batch> host;
-    for (Batch& o : outs) { co.rows.push_back(o.nrows); host.push_back(o.on_device ? to_host(ctx, o) : std::move(o)); }
-    Batch cat = concat_host_batches(host, 0, host.size());
-    co.out = out_on_device ? to_device(ctx, cat) : std::move(cat);
-    if (out_on_device) check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-    ctx.stats = st;
-  }
-  if (rows_per_record) *rows_per_record = co.rows;
-  return std::move(co.out);
+std::vector<int64_t> rows_of(const std::vector<Batch>& recs) {
+  std::vector<int64_t> rows;
+  for (const Batch& r : recs) rows.push_back(r.nrows);
+  return rows;
 }
 
-namespace {
-std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const chq_table_aliases* aliases,
-                                       const Expr& expr, bool out_on_device, Coalesced* co, GroupSliced* sliced) {
-  const std::vector<Batch>& recs = *gi.batches;   // (batch 0 is always there; the others after need_batches() when `lite` is set)
-  const GroupLite* lite = gi.lite;
-  if (lite && (lite->rows.empty() || recs.empty() || lite->ncols != recs[0].cols.size())) lite = nullptr;
-  auto need_batches = [&]() { if (gi.materialise) gi.materialise(); };
-  if (!lite) need_batches();
-  const size_t nb = lite ? lite->rows.size() : recs.size();
-  auto per_batch_loop = [&]() {
-    need_batches();
-    std::vector<Batch> outs;
-    chq_call_stats acc{};
-    for (const Batch& r : recs) {
-      Batch dev = to_device(ctx, r);
-      Batch o = filter_record(ctx, dev, plan_columns(dev, aliases), expr);
-      add_stats(acc, ctx.stats);
-      outs.push_back(out_on_device ? std::move(o) : to_host(ctx, o));
-    }
-    ctx.stats = acc;
-    return outs;
-  };
-  if (nb < 2) return per_batch_loop();
+// batch b of a group as a view built from the flat arrays, with the schema of `first` (the head batch of a sub-group)
+Batch lite_head(const Batch& first, const GroupLite& lite, size_t b) {
+  Batch h = first;
+  h.nrows = lite.rows[b];
+  for (size_t i = 0; i < lite.ncols; ++i) {
+    Column& c = h.cols[i];
+    const size_t at = b * lite.ncols + i;
+    c.owned.clear();
+    c.offset = lite.offset[at]; c.length = lite.rows[b];
+    c.values = c.type == T_BOOL ? lite.values0[at] : lite.values0[at] - (int64_t)(c.type == T_UTF8 ? 4 : c.width) * c.offset;
+    c.data = lite.data[at]; c.data_bytes = -1;
+    c.validity = lite.validity[at]; c.null_count = c.validity ? 1 : 0;   // (unknown count: may have nulls)
+  }
+  return h;
+}
 
-  // ---- host batches with Utf8 / Boolean / nullable columns: concatenate on the host while staging, filter the one
-  // big batch (every column kind is supported there), copy the result back once and slice it per input batch at the
-  // positions the device reports (split_bounds_kernel).  Chunks keep every Utf8 column below 1 GiB of bytes.
-  auto host_concat_path = [&]() -> std::vector<Batch> {
-    need_batches();
-    const size_t nc = recs[0].cols.size();
-    std::vector<size_t> cuts{0};
-    {
-      std::vector<int64_t> bytes(nc, 0);
-      int64_t rows = 0;
-      for (size_t b = 0; b < nb; ++b) {
-        bool over = rows + recs[b].nrows > (1ll << 30);
-        const int64_t limit = ctx.opt_group_chunk_bytes;
-        std::vector<int64_t> add(nc, 0);
-        for (size_t i = 0; i < nc; ++i) {
-          const Column& c = recs[b].cols[i];
-          if (c.type == T_UTF8 && c.values && c.length) { const int32_t* o = (const int32_t*)c.values + c.offset; add[i] = (int64_t)o[c.length] - o[0]; }
-          over |= bytes[i] + add[i] > limit;
-        }
-        if (over && b > cuts.back()) { cuts.push_back(b); std::fill(bytes.begin(), bytes.end(), 0); rows = 0; }
-        for (size_t i = 0; i < nc; ++i) bytes[i] += add[i];
-        rows += recs[b].nrows;
-      }
-      cuts.push_back(nb);
-    }
-    std::vector<Batch> outs;
-    outs.reserve(nb);
-    chq_call_stats acc{};
-    for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-      const size_t b0 = cuts[k], b1 = cuts[k + 1];
-      Batch cat = concat_host_batches(recs, b0, b1);
-      SplitRequest split;
-      int64_t at = 0;
-      for (size_t b = b0; b < b1; ++b) { split.starts.push_back(at); at += recs[b].nrows; }
-      split.starts.push_back(at);
-      Batch dev = to_device(ctx, cat);
-      Batch res = to_host(ctx, filter_record(ctx, dev, plan_columns(dev, aliases), expr, &split));
-      add_stats(acc, ctx.stats);
-      for (size_t b = b0; b < b1; ++b) {
-        const int64_t begin = split.bounds[b - b0], end = split.bounds[b - b0 + 1];
-        Batch o;
-        o.on_device = false; o.device_id = -1; o.nrows = end - begin;
-        for (const Column& c : res.cols) {
-          Column sc = c;   // shares the result buffers
-          sc.offset = c.offset + begin; sc.length = end - begin;
-          if (sc.validity) {
-            sc.null_count = count_nulls_host(sc.validity, sc.offset, sc.length);
-            if (sc.null_count == 0) sc.validity = nullptr;   // arrow drops an all-valid null buffer
-          } else sc.null_count = 0;
-          o.cols.push_back(std::move(sc));
-        }
-        outs.push_back(std::move(o));
-      }
-    }
-    ctx.stats = acc;
-    return outs;
-  };
+// filter_record over `cat`, the batches recs[b0, b1) back to back, with the output position of every batch reported by the
+// device (split_bounds_kernel); the result where `out_on_device` says
+JoinedGroup filter_joined(Context& ctx, const Batch& cat, const std::vector<Batch>& recs, size_t b0, size_t b1,
+                          const chq_table_aliases* aliases, const Expr& expr, bool out_on_device) {
+  SplitRequest split;
+  int64_t at = 0;
+  for (size_t b = b0; b < b1; ++b) { split.starts.push_back(at); at += recs[b].nrows; }
+  split.starts.push_back(at);
+  Batch res = filter_record(ctx, cat, plan_columns(cat, aliases), expr, &split);
+  JoinedGroup g;
+  g.joined = out_on_device ? std::move(res) : to_host(ctx, res);
+  g.ends.assign(split.bounds.begin() + 1, split.bounds.end());
+  return g;
+}
 
-  // ---- device-resident batches with Utf8 / Boolean / nullable columns (the reference's own schema is Int32, Utf8,
-  // Float32: create_sample_data.rs:157-204): joined on the device by the concat kernels, filtered as ONE batch by the
-  // ordinary kernels, cut at the batch boundaries the device reports (split_bounds_kernel).  Every output batch is a
-  // slice (Arrow offset) of the shared result buffers; chunks keep every Utf8 column below the int32 offset range.
-  auto device_concat_path = [&]() -> std::vector<Batch> {
-    need_batches();
-    const size_t nc = recs[0].cols.size();
-    std::vector<int> utf8_cols;
-    for (size_t i = 0; i < nc; ++i) if (recs[0].cols[i].type == T_UTF8) utf8_cols.push_back((int)i);
-    PhaseTimer pt("device_concat_path");
-    const std::vector<std::vector<int64_t>> ubytes = device_utf8_bytes(ctx, recs, utf8_cols);
-    pt.mark("utf8_sizes");
-    std::vector<size_t> cuts{0};
-    {
-      std::vector<int64_t> bytes(utf8_cols.size(), 0);
-      int64_t rows = 0;
-      for (size_t b = 0; b < nb; ++b) {
-        bool over = rows + recs[b].nrows > (1ll << 30);
-        for (size_t k = 0; k < utf8_cols.size(); ++k) over |= bytes[k] + ubytes[k][b] > ctx.opt_group_chunk_bytes;
-        if (over && b > cuts.back()) { cuts.push_back(b); std::fill(bytes.begin(), bytes.end(), 0); rows = 0; }
-        for (size_t k = 0; k < utf8_cols.size(); ++k) bytes[k] += ubytes[k][b];
-        rows += recs[b].nrows;
-      }
-      cuts.push_back(nb);
-    }
-    if (co && cuts.size() > 2) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "offset overflow: the joined Utf8 output of this group does not fit int32 offsets; use chq_filter_records"};
-    std::vector<Batch> outs;
-    if (!co) outs.reserve(nb);
-    chq_call_stats acc{};
-    for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-      const size_t b0 = cuts[k], b1 = cuts[k + 1];
-      // (a chunk of one batch -- e.g. a 2 GB Utf8 column on its own -- is filtered in place: nothing to join)
-      Batch cat = b1 - b0 == 1 ? to_device(ctx, recs[b0]) : concat_device_batches(ctx, recs, b0, b1, utf8_cols, ubytes);
-      pt.mark("join_launch");
-      SplitRequest split;
-      int64_t at = 0;
-      for (size_t b = b0; b < b1; ++b) { split.starts.push_back(at); at += recs[b].nrows; }
-      split.starts.push_back(at);
-      Batch res = filter_record(ctx, cat, plan_columns(cat, aliases), expr, &split);
-      pt.mark("filter_record");
-      add_stats(acc, ctx.stats);
-      if (co) {
-        for (size_t b = b0; b < b1; ++b) co->rows.push_back(split.bounds[b - b0 + 1] - split.bounds[b - b0]);
-        co->out = out_on_device ? std::move(res) : to_host(ctx, res);
-        co->done = true;
-        continue;
-      }
-      Batch whole = out_on_device ? std::move(res) : to_host(ctx, res);
-      for (size_t b = b0; b < b1; ++b) {
-        const int64_t begin = split.bounds[b - b0], end = split.bounds[b - b0 + 1];
-        Batch o;
-        o.on_device = out_on_device; o.device_id = out_on_device ? ctx.device : -1; o.nrows = end - begin;
-        o.cols.reserve(whole.cols.size());
-        for (const Column& c : whole.cols) {
-          Column sc = c;   // shares the result buffers
-          sc.offset = c.offset + begin; sc.length = end - begin;
-          if (sc.validity) {
-            if (out_on_device) sc.null_count = -1;   // unknown for the slice (Arrow C Data Interface: -1)
-            else { sc.null_count = count_nulls_host(sc.validity, sc.offset, sc.length); if (sc.null_count == 0) sc.validity = nullptr; }
-          } else sc.null_count = 0;
-          o.cols.push_back(std::move(sc));
-        }
-        outs.push_back(std::move(o));
-      }
-    }
-    ctx.stats = acc;
-    return outs;
-  };
+// One group call.  `coalesce`: the caller wants ONE output batch (chq_filter_records_coalesced) -- the device join then
+// declines a group it would have to cut, and the one-launch path does not split into short-string sub-groups.
+struct GroupCall {
+  Context& ctx;
+  const GroupInput& gi;
+  const chq_table_aliases* aliases;
+  const Expr& expr;
+  bool out_on_device, coalesce;
+  const std::vector<Batch>& recs;   // (batch 0 is always there; the others after need_batches() when `lite` is set)
+  const GroupLite* lite;
+  size_t nb;
+  // a sub-group (the uniform-length rewrite, the short-string split) carries its head batch only: the paths that read Batch
+  // objects decline it -- no parts, no per-batch results -- and the caller goes on with the whole group
+  bool sub_group;
 
-  // ---- eligibility -----------------------------------------------------------------------------------
-  PhaseTimer pt("filter_records (one-launch path)");
-  const size_t ncols = recs[0].cols.size();
-  if (ncols == 0) return per_batch_loop();
-  bool plain = (int)ncols <= MAX_OUT, same_schema = true, all_host = !recs[0].on_device;
-  // `foldable`: device-resident, non-null, fixed-width or Utf8 columns -- short-string Utf8 columns can then be filtered
-  // straight out of the batches by the one-launch path (their offsets and bytes per batch ride in the group table)
-  bool foldable = (int)ncols <= MAX_OUT && ctx.opt_fold_utf8 && ctx.opt_group_fold;
-  bool has_bool = false, has_utf8 = false, need_bits = false;
-  for (size_t i = 0; i < ncols; ++i) { has_bool |= recs[0].cols[i].type == T_BOOL; has_utf8 |= recs[0].cols[i].type == T_UTF8; }
-  if (lite && recs[0].on_device) {
-    // device-resident group: the facts were gathered per batch at import (GroupLite) -- one pass over nb bytes
-    uint8_t any = 0, all = 0xff;
-    for (uint8_t f : lite->flags) { any |= f; all &= f; }
-    if (any & (GroupLite::GL_SHORT | GroupLite::GL_SCHEMA_DIFFERS)) { if (any & GroupLite::GL_SHORT) return per_batch_loop(); same_schema = false; }
-    all_host = false;
-    // validity bitmaps and Boolean columns ride along in the one-launch path when the group is wave-packed (decided below):
-    // their bitmaps are compacted by bit_compact_group_kernel behind the main kernel
-    need_bits = has_bool || (any & GroupLite::GL_NULLS);
-    const bool all_dev = all & GroupLite::GL_ON_DEVICE;
-    plain = plain && !has_utf8 && (!need_bits || (all_dev && ctx.opt_group_bits));
-    foldable = foldable && all_dev && !(any & GroupLite::GL_NO_UTF8_DATA) && (!need_bits || ctx.opt_group_bits);
-  } else {
-  need_batches();
-  for (const Batch& r : recs) {
-    if (r.cols.size() != ncols || r.nrows < 2) return per_batch_loop();
-    all_host &= !r.on_device;
-    foldable &= r.on_device && r.device_id == ctx.device;
-    for (size_t i = 0; i < ncols; ++i) {
-      const Column& c = r.cols[i];
-      same_schema &= c.type == recs[0].cols[i].type && c.width == recs[0].cols[i].width && c.format == recs[0].cols[i].format;
-      plain &= c.type != T_BOOL && c.type != T_UTF8 && !(c.validity && c.null_count != 0 && (r.on_device || c.null_count > 0 ||
-               count_nulls_host(c.validity, c.offset, c.length) != 0));
-      foldable &= c.type != T_BOOL && !(c.validity && c.null_count != 0) && (c.type != T_UTF8 || c.data != nullptr);
-    }
+  GroupCall(Context& c, const GroupInput& g, const chq_table_aliases* a, const Expr& e, bool dev, bool co)
+      : ctx(c), gi(g), aliases(a), expr(e), out_on_device(dev), coalesce(co), recs(*g.batches), lite(g.lite) {
+    if (lite && (lite->rows.empty() || recs.empty() || lite->ncols != recs[0].cols.size())) lite = nullptr;
+    if (!lite) need_batches();
+    nb = lite ? lite->rows.size() : recs.size();
+    sub_group = !gi.materialise && recs.size() < nb;
   }
-  }
-  if (!same_schema) return per_batch_loop();
-  std::vector<int> fold_utf8;                          // the Utf8 columns of a foldable group
-  std::vector<std::vector<int64_t>> fold_bytes;        // their data bytes per batch
-  std::vector<int64_t> fold_cap;
-  Utf8Sizes sizes_in_flight;
-  int64_t fold_rows_all = 0;
-  if (!plain && foldable) {
-    for (size_t i = 0; i < ncols; ++i) if (recs[0].cols[i].type == T_UTF8) fold_utf8.push_back((int)i);
-    if (lite) for (int64_t r : lite->rows) fold_rows_all += r; else for (const Batch& r : recs) fold_rows_all += r.nrows;
-    foldable = !fold_utf8.empty() && (int)fold_utf8.size() <= MAX_FOLD_UTF8 && fold_rows_all < (1ll << 31) - 64;
-    // the batches' string sizes are read back from the device: queued here, awaited only after the predicate has been
-    // typed and the group table built (`finish_fold_sizes` below)
-    if (foldable) sizes_in_flight = device_utf8_bytes_issue(ctx, recs, lite, fold_utf8);
-  }
-  bool fold = !plain && foldable;
-  bool sizes_done = false, sizes_ok = false;
-  auto finish_fold_sizes = [&]() -> bool {   // false: long strings, or more than one output column can address
-    if (sizes_done) return sizes_ok;
-    sizes_done = true;
-    fold_bytes = device_utf8_bytes_finish(ctx, sizes_in_flight);
-    bool ok = true;
-    for (const auto& per_batch : fold_bytes) {
-      int64_t cap = 0;
-      for (int64_t v : per_batch) cap += v;
-      fold_cap.push_back(cap);
-      // short strings that fit ONE output column (int32 offsets: 2 x group_chunk_bytes = 2 GiB unless a test lowers the option)
-      ok &= cap <= fold_rows_all * 24 && cap < 2 * ctx.opt_group_chunk_bytes - 64;
-    }
-    sizes_ok = ok;
-    return ok;
-  };
-  pt.mark("eligibility+utf8_sizes");
-  if (!plain && !fold) {
-    bool all_device = true;
-    for (const Batch& r : recs) all_device &= r.on_device && r.device_id == ctx.device;
-    const bool host_case = all_host && !out_on_device;
-    if (!host_case && !all_device) return per_batch_loop();
+  void need_batches() const { if (gi.materialise) gi.materialise(); }
+  GroupResult per_batch_loop() const;
+  GroupResult host_concat() const;
+  GroupResult device_concat() const;
+  // a concat path; a data-dependent error takes the per-batch loop, which reports the earliest failing batch's
+  GroupResult concat(bool host) const {
+    if (sub_group) return {};
     try {
-      TypedExpr probe = type_expr(expr, plan_columns(recs[0], aliases), recs[0].nrows, ctx.opt_enable_minus);
-      if (probe.pending_code || probe.at(probe.root).type != T_BOOL || probe.at(probe.root).len1) return per_batch_loop();
-    } catch (const ChqError&) {
-      return per_batch_loop();   // reports the first batch's (static) error
-    }
-    try {
-      return host_case ? host_concat_path() : device_concat_path();
-    } catch (const ChqError& e) {
-      if (e.code == CHQ_ERR_OUT_OF_MEMORY || e.code == CHQ_ERR_DEVICE) throw;
-      return per_batch_loop();   // a data-dependent error: the loop reports the earliest failing batch's
-    }
-  }
-  // a foldable group that turns out not to fit the one-launch path is joined on the device instead
-  auto other_path = [&]() -> std::vector<Batch> {
-    if (!sizes_in_flight.cols.empty()) check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");   // (the size gather reads back into pinned memory the next call reuses)
-    if (!fold) return per_batch_loop();
-    try {
-      return device_concat_path();
+      return host ? host_concat() : device_concat();
     } catch (const ChqError& e) {
       if (e.code == CHQ_ERR_OUT_OF_MEMORY || e.code == CHQ_ERR_DEVICE) throw;
       return per_batch_loop();
     }
-  };
-  int64_t total_rows = 0, max_rows = 0;
-  const bool host_in = !recs[0].on_device;
-  if (lite && !host_in) {   // (everything this loop checks per batch is in the flags reduced above)
-    for (int64_t r : lite->rows) { total_rows += r; max_rows = std::max(max_rows, r); }
-    bool all_dev = true;
-    for (uint8_t f : lite->flags) all_dev &= (f & GroupLite::GL_ON_DEVICE) != 0;
-    if (!all_dev || (has_utf8 && !fold) || !(plain || fold)) return per_batch_loop();
-  } else
-  for (const Batch& r : recs) {
-    if (r.cols.size() != ncols || r.nrows < 2 || r.on_device == host_in) return per_batch_loop();
-    for (size_t i = 0; i < ncols; ++i) {
-      const Column& c = r.cols[i];
-      if (c.type == T_BOOL || (c.type == T_UTF8 && !fold) || c.type != recs[0].cols[i].type || c.width != recs[0].cols[i].width) return per_batch_loop();
-      if (c.validity && c.null_count != 0) {
-        if (r.on_device || c.null_count > 0) return per_batch_loop();
-        if (count_nulls_host(c.validity, c.offset, c.length) != 0) return per_batch_loop();
-      }
-    }
-    total_rows += r.nrows; max_rows = std::max(max_rows, r.nrows);
   }
-  const std::vector<PlanColumn> pcols = plan_columns(recs[0], aliases);
-  TypedExpr te = type_expr(expr, pcols, recs[0].nrows, ctx.opt_enable_minus);
-  if (te.pending_code) return per_batch_loop();
-  const Node& root = te.at(te.root);
-  if (root.type != T_BOOL || root.len1) return per_batch_loop();
-  Lowered lw;
-  try {
-    lower_expr(te, te.root, pcols, lw);
-  } catch (const ChqError& e) {
-    if (e.code != CHQ_INTERNAL_PROGRAM_LIMIT) throw;
-    return per_batch_loop();   // oversized predicate: every batch materialises its own temporaries
-  }
-  if (!lw.strs.empty()) return other_path();
-  // ---- a device group whose string columns all hold values of ONE length (the reference's sample strings, keys, hashes):
-  // fixed-width columns in disguise, as in filter_record -- one pass over every batch's offsets proves it, then the group
-  // runs as a PLAIN group (value pointer of batch b = its data + its first offset) and the joined output gets the offsets
-  // 0, L, 2 L, ...; per-batch results are Arrow slices of that column as before.
-  if (fold && lite && !host_in && (sliced || co) && ctx.opt_uniform_utf8_rows > 0 && total_rows >= ctx.opt_uniform_utf8_rows) {
-    bool pred_reads_utf8 = false;
-    for (int r : lw.refs) pred_reads_utf8 |= recs[0].cols[(size_t)r].type == T_UTF8;
-    // a Utf8 column with a bitmap in any batch keeps the string path, as in filter_record: the conversion below zeroes the
-    // Arrow offset the bitmap is read at, and the coalesced form rebuilds the column without its validity
-    bool utf8_bitmap = false;
-    for (int i : fold_utf8)
-      for (size_t b = 0; b < nb && !utf8_bitmap; ++b) utf8_bitmap = lite->validity[b * ncols + (size_t)i] != nullptr;
-    // (a group whose joined strings do not fit ONE output column is cut into sub-groups first: each comes back here)
-    if (!pred_reads_utf8 && !utf8_bitmap && finish_fold_sizes()) {
-      const size_t nu = fold_utf8.size();
-      std::vector<unsigned long long> h_in((nu + 1) * nb);
-      for (size_t b = 0; b < nb; ++b) h_in[b] = (unsigned long long)lite->rows[b];
-      for (size_t k = 0; k < nu; ++k)
-        for (size_t b = 0; b < nb; ++b) h_in[(k + 1) * nb + b] = (unsigned long long)(uintptr_t)lite->values0[b * ncols + (size_t)fold_utf8[k]];
-      auto d_in = make_device_buffer(h_in.size() * 8 + 16, ctx.device);
-      auto d_out = make_device_buffer(nu * nb * 12 + 16, ctx.device);
-      check_hip(hipMemcpyAsync(d_in->ptr, h_in.data(), h_in.size() * 8, hipMemcpyHostToDevice, ctx.stream), "upload offsets table");
-      check_hip(hipMemsetAsync(d_out->ptr, 0, nu * nb * 12, ctx.stream), "memset");
-      for (size_t k = 0; k < nu; ++k) {
-        Utf8UniformGroupParams up{(const unsigned long long*)d_in->ptr + (k + 1) * nb, (const long long*)d_in->ptr, (int64_t)nb, (int32_t*)d_out->ptr + 3 * k * nb};
-        check_hip(launch_utf8_uniform_group(up, max_rows, ctx.stream), "launch utf8_uniform_group_kernel");
-      }
-      std::vector<int32_t> h_out(nu * nb * 3);
-      check_hip(hipMemcpyAsync(h_out.data(), d_out->ptr, h_out.size() * 4, hipMemcpyDeviceToHost, ctx.stream), "read back");
-      check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-      bool uniform = true;
-      std::vector<int32_t> len_of(nu, 0);
-      for (size_t k = 0; k < nu && uniform; ++k) {
-        len_of[k] = h_out[3 * k * nb + 1];
-        const int32_t L = len_of[k];
-        uniform = (L == 1 || L == 2 || L == 4 || L == 8 || L == 16) && total_rows * (int64_t)L < (1ll << 31) - 64;
-        for (size_t b = 0; b < nb && uniform; ++b) {
-          const int32_t* o = &h_out[3 * (k * nb + b)];
-          uniform = !o[0] && o[1] == L && o[2] >= 0 && lite->data[b * ncols + (size_t)fold_utf8[k]] != nullptr;
-        }
-      }
-      if (uniform) {
-        GroupLite sub = *lite;
-        std::vector<Batch> head(1);
-        head[0] = recs[0];
-        for (size_t k = 0; k < nu; ++k) {
-          const size_t i = (size_t)fold_utf8[k];
-          for (size_t b = 0; b < nb; ++b) {
-            sub.values0[b * ncols + i] = lite->data[b * ncols + i] + h_out[3 * (k * nb + b) + 2];
-            sub.data[b * ncols + i] = nullptr;
-            sub.offset[b * ncols + i] = 0;
-          }
-          Column& c = head[0].cols[i];
-          c.owned.clear();
-          c.type = T_FIXED_OPAQUE; c.format = "w:" + std::to_string(len_of[k]); c.width = len_of[k];
-          c.values = sub.values0[i]; c.data = nullptr; c.data_bytes = -1; c.offset = 0;
-        }
-        for (uint8_t& f : sub.flags) f &= (uint8_t)~GroupLite::GL_NO_UTF8_DATA;
-        GroupInput sgi; sgi.batches = &head; sgi.lite = &sub;
-        // offsets 0, L, 2 L, ... for `n` values, where the results live
-        auto iota = [&](int64_t n, int32_t L) -> BufferPtr {
-          if (out_on_device) {
-            auto ob = make_device_buffer((size_t)(n + 1) * 4 + 16, ctx.device);
-            IotaOffsetsParams ip{(int32_t*)ob->ptr, n + 1, L, 0};
-            check_hip(launch_iota_offsets(ip, ctx.stream), "launch iota_offsets_kernel");
-            return ob;
-          }
-          auto ob = make_host_buffer((size_t)(n + 1) * 4 + 16);
-          int32_t* o = (int32_t*)ob->ptr;
-          for (int64_t r = 0; r <= n; ++r) o[r] = (int32_t)(r * L);
-          return ob;
-        };
-        if (sliced) {
-          GroupSliced part;
-          (void)filter_records_impl(ctx, sgi, aliases, expr, out_on_device, nullptr, &part);
-          if (part.filled) {
-            std::vector<GroupSliced*> all{&part};
-            for (GroupSliced& m : part.more) all.push_back(&m);
-            for (GroupSliced* g : all) {
-              const int64_t n_out = g->ends.empty() ? 0 : g->ends.back();
-              for (size_t k = 0; k < nu; ++k) {
-                const size_t i = (size_t)fold_utf8[k];
-                g->proto[i] = empty_like(recs[0].cols[i]);
-                g->data[i] = g->values[i];
-                g->values[i] = iota(n_out, len_of[k]);
-              }
-              ctx.stats.bytes_written_alg += (n_out + 1) * 4 * (int64_t)nu;
-            }
-            if (out_on_device) check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-            ctx.stats.bytes_read_alg += (total_rows + (int64_t)nb) * 4 * (int64_t)nu;
-            *sliced = std::move(part);
-            return {};
-          }
-        } else {
-          Coalesced part;
-          (void)filter_records_impl(ctx, sgi, aliases, expr, out_on_device, &part, nullptr);
-          if (part.done) {
-            for (size_t k = 0; k < nu; ++k) {
-              const size_t i = (size_t)fold_utf8[k];
-              Column& o = part.out.cols[i];
-              Column u = empty_like(recs[0].cols[i]);
-              u.length = part.out.nrows; u.null_count = 0; u.offset = 0;
-              u.data = o.values; u.data_bytes = part.out.nrows * (int64_t)len_of[k];
-              BufferPtr ob = iota(part.out.nrows, len_of[k]);
-              u.values = (const uint8_t*)ob->ptr;
-              u.owned = std::move(o.owned); u.owned.push_back(ob);
-              o = std::move(u);
-            }
-            if (out_on_device) check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-            ctx.stats.bytes_read_alg += (total_rows + (int64_t)nb) * 4 * (int64_t)nu;
-            *co = std::move(part);
-            return {};
-          }
-        }
-        // (the plain path declined -- e.g. a data-dependent error that the per-batch loop must attribute: go on as before)
-      }
-    }
-  }
-  if (fold) {   // the predicate itself must not read a string column, and the wide / temporaries instantiation has no Utf8 form
-    for (int r : lw.refs) if (recs[0].cols[(size_t)r].type == T_UTF8) return other_path();
-    if (lw.wide || lw.num_temps > 0) return other_path();
-  }
+};
 
+GroupResult GroupCall::per_batch_loop() const {
+  if (sub_group) return {};
+  need_batches();
+  GroupResult r;
+  chq_call_stats acc{};
+  for (const Batch& rb : recs) {
+    Batch dev = to_device(ctx, rb);
+    Batch o = filter_record(ctx, dev, plan_columns(dev, aliases), expr);
+    add_stats(acc, ctx.stats);
+    r.per_batch.push_back(out_on_device ? std::move(o) : to_host(ctx, o));
+  }
+  ctx.stats = acc;
+  return r;
+}
+
+// ---- host batches with Utf8 / Boolean / nullable columns: concatenated on the host while staging, filtered as ONE batch
+// (every column kind is supported there), copied back once.  Chunks keep every Utf8 column below 1 GiB of bytes.
+GroupResult GroupCall::host_concat() const {
+  need_batches();
+  std::vector<std::vector<int64_t>> bytes;
+  for (size_t i = 0; i < recs[0].cols.size(); ++i) {
+    if (recs[0].cols[i].type != T_UTF8) continue;
+    bytes.emplace_back(nb, 0);
+    for (size_t b = 0; b < nb; ++b) {
+      const Column& c = recs[b].cols[i];
+      if (c.values && c.length) { const int32_t* o = (const int32_t*)c.values + c.offset; bytes.back()[b] = (int64_t)o[c.length] - o[0]; }
+    }
+  }
+  const std::vector<size_t> cuts = chunk_cuts(rows_of(recs), bytes, ctx.opt_group_chunk_bytes);
+  GroupResult r;
+  chq_call_stats acc{};
+  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+    Batch dev = to_device(ctx, concat_host_batches(recs, cuts[k], cuts[k + 1]));
+    r.parts.push_back(filter_joined(ctx, dev, recs, cuts[k], cuts[k + 1], aliases, expr, out_on_device));
+    add_stats(acc, ctx.stats);
+  }
+  ctx.stats = acc;
+  return r;
+}
+
+// ---- device-resident batches with Utf8 / Boolean / nullable columns (the reference's own schema is Int32, Utf8, Float32:
+// create_sample_data.rs:157-204): joined on the device by the concat kernels, filtered as ONE batch by the ordinary kernels.
+// Chunks keep every Utf8 column below the int32 offset range.
+GroupResult GroupCall::device_concat() const {
+  need_batches();
+  std::vector<int> utf8_cols;
+  for (size_t i = 0; i < recs[0].cols.size(); ++i) if (recs[0].cols[i].type == T_UTF8) utf8_cols.push_back((int)i);
+  PhaseTimer pt("device_concat_path");
+  const std::vector<std::vector<int64_t>> ubytes = device_utf8_bytes(ctx, recs, utf8_cols);
+  pt.mark("utf8_sizes");
+  const std::vector<size_t> cuts = chunk_cuts(rows_of(recs), ubytes, ctx.opt_group_chunk_bytes);
+  if (coalesce && cuts.size() > 2) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "offset overflow: the joined Utf8 output of this group does not fit int32 offsets; use chq_filter_records"};
+  GroupResult r;
+  chq_call_stats acc{};
+  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+    const size_t b0 = cuts[k], b1 = cuts[k + 1];
+    // (a chunk of one batch -- e.g. a 2 GB Utf8 column on its own -- is filtered in place: nothing to join)
+    Batch cat = b1 - b0 == 1 ? to_device(ctx, recs[b0]) : concat_device_batches(ctx, recs, b0, b1, utf8_cols, ubytes);
+    pt.mark("join_launch");
+    r.parts.push_back(filter_joined(ctx, cat, recs, b0, b1, aliases, expr, out_on_device));
+    pt.mark("filter_record");
+    add_stats(acc, ctx.stats);
+  }
+  ctx.stats = acc;
+  return r;
+}
+
+GroupResult filter_group(Context& ctx, const GroupInput& gi, const chq_table_aliases* aliases, const Expr& expr,
+                         bool out_on_device, bool coalesce);
+
+// ---- stage 1: eligibility -- one scan of the batches ---------------------------------------------------------------------
+struct GroupPlan {
+  bool per_batch = false;    // a batch of fewer than 2 rows, or another schema: the per-batch loop
+  bool plain = false;        // fixed-width columns without nulls (wave-packed device groups: bitmaps too): the one-launch path
+  bool fold = false;         // device-resident short-string Utf8 columns (`fold_utf8`): filtered straight out of the batches
+  bool need_bits = false;    // validity bitmaps / Boolean columns ride along (compacted behind the main kernel)
+  bool host_in = false, all_host = false;
+  bool all_device = false;   // every batch in this GPU's memory
+  bool resident = false;     // every batch where batch 0 is (a device group described by `lite`: in this GPU's memory)
+  int64_t total_rows = 0, max_rows = 0;
+  std::vector<int> fold_utf8;
+};
+
+GroupPlan plan_group(const GroupCall& g) {
+  const Context& ctx = g.ctx;
+  const std::vector<Batch>& recs = g.recs;
+  const size_t ncols = recs[0].cols.size();
+  GroupPlan pl;
+  pl.host_in = pl.all_host = !recs[0].on_device;
+  bool plain = (int)ncols <= MAX_OUT, same_schema = true;
+  // `foldable`: device-resident, non-null, fixed-width or Utf8 columns -- short-string Utf8 columns can then be filtered
+  // straight out of the batches by the one-launch path (their offsets and bytes per batch ride in the group table)
+  bool foldable = (int)ncols <= MAX_OUT && ctx.opt_fold_utf8 && ctx.opt_group_fold;
+  bool has_bool = false, has_utf8 = false;
+  for (const Column& c : recs[0].cols) { has_bool |= c.type == T_BOOL; has_utf8 |= c.type == T_UTF8; }
+  if (g.lite && !pl.host_in) {
+    // device-resident group: the facts were gathered per batch at import (GroupLite) -- one pass over nb bytes
+    uint8_t any = 0, all = 0xff;
+    for (uint8_t f : g.lite->flags) { any |= f; all &= f; }
+    if (any & (GroupLite::GL_SHORT | GroupLite::GL_SCHEMA_DIFFERS)) { pl.per_batch = true; return pl; }
+    pl.all_host = false;
+    pl.all_device = pl.resident = (all & GroupLite::GL_ON_DEVICE) != 0;
+    // validity bitmaps and Boolean columns ride along in the one-launch path when the group is wave-packed (decided with
+    // the table): their bitmaps are compacted by bit_compact_group_kernel behind the main kernel
+    pl.need_bits = has_bool || (any & GroupLite::GL_NULLS);
+    plain = plain && !has_utf8 && (!pl.need_bits || (pl.all_device && ctx.opt_group_bits));
+    foldable = foldable && pl.all_device && !(any & GroupLite::GL_NO_UTF8_DATA) && (!pl.need_bits || ctx.opt_group_bits);
+    for (int64_t r : g.lite->rows) { pl.total_rows += r; pl.max_rows = std::max(pl.max_rows, r); }
+  } else {
+    g.need_batches();
+    pl.all_device = pl.resident = true;
+    for (const Batch& r : recs) {
+      if (r.cols.size() != ncols || r.nrows < 2) { pl.per_batch = true; return pl; }
+      pl.all_host &= !r.on_device;
+      pl.all_device &= r.on_device && r.device_id == ctx.device;
+      pl.resident &= r.on_device != pl.host_in;
+      for (size_t i = 0; i < ncols; ++i) {
+        const Column& c = r.cols[i];
+        same_schema &= c.type == recs[0].cols[i].type && c.width == recs[0].cols[i].width && c.format == recs[0].cols[i].format;
+        plain &= c.type != T_BOOL && c.type != T_UTF8 && !(c.validity && c.null_count != 0 && (r.on_device || c.null_count > 0 ||
+                 count_nulls_host(c.validity, c.offset, c.length) != 0));
+        foldable &= c.type != T_BOOL && !(c.validity && c.null_count != 0) && (c.type != T_UTF8 || c.data != nullptr);
+      }
+      pl.total_rows += r.nrows; pl.max_rows = std::max(pl.max_rows, r.nrows);
+    }
+    foldable &= pl.all_device;
+  }
+  if (!same_schema) { pl.per_batch = true; return pl; }
+  pl.plain = plain;
+  if (!plain && foldable) {
+    for (size_t i = 0; i < ncols; ++i) if (recs[0].cols[i].type == T_UTF8) pl.fold_utf8.push_back((int)i);
+    pl.fold = !pl.fold_utf8.empty() && (int)pl.fold_utf8.size() <= MAX_FOLD_UTF8 && pl.total_rows < (1ll << 31) - 64;
+    if (!pl.fold) pl.fold_utf8.clear();
+  }
+  return pl;
+}
+
+// ---- stage 2: a device group whose string columns all hold values of ONE length (the reference's sample strings, keys,
+// hashes): fixed-width columns in disguise, as in filter_record -- one pass over every batch's offsets proves it, the group
+// runs as a PLAIN group (value pointer of batch b = its data + its first offset) and every joined part gets back its Utf8
+// columns (uniform_to_utf8).  False: a column does not qualify, or the plain group declined (e.g. a data-dependent error
+// that the per-batch loop must attribute) -- the caller goes on as before.  `sizes_fit`: the fold's size check.
+bool uniform_group(const GroupCall& g, const GroupPlan& pl, const std::function<bool()>& sizes_fit, GroupResult* out) {
+  Context& ctx = g.ctx;
+  const GroupLite& lite = *g.lite;
+  const size_t nb = g.nb, ncols = lite.ncols, nu = pl.fold_utf8.size();
+  for (int i : pl.fold_utf8) {
+    bool bitmap = false;
+    for (size_t b = 0; b < nb && !bitmap; ++b) bitmap = lite.validity[b * ncols + (size_t)i] != nullptr;
+    if (!uniform_utf8_ok(bitmap, pl.total_rows, 1)) return false;
+  }
+  // (a group whose joined strings do not fit ONE output column is cut into sub-groups first: each comes back here)
+  if (!sizes_fit()) return false;
+  std::vector<unsigned long long> h_in((nu + 1) * nb);
+  for (size_t b = 0; b < nb; ++b) h_in[b] = (unsigned long long)lite.rows[b];
+  for (size_t k = 0; k < nu; ++k)
+    for (size_t b = 0; b < nb; ++b) h_in[(k + 1) * nb + b] = (unsigned long long)(uintptr_t)lite.values0[b * ncols + (size_t)pl.fold_utf8[k]];
+  auto d_in = make_device_buffer(h_in.size() * 8 + 16, ctx.device);
+  auto d_out = make_device_buffer(nu * nb * 12 + 16, ctx.device);
+  check_hip(hipMemcpyAsync(d_in->ptr, h_in.data(), h_in.size() * 8, hipMemcpyHostToDevice, ctx.stream), "upload offsets table");
+  check_hip(hipMemsetAsync(d_out->ptr, 0, nu * nb * 12, ctx.stream), "memset");
+  for (size_t k = 0; k < nu; ++k) {
+    Utf8UniformGroupParams up{(const unsigned long long*)d_in->ptr + (k + 1) * nb, (const long long*)d_in->ptr, (int64_t)nb, (int32_t*)d_out->ptr + 3 * k * nb};
+    check_hip(launch_utf8_uniform_group(up, pl.max_rows, ctx.stream), "launch utf8_uniform_group_kernel");
+  }
+  std::vector<int32_t> h_out(nu * nb * 3);
+  check_hip(hipMemcpyAsync(h_out.data(), d_out->ptr, h_out.size() * 4, hipMemcpyDeviceToHost, ctx.stream), "read back");
+  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  GroupLite sub = lite;
+  Batch first = g.recs[0];
+  for (size_t k = 0; k < nu; ++k) {
+    const size_t i = (size_t)pl.fold_utf8[k];
+    const int32_t L = h_out[3 * k * nb + 1];
+    if (!uniform_utf8_ok(false, pl.total_rows, L)) return false;
+    for (size_t b = 0; b < nb; ++b) {
+      const int32_t* o = &h_out[3 * (k * nb + b)];
+      if (o[0] || o[1] != L || o[2] < 0 || lite.data[b * ncols + i] == nullptr) return false;
+      sub.values0[b * ncols + i] = lite.data[b * ncols + i] + o[2];
+      sub.data[b * ncols + i] = nullptr;
+      sub.offset[b * ncols + i] = 0;
+    }
+    Column& c = first.cols[i];
+    c.type = T_FIXED_OPAQUE; c.format = "w:" + std::to_string(L); c.width = L;
+  }
+  for (uint8_t& f : sub.flags) f &= (uint8_t)~GroupLite::GL_NO_UTF8_DATA;
+  std::vector<Batch> head{lite_head(first, sub, 0)};
+  GroupInput sgi; sgi.batches = &head; sgi.lite = &sub;
+  GroupResult r = filter_group(ctx, sgi, g.aliases, g.expr, g.out_on_device, g.coalesce);
+  if (r.parts.empty() || r.batches() != nb) return false;
+  for (JoinedGroup& part : r.parts)
+    for (int i : pl.fold_utf8) {
+      Column& c = part.joined.cols[(size_t)i];
+      c = uniform_to_utf8(ctx, std::move(c), g.recs[0].cols[(size_t)i], part.joined.nrows, g.out_on_device);
+    }
+  if (g.out_on_device) check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  ctx.stats.bytes_read_alg += (pl.total_rows + (int64_t)nb) * 4 * (int64_t)nu;
+  *out = std::move(r);
+  return true;
+}
+
+// ---- stage 3: the group table --------------------------------------------------------------------------------------------
+struct BitCol { int col; bool validity; size_t word; };   // word: index of {bitmap, bit offset} in a batch's table row
+struct GroupTable {
+  std::vector<BufferPtr> staged;   // host groups: every column packed and uploaded
+  Batch proto;                     // batch 0 with every column that has nulls in ANY batch marked nullable
+  std::vector<BitCol> bit_cols;
+  std::vector<int> launch_cols;
+  FilterParams p{};
+  int tile_kind = 0;
+  int64_t wpb = 0, ntiles = 0;     // wpb > 0: wave-granular mode
+  size_t stride = 0, bits_at = 0, bytes_tbl = 0, bytes_idx = 0, bytes_cnt = 0;
+};
+constexpr int64_t kWaveRows[3] = {64 * 16, 64 * 8, 64 * 8};
+constexpr int64_t kWavesPerTile[3] = {16, 4, 4};
+
+// input pointers, tiling and the table (in ctx.pinned_tbl); false: the group does not fit the one-launch path after all
+bool build_group_table(const GroupCall& g, const GroupPlan& pl, const Lowered& lw, GroupTable& t) {
+  Context& ctx = g.ctx;
+  const std::vector<Batch>& recs = g.recs;
+  const GroupLite* lite = g.lite;
+  const size_t nb = g.nb, ncols = recs[0].cols.size();
+  const int64_t total_rows = pl.total_rows;
   ctx.stats = chq_call_stats{};
   ctx.stats.rows_in = total_rows;
-  pt.mark("typing");
 
   // ---- inputs: device pointers per batch and column ------------------------------------------------------
   // host batches are packed column-wise into one staging block per column and uploaded with one copy each
-  std::vector<BufferPtr> staged;
   struct PtrTable {   // [batch][column], flat: one allocation for 10^5 batches
     std::vector<const uint8_t*> v; size_t ncols;
     const uint8_t** operator[](size_t b) { return v.data() + b * ncols; }
   } in_ptr{std::vector<const uint8_t*>(nb * ncols), ncols};
-  if (host_in) {
+  if (pl.host_in) {
     for (size_t i = 0; i < ncols; ++i) {
       const int64_t w = recs[0].cols[i].width;
       auto pack = make_host_buffer((size_t)(total_rows * w) + 16);   // recycled block: no page faults
@@ -2389,7 +2299,7 @@ std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const
         for (size_t b = k0; b < k1; ++b) memcpy((uint8_t*)pack->ptr + at[b], recs[b].cols[i].values0(), (size_t)(recs[b].nrows * w));
       });
       check_hip(hipMemcpyAsync(db->ptr, pack->ptr, (size_t)at[nb], hipMemcpyHostToDevice, ctx.stream), "upload packed column");
-      staged.push_back(db); staged.push_back(pack);
+      t.staged.push_back(db); t.staged.push_back(pack);
     }
     check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
   } else if (lite) {
@@ -2402,179 +2312,118 @@ std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const
   // ---- tiling ------------------------------------------------------------------------------------------------
   // Wave-granular packing when the batches are near-uniform (every batch gets the wave count of the longest one and
   // at most a fifth of the waves idle); otherwise whole tiles per batch, described by a per-tile table.
-  constexpr int64_t kWaveRows[3] = {64 * 16, 64 * 8, 64 * 8};
-  constexpr int64_t kWavesPerTile[3] = {16, 4, 4};
   int tile_kind;
-  int64_t wpb = 0;   // > 0: wave-granular mode
   if (lw.wide || lw.num_temps > 0) tile_kind = 2;
   else if (ctx.opt_tile_kind >= 0) tile_kind = (int)ctx.opt_tile_kind;
   else tile_kind = -1;
   {
     const int k = tile_kind < 0 ? 0 : tile_kind;
-    const int64_t w = (max_rows + kWaveRows[k] - 1) / kWaveRows[k];
+    const int64_t w = (pl.max_rows + kWaveRows[k] - 1) / kWaveRows[k];
     if (ctx.opt_group_mode != 1 && w * (int64_t)nb * kWaveRows[k] * 4 <= total_rows * 5 && w * (int64_t)nb < (1ll << 31) - 64) {
-      wpb = w; tile_kind = k;
+      t.wpb = w; tile_kind = k;
     } else if (ctx.opt_group_mode == 2) {
-      wpb = w; tile_kind = k;
+      t.wpb = w; tile_kind = k;
     }
   }
+  auto rows_of_batch = [&](size_t b) { return lite ? lite->rows[b] : recs[b].nrows; };
   if (tile_kind < 0) {   // the large tile unless padding every batch to a multiple of it idles more than a quarter of the lanes
     int64_t padded = 0;
-    for (size_t b = 0; b < nb; ++b) { const int64_t r = lite ? lite->rows[b] : recs[b].nrows; padded += (r + kTileRows[0] - 1) / kTileRows[0] * kTileRows[0]; }
+    for (size_t b = 0; b < nb; ++b) padded += (rows_of_batch(b) + kTileRows[0] - 1) / kTileRows[0] * kTileRows[0];
     tile_kind = padded * 4 <= total_rows * 5 ? 0 : 1;
   }
-  const int64_t tile_rows = kTileRows[tile_kind];
-  int64_t ntiles = 0;
-  if (wpb > 0) ntiles = (wpb * (int64_t)nb + kWavesPerTile[tile_kind] - 1) / kWavesPerTile[tile_kind];
-  else for (size_t b = 0; b < nb; ++b) ntiles += ((lite ? lite->rows[b] : recs[b].nrows) + tile_rows - 1) / tile_rows;
-  ensure_scratch(ctx, ntiles);
-  Scratch* ds = dev_scratch(ctx);
+  t.tile_kind = tile_kind;
+  const int64_t tile_rows = kTileRows[tile_kind], wpb = t.wpb;
+  if (wpb > 0) t.ntiles = (wpb * (int64_t)nb + kWavesPerTile[tile_kind] - 1) / kWavesPerTile[tile_kind];
+  else for (size_t b = 0; b < nb; ++b) t.ntiles += (rows_of_batch(b) + tile_rows - 1) / tile_rows;
+  ensure_scratch(ctx, t.ntiles);
 
   // ---- bitmaps (validity of any column, values of Boolean columns): wave-packed groups only --------------------------
-  // `proto` = batch 0 with every column that has nulls in ANY batch marked nullable: the program is lowered / pre-decoded
-  // against it (a ref that may be null must take the generic interpreter even if batch 0 happens to be null-free)
-  Batch proto = recs[0];
-  std::vector<char> col_nulls(ncols, 0);
-  struct BitCol { int col; bool validity; size_t word; };   // word: index of {bitmap, bit offset} in a batch's table row
-  std::vector<BitCol> bit_cols;
-  if (need_bits) {
-    if (wpb == 0) return other_path();   // ragged group: joined on the device
+  // `proto`: the program is lowered / pre-decoded against it (a ref that may be null must take the generic interpreter
+  // even if batch 0 happens to be null-free)
+  t.proto = recs[0];
+  if (pl.need_bits) {
+    if (wpb == 0) return false;   // ragged group: joined on the device
     // (the bitmaps' addresses and offsets come from the flat per-batch arrays: no Batch objects, as in the null-free case)
+    std::vector<char> col_nulls(ncols, 0);
     for (size_t b = 0; b < nb; ++b) {
       if (!(lite->flags[b] & GroupLite::GL_NULLS)) continue;
       for (size_t i = 0; i < ncols; ++i) if (lite->validity[b * ncols + i]) col_nulls[i] = 1;
     }
     for (size_t i = 0; i < ncols; ++i) {
-      if (col_nulls[i]) { proto.cols[i].validity = (const uint8_t*)proto.cols[i].values; proto.cols[i].null_count = 1; }   // (never read: a marker)
-      else { proto.cols[i].validity = nullptr; proto.cols[i].null_count = 0; }
-      if (recs[0].cols[i].type == T_BOOL) bit_cols.push_back(BitCol{(int)i, false, 0});
-      if (col_nulls[i]) bit_cols.push_back(BitCol{(int)i, true, 0});
+      Column& pc = t.proto.cols[i];
+      if (col_nulls[i]) { pc.validity = (const uint8_t*)pc.values; pc.null_count = 1; }   // (never read: a marker)
+      else { pc.validity = nullptr; pc.null_count = 0; }
+      if (recs[0].cols[i].type == T_BOOL) t.bit_cols.push_back(BitCol{(int)i, false, 0});
+      if (col_nulls[i]) t.bit_cols.push_back(BitCol{(int)i, true, 0});
     }
-    if (bit_cols.size() > 16) return other_path();   // (one null counter each in the scratch header)
+    if (t.bit_cols.size() > 16) return false;   // (one null counter each in the scratch header)
   }
 
   // column order of the launch: the stashed predicate column goes last (see filter_record)
-  std::vector<int> launch_cols;
-  for (size_t i = 0; i < ncols; ++i) if (recs[0].cols[i].type != T_UTF8 && recs[0].cols[i].type != T_BOOL) launch_cols.push_back((int)i);
-  FilterParams p{};
-  pick_stash(p, ctx, lw, proto.cols, launch_cols, tile_kind);
-  const size_t nrefs = lw.refs.size(), nout = launch_cols.size(), nu = fold ? fold_utf8.size() : 0;
-  size_t stride = (wpb > 0 ? 1 : 2) + nrefs + nout + 2 * nu;   // per Utf8 column: the batch's offsets and bytes
-  const size_t bits_at = need_bits ? stride : 0;               // validity bitmap + bit offset of every program ref
-  if (need_bits) { stride += 2 * nrefs; for (BitCol& q : bit_cols) { q.word = stride; stride += 2; } }
-  if (fold && tile_kind == 2) return other_path();
+  for (size_t i = 0; i < ncols; ++i) if (recs[0].cols[i].type != T_UTF8 && recs[0].cols[i].type != T_BOOL) t.launch_cols.push_back((int)i);
+  pick_stash(t.p, ctx, lw, t.proto.cols, t.launch_cols, tile_kind);
+  const size_t nrefs = lw.refs.size(), nout = t.launch_cols.size(), nu = pl.fold_utf8.size();
+  t.stride = (wpb > 0 ? 1 : 2) + nrefs + nout + 2 * nu;   // per Utf8 column: the batch's offsets and bytes
+  t.bits_at = pl.need_bits ? t.stride : 0;               // validity bitmap + bit offset of every program ref
+  if (pl.need_bits) { t.stride += 2 * nrefs; for (BitCol& q : t.bit_cols) { q.word = t.stride; t.stride += 2; } }
+  if (pl.fold && tile_kind == 2) return false;
 
   // ---- table (+ index of every batch's last tile in tile mode): built in pinned memory, one upload ---------------
-  const size_t tbl_words = (wpb > 0 ? nb : (size_t)ntiles) * stride;
-  const size_t bytes_tbl = tbl_words * 8, bytes_idx = wpb > 0 ? 0 : nb * 8, bytes_cnt = nb * 8;
-  ensure_pinned_table(ctx, bytes_tbl + bytes_idx + bytes_cnt);
-  u64* h_tbl = (u64*)ctx.pinned_tbl;
-  int64_t* h_idx = (int64_t*)(h_tbl + tbl_words);
-  u64* h_cnt = (u64*)((uint8_t*)h_tbl + bytes_tbl + bytes_idx);
-  {
-    u64* w = h_tbl;
-    int64_t tile = 0;
-    auto utf8_data = [&](size_t b, size_t k) -> u64 {
-      return (u64)(uintptr_t)(lite ? lite->data[b * ncols + (size_t)fold_utf8[k]] : recs[b].cols[(size_t)fold_utf8[k]].data);
-    };
-    for (size_t b = 0; b < nb; ++b) {
-      const int64_t rows = lite ? lite->rows[b] : recs[b].nrows;
-      if (wpb > 0) {
-        *w++ = (u64)rows;
-        for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][lw.refs[k]];
-        for (size_t k = 0; k < nout; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][launch_cols[k]];
-        for (size_t k = 0; k < nu; ++k) { *w++ = (u64)(uintptr_t)in_ptr[b][fold_utf8[k]]; *w++ = utf8_data(b, k); }
-        if (need_bits) {
-          const size_t at = b * ncols;
-          for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)lite->validity[at + (size_t)lw.refs[k]];
-          for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)lite->offset[at + (size_t)lw.refs[k]];
-          for (const BitCol& q : bit_cols) {
-            *w++ = (u64)(uintptr_t)(q.validity ? lite->validity[at + (size_t)q.col] : lite->values0[at + (size_t)q.col]);   // (a Boolean column's values0 is its bitmap)
-            *w++ = (u64)lite->offset[at + (size_t)q.col];
-          }
+  const size_t tbl_words = (wpb > 0 ? nb : (size_t)t.ntiles) * t.stride;
+  t.bytes_tbl = tbl_words * 8; t.bytes_idx = wpb > 0 ? 0 : nb * 8; t.bytes_cnt = nb * 8;
+  ensure_pinned_table(ctx, t.bytes_tbl + t.bytes_idx + t.bytes_cnt);
+  u64* w = (u64*)ctx.pinned_tbl;
+  int64_t* h_idx = (int64_t*)(w + tbl_words);
+  int64_t tile = 0;
+  auto utf8_data = [&](size_t b, size_t k) -> u64 {
+    return (u64)(uintptr_t)(lite ? lite->data[b * ncols + (size_t)pl.fold_utf8[k]] : recs[b].cols[(size_t)pl.fold_utf8[k]].data);
+  };
+  for (size_t b = 0; b < nb; ++b) {
+    const int64_t rows = rows_of_batch(b);
+    if (wpb > 0) {
+      *w++ = (u64)rows;
+      for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][lw.refs[k]];
+      for (size_t k = 0; k < nout; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][t.launch_cols[k]];
+      for (size_t k = 0; k < nu; ++k) { *w++ = (u64)(uintptr_t)in_ptr[b][pl.fold_utf8[k]]; *w++ = utf8_data(b, k); }
+      if (pl.need_bits) {
+        const size_t at = b * ncols;
+        for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)lite->validity[at + (size_t)lw.refs[k]];
+        for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)lite->offset[at + (size_t)lw.refs[k]];
+        for (const BitCol& q : t.bit_cols) {
+          *w++ = (u64)(uintptr_t)(q.validity ? lite->validity[at + (size_t)q.col] : lite->values0[at + (size_t)q.col]);   // (a Boolean column's values0 is its bitmap)
+          *w++ = (u64)lite->offset[at + (size_t)q.col];
         }
-        continue;
       }
-      for (int64_t r0 = 0; r0 < rows; r0 += tile_rows, ++tile) {
-        *w++ = (u64)r0; *w++ = (u64)rows;
-        for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][lw.refs[k]];
-        for (size_t k = 0; k < nout; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][launch_cols[k]];
-        for (size_t k = 0; k < nu; ++k) { *w++ = (u64)(uintptr_t)in_ptr[b][fold_utf8[k]]; *w++ = utf8_data(b, k); }
-      }
-      h_idx[b] = tile - 1;   // rows >= 2: every batch owns at least one tile
+      continue;
     }
-  }
-  pt.mark("table");
-  if (fold && !finish_fold_sizes()) {
-    // Short strings whose JOINED output would not fit int32 offsets (the reference's batch size at config-5 scale: 10^5
-    // batches, 8 GB of strings): consecutive sub-groups, each through this one-launch path -- no join on the device
-    // (2.7 ms per GiB chunk) and no Batch objects; the per-batch outputs are exported per sub-group.
-    bool short_strings = lite && !host_in && sliced && !co;
-    for (const auto& per_batch : fold_bytes) { int64_t cap = 0; for (int64_t v : per_batch) cap += v; short_strings = short_strings && cap <= fold_rows_all * 24; }
-    if (short_strings) {
-      std::vector<size_t> cuts{0};
-      {
-        std::vector<int64_t> bytes(fold_bytes.size(), 0);
-        int64_t rows = 0;
-        for (size_t b = 0; b < nb; ++b) {
-          bool over = rows + lite->rows[b] > (1ll << 30);
-          for (size_t k = 0; k < fold_bytes.size(); ++k) over |= bytes[k] + fold_bytes[k][b] > ctx.opt_group_chunk_bytes;
-          if (over && b > cuts.back()) { cuts.push_back(b); std::fill(bytes.begin(), bytes.end(), 0); rows = 0; }
-          for (size_t k = 0; k < fold_bytes.size(); ++k) bytes[k] += fold_bytes[k][b];
-          rows += lite->rows[b];
-        }
-        cuts.push_back(nb);
-      }
-      bool groups_of_two = cuts.size() > 2;   // (a sub-group of ONE batch would take the per-batch path: nothing gained -- e.g. ten 1 GB batches)
-      for (size_t k = 0; k + 1 < cuts.size(); ++k) groups_of_two = groups_of_two && cuts[k + 1] - cuts[k] >= 2;
-      if (groups_of_two) {
-        chq_call_stats acc{};
-        bool ok = true;
-        std::vector<GroupSliced> parts;
-        for (size_t k = 0; k + 1 < cuts.size() && ok; ++k) {
-          const size_t b0 = cuts[k], b1 = cuts[k + 1], n = b1 - b0;
-          GroupLite sub;
-          sub.resize(n, ncols);
-          std::copy(lite->rows.begin() + b0, lite->rows.begin() + b1, sub.rows.begin());
-          std::copy(lite->flags.begin() + b0, lite->flags.begin() + b1, sub.flags.begin());
-          std::copy(lite->values0.begin() + b0 * ncols, lite->values0.begin() + b1 * ncols, sub.values0.begin());
-          std::copy(lite->data.begin() + b0 * ncols, lite->data.begin() + b1 * ncols, sub.data.begin());
-          std::copy(lite->validity.begin() + b0 * ncols, lite->validity.begin() + b1 * ncols, sub.validity.begin());
-          std::copy(lite->offset.begin() + b0 * ncols, lite->offset.begin() + b1 * ncols, sub.offset.begin());
-          // the sub-group's first batch as a view built from the flat arrays (schema and flags of batch 0)
-          std::vector<Batch> head(1);
-          head[0] = recs[0];
-          head[0].nrows = lite->rows[b0];
-          for (size_t i = 0; i < ncols; ++i) {
-            Column& c = head[0].cols[i];
-            const size_t at = b0 * ncols + i;
-            c.owned.clear();
-            c.offset = lite->offset[at]; c.length = lite->rows[b0];
-            c.values = c.type == T_BOOL ? lite->values0[at] : lite->values0[at] - (int64_t)(c.type == T_UTF8 ? 4 : c.width) * c.offset;
-            c.data = lite->data[at]; c.data_bytes = -1;
-            c.validity = lite->validity[at]; c.null_count = c.validity ? 1 : 0;   // (unknown count: may have nulls)
-          }
-          GroupInput sgi; sgi.batches = &head; sgi.lite = &sub;
-          GroupSliced part;
-          (void)filter_records_impl(ctx, sgi, aliases, expr, out_on_device, nullptr, &part);
-          add_stats(acc, ctx.stats);
-          ok = part.filled && part.more.empty();
-          parts.push_back(std::move(part));
-        }
-        if (ok) {
-          *sliced = std::move(parts[0]);
-          for (size_t k = 1; k < parts.size(); ++k) sliced->more.push_back(std::move(parts[k]));
-          ctx.stats = acc;
-          return {};
-        }
-      }
+    for (int64_t r0 = 0; r0 < rows; r0 += tile_rows, ++tile) {
+      *w++ = (u64)r0; *w++ = (u64)rows;
+      for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][lw.refs[k]];
+      for (size_t k = 0; k < nout; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][t.launch_cols[k]];
+      for (size_t k = 0; k < nu; ++k) { *w++ = (u64)(uintptr_t)in_ptr[b][pl.fold_utf8[k]]; *w++ = utf8_data(b, k); }
     }
-    return other_path();   // (long strings / too many bytes for one column: joined on the device)
+    h_idx[b] = tile - 1;   // rows >= 2: every batch owns at least one tile
   }
-  pt.mark("utf8_sizes");
-  auto d_tbl = make_device_buffer(bytes_tbl + bytes_idx + bytes_cnt + 16, ctx.device);
-  check_hip(hipMemcpyAsync(d_tbl->ptr, h_tbl, bytes_tbl + bytes_idx, hipMemcpyHostToDevice, ctx.stream), "upload group table");
-  u64* d_cnt = (u64*)((uint8_t*)d_tbl->ptr + bytes_tbl + bytes_idx);
+  return true;
+}
+
+// ---- stage 4: ONE launch over the table, the joined outputs collected into `out` -------------------------------------------
+// False: a data-dependent error was flagged (the per-batch loop reports the earliest failing batch, as the reference's
+// loop would).  `fold_cap`: capacity of every folded Utf8 column's joined bytes.
+bool launch_group(const GroupCall& g, const GroupPlan& pl, const Lowered& lw, GroupTable& t, const std::vector<int64_t>& fold_cap,
+                  JoinedGroup& out) {
+  Context& ctx = g.ctx;
+  const std::vector<Batch>& recs = g.recs;
+  const size_t nb = g.nb, ncols = recs[0].cols.size(), nu = pl.fold_utf8.size(), nout = t.launch_cols.size();
+  const int64_t total_rows = pl.total_rows, ntiles = t.ntiles, wpb = t.wpb;
+  const int tile_kind = t.tile_kind;
+  FilterParams& p = t.p;
+  PhaseTimer pt("filter_records (launch)");
+  u64* h_cnt = (u64*)((uint8_t*)ctx.pinned_tbl + t.bytes_tbl + t.bytes_idx);
+  auto d_tbl = make_device_buffer(t.bytes_tbl + t.bytes_idx + t.bytes_cnt + 16, ctx.device);
+  check_hip(hipMemcpyAsync(d_tbl->ptr, ctx.pinned_tbl, t.bytes_tbl + t.bytes_idx, hipMemcpyHostToDevice, ctx.stream), "upload group table");
+  u64* d_cnt = (u64*)((uint8_t*)d_tbl->ptr + t.bytes_tbl + t.bytes_idx);
+  Scratch* ds = dev_scratch(ctx);
 
   // ---- dense outputs ---------------------------------------------------------------------------------------
   std::vector<BufferPtr> dense(ncols), dense_data(ncols), fold_status;
@@ -2584,14 +2433,14 @@ std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const
     ctx.stats.bytes_read_alg += total_rows * recs[0].cols[i].width;
   }
   BufferPtr g_sel, g_base;
-  const int64_t nslots = need_bits ? ntiles * kWavesPerTile[tile_kind] * (kWaveRows[tile_kind] / 64) : 0;
-  if (need_bits) {
+  const int64_t nslots = pl.need_bits ? ntiles * kWavesPerTile[tile_kind] * (kWaveRows[tile_kind] / 64) : 0;
+  if (pl.need_bits) {
     g_sel = make_device_buffer((size_t)(nslots + 8) * 8, ctx.device);
     g_base = make_device_buffer((size_t)(nslots + 8) * 8, ctx.device);
-    p.sel_mask = (u64*)g_sel->ptr; p.grp_base = (u64*)g_base->ptr; p.group_bits_at = (int32_t)bits_at; p.pb.group_bits_at = (int32_t)bits_at;
+    p.sel_mask = (u64*)g_sel->ptr; p.grp_base = (u64*)g_base->ptr; p.group_bits_at = (int32_t)t.bits_at; p.pb.group_bits_at = (int32_t)t.bits_at;
   }
   for (size_t k = 0; k < nu; ++k) {   // Utf8 columns: joined offsets (from 0) and bytes, capacity = the input bytes
-    const size_t i = (size_t)fold_utf8[k];
+    const size_t i = (size_t)pl.fold_utf8[k];
     dense[i] = make_device_buffer((size_t)(total_rows + 2) * 4, ctx.device);
     dense_data[i] = make_device_buffer((size_t)fold_cap[k] + 64, ctx.device);
     auto st = make_device_buffer((size_t)(ntiles + 1) * 8, ctx.device);
@@ -2604,15 +2453,15 @@ std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const
     ctx.stats.bytes_read_alg += total_rows * 8;
   }
   p.n_utf8 = (int32_t)nu;
-  p.nrows = ntiles * tile_rows;   // only locates the last tile; per-tile row ranges come from the table
+  p.nrows = ntiles * kTileRows[tile_kind];   // only locates the last tile; per-tile row ranges come from the table
   p.status = dev_status(ctx);
   p.ticket = &ds->ticket; p.total = &ds->total; p.err = &ds->err;
-  fill_refs(p.pb, lw, proto, {});
+  fill_refs(p.pb, lw, t.proto, {});
   for (size_t k = 0; k < nout; ++k) {
-    p.outs[k].in = nullptr; p.outs[k].out = dense[launch_cols[k]]->ptr; p.outs[k].width = (uint32_t)recs[0].cols[launch_cols[k]].width;
+    p.outs[k].in = nullptr; p.outs[k].out = dense[t.launch_cols[k]]->ptr; p.outs[k].width = (uint32_t)recs[0].cols[t.launch_cols[k]].width;
   }
   p.n_out = (int16_t)nout;
-  p.group = (const u64*)d_tbl->ptr; p.group_stride = (int64_t)stride;
+  p.group = (const u64*)d_tbl->ptr; p.group_stride = (int64_t)t.stride;
   p.group_wpb = (int32_t)wpb; p.group_nb = (int32_t)nb; p.group_batch_end = d_cnt;
   p.tile_begin = 0; p.tile_end = ntiles;
   check_hip(hipMemsetAsync(ds, 0, kHeader + (size_t)(ntiles + 1) * 8, ctx.stream), "memset scratch + status");
@@ -2624,38 +2473,37 @@ std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const
   ctx.stats.launches = 1; ctx.stats.tiles = ntiles;
   if (wpb == 0) {   // tile mode: the inclusive prefix at every batch's last tile
     GatherStatusParams gp{};
-    gp.status = dev_status(ctx); gp.idx = (const int64_t*)((const uint8_t*)d_tbl->ptr + bytes_tbl);
+    gp.status = dev_status(ctx); gp.idx = (const int64_t*)((const uint8_t*)d_tbl->ptr + t.bytes_tbl);
     gp.dst = d_cnt; gp.n = (int64_t)nb;
     check_hip(launch_gather_status(gp, ctx.stream), "launch gather_status_kernel");
     ctx.stats.launches = 2;
   }
-  std::vector<BufferPtr> bit_out(bit_cols.size());
+  std::vector<BufferPtr> bit_out(t.bit_cols.size());
   const size_t bit_bytes = (size_t)(total_rows + 31) / 32 * 4 + 16;
-  for (size_t q = 0; q < bit_cols.size(); ++q) {   // one joined bitmap per Boolean column / per column with nulls
+  for (size_t q = 0; q < t.bit_cols.size(); ++q) {   // one joined bitmap per Boolean column / per column with nulls
     bit_out[q] = make_device_buffer(bit_bytes, ctx.device);
     check_hip(hipMemsetAsync(bit_out[q]->ptr, 0, bit_bytes, ctx.stream), "memset bits");
     BitCompactGroupParams bp{};
-    bp.sel_mask = (const u64*)g_sel->ptr; bp.grp_base = (const u64*)g_base->ptr; bp.table = (const u64*)d_tbl->ptr; bp.stride = (int64_t)stride;
-    bp.word_ptr = (int32_t)bit_cols[q].word; bp.word_off = (int32_t)bit_cols[q].word + 1; bp.wpb = (int32_t)wpb; bp.nb = (int32_t)nb;
+    bp.sel_mask = (const u64*)g_sel->ptr; bp.grp_base = (const u64*)g_base->ptr; bp.table = (const u64*)d_tbl->ptr; bp.stride = (int64_t)t.stride;
+    bp.word_ptr = (int32_t)t.bit_cols[q].word; bp.word_off = (int32_t)t.bit_cols[q].word + 1; bp.wpb = (int32_t)wpb; bp.nb = (int32_t)nb;
     bp.rows_per_wave = (int32_t)kWaveRows[tile_kind]; bp.out_bits = (uint32_t*)bit_out[q]->ptr;
-    bp.zero_count = bit_cols[q].validity ? &ds->counters[q] : nullptr;
+    bp.zero_count = t.bit_cols[q].validity ? &ds->counters[q] : nullptr;
     check_hip(launch_bit_compact_group(bp, (int)std::min<int64_t>((wpb * (int64_t)nb + 3) / 4, (int64_t)ctx.num_cus * 8), ctx.stream), "launch bit_compact_group_kernel");
     ++ctx.stats.launches;
   }
   Scratch* hs = (Scratch*)ctx.pinned;
   check_hip(hipMemcpyAsync(hs, ds, sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
-  check_hip(hipMemcpyAsync(h_cnt, d_cnt, bytes_cnt, hipMemcpyDeviceToHost, ctx.stream), "read back batch prefixes");
+  check_hip(hipMemcpyAsync(h_cnt, d_cnt, t.bytes_cnt, hipMemcpyDeviceToHost, ctx.stream), "read back batch prefixes");
   pt.mark("alloc+launch");
   check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
   pt.mark("kernel+readback");
   if (ctx.opt_time_kernels) { float ms = 0; check_hip(hipEventElapsedTime(&ms, ctx.ev0, ctx.ev1), "hipEventElapsedTime"); ctx.stats.kernel_ns = (int64_t)(ms * 1e6); }
-  if (hs->err != ERR_NONE) return per_batch_loop();   // reports the earliest failing batch, as the reference's loop would
-  (void)fold_status;
+  if (hs->err != ERR_NONE) return false;
   const int64_t total = (int64_t)hs->total;
   ctx.stats.rows_out = total;
   std::vector<int64_t> out_bytes(ncols, 0);   // Utf8 columns: bytes of the joined output
   for (size_t k = 0; k < nu; ++k) {
-    out_bytes[(size_t)fold_utf8[k]] = (int64_t)hs->fold_bytes[k];
+    out_bytes[(size_t)pl.fold_utf8[k]] = (int64_t)hs->fold_bytes[k];
     ctx.stats.bytes_read_alg += (int64_t)hs->fold_bytes[k]; ctx.stats.bytes_written_alg += (total + 1) * 4 + (int64_t)hs->fold_bytes[k];
   }
   for (size_t i = 0; i < ncols; ++i) if (recs[0].cols[i].type != T_UTF8 && recs[0].cols[i].type != T_BOOL) ctx.stats.bytes_written_alg += total * recs[0].cols[i].width;
@@ -2664,12 +2512,12 @@ std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const
   struct JoinedCol { BufferPtr values, data, validity; int64_t nulls = 0; };
   std::vector<JoinedCol> joined(ncols);
   for (size_t i = 0; i < ncols; ++i) { joined[i].values = dense[i]; joined[i].data = dense_data[i]; }
-  for (size_t q = 0; q < bit_cols.size(); ++q) {
-    JoinedCol& jc = joined[(size_t)bit_cols[q].col];
-    if (!bit_cols[q].validity) jc.values = bit_out[q];
+  for (size_t q = 0; q < t.bit_cols.size(); ++q) {
+    JoinedCol& jc = joined[(size_t)t.bit_cols[q].col];
+    if (!t.bit_cols[q].validity) jc.values = bit_out[q];
     else if (hs->counters[q] != 0) { jc.validity = bit_out[q]; jc.nulls = (int64_t)hs->counters[q]; }   // (arrow drops an all-valid null buffer)
   }
-  if (!out_on_device) {   // host result: every joined buffer comes down once
+  if (!g.out_on_device) {   // host result: every joined buffer comes down once
     for (size_t i = 0; i < ncols; ++i) {
       const DType ty = recs[0].cols[i].type;
       auto down = [&](BufferPtr& b, size_t bytes) {
@@ -2684,62 +2532,158 @@ std::vector<Batch> filter_records_impl(Context& ctx, const GroupInput& gi, const
     }
     check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
   }
-  if (co) {   // the joined buffers ARE the coalesced batch
-    co->out.on_device = out_on_device; co->out.device_id = out_on_device ? ctx.device : -1;
-    co->out.nrows = total;
-    for (size_t i = 0; i < ncols; ++i) {
-      Column c = empty_like(recs[0].cols[i]);
-      const JoinedCol& jc = joined[i];
-      c.values = (const uint8_t*)jc.values->ptr; c.length = total; c.owned.push_back(jc.values);
-      if (c.type == T_UTF8) { c.data = (const uint8_t*)jc.data->ptr; c.data_bytes = out_bytes[i]; c.owned.push_back(jc.data); }
-      if (jc.validity) { c.validity = (const uint8_t*)jc.validity->ptr; c.null_count = jc.nulls; c.owned.push_back(jc.validity); }
-      co->out.cols.push_back(std::move(c));
-    }
-    int64_t prev = 0;
-    for (size_t b = 0; b < nb; ++b) { co->rows.push_back((int64_t)h_cnt[b] - prev); prev = (int64_t)h_cnt[b]; }
-    co->done = true;
-    return {};
+  out.joined.on_device = g.out_on_device; out.joined.device_id = g.out_on_device ? ctx.device : -1;
+  out.joined.nrows = total;
+  for (size_t i = 0; i < ncols; ++i) {
+    Column c = empty_like(recs[0].cols[i]);
+    const JoinedCol& jc = joined[i];
+    c.values = (const uint8_t*)jc.values->ptr; c.length = total; c.owned.push_back(jc.values);
+    if (c.type == T_UTF8) { c.data = (const uint8_t*)jc.data->ptr; c.data_bytes = out_bytes[i]; c.owned.push_back(jc.data); }
+    if (jc.validity) { c.validity = (const uint8_t*)jc.validity->ptr; c.null_count = jc.nulls; c.owned.push_back(jc.validity); }
+    out.joined.cols.push_back(std::move(c));
   }
-  if (sliced) {   // the caller cuts the joined buffers into Arrow structs itself (capi.cpp: one block for the whole group)
-    sliced->filled = true; sliced->on_device = out_on_device; sliced->device_id = out_on_device ? ctx.device : -1;
-    for (size_t i = 0; i < ncols; ++i) {
-      sliced->proto.push_back(empty_like(recs[0].cols[i]));
-      sliced->values.push_back(joined[i].values);
-      sliced->data.push_back(joined[i].data);
-      sliced->validity.push_back(joined[i].validity);
-    }
-    sliced->ends.assign(h_cnt, h_cnt + nb);
-    return {};
+  out.ends.assign(h_cnt, h_cnt + nb);
+  return true;
+}
+
+// Short strings whose JOINED output would not fit int32 offsets (the reference's batch size at config-5 scale: 10^5 batches,
+// 8 GB of strings): consecutive sub-groups, each through the one-launch path -- no join on the device (2.7 ms per GiB
+// chunk) and no Batch objects.  False: a sub-group of ONE batch (it would take the per-batch path: nothing gained -- e.g.
+// ten 1 GB batches), or one that did not run as one launch.
+bool split_short_strings(const GroupCall& g, const std::vector<std::vector<int64_t>>& fold_bytes, GroupResult* out) {
+  const std::vector<size_t> cuts = chunk_cuts(g.lite->rows, fold_bytes, g.ctx.opt_group_chunk_bytes);
+  bool groups_of_two = cuts.size() > 2;
+  for (size_t k = 0; k + 1 < cuts.size(); ++k) groups_of_two = groups_of_two && cuts[k + 1] - cuts[k] >= 2;
+  if (!groups_of_two) return false;
+  chq_call_stats acc{};
+  GroupResult r;
+  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+    GroupLite sub = g.lite->slice(cuts[k], cuts[k + 1]);
+    std::vector<Batch> head{lite_head(g.recs[0], *g.lite, cuts[k])};
+    GroupInput sgi; sgi.batches = &head; sgi.lite = &sub;
+    GroupResult part = filter_group(g.ctx, sgi, g.aliases, g.expr, g.out_on_device, g.coalesce);
+    add_stats(acc, g.ctx.stats);
+    if (part.parts.size() != 1 || part.batches() != cuts[k + 1] - cuts[k]) return false;
+    r.parts.push_back(std::move(part.parts[0]));
   }
-  std::vector<Batch> outs(nb);
-  int64_t begin = 0;
-  for (size_t b = 0; b < nb; ++b) {
-    const int64_t end = (int64_t)h_cnt[b];
-    Batch& o = outs[b];
-    o.on_device = out_on_device; o.device_id = out_on_device ? ctx.device : -1;
-    o.nrows = end - begin;
-    for (size_t i = 0; i < ncols; ++i) {
-      Column c = empty_like(recs[0].cols[i]);
-      const JoinedCol& jc = joined[i];
-      c.length = o.nrows;
-      c.owned.push_back(jc.values);
-      if (c.type == T_UTF8 || c.type == T_BOOL || jc.validity) {
-        // a slice of the joined column: shared buffers, Arrow offset = first row (one offset serves values and validity)
-        c.values = (const uint8_t*)jc.values->ptr; c.offset = begin;
-        if (c.type == T_UTF8) { c.data = (const uint8_t*)jc.data->ptr; c.owned.push_back(jc.data); }
-        if (jc.validity) {
-          c.validity = (const uint8_t*)jc.validity->ptr; c.owned.push_back(jc.validity);
-          if (out_on_device) c.null_count = -1;   // unknown for the slice (Arrow C Data Interface: -1)
-          else { c.null_count = count_nulls_host(c.validity, c.offset, c.length); if (c.null_count == 0) c.validity = nullptr; }
-        }
-      } else c.values = (const uint8_t*)jc.values->ptr + begin * c.width;
-      o.cols.push_back(std::move(c));
+  g.ctx.stats = acc;
+  *out = std::move(r);
+  return true;
+}
+
+GroupResult filter_group(Context& ctx, const GroupInput& gi, const chq_table_aliases* aliases, const Expr& expr,
+                         bool out_on_device, bool coalesce) {
+  const GroupCall g(ctx, gi, aliases, expr, out_on_device, coalesce);
+  if (g.nb < 2 || g.recs[0].cols.empty()) return g.per_batch_loop();
+  PhaseTimer pt("filter_records (one-launch path)");
+  const GroupPlan pl = plan_group(g);
+  if (pl.per_batch) return g.per_batch_loop();
+  // the batches' string sizes are read back from the device: queued here, awaited only after the predicate has been typed
+  // and the group table built (`sizes_fit` below)
+  Utf8Sizes sizes_in_flight;
+  if (pl.fold) sizes_in_flight = device_utf8_bytes_issue(ctx, g.recs, g.lite, pl.fold_utf8);
+  std::vector<std::vector<int64_t>> fold_bytes;   // bytes of every folded Utf8 column per batch
+  std::vector<int64_t> fold_cap;                  // and in all
+  bool sizes_done = false, sizes_ok = false;
+  auto sizes_fit = [&]() -> bool {   // false: long strings, or more than one output column can address
+    if (sizes_done) return sizes_ok;
+    sizes_done = true;
+    fold_bytes = device_utf8_bytes_finish(ctx, sizes_in_flight);
+    bool ok = true;
+    for (const auto& per_batch : fold_bytes) {
+      int64_t cap = 0;
+      for (int64_t v : per_batch) cap += v;
+      fold_cap.push_back(cap);
+      // short strings that fit ONE output column (int32 offsets: 2 x group_chunk_bytes = 2 GiB unless a test lowers the option)
+      ok &= cap <= pl.total_rows * 24 && cap < 2 * ctx.opt_group_chunk_bytes - 64;
     }
-    begin = end;
+    sizes_ok = ok;
+    return ok;
+  };
+  pt.mark("eligibility+utf8_sizes");
+  if (!pl.plain && !pl.fold) {   // joined first, on the host or on the device
+    const bool host_case = pl.all_host && !out_on_device;
+    if (!host_case && !pl.all_device) return g.per_batch_loop();
+    try {
+      TypedExpr probe = type_expr(expr, plan_columns(g.recs[0], aliases), g.recs[0].nrows, ctx.opt_enable_minus);
+      if (probe.pending_code || probe.at(probe.root).type != T_BOOL || probe.at(probe.root).len1) return g.per_batch_loop();
+    } catch (const ChqError&) {
+      return g.per_batch_loop();   // reports the first batch's (static) error
+    }
+    return g.concat(host_case);
   }
-  return outs;
+  // a foldable group that turns out not to fit the one-launch path is joined on the device instead
+  auto other_path = [&]() -> GroupResult {
+    if (!sizes_in_flight.cols.empty()) check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");   // (the size gather reads back into pinned memory the next call reuses)
+    return pl.fold ? g.concat(false) : g.per_batch_loop();
+  };
+  if (!pl.resident) return g.per_batch_loop();
+  const std::vector<PlanColumn> pcols = plan_columns(g.recs[0], aliases);
+  TypedExpr te = type_expr(expr, pcols, g.recs[0].nrows, ctx.opt_enable_minus);
+  if (te.pending_code) return g.per_batch_loop();
+  const Node& root = te.at(te.root);
+  if (root.type != T_BOOL || root.len1) return g.per_batch_loop();
+  Lowered lw;
+  try {
+    lower_expr(te, te.root, pcols, lw);
+  } catch (const ChqError& e) {
+    if (e.code != CHQ_INTERNAL_PROGRAM_LIMIT) throw;
+    return g.per_batch_loop();   // oversized predicate: every batch materialises its own temporaries
+  }
+  if (!lw.strs.empty()) return other_path();
+  bool reads_utf8 = false;
+  for (int r : lw.refs) reads_utf8 |= g.recs[0].cols[(size_t)r].type == T_UTF8;
+  if (pl.fold && g.lite && !pl.host_in && !reads_utf8 && ctx.opt_uniform_utf8_rows > 0 && pl.total_rows >= ctx.opt_uniform_utf8_rows) {
+    GroupResult r;
+    if (uniform_group(g, pl, sizes_fit, &r)) return r;
+  }
+  // the predicate itself must not read a string column, and the wide / temporaries instantiation has no Utf8 form
+  if (pl.fold && (reads_utf8 || lw.wide || lw.num_temps > 0)) return other_path();
+
+  GroupTable t;
+  if (!build_group_table(g, pl, lw, t)) return other_path();
+  pt.mark("table");
+  if (pl.fold && !sizes_fit()) {
+    bool short_strings = g.lite && !pl.host_in && !coalesce;
+    for (int64_t cap : fold_cap) short_strings = short_strings && cap <= pl.total_rows * 24;
+    GroupResult r;
+    if (short_strings && split_short_strings(g, fold_bytes, &r)) return r;
+    return other_path();   // (long strings / too many bytes for one column: joined on the device)
+  }
+  pt.mark("utf8_sizes");
+  GroupResult r;
+  r.parts.emplace_back();
+  if (!launch_group(g, pl, lw, t, fold_cap, r.parts[0])) return g.per_batch_loop();
+  return r;
 }
 }  // namespace
+
+GroupResult filter_records(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases, const Expr& expr,
+                           bool out_on_device) {
+  return filter_group(ctx, in, aliases, expr, out_on_device, false);
+}
+
+Batch filter_records_coalesced(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases,
+                               const Expr& expr, bool out_on_device, std::vector<int64_t>* rows_per_record) {
+  if (!in.batches || in.batches->empty()) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "no record batches to coalesce"};
+  GroupResult r = filter_group(ctx, in, aliases, expr, out_on_device, true);
+  std::vector<int64_t> rows;
+  for (const JoinedGroup& part : r.parts)
+    for (size_t b = 0; b < part.ends.size(); ++b) rows.push_back(part.ends[b] - (b ? part.ends[b - 1] : 0));
+  for (const Batch& o : r.per_batch) rows.push_back(o.nrows);
+  if (rows_per_record) *rows_per_record = rows;
+  if (r.parts.size() == 1) return std::move(r.parts[0].joined);   // the joined batch IS the result
+  // several host-joined parts, or the per-batch results: joined on the host, then moved where they are wanted
+  const chq_call_stats st = ctx.stats;
+  std::vector<Batch> host;
+  for (JoinedGroup& part : r.parts) host.push_back(part.joined.on_device ? to_host(ctx, part.joined) : std::move(part.joined));
+  for (Batch& o : r.per_batch) host.push_back(o.on_device ? to_host(ctx, o) : std::move(o));
+  Batch cat = concat_host_batches(host, 0, host.size());
+  Batch out = out_on_device ? to_device(ctx, cat) : std::move(cat);
+  if (out_on_device) check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  ctx.stats = st;
+  return out;
+}
 
 // =================================================================================================
 // project_record / compute_value

@@ -217,18 +217,26 @@ struct GroupLite {
   enum : uint8_t { GL_NULLS = 1, GL_NO_UTF8_DATA = 2, GL_SCHEMA_DIFFERS = 4, GL_ON_DEVICE = 8, GL_SHORT = 16 };
   void resize(size_t nb, size_t nc) { ncols = nc; rows.assign(nb, 0); values0.assign(nb * nc, nullptr); data.assign(nb * nc, nullptr); validity.assign(nb * nc, nullptr); offset.assign(nb * nc, 0); flags.assign(nb, 0); }
   void set(size_t b, const Batch& r, const Batch& first, int device);
+  GroupLite slice(size_t b0, size_t b1) const;   // the facts of batches [b0, b1)
 };
-// The one-launch result of a group call before it is cut into per-batch Arrow structs: dense output buffers every batch's
-// output is a slice of (capi.cpp exports them from one block instead of ~20 allocations per batch).
-struct GroupSliced {
-  bool filled = false, on_device = false;
-  int device_id = -1;
-  std::vector<Column> proto;               // per column: name / format / type / width / nullable flag
-  std::vector<BufferPtr> values, data, validity;   // per column: values (Utf8: joined offsets; Boolean: joined bitmap), Utf8 bytes, joined validity bitmap or null
-  std::vector<int64_t> ends;               // [nb] exclusive end row of every batch in the dense output
-  // a group too large for ONE launch (int32 offsets of the joined Utf8 output, 2^31 rows) is run as consecutive sub-groups:
-  // this struct then describes the first `ends.size()` batches and `more` the following ones, in order
-  std::vector<GroupSliced> more;
+// The joined result of a group call, or of consecutive batches of it: ONE batch holding every surviving row in input order
+// (columns as the producing path built them, buffers kept alive by Column::owned) and the exclusive end row of every input
+// batch it covers.  chq_filter_records cuts it into per-batch Arrow structs from one block (capi.cpp: export_group);
+// chq_filter_records_coalesced hands the batch on whole.
+struct JoinedGroup {
+  Batch joined;
+  std::vector<int64_t> ends;
+};
+// What a group call returns: consecutive joined parts that cover the batches in order, or (no parts) the per-batch results
+// of the per-batch loop.
+struct GroupResult {
+  std::vector<JoinedGroup> parts;
+  std::vector<Batch> per_batch;
+  size_t batches() const {   // input batches the result covers
+    size_t n = per_batch.size();
+    for (const JoinedGroup& p : parts) n += p.ends.size();
+    return n;
+  }
 };
 // The batches of a group call.  `batches` always holds batch 0; with `lite` the others may be missing until `materialise`
 // (imports every batch; idempotent) has run -- the one-launch path of a device-resident group works from `lite` alone, and
@@ -238,10 +246,9 @@ struct GroupInput {
   const GroupLite* lite = nullptr;
   std::function<void()> materialise;
 };
-// one launch for a group of same-schema batches (host or device resident); outputs where `out_on_device` says.
-// `sliced` (optional): filled instead of the returned vector when the one-launch path ran
-std::vector<Batch> filter_records(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases,
-                                  const Expr& expr, bool out_on_device, GroupSliced* sliced = nullptr);
+// one launch for a group of same-schema batches (host or device resident); outputs where `out_on_device` says
+GroupResult filter_records(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases, const Expr& expr,
+                           bool out_on_device);
 // the same, but ONE output batch holding every surviving row in input order (+ surviving rows per input batch)
 Batch filter_records_coalesced(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases,
                                const Expr& expr, bool out_on_device, std::vector<int64_t>* rows_per_record);

@@ -501,6 +501,36 @@ def test_groups_too_large_for_one_launch_run_as_sub_groups(nulls):
     c.close()
 
 
+def test_a_sub_group_of_long_strings_falls_back_to_the_whole_group():
+    """the short-string split of a group whose first chunk holds long strings (40 bytes a row, over the fold's 24): that
+    sub-group cannot run as one launch, so the split gives up and the WHOLE group is joined on the device -- every input
+    batch gets its own output, none shifted onto another"""
+    c = chq.Context(0)
+    R = 1000
+    recs = []
+    for i in range(22):   # 2 x 40 kB of long strings (one chunk of exactly group_chunk_bytes), then 20 x 4 kB of short ones
+        r = np.random.default_rng(1300 + i)
+        width = 40 if i < 2 else 4
+        recs.append(pa.record_batch({"id": pa.array(r.integers(0, 1000, R).astype(np.int32)),
+                                     "s": pa.array(["".join(chr(97 + int(x) % 26) for x in r.integers(0, 26, width)) for _ in range(R)]),
+                                     "v": pa.array((r.random(R) * 100).astype(np.float32))}))
+    al = empty_aliases(recs[0])
+    devs = [chq.DeviceRecordBatch.from_host(r, c) for r in recs]
+    c.set_option("group_chunk_bytes", 80 * R)   # 160 kB of strings in all: too many for one output column of this limit
+    for sql in ["id % 2 = 0", "v > 50.0"]:
+        e = parse_expr(sql)
+        want = [O.filter_record(r, al, e) for r in recs]
+        for device in (True, False):
+            got = chq.filter_records(devs, al, e, ctx=c, device_result=device)
+            assert len(got) == len(recs) and c.last_stats()["rows_in"] == 22 * R
+            for i, (g, w) in enumerate(zip(got, want)):
+                gh = g.to_host() if device else g
+                assert batches_identical(gh, w), f"{sql}, device={device}, batch {i}:\n{explain_diff(gh, w)}"
+        big, per = chq.filter_records_coalesced(devs, al, e, ctx=c, device_result=False)
+        assert per == [w.num_rows for w in want]
+    c.close()
+
+
 @pytest.mark.parametrize("nulls", [False, True], ids=["non-null", "value2-with-nulls"])
 def test_groups_of_uniform_length_strings_run_as_plain_groups(nulls):
     """device groups whose string columns all hold values of ONE length (the reference's sample strings) are proved uniform by

@@ -206,12 +206,14 @@ def test_uniform_group_path_runs_on_views():
     row) against the fold's 8 per row and the kept bytes; the writes agree"""
     rec = host_parent("k4+k16")
     lens = [4, 16]
-    st = {}
+    st, co = {}, {}
     for u in (1, 0):
         c = fresh_ctx(uniform_utf8_rows=u, group_mode=2)   # (the nullable columns need the wave-packed form)
         views = make_views(c, rec, WINDOWS)
         for sql in ["id % 2 = 0", "flag = true or x > 600"]:
             st[(u, sql)] = check_group_calls(c, views, sql, f"uniform_utf8_rows={u}")
+            chq.filter_records_coalesced([v for v, _ in views], empty_aliases(rec), parse_expr(sql), ctx=c)
+            co[(u, sql)] = stats_of(c)
         c.close()
     rows, nb = sum(ln for _, ln in WINDOWS), len(WINDOWS)
     for sql in ["id % 2 = 0", "flag = true or x > 600"]:
@@ -219,8 +221,11 @@ def test_uniform_group_path_runs_on_views():
         out = on["rows_out"]
         assert out == off["rows_out"] and on["rows_in"] == off["rows_in"] == rows
         assert on["bytes_written_alg"] == off["bytes_written_alg"], (sql, on, off)
+        # the coalesced call counts the same writes: its offsets (rows_out + 1) x 4 per column like the fold's
+        assert co[(1, sql)]["rows_out"] == out and co[(1, sql)]["bytes_written_alg"] == co[(0, sql)]["bytes_written_alg"], (sql, co)
         extra = sum((rows + nb) * 4 + rows * L - rows * 8 - out * L for L in lens)
         assert on["bytes_read_alg"] - off["bytes_read_alg"] == extra, (sql, on, off, extra)
+        assert co[(1, sql)]["bytes_read_alg"] - co[(0, sql)]["bytes_read_alg"] == extra, (sql, co, extra)   # (the coalesced call ran it too)
 
 
 def test_wave_packed_bitmap_path_runs_on_views():
