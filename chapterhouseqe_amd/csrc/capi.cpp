@@ -7,6 +7,7 @@
 
 #include "engine.hpp"
 #include "parquet.hpp"
+#include "sort.hpp"
 #include <atomic>
 
 using namespace chq;
@@ -473,6 +474,56 @@ chq_status chq_filter_records_coalesced(chq_ctx* ctx, int n_records, const Arrow
     export_batch(std::move(res), out_device, out, out_schema);
     pt.mark("export");
   });
+}
+
+// ---- ORDER BY (sort.cpp) ---------------------------------------------------------------------------------------------------
+namespace {
+chq_status sort_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                     const chq_table_aliases* table_aliases, const chq_sort_key* keys, int n_keys, int64_t limit, int out_device,
+                     ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
+  mark_released(out, out_schema);
+  return guarded(ctx, [&] {
+    require(out, "output array"); require(out_schema, "output schema");
+    if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
+    require(recs, "record array");
+    if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative sort key count"};
+    if (n_keys > 0) require(keys, "sort keys");
+    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
+      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    std::vector<SortKeyArg> args((size_t)n_keys);
+    for (int k = 0; k < n_keys; ++k) {
+      require(keys[k].column, "sort key column");
+      args[(size_t)k].column = &keys[k].column->e;
+      args[(size_t)k].descending = keys[k].descending != 0;
+      args[(size_t)k].nulls_first = keys[k].nulls_first != 0;
+    }
+    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+    PhaseTimer pt("chq_sort_records");
+    std::vector<Batch> in((size_t)n_records);
+    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
+    for_each_parallel(n_records, [&](int i) { in[(size_t)i] = import_batch(recs[i], schema); });
+    pt.mark("import");
+    Batch res = sort_records(ctx->c, in, table_aliases, args, limit);
+    pt.mark("sort");
+    finish(ctx->c, std::move(res), out_device, out, out_schema);
+    pt.mark("export");
+  });
+}
+}  // namespace
+
+chq_status chq_sort_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, const chq_table_aliases* table_aliases,
+                           const chq_sort_key* keys, int n_keys, int64_t limit, int out_device, ArrowDeviceArray* out,
+                           ArrowSchema* out_schema) {
+  const ArrowDeviceArray* recs[1] = {rec};
+  if (!rec) { if (!ctx) return CHQ_ERR_INVALID_HANDLE; mark_released(out, out_schema); ctx->c.last_error = "null record"; return CHQ_ERR_INVALID_HANDLE; }
+  return sort_call(ctx, 1, recs, schema, table_aliases, keys, n_keys, limit, out_device, out, out_schema);
+}
+
+chq_status chq_sort_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                            const chq_table_aliases* table_aliases, const chq_sort_key* keys, int n_keys, int64_t limit,
+                            int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  return sort_call(ctx, n_records, recs, schema, table_aliases, keys, n_keys, limit, out_device, out, out_schema);
 }
 
 chq_status chq_project_record(chq_ctx* ctx, const chq_select_item* fields, int n_fields, const ArrowDeviceArray* rec,

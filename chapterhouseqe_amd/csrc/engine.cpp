@@ -1962,6 +1962,24 @@ std::vector<std::vector<int64_t>> device_utf8_bytes(Context& ctx, const std::vec
 }
 }  // namespace
 
+// sort.hpp
+Batch join_group(Context& ctx, const std::vector<Batch>& recs) {
+  std::vector<Batch> dev(recs.size());
+  for (size_t b = 0; b < recs.size(); ++b) dev[b] = to_device(ctx, recs[b]);
+  if (dev.size() == 1) return std::move(dev[0]);
+  std::vector<int> utf8_cols;
+  for (size_t c = 0; c < dev[0].cols.size(); ++c) if (dev[0].cols[c].type == T_UTF8) utf8_cols.push_back((int)c);
+  const auto bytes = device_utf8_bytes(ctx, dev, utf8_cols);
+  for (size_t k = 0; k < utf8_cols.size(); ++k) {
+    int64_t total = 0;
+    for (int64_t x : bytes[k]) total += x;
+    if (total > INT32_MAX)
+      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Utf8 column '" + dev[0].cols[(size_t)utf8_cols[k]].name + "' of the joined group holds " +
+                                                     std::to_string(total) + " bytes, more than int32 offsets can address"};
+  }
+  return concat_device_batches(ctx, dev, 0, dev.size(), utf8_cols, bytes);
+}
+
 namespace {
 // ---- the pieces of a group call ------------------------------------------------------------------------------------------
 // Chunks [cuts[k], cuts[k+1]) of a group: a cut before the batch at which the rows would pass 2^30 or the bytes of any Utf8

@@ -1,0 +1,37 @@
+// sort.hpp -- ORDER BY: the stable multi-key sort of a record batch, or of a group of them joined into one (sort.cpp).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "engine.hpp"
+#include "sort_device.h"
+
+namespace chq {
+
+// sort.hip
+hipError_t launch_sort_norm(const SortNormParams& p, hipStream_t stream);
+hipError_t launch_sort_hist(const SortHistParams& p, int grid, hipStream_t stream);
+hipError_t launch_sort_pass(const SortPassParams& p, hipStream_t stream);   // count, scan, scatter: 3 launches
+hipError_t launch_sort_utf8_maxlen(const SortMaxLenParams& p, int grid, hipStream_t stream);
+hipError_t launch_sort_gather_fixed(const SortGatherParams& p, hipStream_t stream);
+hipError_t launch_sort_gather_bits(const SortGatherParams& p, hipStream_t stream);
+hipError_t launch_sort_utf8_sizes(const SortGatherParams& p, hipStream_t stream);   // 2 launches
+hipError_t launch_sort_utf8_copy(const SortGatherParams& p, hipStream_t stream);    // 2 launches
+
+// one ORDER BY key as the C ABI hands it over (chq_sort_key)
+struct SortKeyArg {
+  const Expr* column = nullptr;   // Identifier / CompoundIdentifier, resolved like compute_value resolves them
+  bool descending = false;
+  bool nulls_first = false;
+};
+
+// The batches of `in` (one schema, host or device resident) in key order, stable (batch order, then row order), cut to
+// the first `limit` rows (-1: all).  The result is ONE device batch with the schema of the input.  Throws ChqError.
+Batch sort_records(Context& ctx, std::vector<Batch>& in, const chq_table_aliases* aliases, const std::vector<SortKeyArg>& keys,
+                   int64_t limit);
+
+// engine.cpp: the batches of a group joined into ONE device batch by the concat kernels (a single batch: its device view).
+// A Utf8 column whose joined bytes pass int32 offsets is CHQ_ERR_ARROW_INVALID_ARGUMENT, naming the column.
+Batch join_group(Context& ctx, const std::vector<Batch>& recs);
+
+}  // namespace chq

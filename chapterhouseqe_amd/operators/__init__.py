@@ -3,5 +3,5 @@ from .exchange_operator import NONE_AVAILABLE, NONE_LEFT, ExchangeOperator, Reco
 from .record_handler import ExchangeRecord, RecordHandler, RecordHandlerError  # noqa: F401
 from .tasks import (FilterConfig, FilterOperatorTask, FilterTask, FilterTaskBuilder, MaterializeFilesConfig,  # noqa: F401
                     MaterializeFilesOperatorTask, MaterializeFilesTask, MaterializeFilesTaskBuilder,
-                    OperatorInstanceConfig, OperatorTaskRegistry, OperatorTaskRegistryError, TaskBuilder,
-                    build_default_operator_task_registry)
+                    OperatorInstanceConfig, OperatorTaskRegistry, OperatorTaskRegistryError, OrderByConfig,
+                    OrderByOperatorTask, OrderByTask, OrderByTaskBuilder, TaskBuilder, build_default_operator_task_registry)

@@ -154,6 +154,12 @@ class ExchangeOperator:
                 return NONE_LEFT
             return NONE_AVAILABLE
 
+    def nothing_left_to_reserve(self, operator_id: str) -> bool:
+        """every producer is done and no record waits in `operator_id`'s queue (its outstanding records are all
+        reserved): a blocking consumer that holds what it pulled is done pulling, though NoneLeft never comes"""
+        with self._lock:
+            return self.received_all_data_from_producers and not self._pool._queue(operator_id).records_to_process
+
     def heartbeat(self, operator_id: str, record_id: int) -> None:
         with self._lock:
             self._pool.update_reserved_record_heartbeat(operator_id, record_id)

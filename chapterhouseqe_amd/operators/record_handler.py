@@ -109,6 +109,28 @@ class RecordHandler:
             self._track(record_id, 0)
             return ExchangeRecord(record_id, record, aliases)
 
+    def next_record_to_hold(self) -> Optional[ExchangeRecord]:
+        """next_record for a blocking operator (order by) that holds every record it pulls until it has them all.  The
+        exchange reports NoneLeft only once nothing is reserved either, so "producers done, nothing queued" ends the
+        pull instead.  Not in the reference."""
+        self._check_heartbeats()
+        if not self.inbound_exchanges:
+            raise RecordHandlerError("inbound exchanges is empty")
+        ex = self.inbound_exchanges[0]
+        while True:
+            got = ex.get_next_record(self.operator_id, self.operator_instance_id)
+            if got == NONE_LEFT:
+                return None
+            if got == NONE_AVAILABLE:
+                if ex.nothing_left_to_reserve(self.operator_id):
+                    return None
+                time.sleep(self.none_available_wait_time_s)
+                self._check_heartbeats()
+                continue
+            record_id, record, aliases = got
+            self._track(record_id, 0)
+            return ExchangeRecord(record_id, record, aliases)
+
     def try_next_record(self) -> Optional[ExchangeRecord]:
         """Non-blocking pull: a record that is queued right now, else None (nothing available yet, or nothing left).
         Not in the reference -- the GPU filter task uses it to drain the queue into one batch-group launch."""

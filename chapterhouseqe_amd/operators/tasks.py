@@ -6,6 +6,8 @@ Reference (OPS = src/handlers/operator_handler/operators):
   FilterConfig / FilterTask / FilterTaskBuilder        OPS/filter_tasks/{config.rs, filter_task.rs:30-199}
   MaterializeFilesConfig / MaterializeFilesTask / ...  OPS/materialize_tasks/{config.rs, materialize_files_task.rs:30-230}
   OperatorTask::{Filter{expr}, MaterializeFiles{data_format, fields}}  src/planner/physical_planner.rs:58-65
+  OrderByOperatorTask / OrderByTask         not in the reference (its DEV_NOTES.md lists ORDER BY as the next operator):
+                                            a blocking single-instance sort over `record_utils.sort_records`
 
 The hot loops call `record_utils.filter_record` / `project_record` exactly where the reference does
 (filter_task.rs:99, materialize_files_task.rs:110); here those are the HIP kernels.  The control plane around
@@ -57,6 +59,17 @@ class ReadFilesOperatorTask:
         return "read_files"
 
 
+@dataclasses.dataclass(frozen=True)
+class OrderByOperatorTask:
+    """ORDER BY keys [LIMIT n] (the reference's planner has no such task yet; shaped like its siblings)"""
+    order_by: Sequence[A.OrderByExpr]
+    limit: Optional[int] = None
+    max_rows_per_record: int = 10_000   # physical_planner.rs:323 (the records the read_files task sends)
+
+    def task_name(self) -> str:
+        return "order_by"
+
+
 @dataclasses.dataclass
 class OperatorInstanceConfig:
     """operator_handler_state.rs:28-35 (fields the tasks use)"""
@@ -88,6 +101,7 @@ class OperatorTaskRegistry:
         self.materialize_files_task: Optional[TaskBuilder] = None
         self.materialize_data_formats: List[str] = []
         self.table_func_tasks: dict = {}
+        self.order_by_task: Optional[TaskBuilder] = None
 
     def add_filter_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
         if self.filter_task is not None:
@@ -109,11 +123,19 @@ class OperatorTaskRegistry:
         self.table_func_tasks[func_name] = builder
         return self
 
+    def add_order_by_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        if self.order_by_task is not None:
+            raise OperatorTaskRegistryError("order by task builder already set")
+        self.order_by_task = builder
+        return self
+
     def find_task_builder(self, task) -> Optional[TaskBuilder]:
         if isinstance(task, ReadFilesOperatorTask):
             return self.table_func_tasks.get("read_files")
         if isinstance(task, FilterOperatorTask):
             return self.filter_task
+        if isinstance(task, OrderByOperatorTask):
+            return self.order_by_task
         if isinstance(task, MaterializeFilesOperatorTask):
             if task.data_format in self.materialize_data_formats:
                 return self.materialize_files_task
@@ -220,6 +242,98 @@ class FilterTaskBuilder(TaskBuilder):
                 task.async_main()
                 return None
             except Exception as err:   # noqa: BLE001 -- any error ends the instance (producer_operator.rs:179-183)
+                return err
+
+        run.task = task
+        return run
+
+
+# ---- order by ---------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class OrderByConfig:
+    order_by: Sequence[A.OrderByExpr]
+    limit: Optional[int] = None
+    max_rows_per_record: int = 10_000
+
+    @staticmethod
+    def try_from(op_in_config: OperatorInstanceConfig) -> "OrderByConfig":
+        t = op_in_config.task
+        if not isinstance(t, OrderByOperatorTask):
+            raise ValueError("operator instance config is not an order by task")
+        if not t.order_by:
+            raise ValueError("an order by task needs at least one key")
+        if t.max_rows_per_record < 1:
+            raise ValueError("max_rows_per_record must be at least 1")
+        return OrderByConfig(tuple(t.order_by), t.limit, t.max_rows_per_record)
+
+
+class OrderByTask:
+    """A blocking, single-instance operator: pulls every inbound record (each tracked and heart-beaten by the
+    RecordHandler while it is held), sorts them all with ONE `sort_records` call, sends the result cut into records of
+    at most `max_rows_per_record` rows with record ids 0, 1, 2, ... in sorted order, and only then acks its inputs --
+    if anything fails before that, the exchange requeues them (the ack-after-send rule of FilterTask).  `sort_fn(records,
+    table_aliases, order_by, limit)` replaces the library call (tests on the CPU)."""
+
+    def __init__(self, op_in_config: OperatorInstanceConfig, config: OrderByConfig, inbound_exchanges, outbound_exchange,
+                 sort_fn=None, ctx=None):
+        self.operator_instance_config = op_in_config
+        self.config = config
+        self.inbound_exchanges = inbound_exchanges
+        self.outbound_exchange = outbound_exchange
+        self._sort = sort_fn
+        self._ctx = ctx
+        self.rows_in = 0
+        self.rows_out = 0
+        self.records_sent = 0
+
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
+        return self._ctx
+
+    def _sort_records(self, records, aliases):
+        if self._sort is not None:
+            return self._sort(records, aliases, self.config.order_by, self.config.limit)
+        return record_utils.sort_records(records, aliases, self.config.order_by, limit=self.config.limit, ctx=self._context())
+
+    def async_main(self) -> None:
+        rec_handler = RecordHandler.initiate(self.operator_instance_config, self.inbound_exchanges, self.outbound_exchange)
+        try:
+            held = []
+            while True:
+                exchange_rec = rec_handler.next_record_to_hold()
+                if exchange_rec is None:
+                    break
+                held.append(exchange_rec)
+            if not held:
+                return
+            self.rows_in = sum(h.record.num_rows for h in held)
+            aliases = held[0].table_aliases
+            result = self._sort_records([h.record for h in held], aliases)
+            n, step = result.num_rows, self.config.max_rows_per_record
+            for record_id, start in enumerate(range(0, max(n, 1), step)):
+                rec_handler.send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), aliases)
+                self.records_sent += 1
+            self.rows_out = n
+            for h in held:
+                rec_handler.complete_record(h)
+        finally:
+            rec_handler.close()
+
+
+class OrderByTaskBuilder(TaskBuilder):
+    def __init__(self, sort_fn=None):
+        self._sort_fn = sort_fn
+
+    def build(self, op_in_config, inbound_exchanges, outbound_exchange):
+        task = OrderByTask(op_in_config, OrderByConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
+                           sort_fn=self._sort_fn)
+
+        def run():
+            try:
+                task.async_main()
+                return None
+            except Exception as err:   # noqa: BLE001 -- any error ends the instance
                 return err
 
         run.task = task
@@ -430,4 +544,5 @@ def build_default_operator_task_registry(storage_root: str) -> OperatorTaskRegis
     return (OperatorTaskRegistry()
             .add_table_func_task_builder("read_files", ReadFilesTaskBuilder(storage_root))
             .add_filter_task_builder(FilterTaskBuilder())
+            .add_order_by_task_builder(OrderByTaskBuilder())
             .add_materialize_files_builder(MaterializeFilesTaskBuilder(storage_root), ["parquet"]))

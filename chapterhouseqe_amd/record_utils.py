@@ -759,6 +759,79 @@ def filter_records_coalesced(recs, table_aliases: Optional[Sequence[Sequence[str
     return _finish(ctx, rc, out, dev_out), list(rows)
 
 
+# ------------------------------------------------------------------------------------------ ORDER BY
+def _sort_keys_to_c(order_by: Sequence[A.OrderByExpr]):
+    keys = (L.SortKey * max(1, len(order_by)))()
+    for i, o in enumerate(order_by):
+        if not isinstance(o, A.OrderByExpr):
+            raise TypeError(f"not an OrderByExpr: {o!r}")
+        desc, nulls_first = o.sort_options()
+        keys[i].column = _expr_to_c(o.expr)
+        keys[i].descending = int(desc)
+        keys[i].nulls_first = int(nulls_first)
+    return keys
+
+
+def _free_sort_keys(keys, n: int) -> None:
+    for i in range(n):
+        if keys[i].column:
+            L.lib().chq_expr_free(keys[i].column)
+
+
+def _limit_arg(limit: Optional[int]) -> int:
+    if limit is None:
+        return -1
+    if limit < 0:
+        raise ValueError("limit must be None or >= 0")
+    return int(limit)
+
+
+def sort_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]]], order_by: Sequence[A.OrderByExpr], *,
+                limit: Optional[int] = None, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
+    """ORDER BY (`chq_sort_record`): every column of `rec` permuted into the order of `order_by`, stable, cut to the
+    first `limit` rows.  Result residency follows the input unless `device_result` says otherwise."""
+    ctx, src, own_src, on_dev = _prepare(rec, ctx)
+    dev_out = on_dev if device_result is None else device_result
+    al = _Aliases(table_aliases)
+    keys = _sort_keys_to_c(order_by)
+    out = _CBatch()
+    try:
+        rc = L.lib().chq_sort_record(ctx.handle, C.byref(src.array), C.byref(src.schema), al.ptr, keys, len(order_by),
+                                     _limit_arg(limit), L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
+                                     C.byref(out.array), C.byref(out.schema))
+    finally:
+        _free_sort_keys(keys, len(order_by))
+        if own_src:
+            src.release()
+    return _finish(ctx, rc, out, dev_out)
+
+
+def sort_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], order_by: Sequence[A.OrderByExpr], *,
+                 limit: Optional[int] = None, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
+    """ORDER BY over a group (`chq_sort_records`): ONE batch holding the rows of every batch of `recs` (a sequence of
+    same-schema batches or a `RecordGroup`) in sorted order; ties keep batch order, then row order."""
+    if not isinstance(recs, RecordGroup):
+        recs = list(recs)
+        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
+        if any(x != sig[0] for x in sig[1:]):   # (the C call takes ONE schema for the group)
+            raise ChqError(22, "sort_records: every record batch must have the schema of the first")
+    grp = recs if isinstance(recs, RecordGroup) else RecordGroup(recs, ctx)
+    ctx = ctx or grp.ctx
+    dev_out = grp.on_device if device_result is None else device_result
+    al = _Aliases(table_aliases)
+    keys = _sort_keys_to_c(order_by)
+    out = _CBatch()
+    try:
+        rc = L.lib().chq_sort_records(ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema), al.ptr, keys, len(order_by),
+                                      _limit_arg(limit), L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
+                                      C.byref(out.array), C.byref(out.schema))
+    finally:
+        _free_sort_keys(keys, len(order_by))
+        if grp is not recs:
+            grp.release()
+    return _finish(ctx, rc, out, dev_out)
+
+
 def project_record(fields: Sequence[A.SelectItem], record: Record, table_aliases: Optional[Sequence[Sequence[str]]], *,
                    ctx: Optional[Context] = None, device_result: Optional[bool] = None):
     """RU/record_projection.rs:16-76."""

@@ -136,6 +136,21 @@ class ExprWithAlias(SelectItem):
     alias: Ident
 
 
+# ---- sqlparser::ast::OrderByExpr ---------------------------------------------------------------
+@dataclass(frozen=True)
+class OrderByExpr:
+    """`expr [ASC|DESC] [NULLS FIRST|LAST]`; None = not written.  The SQL defaults (resolved by `sort_options`):
+    ASC, and NULLS LAST for ASC / NULLS FIRST for DESC (PostgreSQL, DataFusion)."""
+    expr: Expr
+    asc: Optional[bool] = None
+    nulls_first: Optional[bool] = None
+
+    def sort_options(self) -> Tuple[bool, bool]:
+        """(descending, nulls_first) as the library's sort takes them"""
+        asc = True if self.asc is None else self.asc
+        return (not asc, (not asc) if self.nulls_first is None else self.nulls_first)
+
+
 # ---- small constructors used by tests (the reference builds these structs literally) ----------
 def ident(name: str) -> Identifier:
     return Identifier(Ident(name))

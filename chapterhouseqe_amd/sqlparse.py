@@ -8,6 +8,7 @@ associativity, `Nested` for parentheses, `Number` text kept verbatim -- for test
 sample queries (reference: sample_queries/simple.sql) to be written as SQL text.
 
     select <items> from <func>('<path>') [[as] alias] [where <expr>]
+        [order by <expr> [asc|desc] [nulls first|last] {, ...}] [limit <n>]
 """
 from __future__ import annotations
 
@@ -66,6 +67,8 @@ class Select:
     projection: Tuple[A.SelectItem, ...]
     from_: Optional[TableFunc]
     selection: Optional[A.Expr]
+    order_by: Tuple[A.OrderByExpr, ...] = ()
+    limit: Optional[int] = None
 
 
 def _tokenize(text: str) -> List[Tuple[str, str]]:
@@ -254,8 +257,35 @@ class _Parser:
         selection = None
         if self.accept_word("WHERE"):
             selection = self.parse_expr(0)
+        order_by: List[A.OrderByExpr] = []
+        if self.accept_word("ORDER"):
+            if not self.accept_word("BY"):
+                raise SqlParseError(f"expected BY after ORDER, found {self.peek()[1]!r}")
+            order_by.append(self.parse_order_by_expr())
+            while self.accept_op(","):
+                order_by.append(self.parse_order_by_expr())
+        limit = None
+        if self.accept_word("LIMIT"):
+            k, v = self.next()
+            if k != "number" or not v.isdigit():
+                raise SqlParseError(f"expected a non-negative integer after LIMIT, found {v!r}")
+            limit = int(v)
         self.accept_op(";")
-        return Select(tuple(items), from_, selection)
+        return Select(tuple(items), from_, selection, tuple(order_by), limit)
+
+    def parse_order_by_expr(self) -> A.OrderByExpr:
+        """sqlparser Parser::parse_order_by_expr"""
+        expr = self.parse_expr(0)
+        asc = True if self.accept_word("ASC") else (False if self.accept_word("DESC") else None)
+        nulls_first = None
+        if self.accept_word("NULLS"):
+            if self.accept_word("FIRST"):
+                nulls_first = True
+            elif self.accept_word("LAST"):
+                nulls_first = False
+            else:
+                raise SqlParseError(f"expected FIRST or LAST after NULLS, found {self.peek()[1]!r}")
+        return A.OrderByExpr(expr, asc, nulls_first)
 
 
 def parse_expr(text: str) -> A.Expr:

@@ -353,6 +353,38 @@ chq_status chq_record_to_parquet(chq_ctx* ctx, const struct ArrowDeviceArray* re
 chq_status chq_records_to_parquet(chq_ctx* ctx, int n_records, const struct ArrowDeviceArray* const* recs,
                                   const struct ArrowSchema* schema, chq_parquet_image* out);
 
+/* ---- ORDER BY: stable multi-key sort of a record batch --------------------------------------------
+ * The reference has no ORDER BY yet; these semantics are this library's (arrow-rs lexsort_to_indices with explicit
+ * SortOptions):
+ *   - a key is a column (Identifier / CompoundIdentifier), resolved through `table_aliases` like compute_value resolves
+ *     them (a missing column: the same status); any other expression: CHQ_ERR_NOT_SUPPORTED.
+ *   - key types: Int8..64, UInt8..64, Float16/32/64, Boolean (false < true), Date32/64, Time32/64, Timestamp and Duration
+ *     (as their signed integers), Decimal128 (signed 128-bit), Utf8 (bytewise, a proper prefix first).  Floats follow
+ *     totalOrder: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN.  Other types (FixedSizeBinary, ...): CHQ_ERR_NOT_SUPPORTED.
+ *   - `descending` reverses the value order; `nulls_first` puts null keys before (else after) the others, whatever the
+ *     direction.  Both are explicit here (the SQL defaults, ASC and NULLS LAST for ASC / NULLS FIRST for DESC, are the
+ *     front-end's).
+ *   - stable: rows with equal keys keep input order (for a group: batch order, then row order).
+ *   - every column comes out permuted; the schema is the input's; null counts are exact; output conventions are those of
+ *     chq_filter_record.  `limit` -1: every row, else the first min(limit, rows) rows of the sorted order.
+ *   - fewer than 2^32 rows per call (else CHQ_ERR_NOT_SUPPORTED); an output Utf8 column past int32 offsets:
+ *     CHQ_ERR_ARROW_INVALID_ARGUMENT naming it.
+ * Inputs may be host or device resident and sliced; `out_device` is ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM.  On failure
+ * nothing is returned (release == NULL). */
+typedef struct chq_sort_key {
+  const chq_expr* column;
+  int descending;
+  int nulls_first;
+} chq_sort_key;
+chq_status chq_sort_record(chq_ctx* ctx, const struct ArrowDeviceArray* rec, const struct ArrowSchema* schema,
+                           const chq_table_aliases* table_aliases, const chq_sort_key* keys, int n_keys, int64_t limit,
+                           int out_device, struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
+/* The same over `n_records` batches of ONE schema: ONE joined, sorted batch (the group is joined on the device first). */
+chq_status chq_sort_records(chq_ctx* ctx, int n_records, const struct ArrowDeviceArray* const* recs,
+                            const struct ArrowSchema* schema, const chq_table_aliases* table_aliases,
+                            const chq_sort_key* keys, int n_keys, int64_t limit, int out_device,
+                            struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
+
 /* Wrap caller-owned device (or host) buffers as a record batch without copying; the buffers must
  * outlive the returned structs, whose release callbacks free only the descriptors. `format` is an
  * Arrow C format string ("i","f","g","l","b","u", ...). */

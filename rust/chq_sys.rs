@@ -44,6 +44,14 @@ pub struct chq_select_item {
     pub alias: *const c_char,
 }
 
+/// struct chq_sort_key: one ORDER BY key (explicit direction and null placement)
+#[repr(C)]
+pub struct chq_sort_key {
+    pub column: *const chq_expr,
+    pub descending: c_int,
+    pub nulls_first: c_int,
+}
+
 #[repr(C)]
 pub struct chq_alias_list {
     pub aliases: *const *const c_char,
@@ -150,6 +158,18 @@ extern "C" {
         ctx: *mut chq_ctx, n_records: c_int, recs: *const *const ArrowDeviceArray, schema: *const FFI_ArrowSchema,
         table_aliases: *const chq_table_aliases, expr: *const chq_expr, out_device: c_int,
         out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema, rows_per_record: *mut i64,
+    ) -> c_int;
+    /// ORDER BY (stable multi-key sort): one sorted batch; `limit` -1 = every row
+    pub fn chq_sort_record(
+        ctx: *mut chq_ctx, rec: *const ArrowDeviceArray, schema: *const FFI_ArrowSchema,
+        table_aliases: *const chq_table_aliases, keys: *const chq_sort_key, n_keys: c_int, limit: i64,
+        out_device: c_int, out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
+    ) -> c_int;
+    /// the same over a group of batches of one schema: ONE joined, sorted batch
+    pub fn chq_sort_records(
+        ctx: *mut chq_ctx, n_records: c_int, recs: *const *const ArrowDeviceArray, schema: *const FFI_ArrowSchema,
+        table_aliases: *const chq_table_aliases, keys: *const chq_sort_key, n_keys: c_int, limit: i64,
+        out_device: c_int, out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
     ) -> c_int;
     pub fn chq_project_record(
         ctx: *mut chq_ctx, fields: *const chq_select_item, n_fields: c_int, rec: *const ArrowDeviceArray,

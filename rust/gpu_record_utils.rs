@@ -13,7 +13,7 @@ use std::sync::Arc;
 use anyhow::{anyhow, Result};
 use arrow::array::{Array, RecordBatch, StructArray};
 use arrow::ffi::{from_ffi, to_ffi, FFI_ArrowArray, FFI_ArrowSchema};
-use sqlparser::ast::{BinaryOperator, Expr, SelectItem, Value};
+use sqlparser::ast::{BinaryOperator, Expr, OrderByExpr, SelectItem, Value};
 
 use super::chq_sys::*;
 
@@ -142,6 +142,36 @@ pub fn filter_records(ctx: &GpuContext, recs: &[Arc<RecordBatch>], table_aliases
         return Err(ctx.err(rc)); // the error of the earliest failing batch; nothing was returned
     }
     outs.into_iter().zip(schemas.into_iter()).map(|(a, s)| import(a, s)).collect()
+}
+
+/// ORDER BY over every record an order-by task holds: ONE sorted batch (chq_sort_records).  `order_by` mirrors
+/// sqlparser's OrderByExpr: `asc` None = ASC, `nulls_first` None = NULLS LAST for ASC, NULLS FIRST for DESC.
+pub fn sort_records(ctx: &GpuContext, recs: &[Arc<RecordBatch>], table_aliases: &Vec<Vec<String>>, order_by: &[OrderByExpr],
+                    limit: Option<usize>) -> Result<RecordBatch> {
+    if recs.is_empty() {
+        return Err(anyhow!("sort_records: no record batch"));
+    }
+    let exported: Vec<(ArrowDeviceArray, FFI_ArrowSchema)> = recs.iter().map(|r| export(r)).collect::<Result<_>>()?;
+    let ptrs: Vec<*const ArrowDeviceArray> = exported.iter().map(|(a, _)| a as *const ArrowDeviceArray).collect();
+    let al = lower_aliases(table_aliases);
+    let ta = chq_table_aliases { columns: al.lists.as_ptr(), n_columns: al.lists.len() as i32 };
+    let keys: Vec<chq_sort_key> = order_by.iter().map(|o| {
+        let asc = o.asc.unwrap_or(true);
+        chq_sort_key { column: lower_expr(&o.expr), descending: (!asc) as i32, nulls_first: o.nulls_first.unwrap_or(!asc) as i32 }
+    }).collect();
+    let mut out: ArrowDeviceArray = unsafe { std::mem::zeroed() };
+    let mut out_schema = FFI_ArrowSchema::empty();
+    let rc = unsafe {
+        chq_sort_records(ctx.0, recs.len() as i32, ptrs.as_ptr(), &exported[0].1, &ta, keys.as_ptr(), keys.len() as i32,
+                         limit.map(|l| l as i64).unwrap_or(-1), ARROW_DEVICE_CPU, &mut out, &mut out_schema)
+    };
+    for k in &keys {
+        unsafe { chq_expr_free(k.column as *mut chq_expr) };
+    }
+    if rc != 0 {
+        return Err(ctx.err(rc));
+    }
+    import(out, out_schema)
 }
 
 /// record_utils::project_record on the GPU (record_projection.rs:16-76)
