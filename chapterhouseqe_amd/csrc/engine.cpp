@@ -156,6 +156,17 @@ void join_aux_streams(Context& ctx) {
   }
 }
 
+void kernel_span_begin(Context& ctx) {
+  if (ctx.opt_time_kernels && !ctx.ev0) { check_hip(hipEventCreate(&ctx.ev0), "hipEventCreate"); check_hip(hipEventCreate(&ctx.ev1), "hipEventCreate"); }
+  if (ctx.opt_time_kernels) check_hip(hipEventRecord(ctx.ev0, ctx.stream), "hipEventRecord");
+}
+void kernel_span_end(Context& ctx) { if (ctx.opt_time_kernels) check_hip(hipEventRecord(ctx.ev1, ctx.stream), "hipEventRecord"); }
+int64_t kernel_span_ns(Context& ctx) {
+  float ms = 0;
+  if (ctx.opt_time_kernels) check_hip(hipEventElapsedTime(&ms, ctx.ev0, ctx.ev1), "hipEventElapsedTime");
+  return (int64_t)(ms * 1e6);
+}
+
 Context::~Context() {
   if (ev0) (void)hipEventDestroy(ev0);
   if (ev1) (void)hipEventDestroy(ev1);
@@ -641,6 +652,45 @@ void ensure_scratch(Context& ctx, int64_t ntiles) {
 }
 Scratch* dev_scratch(Context& ctx) { return (Scratch*)ctx.small->ptr; }
 u64* dev_status(Context& ctx) { return (u64*)((uint8_t*)ctx.small->ptr + kHeader); }
+// The header into its pinned mirror, the stream synchronised.  (ensure_scratch may replace ctx.small: looked up per call.)
+Scratch* read_scratch(Context& ctx) {
+  Scratch* hs = (Scratch*)ctx.pinned;
+  check_hip(hipMemcpyAsync(hs, dev_scratch(ctx), sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
+  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  return hs;
+}
+// header + the status words of `ntiles` tiles: cleared before a call's first chained-scan launch
+void clear_scratch(Context& ctx, int64_t ntiles) {
+  check_hip(hipMemsetAsync(dev_scratch(ctx), 0, kHeader + (size_t)(ntiles + 1) * 8, ctx.stream), "memset scratch + status");
+}
+template <class P>   // FilterParams, FusedParams
+void bind_scratch(P& p, Context& ctx) {
+  Scratch* ds = dev_scratch(ctx);
+  p.status = dev_status(ctx); p.ticket = &ds->ticket; p.total = &ds->total; p.err = &ds->err;
+}
+// p.outs[k] copies launch column k from in(ci) to out(ci)
+template <class In, class Out>
+void fill_outs(FilterParams& p, const std::vector<int>& launch_cols, const std::vector<Column>& cols, In in, Out out) {
+  p.n_out = 0;
+  for (int ci : launch_cols) p.outs[p.n_out++] = OutCol{in(ci), out(ci), (uint32_t)cols[ci].width, 0};
+}
+int grid_cap(const Context& ctx, int tile_kind) { return ctx.num_cus * (ctx.opt_grid_per_cu > 0 ? (int)ctx.opt_grid_per_cu : kGridPerCu[tile_kind]); }
+
+// launch(partial, grid, tail) over p's tiles.  Large batches: all complete tiles run in the instantiation without partial-tile
+// code; the (single) incomplete tail tile in a second one-workgroup launch that continues the same chained scan.
+template <class Params, class Launch>
+void launch_tiles(Context& ctx, Params& p, int64_t rows, int64_t tile_rows, int64_t gcap, Launch&& launch) {
+  const int64_t ntiles = (rows + tile_rows - 1) / tile_rows, nfull = rows / tile_rows;
+  const bool split = rows >= ctx.opt_split_rows && nfull > 0;
+  p.tile_begin = 0; p.tile_end = split ? nfull : ntiles;
+  launch(!split, (int)std::min<int64_t>(p.tile_end, gcap), false);
+  ++ctx.stats.launches;
+  if (split && nfull < ntiles) {
+    p.tile_begin = nfull; p.tile_end = ntiles;
+    launch(true, 1, true);
+    ++ctx.stats.launches;
+  }
+}
 
 // FAST_UOPS (device_program.h): pre-decode a program whose every instruction works on non-null Int32 / UInt32 / Float32
 // columns, 32-bit literals and boolean temporaries into (operand kind, loop body) pairs.  Returns false -- the generic
@@ -967,6 +1017,13 @@ TypedExpr typed(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& p
   return te;
 }
 
+// what the one-launch paths filter with: no pending error, a Boolean result, not a literal-only (length-1) mask
+bool is_row_predicate(const TypedExpr& te) {
+  if (te.pending_code) return false;
+  const Node& root = te.at(te.root);
+  return root.type == T_BOOL && !root.len1;
+}
+
 Column empty_like(const Column& c) {
   Column o;
   o.name = c.name; o.format = c.format; o.type = c.type; o.width = c.width; o.nullable = c.nullable;
@@ -1003,12 +1060,11 @@ Column uniform_to_utf8(Context& ctx, Column&& fixed, const Column& like, int64_t
   return u;
 }
 
-}  // namespace
-
-// =================================================================================================
-// filter_record
-// =================================================================================================
-Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& expr, SplitRequest* split) {
+// ---- filter_record, stage by stage ---------------------------------------------------------------------------------------
+constexpr size_t kNullPerRound = 16, kUtf8PerRound = 8;   // follow-up rounds: null counters / Utf8 columns per read-back
+// Stage 1, typing and lowering.  `rec`: what the program's column refs index, the batch or (fit_to_device) `work`.
+struct FilterProgram { Lowered lw; int64_t mask_len = 0; const Batch* rec = nullptr; Batch work; std::vector<PlanColumn> wcols; TypedExpr fitted; };
+void type_filter(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& expr, FilterProgram& fp) {
   const int64_t nrows = rec.nrows;
   TypedExpr te = typed(ctx, rec, pcols, expr);
   if (te.nodes[(size_t)te.root].kind == Node::CONST && te.nodes[(size_t)te.root].cval.null) {
@@ -1023,142 +1079,154 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
   }
   // A literal-only predicate is a length-1 mask: arrow filters just the first row (and rejects a mask
   // longer than the columns) -- reproduced, not "fixed" (SURVEY.md section 8 a8).
-  const int64_t mask_len = root.len1 ? 1 : nrows;
-  if (mask_len > nrows && !rec.cols.empty())
-    throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Filter predicate of length " + std::to_string(mask_len) +
+  fp.mask_len = root.len1 ? 1 : nrows;
+  if (fp.mask_len > nrows && !rec.cols.empty())
+    throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Filter predicate of length " + std::to_string(fp.mask_len) +
                                                        " is larger than target array of length " + std::to_string(nrows)};
-  Lowered lw;
-  Batch work; std::vector<PlanColumn> wcols; TypedExpr fitted;
-  const Batch* prog_rec = &rec;   // what the program's column refs index: the batch, or the batch + temporary columns
+  fp.rec = &rec;
   try {
-    lower_expr(te, te.root, pcols, lw);
+    lower_expr(te, te.root, pcols, fp.lw);
   } catch (const ChqError& e) {
     if (e.code != CHQ_INTERNAL_PROGRAM_LIMIT) throw;
-    fit_to_device(ctx, rec, pcols, te, work, wcols, fitted);   // sub-trees -> temporary columns until the rest fits
-    lw = Lowered{};
-    lower_expr(fitted, fitted.root, wcols, lw);
-    prog_rec = &work;
+    fit_to_device(ctx, rec, pcols, te, fp.work, fp.wcols, fp.fitted);   // sub-trees -> temporary columns until the rest fits
+    fp.lw = Lowered{};
+    lower_expr(fp.fitted, fp.fitted.root, fp.wcols, fp.lw);
+    fp.rec = &fp.work;
   }
+}
 
-  // ---- Utf8 columns whose values all have the same length (keys, hashes, dates as text, the reference's own sample
-  // strings -- create_sample_data.rs) are fixed-width columns in disguise: value i lies at data + offsets[0] + i L.  One
-  // cheap pass over the offsets proves it (4 B/row); the column then goes through the fixed-width copy of the main kernel
-  // (whole 8- or 16-byte values per lane) instead of the per-row string scatter, and its new offsets are 0, L, 2 L, ...
-  // Config-5 shape: 0.99 -> 0.6 ms per 125 M-row batch.  Only columns the predicate does not read, without nulls.
-  if (prog_rec == &rec && mask_len == nrows && ctx.opt_uniform_utf8_rows > 0 && nrows >= ctx.opt_uniform_utf8_rows && rec.on_device) {
-    std::vector<int> cand;
-    for (size_t i = 0; i < rec.cols.size(); ++i) {
-      const Column& c = rec.cols[i];
-      if (c.type != T_UTF8 || !c.values || !c.data || !uniform_utf8_ok(c.validity && c.null_count != 0, nrows, 1)) continue;
-      if (std::find(lw.refs.begin(), lw.refs.end(), (int)i) != lw.refs.end()) continue;
-      cand.push_back((int)i);
-    }
-    if (!cand.empty()) {
-      // (with `time_kernels` the check and the offsets kernels are timed too and added to the call's kernel time: the
-      // roofline of this path must not be flattered by leaving its extra passes out)
-      hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
-      struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } tev_guard{tev};
-      if (ctx.opt_time_kernels) for (auto& e : tev) check_hip(hipEventCreate(&e), "hipEventCreate");
-      auto d_chk = make_device_buffer(cand.size() * 16 + 16, ctx.device);
-      check_hip(hipMemsetAsync(d_chk->ptr, 0, cand.size() * 16, ctx.stream), "memset");
-      if (tev[0]) check_hip(hipEventRecord(tev[0], ctx.stream), "hipEventRecord");
-      for (size_t k = 0; k < cand.size(); ++k) {
-        Utf8UniformParams up{(const int32_t*)rec.cols[(size_t)cand[k]].values0(), nrows, (int32_t*)d_chk->ptr + 4 * k};
-        check_hip(launch_utf8_uniform(up, ctx.stream), "launch utf8_uniform_kernel");
-      }
-      if (tev[1]) check_hip(hipEventRecord(tev[1], ctx.stream), "hipEventRecord");
-      std::vector<int32_t> h_chk(cand.size() * 4);
-      check_hip(hipMemcpyAsync(h_chk.data(), d_chk->ptr, cand.size() * 16, hipMemcpyDeviceToHost, ctx.stream), "read back");
-      check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-      Batch view = rec;
-      std::vector<PlanColumn> vcols = pcols;
-      std::vector<int> turned;
-      for (size_t k = 0; k < cand.size(); ++k) {
-        const int32_t differs = h_chk[4 * k], len = h_chk[4 * k + 1], first = h_chk[4 * k + 2];
-        if (differs || first < 0 || !uniform_utf8_ok(false, nrows, len)) continue;
-        Column& v = view.cols[(size_t)cand[k]];
-        v.type = T_FIXED_OPAQUE; v.format = "w:" + std::to_string(len); v.width = len;
-        v.values = v.data + first; v.data = nullptr; v.data_bytes = -1; v.offset = 0; v.validity = nullptr; v.null_count = 0;
-        vcols[(size_t)cand[k]].type = T_FIXED_OPAQUE; vcols[(size_t)cand[k]].format = v.format; vcols[(size_t)cand[k]].width = len;
-        vcols[(size_t)cand[k]].has_nulls = false;
-        turned.push_back(cand[k]);
-      }
-      if (!turned.empty()) {
-        Batch res = filter_record(ctx, view, vcols, expr, split);   // (no eligible Utf8 column is left in the view: no further recursion)
-        if (tev[2]) check_hip(hipEventRecord(tev[2], ctx.stream), "hipEventRecord");
-        for (int ci : turned) {
-          Column& o = res.cols[(size_t)ci];
-          o = uniform_to_utf8(ctx, std::move(o), rec.cols[(size_t)ci], res.nrows, true);   // (counts the offsets written)
-          ctx.stats.bytes_read_alg += (nrows + 1) * 4;   // the offsets were read by the check
-        }
-        if (tev[3]) check_hip(hipEventRecord(tev[3], ctx.stream), "hipEventRecord");
-        check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-        if (tev[0]) {
-          float a = 0, b = 0;
-          check_hip(hipEventElapsedTime(&a, tev[0], tev[1]), "hipEventElapsedTime");
-          check_hip(hipEventElapsedTime(&b, tev[2], tev[3]), "hipEventElapsedTime");
-          ctx.stats.kernel_ns += (int64_t)((a + b) * 1e6);
-        }
-        ctx.stats.launches += (int64_t)(cand.size() + turned.size());
-        return res;
-      }
-    }
-  }
-
-  Batch out;
-  out.on_device = true; out.device_id = ctx.device;
-  ctx.stats = chq_call_stats{};
-  ctx.stats.rows_in = nrows;
-  for (const Column& c : rec.cols) out.cols.push_back(empty_like(c));
-  if (mask_len == 0) {   // empty in, empty out (schema preserved)
-    for (size_t i = 0; i < rec.cols.size(); ++i) {
-      Column& o = out.cols[i];
-      auto vb = make_device_buffer(16, ctx.device);
-      check_hip(hipMemsetAsync(vb->ptr, 0, 16, ctx.stream), "memset");
-      o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
-      if (o.type == T_UTF8) { auto db = make_device_buffer(16, ctx.device); o.data = (const uint8_t*)db->ptr; o.owned.push_back(db); }
-    }
-    check_hip(hipStreamSynchronize(ctx.stream), "sync");
-    out.nrows = 0;
-    return out;
-  }
-
-  const int tile_kind = pick_tile_kind(ctx, lw, mask_len);
-  const int64_t tile_rows = kTileRows[tile_kind];
-  const int64_t ntiles = (mask_len + tile_rows - 1) / tile_rows;
-  ensure_scratch(ctx, ntiles);
-  Scratch* ds = dev_scratch(ctx);
-  auto str_bufs = upload_strings(ctx, lw);
-
-  // classify columns
-  std::vector<int> fixed_cols, bool_cols, utf8_cols, nullable_cols;
+// Stage 2, the uniform-length Utf8 detour.  Utf8 columns whose values all have the same length (keys, hashes, dates as text,
+// the reference's own sample strings -- create_sample_data.rs) are fixed-width columns in disguise: value i lies at
+// data + offsets[0] + i L.  One cheap pass over the offsets proves it (4 B/row); the column then goes through the fixed-width
+// copy of the main kernel (whole 8- or 16-byte values per lane) instead of the per-row string scatter, and its new offsets
+// are 0, L, 2 L, ...  Config-5 shape: 0.99 -> 0.6 ms per 125 M-row batch.  Only columns the predicate does not read, without
+// nulls.  True: `*res` is the call's result.
+bool uniform_detour(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& expr, SplitRequest* split,
+                    const FilterProgram& fp, Batch* res) {
+  const int64_t nrows = rec.nrows;
+  if (fp.rec != &rec || fp.mask_len != nrows || ctx.opt_uniform_utf8_rows <= 0 || nrows < ctx.opt_uniform_utf8_rows || !rec.on_device) return false;
+  std::vector<int> cand;
   for (size_t i = 0; i < rec.cols.size(); ++i) {
     const Column& c = rec.cols[i];
-    if (c.type == T_BOOL) bool_cols.push_back((int)i);
-    else if (c.type == T_UTF8) utf8_cols.push_back((int)i);
-    else fixed_cols.push_back((int)i);
-    if (c.validity && c.null_count != 0) nullable_cols.push_back((int)i);
+    if (c.type != T_UTF8 || !c.values || !c.data || !uniform_utf8_ok(c.validity && c.null_count != 0, nrows, 1)) continue;
+    if (std::find(fp.lw.refs.begin(), fp.lw.refs.end(), (int)i) != fp.lw.refs.end()) continue;
+    cand.push_back((int)i);
   }
-  Scratch* hs = (Scratch*)ctx.pinned;
-  // Utf8 columns of short strings are filtered inside the main kernel (device_program.h: Utf8Fold).  Their output
-  // capacity is the input byte span: known when the library built the column itself (staged, joined, decoded), one
-  // 8-byte read-back otherwise.
-  // Long strings (more than 24 bytes per row on average) get only their new offsets from the main kernel; the bytes are
-  // moved by utf8_copy_kernel (one wave per 64 rows), launched right behind it without a host round trip in between.
-  std::vector<int> fold_cols; std::vector<int64_t> fold_cap; std::vector<bool> fold_data;
-  if (ctx.opt_fold_utf8 && tile_kind != 2 && !utf8_cols.empty() && mask_len == nrows) {
+  if (cand.empty()) return false;
+  // (with `time_kernels` the check and the offsets kernels are timed too and added to the call's kernel time: the
+  // roofline of this path must not be flattered by leaving its extra passes out)
+  auto d_chk = make_device_buffer(cand.size() * 16 + 16, ctx.device);
+  check_hip(hipMemsetAsync(d_chk->ptr, 0, cand.size() * 16, ctx.stream), "memset");
+  kernel_span_begin(ctx);
+  for (size_t k = 0; k < cand.size(); ++k) {
+    Utf8UniformParams up{(const int32_t*)rec.cols[(size_t)cand[k]].values0(), nrows, (int32_t*)d_chk->ptr + 4 * k};
+    check_hip(launch_utf8_uniform(up, ctx.stream), "launch utf8_uniform_kernel");
+  }
+  kernel_span_end(ctx);
+  std::vector<int32_t> h_chk(cand.size() * 4);
+  check_hip(hipMemcpyAsync(h_chk.data(), d_chk->ptr, cand.size() * 16, hipMemcpyDeviceToHost, ctx.stream), "read back");
+  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  const int64_t check_ns = kernel_span_ns(ctx);   // (now: the inner call reuses the events)
+  Batch view = rec;
+  std::vector<PlanColumn> vcols = pcols;
+  std::vector<int> turned;
+  for (size_t k = 0; k < cand.size(); ++k) {
+    const int32_t differs = h_chk[4 * k], len = h_chk[4 * k + 1], first = h_chk[4 * k + 2];
+    if (differs || first < 0 || !uniform_utf8_ok(false, nrows, len)) continue;
+    Column& v = view.cols[(size_t)cand[k]];
+    v.type = T_FIXED_OPAQUE; v.format = "w:" + std::to_string(len); v.width = len;
+    v.values = v.data + first; v.data = nullptr; v.data_bytes = -1; v.offset = 0; v.validity = nullptr; v.null_count = 0;
+    PlanColumn& vc = vcols[(size_t)cand[k]];
+    vc.type = T_FIXED_OPAQUE; vc.format = v.format; vc.width = len; vc.has_nulls = false;
+    turned.push_back(cand[k]);
+  }
+  if (turned.empty()) return false;
+  *res = filter_record(ctx, view, vcols, expr, split);   // (no eligible Utf8 column is left in the view: no further recursion)
+  kernel_span_begin(ctx);
+  for (int ci : turned) {
+    Column& o = res->cols[(size_t)ci];
+    o = uniform_to_utf8(ctx, std::move(o), rec.cols[(size_t)ci], res->nrows, true);   // (counts the offsets written)
+    ctx.stats.bytes_read_alg += (nrows + 1) * 4;   // the offsets were read by the check
+  }
+  kernel_span_end(ctx);
+  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  ctx.stats.kernel_ns += check_ns + kernel_span_ns(ctx);
+  ctx.stats.launches += (int64_t)(cand.size() + turned.size());
+  return true;
+}
+
+// Stage 3: empty in, empty out (schema preserved)
+Batch empty_filter_result(Context& ctx, const Batch& rec) {
+  Batch out;
+  out.on_device = true; out.device_id = ctx.device; out.nrows = 0;
+  for (const Column& c : rec.cols) {
+    Column o = empty_like(c);
+    auto vb = make_device_buffer(16, ctx.device);
+    check_hip(hipMemsetAsync(vb->ptr, 0, 16, ctx.stream), "memset");
+    o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
+    if (o.type == T_UTF8) { auto db = make_device_buffer(16, ctx.device); o.data = (const uint8_t*)db->ptr; o.owned.push_back(db); }
+    out.cols.push_back(std::move(o));
+  }
+  check_hip(hipStreamSynchronize(ctx.stream), "sync");
+  return out;
+}
+
+// Stages 4 to 7 of one call: launch geometry, columns by kind, the fold plan, the selection bitmap and the output
+struct FilterCall {
+  Context& ctx; const Batch& rec; const FilterProgram& fp; SplitRequest* split;
+  int tile_kind;
+  int64_t mask_len, tile_rows, ntiles, ngroups, total = 0;
+  std::vector<BufferPtr> str_bufs;
+  std::vector<int> fixed_cols, bool_cols, utf8_cols, nullable_cols;   // (utf8_cols: those the follow-up rounds filter)
+  std::vector<int> fold_cols; std::vector<int64_t> fold_cap; std::vector<bool> fold_data;   // filtered by the main kernel
+  std::vector<BufferPtr> fold_status;
+  bool need_followup = false;   // (then the main kernel writes the selection bitmap)
+  BufferPtr sel_mask, grp_base;
+  Batch out;
+
+  FilterCall(Context& c, const Batch& r, const FilterProgram& p, SplitRequest* s)
+      : ctx(c), rec(r), fp(p), split(s), tile_kind(pick_tile_kind(c, p.lw, p.mask_len)), mask_len(p.mask_len), tile_rows(kTileRows[tile_kind]),
+        ntiles((mask_len + tile_rows - 1) / tile_rows), ngroups((mask_len + 63) / 64) {
+    out.on_device = true; out.device_id = ctx.device;
+    for (const Column& col : rec.cols) out.cols.push_back(empty_like(col));
+    ensure_scratch(ctx, ntiles);
+    str_bufs = upload_strings(ctx, fp.lw);
+    for (size_t i = 0; i < rec.cols.size(); ++i) {
+      const Column& col = rec.cols[i];
+      if (col.type == T_BOOL) bool_cols.push_back((int)i);
+      else if (col.type == T_UTF8) utf8_cols.push_back((int)i);
+      else fixed_cols.push_back((int)i);
+      if (col.validity && col.null_count != 0) nullable_cols.push_back((int)i);
+    }
+  }
+  void plan_fold(); void launch_main(); void read_main(); void follow_ups();   // (the stages)
+  // first / last input offset of Utf8 columns [u0, u1) into the scratch header: their outputs' byte capacity
+  void gather_utf8_ends(size_t u0, size_t u1) {
+    if (u1 <= u0) return;
+    GatherParams gp{};
+    for (size_t k = u0; k < u1; ++k) {
+      const int32_t* offs = (const int32_t*)rec.cols[utf8_cols[k]].values0();
+      gp.src[2 * (k - u0)] = offs; gp.src[2 * (k - u0) + 1] = offs + mask_len;
+    }
+    gp.n = (int32_t)(2 * (u1 - u0)); gp.dst = dev_scratch(ctx)->utf8_ends;
+    check_hip(launch_gather_i32(gp, ctx.stream), "launch gather_i32_kernel");
+  }
+};
+
+// Stage 4, the fold plan.  Utf8 columns of short strings are filtered inside the main kernel (device_program.h: Utf8Fold).
+// Their output capacity is the input byte span: known when the library built the column itself (staged, joined, decoded),
+// one 8-byte read-back otherwise.  Long strings (more than 24 bytes per row on average) get only their new offsets from the
+// main kernel; the bytes are moved by utf8_copy_kernel (one wave per 64 rows), launched right behind it.
+void FilterCall::plan_fold() {
+  if (ctx.opt_fold_utf8 && tile_kind != 2 && !utf8_cols.empty() && mask_len == rec.nrows) {
     const size_t ncand = std::min<size_t>(MAX_FOLD_UTF8, utf8_cols.size());
     std::vector<int64_t> cap(ncand, -1);
     bool unknown = false;
     for (size_t k = 0; k < ncand; ++k) { cap[k] = rec.cols[utf8_cols[k]].data_bytes; unknown |= cap[k] < 0; }
     if (unknown) {
-      GatherParams gp{};
-      for (size_t k = 0; k < ncand; ++k) {
-        const int32_t* offs = (const int32_t*)rec.cols[utf8_cols[k]].values0();
-        gp.src[2 * k] = offs; gp.src[2 * k + 1] = offs + mask_len;
-      }
-      gp.n = (int32_t)(2 * ncand); gp.dst = ds->utf8_ends;
-      check_hip(launch_gather_i32(gp, ctx.stream), "launch gather_i32_kernel");
+      Scratch* ds = dev_scratch(ctx);
+      Scratch* hs = (Scratch*)ctx.pinned;
+      gather_utf8_ends(0, ncand);
       check_hip(hipMemcpyAsync(hs->utf8_ends, ds->utf8_ends, sizeof(hs->utf8_ends), hipMemcpyDeviceToHost, ctx.stream), "read back");
       check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
       for (size_t k = 0; k < ncand; ++k) cap[k] = (int64_t)hs->utf8_ends[2 * k + 1] - hs->utf8_ends[2 * k];
@@ -1170,19 +1238,19 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
     }
     utf8_cols.swap(rest);
   }
-  std::vector<BufferPtr> fold_status;
   const bool fold_long = std::find(fold_data.begin(), fold_data.end(), false) != fold_data.end();
-  const bool need_followup = !bool_cols.empty() || !utf8_cols.empty() || !nullable_cols.empty() || (int)fixed_cols.size() > MAX_OUT ||
-                             (split && !split->starts.empty()) || fold_long;
-  const int64_t ngroups = (mask_len + 63) / 64;
-  BufferPtr sel_mask, grp_base;
+  need_followup = !bool_cols.empty() || !utf8_cols.empty() || !nullable_cols.empty() || (int)fixed_cols.size() > MAX_OUT ||
+                    (split && !split->starts.empty()) || fold_long;
   if (need_followup) {
     sel_mask = make_device_buffer((size_t)(ngroups + 2) * 8, ctx.device);
     grp_base = make_device_buffer((size_t)(ngroups + 2) * 8, ctx.device);
   }
+}
 
-  // output buffers for fixed-width columns: capacity = mask_len rows
-  for (int ci : fixed_cols) {
+// Stage 5, the main kernel: MAX_OUT fixed-width columns per pass.  Only the first pass evaluates the predicate (writing the
+// selection bitmap when anything follows up) and is timed.
+void FilterCall::launch_main() {
+  for (int ci : fixed_cols) {   // output capacity = mask_len rows
     Column& o = out.cols[ci];
     auto vb = make_device_buffer((size_t)mask_len * o.width + 16, ctx.device);
     o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
@@ -1190,21 +1258,17 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
   }
   // predicate inputs that are not output columns cannot occur for filter_record (SELECT * semantics):
   // every referenced column is also copied, so it is counted once above.
-
-  const int grid_cap = ctx.num_cus * (ctx.opt_grid_per_cu > 0 ? (int)ctx.opt_grid_per_cu : kGridPerCu[tile_kind]);
-  const int grid = (int)std::min<int64_t>(ntiles, grid_cap);
+  Scratch* ds = dev_scratch(ctx);
+  const int gcap = grid_cap(ctx, tile_kind);
   size_t next_fixed = 0;
   bool first = true;
-  if (ctx.opt_time_kernels && !ctx.ev0) { check_hip(hipEventCreate(&ctx.ev0), "hipEventCreate"); check_hip(hipEventCreate(&ctx.ev1), "hipEventCreate"); }
-
   do {
     FilterParams p{};
     p.nrows = mask_len;
-    p.status = dev_status(ctx);
-    p.ticket = &ds->ticket; p.total = &ds->total; p.err = &ds->err;
+    bind_scratch(p, ctx);
     p.sel_mask = (first && need_followup) ? (u64*)sel_mask->ptr : nullptr;
     p.grp_base = (first && need_followup) ? (u64*)grp_base->ptr : nullptr;
-    if (first) fill_refs(p.pb, lw, *prog_rec, str_bufs);
+    if (first) fill_refs(p.pb, fp.lw, *fp.rec, str_bufs);
     else {   // later passes re-read the selection bitmap as a Boolean column
       p.pb.n_instr = 1; p.pb.n_refs = 1;
       Instr in{}; in.op = OP_LOAD; in.type = T_BOOL; in.src_kind = SRC_COL; in.src_type = T_BOOL; in.src_idx = 0;
@@ -1215,14 +1279,9 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
     while (next_fixed < fixed_cols.size() && (int)launch_cols.size() < MAX_OUT) launch_cols.push_back(fixed_cols[next_fixed++]);
     // narrow predicate input columns stay on chip between the predicate and copy phases (placed last)
     p.n_stash = 0;
-    if (first) pick_stash(p, ctx, lw, rec.cols, launch_cols, tile_kind);
-    int n = 0;
-    for (int ci : launch_cols) {
-      p.outs[n].in = rec.cols[ci].values0(); p.outs[n].out = (void*)out.cols[ci].values; p.outs[n].width = (uint32_t)rec.cols[ci].width;
-      ++n;
-    }
-    p.n_out = (int16_t)n;
-    if (first) {
+    if (first) pick_stash(p, ctx, fp.lw, rec.cols, launch_cols, tile_kind);
+    fill_outs(p, launch_cols, rec.cols, [&](int ci) { return rec.cols[ci].values0(); }, [&](int ci) { return (void*)out.cols[ci].values; });
+    if (first) {   // the Utf8Fold slots: output offsets / bytes at input capacity, a byte-scan status word per tile
       for (size_t u = 0; u < fold_cols.size(); ++u) {
         const Column& c = rec.cols[fold_cols[u]];
         Column& o = out.cols[fold_cols[u]];
@@ -1231,87 +1290,60 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
         auto st = make_device_buffer((size_t)(ntiles + 1) * 8, ctx.device);
         check_hip(hipMemsetAsync(st->ptr, 0, (size_t)(ntiles + 1) * 8, ctx.stream), "memset byte-scan status");
         fold_status.push_back(st);
-        Utf8Fold& f = p.utf8[u];
-        f.in_offsets = (const int32_t*)c.values0(); f.in_data = c.data;
-        f.out_offsets = (int32_t*)offb->ptr; f.out_data = fold_data[u] ? (uint8_t*)db->ptr : nullptr;
-        f.status = (u64*)st->ptr; f.total_bytes = &ds->fold_bytes[u];
+        Utf8Fold& u8 = p.utf8[u];
+        u8.in_offsets = (const int32_t*)c.values0(); u8.in_data = c.data;
+        u8.out_offsets = (int32_t*)offb->ptr; u8.out_data = fold_data[u] ? (uint8_t*)db->ptr : nullptr;
+        u8.status = (u64*)st->ptr; u8.total_bytes = &dev_scratch(ctx)->fold_bytes[u];
         o.values = (const uint8_t*)offb->ptr; o.owned.push_back(offb);
         o.data = (const uint8_t*)db->ptr; o.owned.push_back(db);
         ctx.stats.bytes_read_alg += mask_len * 8;   // offsets, by both phases (as the separate Utf8 pass counts them)
       }
       p.n_utf8 = (int32_t)fold_cols.size();
-    }
-    if (first) check_hip(hipMemsetAsync(ds, 0, kHeader + (size_t)(ntiles + 1) * 8, ctx.stream), "memset scratch + status");
-    else {
+      clear_scratch(ctx, ntiles);
+    } else {
       check_hip(hipMemsetAsync(ds, 0, kPerPass, ctx.stream), "memset scratch");
       check_hip(hipMemsetAsync(dev_status(ctx), 0, (size_t)(ntiles + 1) * 8, ctx.stream), "memset status");
     }
     const int kind = first ? tile_kind : (tile_kind == 2 ? 1 : tile_kind);   // kinds 1 and 2 share a tile size
-    if (ctx.opt_time_kernels && first) check_hip(hipEventRecord(ctx.ev0, ctx.stream), "hipEventRecord");
-    // Large batches: all complete tiles run in the instantiation that contains no partial-tile code at all; the
-    // (single) incomplete tail tile runs in a second one-workgroup launch that continues the same chained scan.
-    const int64_t nfull = mask_len / tile_rows;
-    if (mask_len >= ctx.opt_split_rows && nfull > 0) {
-      p.tile_begin = 0; p.tile_end = nfull;
-      check_hip(launch_filter(p, kind, false, (int)std::min<int64_t>(nfull, grid_cap), ctx.stream), "launch filter_fused_kernel");
-      if (nfull < ntiles) {
-        p.tile_begin = nfull; p.tile_end = ntiles; p.ticket = &ds->ticket2;
-        check_hip(launch_filter(p, kind, true, 1, ctx.stream), "launch filter_fused_kernel (tail)");
-        ++ctx.stats.launches;
-      }
-    } else {
-      p.tile_begin = 0; p.tile_end = ntiles;
-      check_hip(launch_filter(p, kind, true, grid, ctx.stream), "launch filter_fused_kernel");
-    }
-    if (ctx.opt_time_kernels && first) check_hip(hipEventRecord(ctx.ev1, ctx.stream), "hipEventRecord");
-    ++ctx.stats.launches;
-    if (first) {
-      for (size_t u = 0; u < fold_cols.size(); ++u) {
-        if (fold_data[u]) continue;
-        Utf8Params up{};
-        up.nrows = mask_len; up.sel_mask = (const u64*)sel_mask->ptr; up.grp_base = (const u64*)grp_base->ptr;
-        up.in_offsets = p.utf8[u].in_offsets; up.in_data = p.utf8[u].in_data;
-        up.out_offsets = p.utf8[u].out_offsets; up.out_data = (uint8_t*)out.cols[fold_cols[u]].data;
-        check_hip(launch_utf8_copy(up, (int)std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx.num_cus * 16), ctx.stream), "launch utf8_copy_kernel");
-        ++ctx.stats.launches;
-      }
+    if (first) kernel_span_begin(ctx);
+    launch_tiles(ctx, p, mask_len, tile_rows, gcap, [&](bool partial, int grid, bool tail) {
+      if (tail) p.ticket = &ds->ticket2;
+      check_hip(launch_filter(p, kind, partial, grid, ctx.stream), tail ? "launch filter_fused_kernel (tail)" : "launch filter_fused_kernel");
+    });
+    if (first) kernel_span_end(ctx);
+    for (size_t u = 0; u < fold_cols.size(); ++u) {   // long folded strings: their bytes (first pass only)
+      if (!first || fold_data[u]) continue;
+      Utf8Params up{};
+      up.nrows = mask_len; up.sel_mask = (const u64*)sel_mask->ptr; up.grp_base = (const u64*)grp_base->ptr;
+      up.in_offsets = p.utf8[u].in_offsets; up.in_data = p.utf8[u].in_data;
+      up.out_offsets = p.utf8[u].out_offsets; up.out_data = (uint8_t*)out.cols[fold_cols[u]].data;
+      check_hip(launch_utf8_copy(up, (int)std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx.num_cus * 16), ctx.stream), "launch utf8_copy_kernel");
+      ++ctx.stats.launches;
     }
     first = false;
   } while (next_fixed < fixed_cols.size());
+}
 
+// Stage 6, the row count; the split bounds and the first follow-up round's Utf8 byte spans ride on its read-back
+void FilterCall::read_main() {
   BufferPtr split_dev;
-  if (split && !split->starts.empty()) {   // output position of every concatenated input batch
+  if (split && !split->starts.empty()) {
     const size_t n = split->starts.size();
     split_dev = make_device_buffer(n * 16 + 16, ctx.device);
     check_hip(hipMemcpyAsync(split_dev->ptr, split->starts.data(), n * 8, hipMemcpyHostToDevice, ctx.stream), "upload split rows");
     SplitBoundsParams sp{};
     sp.nrows = mask_len; sp.n = (int64_t)n; sp.starts = (const int64_t*)split_dev->ptr;
-    sp.sel_mask = (const u64*)sel_mask->ptr; sp.grp_base = (const u64*)grp_base->ptr; sp.total = &ds->total;
+    sp.sel_mask = (const u64*)sel_mask->ptr; sp.grp_base = (const u64*)grp_base->ptr; sp.total = &dev_scratch(ctx)->total;
     sp.out = (u64*)((uint8_t*)split_dev->ptr + n * 8);
     check_hip(launch_split_bounds(sp, ctx.stream), "launch split_bounds_kernel");
     split->bounds.assign(n, 0);
     check_hip(hipMemcpyAsync(split->bounds.data(), sp.out, n * 8, hipMemcpyDeviceToHost, ctx.stream), "read back split bounds");
   }
-  // The follow-up kernels report through the fixed-size scratch header: 16 null counters and 8 Utf8 byte spans /
-  // totals per round; wider batches simply take more rounds (each with its own read-back).
-  constexpr size_t kNullPerRound = 16, kUtf8PerRound = 8;
-  auto gather_utf8_ends = [&](size_t u0, size_t u1) {   // input byte span of Utf8 columns [u0, u1) = capacity of their outputs
-    if (u1 <= u0) return;
-    GatherParams gp{};
-    for (size_t k = u0; k < u1; ++k) {
-      const int32_t* offs = (const int32_t*)rec.cols[utf8_cols[k]].values0();
-      gp.src[2 * (k - u0)] = offs; gp.src[2 * (k - u0) + 1] = offs + mask_len;
-    }
-    gp.n = (int32_t)(2 * (u1 - u0)); gp.dst = ds->utf8_ends;
-    check_hip(launch_gather_i32(gp, ctx.stream), "launch gather_i32_kernel");
-  };
-  gather_utf8_ends(0, std::min(kUtf8PerRound, utf8_cols.size()));   // rides on the read-back of the row count
-  check_hip(hipMemcpyAsync(hs, ds, sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
-  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  if (ctx.opt_time_kernels) { float ms = 0; check_hip(hipEventElapsedTime(&ms, ctx.ev0, ctx.ev1), "hipEventElapsedTime"); ctx.stats.kernel_ns = (int64_t)(ms * 1e6); }
+  gather_utf8_ends(0, std::min(kUtf8PerRound, utf8_cols.size()));
+  const Scratch* hs = read_scratch(ctx);
+  ctx.stats.kernel_ns += kernel_span_ns(ctx);
   if (hs->err != ERR_NONE) throw_device_error(hs->err);
-  const int64_t total = (int64_t)hs->total;
-  out.nrows = total;
+  total = out.nrows = (int64_t)hs->total;
   ctx.stats.rows_out = total; ctx.stats.tiles = ntiles;
   for (int ci : fixed_cols) { out.cols[ci].length = total; ctx.stats.bytes_written_alg += total * out.cols[ci].width; }
   for (size_t u = 0; u < fold_cols.size(); ++u) {
@@ -1319,35 +1351,39 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
     o.length = total; o.data_bytes = (int64_t)hs->fold_bytes[u];
     ctx.stats.bytes_read_alg += o.data_bytes; ctx.stats.bytes_written_alg += (total + 1) * 4 + o.data_bytes;
   }
+}
 
-  if (need_followup) {
-    const int fgrid = (int)std::min<int64_t>((ngroups + 31) / 32, (int64_t)ctx.num_cus * 8);
-    // ---- Boolean value bitmaps and validity bitmaps -------------------------------------------------
-    const size_t words = (size_t)(total + 31) / 32 + 2;
-    auto bit_compact = [&](const uint8_t* in_bits, int64_t bit_off, u64* zero_counter) {
-      auto ob = make_device_buffer(words * 4 + 8, ctx.device);
-      check_hip(hipMemsetAsync(ob->ptr, 0, words * 4 + 8, ctx.stream), "memset bits");
-      BitCompactParams bp{};
-      bp.nrows = mask_len; bp.sel_mask = (const u64*)sel_mask->ptr; bp.grp_base = (const u64*)grp_base->ptr;
-      bp.in_bits = in_bits; bp.in_bit_offset = bit_off; bp.out_bits = (uint32_t*)ob->ptr; bp.zero_count = zero_counter;
-      check_hip(launch_bit_compact(bp, std::max(1, fgrid), ctx.stream), "launch bit_compact_kernel");
-      ++ctx.stats.launches;
-      return ob;
-    };
-    for (int ci : bool_cols) {
-      auto ob = bit_compact(rec.cols[ci].values, rec.cols[ci].offset, nullptr);
-      out.cols[ci].values = (const uint8_t*)ob->ptr; out.cols[ci].owned.push_back(ob); out.cols[ci].length = total;
-    }
-    std::vector<BufferPtr> byte_status(utf8_cols.size());
-    size_t n0 = 0, u0 = 0;
-    for (bool first_round = true; first_round || n0 < nullable_cols.size() || u0 < utf8_cols.size(); first_round = false) {
+// Stage 7, the follow-up kernels: Boolean and validity bitmaps, the Utf8 columns the main kernel did not take.  They report
+// through the scratch header, kNullPerRound / kUtf8PerRound per round; wider batches take more rounds (one read-back each).
+void FilterCall::follow_ups() {
+  if (!need_followup) return;
+  Scratch* ds = dev_scratch(ctx);
+  const Scratch* hs = (const Scratch*)ctx.pinned;   // (read back by read_main)
+  const int fgrid = (int)std::min<int64_t>((ngroups + 31) / 32, (int64_t)ctx.num_cus * 8);
+  const size_t words = (size_t)(total + 31) / 32 + 2;
+  auto bit_compact = [&](const uint8_t* in_bits, int64_t bit_off, u64* zero_counter) {
+    auto ob = make_device_buffer(words * 4 + 8, ctx.device);
+    check_hip(hipMemsetAsync(ob->ptr, 0, words * 4 + 8, ctx.stream), "memset bits");
+    BitCompactParams bp{};
+    bp.nrows = mask_len; bp.sel_mask = (const u64*)sel_mask->ptr; bp.grp_base = (const u64*)grp_base->ptr;
+    bp.in_bits = in_bits; bp.in_bit_offset = bit_off; bp.out_bits = (uint32_t*)ob->ptr; bp.zero_count = zero_counter;
+    check_hip(launch_bit_compact(bp, std::max(1, fgrid), ctx.stream), "launch bit_compact_kernel");
+    ++ctx.stats.launches;
+    return ob;
+  };
+  for (int ci : bool_cols) {
+    auto ob = bit_compact(rec.cols[ci].values, rec.cols[ci].offset, nullptr);
+    out.cols[ci].values = (const uint8_t*)ob->ptr; out.cols[ci].owned.push_back(ob); out.cols[ci].length = total;
+  }
+  std::vector<BufferPtr> byte_status(utf8_cols.size());
+  size_t n0 = 0, u0 = 0;
+  for (bool first_round = true; first_round || n0 < nullable_cols.size() || u0 < utf8_cols.size(); first_round = false) {
     const size_t n1 = std::min(n0 + kNullPerRound, nullable_cols.size()), u1 = std::min(u0 + kUtf8PerRound, utf8_cols.size());
     if (!first_round) {   // fresh counters, and the byte spans of this round's Utf8 columns
       check_hip(hipMemsetAsync(ds->counters, 0, sizeof(ds->counters), ctx.stream), "memset counters");
       if (u1 > u0) {
         gather_utf8_ends(u0, u1);
-        check_hip(hipMemcpyAsync(hs, ds, sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
-        check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+        hs = read_scratch(ctx);
       }
     }
     for (size_t k = n0; k < n1; ++k) {
@@ -1355,7 +1391,6 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
       auto ob = bit_compact(rec.cols[ci].validity, rec.cols[ci].offset, &ds->counters[k - n0]);
       out.cols[ci].validity = (const uint8_t*)ob->ptr; out.cols[ci].owned.push_back(ob);
     }
-    // ---- Utf8 columns: one fused pass each (new offsets + bytes) --------------------------------------
     // Short strings: one fused pass (new offsets + bytes, 8192-row tiles).  Long strings: offsets pass (2048-row
     // tiles) then a copy pass with one wave per 64 rows, which spreads the byte copies over far more waves.
     for (size_t k = u0; k < u1; ++k) {
@@ -1389,8 +1424,7 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
       o.values = (const uint8_t*)offb->ptr; o.owned.push_back(offb); o.length = total;
       o.data = (const uint8_t*)db->ptr; o.owned.push_back(db);
     }
-    check_hip(hipMemcpyAsync(hs, ds, sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
-    check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+    hs = read_scratch(ctx);
     for (size_t k = n0; k < n1; ++k) {
       Column& o = out.cols[nullable_cols[k]];
       o.null_count = (int64_t)hs->counters[k - n0];
@@ -1402,10 +1436,29 @@ Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn
       ctx.stats.bytes_read_alg += mask_len * 8 + o.data_bytes; ctx.stats.bytes_written_alg += (total + 1) * 4 + o.data_bytes;
     }
     n0 = n1; u0 = u1;
-    }
   }
-  for (Column& o : out.cols) o.length = total;
-  return out;
+}
+
+}  // namespace
+
+// =================================================================================================
+// filter_record
+// =================================================================================================
+Batch filter_record(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& expr, SplitRequest* split) {
+  FilterProgram fp;
+  type_filter(ctx, rec, pcols, expr, fp);
+  Batch res;
+  if (uniform_detour(ctx, rec, pcols, expr, split, fp, &res)) return res;
+  ctx.stats = chq_call_stats{};
+  ctx.stats.rows_in = rec.nrows;
+  if (fp.mask_len == 0) return empty_filter_result(ctx, rec);
+  FilterCall f(ctx, rec, fp, split);
+  f.plan_fold();
+  f.launch_main();
+  f.read_main();
+  f.follow_ups();
+  for (Column& o : f.out.cols) o.length = f.total;
+  return std::move(f.out);
 }
 
 // =================================================================================================
@@ -1430,10 +1483,7 @@ bool filter_record_large_host(Context& ctx, const Batch& rec, const chq_table_al
   }
   const std::vector<PlanColumn> pcols = plan_columns(rec, aliases);
   try {
-    TypedExpr te = type_expr(expr, pcols, nrows, ctx.opt_enable_minus);
-    if (te.pending_code) return false;
-    const Node& root = te.at(te.root);
-    if (root.type != T_BOOL || root.len1) return false;
+    if (!is_row_predicate(type_expr(expr, pcols, nrows, ctx.opt_enable_minus))) return false;
   } catch (const ChqError&) {
     return false;   // the general path reports it
   }
@@ -1548,9 +1598,7 @@ bool filter_record_small_host(Context& ctx, const Batch& rec, const chq_table_al
   Lowered lw;
   try {
     TypedExpr te = type_expr(expr, pcols, nrows, ctx.opt_enable_minus);
-    if (te.pending_code) return false;
-    const Node& root = te.at(te.root);
-    if (root.type != T_BOOL || root.len1) return false;
+    if (!is_row_predicate(te)) return false;
     lower_expr(te, te.root, pcols, lw);
   } catch (const ChqError&) {
     return false;   // the general path reports it
@@ -1574,8 +1622,6 @@ bool filter_record_small_host(Context& ctx, const Batch& rec, const chq_table_al
   const int64_t tile_rows = kTileRows[tile_kind];
   const int64_t ntiles = (nrows + tile_rows - 1) / tile_rows;
   ensure_scratch(ctx, ntiles);
-  Scratch* ds = dev_scratch(ctx);
-  Scratch* hs = (Scratch*)ctx.pinned;
 
   // a view of the batch whose columns live in the device block (what the program's column refs resolve against)
   Batch dev;
@@ -1587,25 +1633,19 @@ bool filter_record_small_host(Context& ctx, const Batch& rec, const chq_table_al
   }
   FilterParams p{};
   p.nrows = nrows; p.tile_begin = 0; p.tile_end = ntiles;
-  p.status = dev_status(ctx); p.ticket = &ds->ticket; p.total = &ds->total; p.err = &ds->err;
+  bind_scratch(p, ctx);
   fill_refs(p.pb, lw, dev, {});
   std::vector<int> launch_cols;
   for (size_t i = 0; i < ncols; ++i) launch_cols.push_back((int)i);
   pick_stash(p, ctx, lw, rec.cols, launch_cols, tile_kind);
-  int n = 0;
-  for (int ci : launch_cols) {
-    p.outs[n].in = d_in + at[ci]; p.outs[n].out = d_out + at[ci]; p.outs[n].width = (uint32_t)rec.cols[ci].width;
-    ++n;
-  }
-  p.n_out = (int16_t)n;
+  fill_outs(p, launch_cols, rec.cols, [&](int ci) { return d_in + at[ci]; }, [&](int ci) { return d_out + at[ci]; });
   ctx.stats = chq_call_stats{};
   ctx.stats.rows_in = nrows; ctx.stats.tiles = ntiles; ctx.stats.launches = 1;
-  check_hip(hipMemsetAsync(ds, 0, kHeader + (size_t)(ntiles + 1) * 8, ctx.stream), "memset scratch + status");
-  const int grid_cap = ctx.num_cus * kGridPerCu[tile_kind];
-  check_hip(launch_filter(p, tile_kind, true, (int)std::min<int64_t>(ntiles, grid_cap), ctx.stream), "launch filter_fused_kernel (small host batch)");
+  clear_scratch(ctx, ntiles);
+  const int gcap = ctx.num_cus * kGridPerCu[tile_kind];   // (not grid_cap: this path has never read `grid_per_cu`)
+  check_hip(launch_filter(p, tile_kind, true, (int)std::min<int64_t>(ntiles, gcap), ctx.stream), "launch filter_fused_kernel (small host batch)");
   check_hip(hipMemcpyAsync(h_out, d_out, block, hipMemcpyDeviceToHost, ctx.stream), "download packed result");
-  check_hip(hipMemcpyAsync(hs, ds, sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
-  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  const Scratch* hs = read_scratch(ctx);
   if (hs->err != ERR_NONE) return false;   // the general path reports the error
   const int64_t total = (int64_t)hs->total;
   Batch out;
@@ -2432,7 +2472,7 @@ bool launch_group(const GroupCall& g, const GroupPlan& pl, const Lowered& lw, Gr
                   JoinedGroup& out) {
   Context& ctx = g.ctx;
   const std::vector<Batch>& recs = g.recs;
-  const size_t nb = g.nb, ncols = recs[0].cols.size(), nu = pl.fold_utf8.size(), nout = t.launch_cols.size();
+  const size_t nb = g.nb, ncols = recs[0].cols.size(), nu = pl.fold_utf8.size();
   const int64_t total_rows = pl.total_rows, ntiles = t.ntiles, wpb = t.wpb;
   const int tile_kind = t.tile_kind;
   FilterParams& p = t.p;
@@ -2472,22 +2512,16 @@ bool launch_group(const GroupCall& g, const GroupPlan& pl, const Lowered& lw, Gr
   }
   p.n_utf8 = (int32_t)nu;
   p.nrows = ntiles * kTileRows[tile_kind];   // only locates the last tile; per-tile row ranges come from the table
-  p.status = dev_status(ctx);
-  p.ticket = &ds->ticket; p.total = &ds->total; p.err = &ds->err;
+  bind_scratch(p, ctx);
   fill_refs(p.pb, lw, t.proto, {});
-  for (size_t k = 0; k < nout; ++k) {
-    p.outs[k].in = nullptr; p.outs[k].out = dense[t.launch_cols[k]]->ptr; p.outs[k].width = (uint32_t)recs[0].cols[t.launch_cols[k]].width;
-  }
-  p.n_out = (int16_t)nout;
+  fill_outs(p, t.launch_cols, recs[0].cols, [](int) { return (const void*)nullptr; }, [&](int ci) { return dense[ci]->ptr; });   // (inputs: per batch, from the table)
   p.group = (const u64*)d_tbl->ptr; p.group_stride = (int64_t)t.stride;
   p.group_wpb = (int32_t)wpb; p.group_nb = (int32_t)nb; p.group_batch_end = d_cnt;
   p.tile_begin = 0; p.tile_end = ntiles;
-  check_hip(hipMemsetAsync(ds, 0, kHeader + (size_t)(ntiles + 1) * 8, ctx.stream), "memset scratch + status");
-  const int grid_cap = ctx.num_cus * (ctx.opt_grid_per_cu > 0 ? (int)ctx.opt_grid_per_cu : kGridPerCu[tile_kind]);
-  if (ctx.opt_time_kernels && !ctx.ev0) { check_hip(hipEventCreate(&ctx.ev0), "hipEventCreate"); check_hip(hipEventCreate(&ctx.ev1), "hipEventCreate"); }
-  if (ctx.opt_time_kernels) check_hip(hipEventRecord(ctx.ev0, ctx.stream), "hipEventRecord");
-  check_hip(launch_filter(p, tile_kind, true, (int)std::min<int64_t>(ntiles, grid_cap), ctx.stream), "launch filter_fused_kernel (group)");
-  if (ctx.opt_time_kernels) check_hip(hipEventRecord(ctx.ev1, ctx.stream), "hipEventRecord");
+  clear_scratch(ctx, ntiles);
+  kernel_span_begin(ctx);
+  check_hip(launch_filter(p, tile_kind, true, (int)std::min<int64_t>(ntiles, grid_cap(ctx, tile_kind)), ctx.stream), "launch filter_fused_kernel (group)");
+  kernel_span_end(ctx);
   ctx.stats.launches = 1; ctx.stats.tiles = ntiles;
   if (wpb == 0) {   // tile mode: the inclusive prefix at every batch's last tile
     GatherStatusParams gp{};
@@ -2509,13 +2543,11 @@ bool launch_group(const GroupCall& g, const GroupPlan& pl, const Lowered& lw, Gr
     check_hip(launch_bit_compact_group(bp, (int)std::min<int64_t>((wpb * (int64_t)nb + 3) / 4, (int64_t)ctx.num_cus * 8), ctx.stream), "launch bit_compact_group_kernel");
     ++ctx.stats.launches;
   }
-  Scratch* hs = (Scratch*)ctx.pinned;
-  check_hip(hipMemcpyAsync(hs, ds, sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
   check_hip(hipMemcpyAsync(h_cnt, d_cnt, t.bytes_cnt, hipMemcpyDeviceToHost, ctx.stream), "read back batch prefixes");
   pt.mark("alloc+launch");
-  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  const Scratch* hs = read_scratch(ctx);
   pt.mark("kernel+readback");
-  if (ctx.opt_time_kernels) { float ms = 0; check_hip(hipEventElapsedTime(&ms, ctx.ev0, ctx.ev1), "hipEventElapsedTime"); ctx.stats.kernel_ns = (int64_t)(ms * 1e6); }
+  ctx.stats.kernel_ns += kernel_span_ns(ctx);
   if (hs->err != ERR_NONE) return false;
   const int64_t total = (int64_t)hs->total;
   ctx.stats.rows_out = total;
@@ -2623,8 +2655,7 @@ GroupResult filter_group(Context& ctx, const GroupInput& gi, const chq_table_ali
     const bool host_case = pl.all_host && !out_on_device;
     if (!host_case && !pl.all_device) return g.per_batch_loop();
     try {
-      TypedExpr probe = type_expr(expr, plan_columns(g.recs[0], aliases), g.recs[0].nrows, ctx.opt_enable_minus);
-      if (probe.pending_code || probe.at(probe.root).type != T_BOOL || probe.at(probe.root).len1) return g.per_batch_loop();
+      if (!is_row_predicate(type_expr(expr, plan_columns(g.recs[0], aliases), g.recs[0].nrows, ctx.opt_enable_minus))) return g.per_batch_loop();
     } catch (const ChqError&) {
       return g.per_batch_loop();   // reports the first batch's (static) error
     }
@@ -2637,10 +2668,8 @@ GroupResult filter_group(Context& ctx, const GroupInput& gi, const chq_table_ali
   };
   if (!pl.resident) return g.per_batch_loop();
   const std::vector<PlanColumn> pcols = plan_columns(g.recs[0], aliases);
-  TypedExpr te = type_expr(expr, pcols, g.recs[0].nrows, ctx.opt_enable_minus);
-  if (te.pending_code) return g.per_batch_loop();
-  const Node& root = te.at(te.root);
-  if (root.type != T_BOOL || root.len1) return g.per_batch_loop();
+  TypedExpr te = type_expr(expr, pcols, g.recs[0].nrows, ctx.opt_enable_minus);   // (a static error is thrown, not caught)
+  if (!is_row_predicate(te)) return g.per_batch_loop();
   Lowered lw;
   try {
     lower_expr(te, te.root, pcols, lw);
@@ -2769,8 +2798,6 @@ std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::ve
     return results;
   }
   ensure_scratch(ctx, 1);
-  Scratch* ds = dev_scratch(ctx);
-  Scratch* hs = (Scratch*)ctx.pinned;
   size_t k = 0;
   while (k < exprs.size()) {
     if (!lowers_alone(*exprs[k], exprs[k]->root, pcols)) {
@@ -2781,11 +2808,11 @@ std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::ve
       std::vector<const TypedExpr*> one{&fitted};
       Column c = std::move(evaluate_dense(ctx, work, wcols, one)[0]);
       results[k] = std::move(c);
-      hs = (Scratch*)ctx.pinned; ds = dev_scratch(ctx);
       ++k;
       continue;
     }
     // pack as many expressions as fit the program limits into one launch
+    Scratch* ds = dev_scratch(ctx);   // (looked up here: a nested call above may have replaced the block)
     Lowered lw;
     std::vector<ProjItem> items;
     int null_slots = 0;
@@ -2826,24 +2853,10 @@ std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::ve
     }
     check_hip(hipMemsetAsync(ds, 0, sizeof(Scratch), ctx.stream), "memset scratch");
     const int tile_kind = pick_tile_kind(ctx, lw, nrows);
-    const int64_t ntiles = (nrows + kTileRows[tile_kind] - 1) / kTileRows[tile_kind];
-    const int64_t gcap = tile_kind == 0 ? (int64_t)ctx.num_cus * 2 : (int64_t)ctx.num_cus * 8;
-    const int64_t nfull = nrows / kTileRows[tile_kind];
-    if (nrows >= ctx.opt_split_rows && nfull > 0) {
-      p.tile_begin = 0; p.tile_end = nfull;
-      check_hip(launch_project(p, tile_kind, false, (int)std::min<int64_t>(nfull, gcap), ctx.stream), "launch project_kernel");
-      if (nfull < ntiles) {
-        p.tile_begin = nfull; p.tile_end = ntiles;
-        check_hip(launch_project(p, tile_kind, true, 1, ctx.stream), "launch project_kernel (tail)");
-        ++ctx.stats.launches;
-      }
-    } else {
-      p.tile_begin = 0; p.tile_end = ntiles;
-      check_hip(launch_project(p, tile_kind, true, (int)std::min<int64_t>(ntiles, gcap), ctx.stream), "launch project_kernel");
-    }
-    ++ctx.stats.launches;
-    check_hip(hipMemcpyAsync(hs, ds, sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
-    check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+    launch_tiles(ctx, p, nrows, kTileRows[tile_kind], (int64_t)ctx.num_cus * (tile_kind == 0 ? 2 : 8), [&](bool partial, int grid, bool tail) {
+      check_hip(launch_project(p, tile_kind, partial, grid, ctx.stream), tail ? "launch project_kernel (tail)" : "launch project_kernel");
+    });
+    const Scratch* hs = read_scratch(ctx);
     if (hs->err != ERR_NONE) {
       // Several expressions shared the launch and each numbers its nodes from zero, so the smallest (node, row) key may
       // belong to a later select item.  The reference evaluates the items one after the other: do the same to find
@@ -2862,6 +2875,16 @@ std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::ve
     }
   }
   return results;
+}
+
+// an expression select item's name; `*unnamed_idx` counts the UNNAMED_EXPR items so far
+std::string select_item_name(const chq_select_item& f, const Expr& e, size_t* unnamed_idx) {
+  std::string name;
+  if (f.kind == CHQ_ITEM_EXPR_WITH_ALIAS) name = f.alias ? f.alias : "";
+  else if (e.kind == Expr::IDENT) name = e.text;                 // RU/record_projection.rs:41-48
+  else name = "unnamed_" + std::to_string(*unnamed_idx);         // :49-53
+  if (f.kind == CHQ_ITEM_UNNAMED_EXPR) ++*unnamed_idx;          // :58, counts identifiers too
+  return name;
 }
 
 // the result of one compute_value call: a passthrough column, a literal-built length-1 array, or a program
@@ -2909,17 +2932,19 @@ Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, c
   std::vector<int> computed_slot;        // output column index of each computed item
   std::vector<size_t> passthrough_slot;  // output column index of each identifier item
   size_t unnamed_idx = 0;
+  auto evaluate_items = [&]() -> std::vector<Column> {   // the computed items so far, in one evaluation
+    if (evs.empty()) return {};
+    std::vector<const TypedExpr*> ptrs;
+    for (auto& ev : evs) ptrs.push_back(&ev.typed);
+    return evaluate_dense(ctx, rec, pcols, ptrs);
+  };
   for (const chq_select_item& f : fields) {
     switch (f.kind) {
       case CHQ_ITEM_WILDCARD:   // RU/record_projection.rs:27-32
         for (const Column& c : rec.cols) out.cols.push_back(clone_device_column(ctx, c));
         break;
       case CHQ_ITEM_QUALIFIED_WILDCARD:
-        if (!evs.empty()) {
-          std::vector<const TypedExpr*> ptrs;
-          for (auto& p : evs) ptrs.push_back(&p.typed);
-          (void)evaluate_dense(ctx, rec, pcols, ptrs);
-        }
+        (void)evaluate_items();
         throw ChqError{CHQ_ERR_PROJECT_NOT_IMPLEMENTED, "not implemented: SelectItem::QualifiedWildcard"};
       case CHQ_ITEM_UNNAMED_EXPR:
       case CHQ_ITEM_EXPR_WITH_ALIAS: {
@@ -2929,19 +2954,10 @@ Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, c
         try {
           ev = classify(ctx, rec, e, pcols);
         } catch (const ChqError&) {
-          // the reference evaluates the items in order: errors of earlier computed items come first
-          if (!evs.empty()) {
-            std::vector<const TypedExpr*> ptrs;
-            for (auto& p : evs) ptrs.push_back(&p.typed);
-            (void)evaluate_dense(ctx, rec, pcols, ptrs);
-          }
+          (void)evaluate_items();   // the reference evaluates the items in order: errors of earlier computed items come first
           throw;
         }
-        std::string name;
-        if (f.kind == CHQ_ITEM_EXPR_WITH_ALIAS) name = f.alias ? f.alias : "";
-        else if (e.kind == Expr::IDENT) name = e.text;                 // RU/record_projection.rs:41-48
-        else name = "unnamed_" + std::to_string(unnamed_idx);          // :49-53
-        if (f.kind == CHQ_ITEM_UNNAMED_EXPR) ++unnamed_idx;           // :58, counts identifiers too
+        const std::string name = select_item_name(f, e, &unnamed_idx);
         Column col;
         if (ev.kind == Evaluated::PASSTHROUGH) { col = clone_device_column(ctx, rec.cols[ev.col]); passthrough_slot.push_back(out.cols.size()); }
         else if (ev.kind == Evaluated::SCALAR) col = scalar_column(ctx, ev.value, name);
@@ -2952,15 +2968,11 @@ Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, c
       default: throw ChqError{CHQ_ERR_INVALID_HANDLE, "unknown select item kind"};
     }
   }
-  if (!evs.empty()) {
-    std::vector<const TypedExpr*> ptrs;
-    for (auto& ev : evs) ptrs.push_back(&ev.typed);
-    std::vector<Column> cols = evaluate_dense(ctx, rec, pcols, ptrs);
-    for (size_t i = 0; i < cols.size(); ++i) {
-      std::string name = out.cols[computed_slot[i]].name;
-      out.cols[computed_slot[i]] = std::move(cols[i]);
-      out.cols[computed_slot[i]].name = name;
-    }
+  std::vector<Column> cols = evaluate_items();
+  for (size_t i = 0; i < cols.size(); ++i) {
+    std::string name = out.cols[computed_slot[i]].name;
+    out.cols[computed_slot[i]] = std::move(cols[i]);
+    out.cols[computed_slot[i]].name = name;
   }
   // an identifier over a view keeps the view's bitmap with its null count unknown (imported as "may have nulls"): count the
   // window's nulls, so that its nullability is the reference's null_count > 0 below
@@ -3028,9 +3040,7 @@ bool filter_project_fused(Context& ctx, const Batch& rec, const std::vector<Plan
   Lowered lwp, lwq;
   try {
     TypedExpr tp = type_expr(pred, pcols, nrows, ctx.opt_enable_minus);
-    if (tp.pending_code) return false;
-    const Node& proot = tp.at(tp.root);
-    if (proot.type != T_BOOL || proot.len1) return false;
+    if (!is_row_predicate(tp)) return false;
     lower_expr(tp, tp.root, pcols, lwp);
     if (!lwp.strs.empty()) return false;
     for (int ci : lwp.refs) if (!plain(ci)) return false;
@@ -3050,11 +3060,7 @@ bool filter_project_fused(Context& ctx, const Batch& rec, const std::vector<Plan
       if (te.pending_code) return false;
       const Node& root = te.at(te.root);
       if (root.len1) return false;   // a literal-built column: RecordBatch::try_new decides on the filtered length
-      std::string name;
-      if (f.kind == CHQ_ITEM_EXPR_WITH_ALIAS) name = f.alias ? f.alias : "";
-      else if (e.kind == Expr::IDENT) name = e.text;
-      else name = "unnamed_" + std::to_string(unnamed_idx);
-      if (f.kind == CHQ_ITEM_UNNAMED_EXPR) ++unnamed_idx;
+      const std::string name = select_item_name(f, e, &unnamed_idx);
       if (root.kind == Node::COL) {
         if (!plain(root.col)) return false;
         items.push_back(Item{name, false, root.col, -1, rec.cols[root.col].type});
@@ -3103,8 +3109,6 @@ bool filter_project_fused(Context& ctx, const Batch& rec, const std::vector<Plan
   const int64_t tile_rows = kTileRows[tile_kind];
   const int64_t ntiles = (nrows + tile_rows - 1) / tile_rows;
   ensure_scratch(ctx, ntiles);
-  Scratch* ds = dev_scratch(ctx);
-  Scratch* hs = (Scratch*)ctx.pinned;
 
   ctx.stats = chq_call_stats{};
   ctx.stats.rows_in = nrows;
@@ -3112,7 +3116,7 @@ bool filter_project_fused(Context& ctx, const Batch& rec, const std::vector<Plan
   out.on_device = true; out.device_id = ctx.device;
   FusedParams p{};
   p.nrows = nrows; p.tile_begin = 0; p.tile_end = ntiles;
-  p.status = dev_status(ctx); p.ticket = &ds->ticket; p.total = &ds->total; p.err = &ds->err;
+  bind_scratch(p, ctx);
   fill_refs(p.pred, lwp, rec, {});
   fill_refs(p.proj, lwq, rec, {});
   p.n_proj = (int32_t)computed.size();
@@ -3144,15 +3148,12 @@ bool filter_project_fused(Context& ctx, const Batch& rec, const std::vector<Plan
   }
   for (size_t ci = 0; ci < rec.cols.size(); ++ci) if (read_once[ci]) ctx.stats.bytes_read_alg += nrows * rec.cols[ci].width;
 
-  check_hip(hipMemsetAsync(ds, 0, kHeader + (size_t)(ntiles + 1) * 8, ctx.stream), "memset scratch + status");
-  const int grid_cap = ctx.num_cus * (ctx.opt_grid_per_cu > 0 ? (int)ctx.opt_grid_per_cu : kGridPerCu[tile_kind]);
-  if (ctx.opt_time_kernels && !ctx.ev0) { check_hip(hipEventCreate(&ctx.ev0), "hipEventCreate"); check_hip(hipEventCreate(&ctx.ev1), "hipEventCreate"); }
-  if (ctx.opt_time_kernels) check_hip(hipEventRecord(ctx.ev0, ctx.stream), "hipEventRecord");
-  check_hip(launch_filter_project(p, tile_kind, (int)std::min<int64_t>(ntiles, grid_cap), ctx.stream), "launch filter_project_kernel");
-  if (ctx.opt_time_kernels) check_hip(hipEventRecord(ctx.ev1, ctx.stream), "hipEventRecord");
-  check_hip(hipMemcpyAsync(hs, ds, sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
-  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  if (ctx.opt_time_kernels) { float ms = 0; check_hip(hipEventElapsedTime(&ms, ctx.ev0, ctx.ev1), "hipEventElapsedTime"); ctx.stats.kernel_ns = (int64_t)(ms * 1e6); }
+  clear_scratch(ctx, ntiles);
+  kernel_span_begin(ctx);
+  check_hip(launch_filter_project(p, tile_kind, (int)std::min<int64_t>(ntiles, grid_cap(ctx, tile_kind)), ctx.stream), "launch filter_project_kernel");
+  kernel_span_end(ctx);
+  const Scratch* hs = read_scratch(ctx);
+  ctx.stats.kernel_ns += kernel_span_ns(ctx);
   if (hs->err != ERR_NONE) return false;
   const int64_t total = (int64_t)hs->total;
   for (Column& o : out.cols) o.length = total;
@@ -3193,11 +3194,7 @@ bool project_record_host(Context& ctx, const std::vector<chq_select_item>& field
       if (te.pending_code) return false;
       const Node& root = te.at(te.root);
       if (root.len1) return false;
-      std::string name;
-      if (f.kind == CHQ_ITEM_EXPR_WITH_ALIAS) name = f.alias ? f.alias : "";
-      else if (e.kind == Expr::IDENT) name = e.text;                 // RU/record_projection.rs:41-48
-      else name = "unnamed_" + std::to_string(unnamed_idx);          // :49-53
-      if (f.kind == CHQ_ITEM_UNNAMED_EXPR) ++unnamed_idx;           // :58, counts identifiers too
+      const std::string name = select_item_name(f, e, &unnamed_idx);
       if (root.kind == Node::COL) { items.push_back(Item{root.col, -1, name, false}); continue; }
       items.push_back(Item{-1, (int)computed.size(), name, false});
       computed.push_back(std::move(te));

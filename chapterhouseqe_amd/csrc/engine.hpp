@@ -180,6 +180,11 @@ void check_hip(hipError_t e, const char* what);
 void ensure_aux_streams(Context& ctx);
 void fork_aux_streams(Context& ctx);
 void join_aux_streams(Context& ctx);
+// `time_kernels`: one span of ctx.stream between the context's two events (created on first use).  kernel_span_ns -- once
+// the stream has been synchronised past kernel_span_end -- is its length; callers add it to stats.kernel_ns.  Off: 0.
+void kernel_span_begin(Context& ctx);
+void kernel_span_end(Context& ctx);
+int64_t kernel_span_ns(Context& ctx);
 
 // Arrow C Data Interface <-> Batch
 Batch import_batch(const ArrowDeviceArray* rec, const ArrowSchema* schema);

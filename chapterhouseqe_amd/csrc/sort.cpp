@@ -225,11 +225,10 @@ Batch sort_records(Context& ctx, std::vector<Batch>& in, const chq_table_aliases
     cols.push_back(resolve_key(*k.column, pcols, rows));
   }
   ctx.stats = chq_call_stats{};
-  if (ctx.opt_time_kernels && !ctx.ev0) { check_hip(hipEventCreate(&ctx.ev0), "hipEventCreate"); check_hip(hipEventCreate(&ctx.ev1), "hipEventCreate"); }
   const Batch rec = join_group(ctx, in);
   const int64_t n = rec.nrows, m = limit < 0 ? n : std::min(limit, n);
   ctx.stats.rows_in = n; ctx.stats.rows_out = m; ctx.stats.tiles = (n + kSortTile - 1) / kSortTile;
-  if (ctx.opt_time_kernels) check_hip(hipEventRecord(ctx.ev0, ctx.stream), "hipEventRecord");
+  kernel_span_begin(ctx);
   Traffic t;
   const BufferPtr perm_buf = m > 0 ? sort_permutation(ctx, rec, cols, keys, t) : nullptr;
   const uint32_t* perm = perm_buf ? (const uint32_t*)perm_buf->ptr : nullptr;
@@ -239,13 +238,13 @@ Batch sort_records(Context& ctx, std::vector<Batch>& in, const chq_table_aliases
   check_hip(hipMemsetAsync(ones->ptr, 0, rec.cols.size() * 8, ctx.stream), "hipMemsetAsync");
   for (size_t ci = 0; ci < rec.cols.size(); ++ci)
     out.cols.push_back(gather_column(ctx, rec.cols[ci], perm, m, (uint64_t*)ones->ptr + ci, t));
-  if (ctx.opt_time_kernels) check_hip(hipEventRecord(ctx.ev1, ctx.stream), "hipEventRecord");
+  kernel_span_end(ctx);
   std::vector<uint64_t> h(rec.cols.size());
   if (!h.empty()) check_hip(hipMemcpyAsync(h.data(), ones->ptr, h.size() * 8, hipMemcpyDeviceToHost, ctx.stream), "read back null counts");
   check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
   for (size_t ci = 0; ci < out.cols.size(); ++ci)
     if (out.cols[ci].null_count < 0) out.cols[ci].null_count = m - (int64_t)h[ci];
-  if (ctx.opt_time_kernels) { float ms = 0; check_hip(hipEventElapsedTime(&ms, ctx.ev0, ctx.ev1), "hipEventElapsedTime"); ctx.stats.kernel_ns = (int64_t)(ms * 1e6); }
+  ctx.stats.kernel_ns += kernel_span_ns(ctx);
   ctx.stats.bytes_read_alg = t.read; ctx.stats.bytes_written_alg = t.written;
   return out;
 }
