@@ -39,7 +39,8 @@ __device__ __forceinline__ void flag_error(uint32_t* err, uint32_t code) { atomi
 // The RLE / bit-packed hybrid of Parquet (definition levels, dictionary indices, RLE booleans): a sequence of runs, each
 // introduced by a varint header h -- (h & 1) == 0: RLE, h >> 1 repetitions of one value stored in ceil(bw / 8) bytes;
 // (h & 1) == 1: bit-packed, (h >> 1) groups of 8 values, bw bits each, LSB first.  `emit(k, v)` receives value v for
-// position k < n; returns the number of values emitted (n unless the stream ends early).
+// position k < n; returns the number of values emitted (n unless the stream ends early: inside a header, inside an RLE value,
+// or with fewer values than n -- a last bit-packed group that stops behind the last value wanted is no early end).
 // One workgroup per page, the stream staged through LDS: the run headers are parsed by every thread
 // from LDS (identical scalar work, no dependent HBM loads), each run is expanded by all BLOCK threads, bit-packed values
 // are extracted from LDS.  A bit-packed run that does not fit the window continues after the next staging.
@@ -66,10 +67,13 @@ __device__ __forceinline__ uint32_t hybrid_decode_block(const uint8_t* g, uint32
       else {
         if (pos + 9 > wend && wend < len) break;            // header (<= 5 bytes) + RLE value (<= 4) may straddle the window
         uint32_t h = 0;
-        for (int sh = 0; sh < 35 && pos < wend; sh += 7) { const uint8_t b = sb[pos - wpos + shift]; ++pos; h |= (uint32_t)(b & 0x7f) << sh; if (!(b & 0x80)) break; }
+        bool whole = false;   // (only the stream's end can cut a header or an RLE value: elsewhere 9 bytes lie ahead)
+        for (int sh = 0; sh < 35 && pos < wend; sh += 7) { const uint8_t b = sb[pos - wpos + shift]; ++pos; h |= (uint32_t)(b & 0x7f) << sh; if (!(b & 0x80)) { whole = true; break; } }
+        if (!whole) { stop = true; break; }
         if ((h & 1u) == 0) {
           uint32_t cnt = h >> 1, v = 0;
-          for (int b = 0; b < vbytes && pos < wend; ++b) { v |= (uint32_t)sb[pos - wpos + shift] << (8 * b); ++pos; }
+          if (pos + (uint32_t)vbytes > wend) { stop = true; break; }
+          for (int b = 0; b < vbytes; ++b) { v |= (uint32_t)sb[pos - wpos + shift] << (8 * b); ++pos; }
           v &= mask;
           if (cnt > n - k) cnt = n - k;
           for (uint32_t i = tid; i < cnt; i += BLOCK) emit(k + i, v);
@@ -80,8 +84,9 @@ __device__ __forceinline__ uint32_t hybrid_decode_block(const uint8_t* g, uint32
       }
       const uint32_t fit = bw ? (wend - pos) / (uint32_t)bw : groups;   // whole groups (bw bytes each) inside the window
       const uint32_t now = groups < fit ? groups : fit;
-      if (now == 0) { if (wend >= len) stop = true; else pending = groups; break; }
-      uint32_t cnt = now * 8u;
+      const bool cut = now < groups && wend >= len;   // the stream ends inside the run's last group: the values its bytes hold
+      if (now == 0 && !cut) { if (wend >= len) stop = true; else pending = groups; break; }
+      uint32_t cnt = cut ? (uint32_t)((uint64_t)(wend - pos) * 8u / (uint32_t)bw) : now * 8u;
       if (cnt > n - k) cnt = n - k;
       for (uint32_t i = tid; i < cnt; i += BLOCK) {
         const uint64_t bit = (uint64_t)i * (uint32_t)bw;
@@ -91,6 +96,7 @@ __device__ __forceinline__ uint32_t hybrid_decode_block(const uint8_t* g, uint32
         emit(k + i, (uint32_t)(w >> (bit & 7)) & mask);
       }
       k += cnt;
+      if (cut) { stop = true; break; }
       pos += now * (uint32_t)bw;
       if (now < groups) { pending = groups - now; break; }
     }

@@ -524,6 +524,7 @@ class PageInfo:
     uncompressed: int      # bytes of the section handed to the callback (V2: the values section only)
     levels: bytes = b""    # V2: the stored level sections in front of it
     header: TStruct = None
+    codec: int = 1         # of its chunk (0 uncompressed, 1 snappy)
 
 
 @dataclass
@@ -537,19 +538,20 @@ def footer(raw: bytes) -> TStruct:
     return TReader(raw, len(raw) - 8 - n).struct()
 
 
-def repack(raw: bytes, fn: Callable[[PageInfo, bytes], object]) -> bytes:
-    """`raw` (written by pyarrow with compression="snappy", no page index) with every page's snappy payload replaced by
-    fn(info, inflated bytes): a new raw stream (bytes), Stored(data) for a V2 values section kept uncompressed, or None to
-    keep the page as it is.  Page headers get their new compressed_page_size; the footer its moved offsets and sizes"""
+def rewrite(raw: bytes, page_fn: Callable[[PageInfo, bytes], Optional[bytes]], codec: Optional[int] = SNAPPY) -> bytes:
+    """the page walker behind repack (and tests/parquet_forge.py): `raw` (written by pyarrow, no page index) with every
+    page's stored payload replaced by page_fn(info, payload) -- None keeps it.  page_fn may change info.header (sizes of the
+    sections, flags); compressed_page_size is set here, and the footer gets the chunks' moved offsets and new sizes.
+    `codec`: the compression every chunk must have (None: any; info.codec says which)"""
     assert raw[:4] == b"PAR1" and raw[-4:] == b"PAR1"
     meta = footer(raw)
     out = bytearray(b"PAR1")
     for gi, rg in enumerate(meta.get(4)[1]):
         cols = rg.get(1)[1]
-        rg_start, rg_size = None, 0
+        rg_start, rg_size, rg_usize = None, 0, 0
         for ci, cc in enumerate(cols):
             md = cc.get(3)
-            assert md.get(4) == SNAPPY, "repack wants a snappy chunk"
+            assert codec is None or md.get(4) == codec, "repack wants a snappy chunk"
             for fid in (10, 14):        # index page, bloom filter: not written by the tests' writer settings
                 assert not md.has(fid)
             for fid in (4, 5, 6, 7):    # offset / column index
@@ -566,35 +568,14 @@ def repack(raw: bytes, fn: Callable[[PageInfo, bytes], object]) -> bytes:
                 csize, usize, ptype = ph.get(3), ph.get(2), ph.get(1)
                 payload = raw[hdr_end:hdr_end + csize]
                 assert not ph.has(4), "page CRCs are not rewritten"
-                info = PageInfo(gi, ci, page, ptype, 0, usize, b"", ph)
-                body = payload
-                if ptype == DATA_PAGE_V2:
-                    h2 = ph.get(8)
-                    info.num_values = h2.get(1)
-                    lv = h2.get(5, 0) + h2.get(6, 0)
-                    info.levels, values = payload[:lv], payload[lv:]
-                    info.uncompressed = usize - lv
-                    if h2.get(7, True):
-                        values = pa_decompress(values, usize - lv)
-                    got = fn(info, values)
-                    if isinstance(got, Stored):
-                        h2.set(7, False, T_FALSE)
-                        body = info.levels + got.data
-                    elif got is not None:
-                        if h2.has(7):      # (pyarrow stores a values section that does not shrink: compressed now)
-                            h2.set(7, True)
-                        body = info.levels + got
-                else:
-                    sub = ph.get(5) if ptype == DATA_PAGE else ph.get(7)
-                    info.num_values = sub.get(1)
-                    got = fn(info, pa_decompress(payload, usize))
-                    assert not isinstance(got, Stored), "only V2 pages store their values section uncompressed"
-                    if got is not None:
-                        body = got
+                info = PageInfo(gi, ci, page, ptype, 0, usize, b"", ph, md.get(4))
+                body = page_fn(info, payload)
+                if body is None:
+                    body = payload
                 ph.set(3, len(body))
                 head = thrift_bytes(ph)
                 moved[pos] = len(out)
-                dsize += len(head) - (hdr_end - pos)
+                dsize += len(head) - (hdr_end - pos) + ph.get(2) - usize
                 out += head + body
                 pos = hdr_end + csize
                 page += 1
@@ -610,13 +591,46 @@ def repack(raw: bytes, fn: Callable[[PageInfo, bytes], object]) -> bytes:
                 cc.set(2, moved[cc.get(2)] if cc.get(2) in moved else cc.get(2))
             rg_start = new_start if rg_start is None else rg_start
             rg_size += new_size
+            rg_usize += dsize
         if rg.has(5):
             rg.set(5, rg_start)
         if rg.has(6):
             rg.set(6, rg_size)
+        rg.set(2, rg.get(2) + rg_usize)  # total_byte_size: the chunks' uncompressed sizes
     foot = thrift_bytes(meta)
     out += foot + len(foot).to_bytes(4, "little") + b"PAR1"
     return bytes(out)
+
+
+def repack(raw: bytes, fn: Callable[[PageInfo, bytes], object]) -> bytes:
+    """`raw` (written by pyarrow with compression="snappy", no page index) with every page's snappy payload replaced by
+    fn(info, inflated bytes): a new raw stream (bytes), Stored(data) for a V2 values section kept uncompressed, or None to
+    keep the page as it is.  Page headers get their new compressed_page_size; the footer its moved offsets and sizes"""
+    def page_fn(info: PageInfo, payload: bytes):
+        ph, usize = info.header, info.uncompressed
+        if info.type == DATA_PAGE_V2:
+            h2 = ph.get(8)
+            info.num_values = h2.get(1)
+            lv = h2.get(5, 0) + h2.get(6, 0)
+            info.levels, values = payload[:lv], payload[lv:]
+            info.uncompressed = usize - lv
+            if h2.get(7, True):
+                values = pa_decompress(values, usize - lv)
+            got = fn(info, values)
+            if isinstance(got, Stored):
+                h2.set(7, False, T_FALSE)
+                return info.levels + got.data
+            if got is not None:
+                if h2.has(7):      # (pyarrow stores a values section that does not shrink: compressed now)
+                    h2.set(7, True)
+                return info.levels + got
+            return None
+        sub = ph.get(5) if info.type == DATA_PAGE else ph.get(7)
+        info.num_values = sub.get(1)
+        got = fn(info, pa_decompress(payload, usize))
+        assert not isinstance(got, Stored), "only V2 pages store their values section uncompressed"
+        return got
+    return rewrite(raw, page_fn, SNAPPY)
 
 
 def pages(raw: bytes):
