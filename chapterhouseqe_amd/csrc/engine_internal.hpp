@@ -1,0 +1,113 @@
+// engine_internal.hpp -- what the engine's own translation units (arrow_io.cpp, filter.cpp, group.cpp, project.cpp) share
+// with each other and with nobody else.  The interface for the rest of the library is engine.hpp.
+#pragma once
+#include <algorithm>
+
+#include "engine.hpp"
+
+namespace chq {
+
+// ---- arrow_io.cpp: one column copied across (or within) memory spaces ----------------------------------------------------
+enum class Dir { H2D, D2H, D2D, H2H, P2P };
+// P2P: `ctx` is the DESTINATION context (buffers on its device, copies on its stream), `peer_device` the GPU `c` lives on
+Column copy_column(Context& ctx, const Column& c, Dir dir, int peer_device = -1);
+
+// ---- defined here: what the per-call host paths must be able to inline -----------------------------------------------------
+inline int64_t count_nulls_host(const uint8_t* validity, int64_t offset, int64_t n) {
+  int64_t nulls = 0;
+  for (int64_t i = 0; i < n; ++i) { int64_t b = offset + i; nulls += !((validity[b >> 3] >> (b & 7)) & 1); }
+  return nulls;
+}
+inline void add_stats(chq_call_stats& acc, const chq_call_stats& s) {
+  acc.rows_in += s.rows_in; acc.rows_out += s.rows_out; acc.tiles += s.tiles; acc.launches += s.launches;
+  acc.bytes_read_alg += s.bytes_read_alg; acc.bytes_written_alg += s.bytes_written_alg; acc.kernel_ns += s.kernel_ns;
+}
+
+constexpr int64_t kTileRows[3] = {1024 * 16, 256 * 8, 256 * 8};
+constexpr int kGridPerCu[3] = {1, 4, 4};
+
+struct Scratch {   // header of ctx.small (device) and layout of ctx.pinned (host mirror)
+  uint32_t ticket; uint32_t pad0;      // --- [0, kPerPass): re-cleared before every pass of a multi-pass filter
+  unsigned long long total;
+  uint32_t ticket2; uint32_t pad1;
+  unsigned long long err;             // --- from here on: cleared once per call (errors accumulate over the passes)
+  unsigned long long total_bytes;
+  unsigned long long counters[24];
+  int32_t utf8_ends[16];              // first / last input offset of each Utf8 column (output byte capacity)
+  unsigned long long fold_bytes[MAX_FOLD_UTF8];   // output bytes of the Utf8 columns filtered inside the main kernel
+};
+constexpr size_t kPerPass = 24;
+constexpr size_t kHeader = 512;       // status words start here
+static_assert(sizeof(Scratch) <= kHeader, "scratch header");
+
+inline void ensure_scratch(Context& ctx, int64_t ntiles) {
+  if (!ctx.small || ctx.small_tiles < (size_t)ntiles + 64) {
+    ctx.small_tiles = (size_t)ntiles + 64 + (size_t)ntiles / 4;
+    ctx.small = make_device_buffer(kHeader + ctx.small_tiles * 8, ctx.device);
+  }
+  if (!ctx.pinned) { check_hip(hipHostMalloc(&ctx.pinned, sizeof(Scratch), hipHostMallocDefault), "hipHostMalloc"); ctx.pinned_bytes = sizeof(Scratch); }
+}
+inline Scratch* dev_scratch(Context& ctx) { return (Scratch*)ctx.small->ptr; }
+inline u64* dev_status(Context& ctx) { return (u64*)((uint8_t*)ctx.small->ptr + kHeader); }
+// The header into its pinned mirror, the stream synchronised.  (ensure_scratch may replace ctx.small: looked up per call.)
+inline Scratch* read_scratch(Context& ctx) {
+  Scratch* hs = (Scratch*)ctx.pinned;
+  check_hip(hipMemcpyAsync(hs, dev_scratch(ctx), sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
+  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  return hs;
+}
+// header + the status words of `ntiles` tiles: cleared before a call's first chained-scan launch
+inline void clear_scratch(Context& ctx, int64_t ntiles) {
+  check_hip(hipMemsetAsync(dev_scratch(ctx), 0, kHeader + (size_t)(ntiles + 1) * 8, ctx.stream), "memset scratch + status");
+}
+template <class P>   // FilterParams, FusedParams
+void bind_scratch(P& p, Context& ctx) {
+  Scratch* ds = dev_scratch(ctx);
+  p.status = dev_status(ctx); p.ticket = &ds->ticket; p.total = &ds->total; p.err = &ds->err;
+}
+// p.outs[k] copies launch column k from in(ci) to out(ci)
+template <class In, class Out>
+void fill_outs(FilterParams& p, const std::vector<int>& launch_cols, const std::vector<Column>& cols, In in, Out out) {
+  p.n_out = 0;
+  for (int ci : launch_cols) p.outs[p.n_out++] = OutCol{in(ci), out(ci), (uint32_t)cols[ci].width, 0};
+}
+inline int grid_cap(const Context& ctx, int tile_kind) { return ctx.num_cus * (ctx.opt_grid_per_cu > 0 ? (int)ctx.opt_grid_per_cu : kGridPerCu[tile_kind]); }
+
+// launch(partial, grid, tail) over p's tiles.  Large batches: all complete tiles run in the instantiation without partial-tile
+// code; the (single) incomplete tail tile in a second one-workgroup launch that continues the same chained scan.
+template <class Params, class Launch>
+void launch_tiles(Context& ctx, Params& p, int64_t rows, int64_t tile_rows, int64_t gcap, Launch&& launch) {
+  const int64_t ntiles = (rows + tile_rows - 1) / tile_rows, nfull = rows / tile_rows;
+  const bool split = rows >= ctx.opt_split_rows && nfull > 0;
+  p.tile_begin = 0; p.tile_end = split ? nfull : ntiles;
+  launch(!split, (int)std::min<int64_t>(p.tile_end, gcap), false);
+  ++ctx.stats.launches;
+  if (split && nfull < ntiles) {
+    p.tile_begin = nfull; p.tile_end = ntiles;
+    launch(true, 1, true);
+    ++ctx.stats.launches;
+  }
+}
+
+// ---- filter.cpp: a lowered program and its launch ------------------------------------------------------------------------
+void fill_refs(ProgramBlock& pb, const Lowered& lw, const Batch& rec, const std::vector<BufferPtr>& str_bufs);
+std::vector<BufferPtr> upload_strings(Context& ctx, const Lowered& lw);
+[[noreturn]] void throw_device_error(unsigned long long stored);
+int pick_tile_kind(const Context& ctx, const Lowered& lw, int64_t rows);
+void pick_stash(FilterParams& p, const Context& ctx, const Lowered& lw, const std::vector<Column>& cols, std::vector<int>& launch_cols, int tile_kind);
+// ---- filter.cpp: typing, and expressions that do not fit one device program ------------------------------------------------
+bool lowers_alone(const TypedExpr& te, int node, const std::vector<PlanColumn>& wcols);
+void fit_to_device(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const TypedExpr& original,
+                   Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te);
+TypedExpr typed(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& expr);
+bool is_row_predicate(const TypedExpr& te);
+Column empty_like(const Column& c);
+// ---- filter.cpp: the uniform-length Utf8 rewrite -----------------------------------------------------------------------------
+bool uniform_utf8_ok(bool may_hold_nulls, int64_t rows, int64_t L);
+Column uniform_to_utf8(Context& ctx, Column&& fixed, const Column& like, int64_t rows, bool on_device);
+
+// ---- project.cpp: typed trees evaluated densely over a batch, one column per expression ------------------------------------
+std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols,
+                                   const std::vector<const TypedExpr*>& exprs);
+
+}  // namespace chq

@@ -13,7 +13,7 @@ namespace {
 [[noreturn]] void unsupported(const std::string& what) { throw ChqError{CHQ_ERR_NOT_SUPPORTED, "parquet: " + what}; }
 [[noreturn]] void malformed(const std::string& what) { throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "parquet: " + what}; }
 
-// the columns' streams: forked off ctx.stream and joined back into it with events (engine.cpp: fork_aux_streams /
+// the columns' streams: forked off ctx.stream and joined back into it with events (memory.cpp: fork_aux_streams /
 // join_aux_streams).  Round 2 synchronised on the host instead, after a segfault whose cause is now known: the context ran
 // on the handle hipStreamLegacy, and ROCm 7.2's hipStreamWaitEvent dereferences that handle when it finds it in an event
 // (chq_ctx_create now keeps the null spelling of the same stream).

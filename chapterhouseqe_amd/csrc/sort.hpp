@@ -30,7 +30,7 @@ struct SortKeyArg {
 Batch sort_records(Context& ctx, std::vector<Batch>& in, const chq_table_aliases* aliases, const std::vector<SortKeyArg>& keys,
                    int64_t limit);
 
-// engine.cpp: the batches of a group joined into ONE device batch by the concat kernels (a single batch: its device view).
+// group.cpp: the batches of a group joined into ONE device batch by the concat kernels (a single batch: its device view).
 // A Utf8 column whose joined bytes pass int32 offsets is CHQ_ERR_ARROW_INVALID_ARGUMENT, naming the column.
 Batch join_group(Context& ctx, const std::vector<Batch>& recs);
 

@@ -1,5 +1,5 @@
 """GPU: one large host-resident batch through chq_filter_record -- cut into chunks whose uploads and downloads overlap
-(engine.cpp: filter_record_large_host) -- against the oracle and against the unchunked path: same rows, same order, same
+(filter.cpp: filter_record_large_host) -- against the oracle and against the unchunked path: same rows, same order, same
 status codes (a data-dependent error in a late chunk included)."""
 import numpy as np
 import pyarrow as pa

@@ -720,7 +720,7 @@ def test_default_nan_of_invalid_operations_matches_the_host(ctx):
 @pytest.mark.parametrize("n", [2, 65, 2049, 10_000, 100_000, 262_144, 262_145])
 def test_small_host_batches_take_the_single_sync_path(ctx, n):
     """the reference's calling pattern: a fixed-width host batch in, a host batch out -- staged through one pinned block
-    each way (engine.cpp:filter_record_small_host); identical results with the path switched off"""
+    each way (filter.cpp:filter_record_small_host); identical results with the path switched off"""
     rng = np.random.default_rng(n)
     rec = pa.RecordBatch.from_arrays(
         [pa.array(np.arange(n, dtype=np.int32)), pa.array((rng.random(n) * 100).astype(np.float32)),

@@ -64,7 +64,7 @@ def test_a_failed_call_does_not_leak_in_flight_work_into_the_pool():
     """A call that fails after it has queued its uploads (a typing error is found after staging) releases its blocks while
     the copies may still be in flight; the pools are process-wide, so the next call -- on ANOTHER context, i.e. another
     stream -- gets those blocks as its outputs.  Round 3's fuzz met the corruption twice (first output columns of a small
-    filter overwritten); blocks released during unwinding now wait for the device (engine.cpp: Buffer::~Buffer)."""
+    filter overwritten); blocks released during unwinding now wait for the device (memory.cpp: Buffer::~Buffer)."""
     import numpy as np
     import pyarrow as pa
     from chapterhouseqe_amd.sqlparse import parse_expr
