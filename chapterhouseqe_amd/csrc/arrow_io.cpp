@@ -88,7 +88,7 @@ const void* Column::values0() const {
   return values ? values + (int64_t)width * offset : nullptr;
 }
 
-void parse_arrow_format(const char* f, DType* t, int* width) {
+void parse_arrow_format(const char* f, DType* t, int* width, bool copy_only) {
   *width = 0;
   if (f && f[0] && !f[1]) {   // the primitive types are one character: no string object on the per-batch import path
     switch (f[0]) {
@@ -111,11 +111,11 @@ void parse_arrow_format(const char* f, DType* t, int* width) {
     if (commas == 1) { *width = 16; return; }
     if (commas == 2) { int bw = atoi(s.substr(s.rfind(',') + 1).c_str()); if (bw == 32) { *width = 4; return; } if (bw == 64) { *width = 8; return; } if (bw == 128) { *width = 16; return; } }
   }
-  if (s.rfind("w:", 0) == 0) { int w = atoi(s.c_str() + 2); if (w == 1 || w == 2 || w == 4 || w == 8 || w == 16) { *width = w; return; } }
+  if (s.rfind("w:", 0) == 0) { int w = atoi(s.c_str() + 2); if (w == 1 || w == 2 || w == 4 || w == 8 || w == 16 || (copy_only && w > 0)) { *width = w; return; } }
   throw ChqError{CHQ_ERR_NOT_SUPPORTED, "Arrow type with format '" + s + "' is outside this build's scope"};
 }
 
-Batch import_batch(const ArrowDeviceArray* rec, const ArrowSchema* schema) {
+Batch import_batch(const ArrowDeviceArray* rec, const ArrowSchema* schema, bool copy_only) {
   if (!rec || !schema || !schema->format) throw ChqError{CHQ_ERR_INVALID_HANDLE, "null record batch"};
   if (strcmp(schema->format, "+s") != 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "record batch must be a struct array"};
   const ArrowArray& a = rec->array;
@@ -138,7 +138,7 @@ Batch import_batch(const ArrowDeviceArray* rec, const ArrowSchema* schema) {
     Column c;
     c.name = cs->name ? cs->name : "";
     c.format = cs->format ? cs->format : "";
-    parse_arrow_format(cs->format, &c.type, &c.width);
+    parse_arrow_format(cs->format, &c.type, &c.width, copy_only);
     c.nullable = (cs->flags & ARROW_FLAG_NULLABLE) != 0;
     if (ca->length < b.nrows) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "column shorter than the record batch"};
     if (ca->offset < 0 || b.nrows < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative length or offset"};

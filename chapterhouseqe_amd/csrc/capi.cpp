@@ -611,7 +611,7 @@ chq_status chq_record_to_device(chq_ctx* ctx, const ArrowDeviceArray* rec, const
   return guarded(ctx, [&] {
     require(out, "output array"); require(out_schema, "output schema");
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    Batch in = import_batch(rec, schema);
+    Batch in = import_batch(rec, schema, true);   // (staging copies bytes: every fixed width)
     if (in.on_device) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "record is already device resident"};
     Batch dev = to_device(ctx->c, in);
     check_hip(hipStreamSynchronize(ctx->c.stream), "hipStreamSynchronize");
@@ -625,7 +625,7 @@ chq_status chq_record_copy_to_peer(chq_ctx* src_ctx, chq_ctx* dst_ctx, const Arr
   mark_released(out, out_schema);
   return guarded(dst_ctx, [&] {
     require(out, "output array"); require(out_schema, "output schema");
-    Batch in = import_batch(rec, schema);   // waits on rec->sync_event when the producer left one
+    Batch in = import_batch(rec, schema, true);   // waits on rec->sync_event when the producer left one
     hipEvent_t ev = nullptr;
     Batch moved = copy_to_peer(src_ctx->c, dst_ctx->c, in, &ev);
     export_batch(std::move(moved), ARROW_DEVICE_ROCM, out, out_schema, ev);
@@ -650,7 +650,7 @@ chq_status chq_record_to_ipc(chq_ctx* ctx, const ArrowDeviceArray* rec, const Ar
     if (body_device != ARROW_DEVICE_ROCM && body_device != ARROW_DEVICE_CPU)
       throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "body_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    Batch in = import_batch(rec, schema);
+    Batch in = import_batch(rec, schema, true);
     Batch dev = to_device(ctx->c, in);   // (a host batch is staged: the body is assembled by the device either way)
     // an unknown null count (-1, a view) stays unknown: the encoder counts it; to_device's "may have nulls" 1 would be written
     for (size_t i = 0; i < dev.cols.size(); ++i) if (in.on_device && in.cols[i].validity && in.cols[i].null_count < 0) dev.cols[i].null_count = -1;
@@ -848,7 +848,7 @@ chq_status chq_record_to_host(chq_ctx* ctx, const ArrowDeviceArray* rec, const A
   return guarded(ctx, [&] {
     require(out, "output array"); require(out_schema, "output schema");
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    Batch in = import_batch(rec, schema);
+    Batch in = import_batch(rec, schema, true);
     if (!in.on_device) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "record is already host resident"};
     for (Column& c : in.cols) if (c.validity && c.null_count < 0) c.null_count = 1;
     Batch h = to_host(ctx->c, in);

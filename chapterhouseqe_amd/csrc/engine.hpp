@@ -186,8 +186,8 @@ void kernel_span_begin(Context& ctx);
 void kernel_span_end(Context& ctx);
 int64_t kernel_span_ns(Context& ctx);
 
-// Arrow C Data Interface <-> Batch
-Batch import_batch(const ArrowDeviceArray* rec, const ArrowSchema* schema);
+// Arrow C Data Interface <-> Batch (`copy_only`: see parse_arrow_format)
+Batch import_batch(const ArrowDeviceArray* rec, const ArrowSchema* schema, bool copy_only = false);
 // `sync_event`: optional event the consumer must wait on; the exported array owns it (destroyed on release)
 void export_batch(Batch&& b, int device_type, ArrowDeviceArray* out, ArrowSchema* out_schema, hipEvent_t sync_event = nullptr);
 void export_single_column(Column&& c, bool on_device, int device_id, ArrowDeviceArray* out, ArrowSchema* out_schema);
@@ -272,8 +272,10 @@ Column compute_value(Context& ctx, const Batch& rec_dev, const std::vector<PlanC
 
 std::vector<PlanColumn> plan_columns(const Batch& b, const chq_table_aliases* aliases);
 
-// Arrow C format string -> column kind and byte width (throws CHQ_ERR_NOT_SUPPORTED outside the build's scope)
-void parse_arrow_format(const char* format, DType* type, int* width);
+// Arrow C format string -> column kind and byte width (throws CHQ_ERR_NOT_SUPPORTED outside the build's scope).
+// The kernels move values of 1, 2, 4, 8 and 16 bytes; `copy_only` is for the callers that move a column's bytes and launch no
+// kernel on its values (staging, peer copy, Arrow IPC): they take FixedSizeBinary of every width.
+void parse_arrow_format(const char* format, DType* type, int* width, bool copy_only = false);
 
 // A few persistent host threads for per-batch bookkeeping of large groups (importing / exporting 10^4..10^5 Arrow structs,
 // building pointer tables): f(t) for t in [0, tasks), the caller takes part, the first exception is rethrown.  Creating

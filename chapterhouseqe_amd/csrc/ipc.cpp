@@ -104,27 +104,44 @@ class FlatWriter {
 };
 
 // ----------------------------------------------------------------------------------------------------- flatbuffers: read
+// Positions are byte offsets into the metadata (0 = "absent": offset 0 holds the root offset, never a table).  Every read is
+// bounds-checked by subtraction, so a forged offset can neither leave the buffer nor wrap.
 struct FlatReader {
   const uint8_t* base; size_t len;
   [[noreturn]] void bad() const { throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "malformed Arrow IPC metadata"}; }
-  template <typename T> T rd(const uint8_t* p) const { if (p < base || p + sizeof(T) > base + len) bad(); T v; memcpy(&v, p, sizeof(T)); return v; }
-  const uint8_t* root() const { return base + rd<uint32_t>(base); }
-  const uint8_t* field(const uint8_t* t, int id) const {
-    const uint8_t* vt = t - rd<int32_t>(t);
-    const uint16_t vts = rd<uint16_t>(vt);
-    if (4 + 2 * id + 2 > vts) return nullptr;
-    const uint16_t off = rd<uint16_t>(vt + 4 + 2 * id);
-    return off ? t + off : nullptr;
+  template <typename T> T rd(size_t p) const { if (p > len || len - p < sizeof(T)) bad(); T v; memcpy(&v, base + p, sizeof(T)); return v; }
+  size_t follow(size_t p) const { const uint32_t o = rd<uint32_t>(p); if (o == 0 || o > len - p) bad(); return p + o; }
+  size_t root() const { return follow(0); }
+  size_t field(size_t t, int id) const {
+    const int64_t vt = (int64_t)t - rd<int32_t>(t);
+    if (vt < 0 || (uint64_t)vt > len) bad();
+    const uint16_t vts = rd<uint16_t>((size_t)vt), tsize = rd<uint16_t>((size_t)vt + 2);
+    if (vts < 4 || (vts & 1) || vts > len - (size_t)vt || tsize < 4 || tsize > len - t) bad();
+    if (4 + 2 * id + 2 > vts) return 0;
+    const uint16_t off = rd<uint16_t>((size_t)vt + 4 + 2 * (size_t)id);
+    if (!off) return 0;
+    if (off < 4 || off >= tsize) bad();
+    return t + off;
   }
-  template <typename T> T scalar(const uint8_t* t, int id, T def) const { const uint8_t* p = field(t, id); return p ? rd<T>(p) : def; }
-  const uint8_t* indirect(const uint8_t* t, int id) const { const uint8_t* p = field(t, id); return p ? p + rd<uint32_t>(p) : nullptr; }
-  uint32_t vec_len(const uint8_t* v) const { return rd<uint32_t>(v); }
-  std::string str(const uint8_t* t, int id) const {
-    const uint8_t* s = indirect(t, id);
+  template <typename T> T scalar(size_t t, int id, T def) const {
+    const size_t p = field(t, id);
+    if (!p) return def;
+    const uint16_t tsize = rd<uint16_t>((size_t)((int64_t)t - rd<int32_t>(t)) + 2);
+    if (p - t + sizeof(T) > tsize) bad();
+    return rd<T>(p);
+  }
+  size_t indirect(size_t t, int id) const { const size_t p = field(t, id); return p ? follow(p) : 0; }
+  // a vector's element count, after checking that `elem`-byte elements fit behind it
+  uint32_t vec_len(size_t v, size_t elem) const {
+    const uint32_t n = rd<uint32_t>(v);
+    if ((len - v - 4) / elem < n) bad();
+    return n;
+  }
+  std::string str(size_t t, int id) const {
+    const size_t s = indirect(t, id);
     if (!s) return "";
-    const uint32_t n = rd<uint32_t>(s);
-    if (s + 4 + n > base + len) bad();
-    return std::string((const char*)s + 4, n);
+    const uint32_t n = vec_len(s, 1);
+    return std::string((const char*)base + s + 4, n);
   }
 };
 
@@ -166,28 +183,63 @@ uint32_t write_type(FlatWriter& w, const std::string& f, uint8_t* tag) {
   throw ChqError{CHQ_ERR_NOT_SUPPORTED, "Arrow type with format '" + f + "' cannot be written as Arrow IPC by this build"};
 }
 
-std::string read_type(const FlatReader& r, uint8_t tag, const uint8_t* t) {
+// Type tables off the wire: a value the format does not define is refused (INVALID_ARGUMENT), never mapped onto a
+// neighbouring type's width; a legal type outside this build's scope is NOT_SUPPORTED and named.
+std::string read_type(const FlatReader& r, uint8_t tag, size_t t) {
+  auto invalid = [](const std::string& what) -> ChqError { return ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC type table: " + what}; };
+  auto unit = [&](int id, int16_t def, const char* of) {
+    const int u = r.scalar<int16_t>(t, id, def);
+    if (u < 0 || u > 3) throw invalid(std::string(of) + " unit " + std::to_string(u));
+    return unit_char(u);
+  };
   switch (tag) {
     case TY_Bool: return "b";
     case TY_Utf8: return "u";
     case TY_Int: {
       const int bits = r.scalar<int32_t>(t, 0, 0); const bool sign = r.scalar<uint8_t>(t, 1, 0) != 0;
       switch (bits) { case 8: return sign ? "c" : "C"; case 16: return sign ? "s" : "S"; case 32: return sign ? "i" : "I"; case 64: return sign ? "l" : "L"; default: break; }
-      break;
+      throw invalid("Int bitWidth " + std::to_string(bits));
     }
-    case TY_FloatingPoint: { const int p = r.scalar<int16_t>(t, 0, 0); return p == 0 ? "e" : p == 1 ? "f" : "g"; }
-    case TY_Date: return r.scalar<int16_t>(t, 0, 1) == 0 ? "tdD" : "tdm";
-    case TY_Time: return std::string("tt") + unit_char(r.scalar<int16_t>(t, 0, 1));
-    case TY_Timestamp: return std::string("ts") + unit_char(r.scalar<int16_t>(t, 0, 0)) + ":" + r.str(t, 1);
-    case TY_Duration: return std::string("tD") + unit_char(r.scalar<int16_t>(t, 0, 1));
+    case TY_FloatingPoint: {
+      const int p = r.scalar<int16_t>(t, 0, 0);
+      if (p < 0 || p > 2) throw invalid("FloatingPoint precision " + std::to_string(p));
+      return p == 0 ? "e" : p == 1 ? "f" : "g";
+    }
+    case TY_Date: {
+      const int u = r.scalar<int16_t>(t, 0, 1);
+      if (u != 0 && u != 1) throw invalid("Date unit " + std::to_string(u));
+      return u == 0 ? "tdD" : "tdm";
+    }
+    case TY_Time: {
+      const char u = unit(0, 1, "Time");
+      const int bits = r.scalar<int32_t>(t, 1, 32);
+      if (bits != ((u == 's' || u == 'm') ? 32 : 64)) throw invalid(std::string("Time unit '") + u + "' with bitWidth " + std::to_string(bits));
+      return std::string("tt") + u;
+    }
+    case TY_Timestamp: return std::string("ts") + unit(0, 0, "Timestamp") + ":" + r.str(t, 1);
+    case TY_Duration: return std::string("tD") + unit(0, 1, "Duration");
     case TY_Decimal: {
       const int p = r.scalar<int32_t>(t, 0, 0), s = r.scalar<int32_t>(t, 1, 0), bw = r.scalar<int32_t>(t, 2, 128);
-      return "d:" + std::to_string(p) + "," + std::to_string(s) + (bw == 128 ? "" : "," + std::to_string(bw));
+      if (bw == 32 || bw == 64 || bw == 256)
+        throw ChqError{CHQ_ERR_NOT_SUPPORTED, "Arrow IPC type Decimal" + std::to_string(bw) + " is outside this build's scope"};
+      if (bw != 128) throw invalid("Decimal bitWidth " + std::to_string(bw));
+      if (p < 1 || p > 38) throw invalid("Decimal128 precision " + std::to_string(p));
+      return "d:" + std::to_string(p) + "," + std::to_string(s);
     }
-    case TY_FixedSizeBinary: return "w:" + std::to_string(r.scalar<int32_t>(t, 0, 0));
+    case TY_FixedSizeBinary: {
+      const int w = r.scalar<int32_t>(t, 0, 0);
+      if (w < 0) throw invalid("FixedSizeBinary byteWidth " + std::to_string(w));
+      if (w == 0) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "Arrow IPC type FixedSizeBinary(0) is outside this build's scope"};
+      return "w:" + std::to_string(w);
+    }
     default: break;
   }
-  throw ChqError{CHQ_ERR_NOT_SUPPORTED, "Arrow IPC type id " + std::to_string((int)tag) + " is outside this build's scope"};
+  static const char* const kNames[] = {"NONE", "Null", "Int", "FloatingPoint", "Binary", "Utf8", "Bool", "Decimal", "Date", "Time", "Timestamp",
+                                       "Interval", "List", "Struct", "Union", "FixedSizeBinary", "FixedSizeList", "Map", "Duration",
+                                       "LargeBinary", "LargeUtf8", "LargeList", "RunEndEncoded", "BinaryView", "Utf8View", "ListView", "LargeListView"};
+  if (tag == 0) throw invalid("field without a type");
+  const std::string name = tag < sizeof(kNames) / sizeof(kNames[0]) ? kNames[tag] : "id " + std::to_string((int)tag);
+  throw ChqError{CHQ_ERR_NOT_SUPPORTED, "Arrow IPC type " + name + " is outside this build's scope"};
 }
 
 void append_message(std::vector<uint8_t>& out, const std::vector<uint8_t>& fb) {   // continuation, size (padded to 8), flatbuffer
@@ -338,78 +390,130 @@ IpcMessage record_to_ipc(Context& ctx, const Batch& dev, bool body_on_device) {
 // decode
 // =====================================================================================================================
 namespace {
-struct FieldInfo { std::string name, format; bool nullable = false; };
+struct FieldInfo { std::string name, format; bool nullable = false; DType type = T_BOOL; int width = 0; };
 struct ParsedStream {
   std::vector<FieldInfo> fields;
   int64_t n = 0, body_len = 0;
   std::vector<std::pair<int64_t, int64_t>> nodes, buffers;
-  int64_t body_at = -1;   // position of the body inside the stream (right behind the batch message's metadata)
+  int64_t body_at = -1;       // position of the body inside the stream (right behind the batch message's metadata)
+  bool header_only = false;   // the stream ends with the batch message's metadata: the body travels separately
 };
 
-ParsedStream parse_stream(const uint8_t* stream, int64_t stream_len) {
-  if (!stream || stream_len < 8) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "empty Arrow IPC stream"};
+[[noreturn]] void invalid_stream(const std::string& what) { throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, what}; }
+
+int64_t bitmap_bytes(int64_t n) { return n / 8 + (n % 8 != 0); }
+
+// Everything the METADATA claims is checked here, on the host, before a byte of the body is copied or an allocation is sized
+// by it: framing, the flatbuffers, type tables, row count, null counts and every (offset, length) against bodyLength.  Sizes
+// from the wire are compared by subtraction / division only -- sums and products of forged 64-bit values wrap.
+// `separate_body`: the caller passes the body on its own, so `stream` holds metadata only.
+ParsedStream parse_stream(const uint8_t* stream, int64_t stream_len, bool separate_body) {
+  if (!stream || stream_len < 8) invalid_stream("empty Arrow IPC stream");
   ParsedStream ps;
   bool have_schema = false, have_batch = false;
   int64_t at = 0;
-  while (at + 8 <= stream_len && !have_batch) {
+  while (stream_len - at >= 4) {
     uint32_t first; memcpy(&first, stream + at, 4);
     int32_t msize;
-    if (first == 0xFFFFFFFFu) { memcpy(&msize, stream + at + 4, 4); at += 8; }
-    else { msize = (int32_t)first; at += 4; }   // pre-0.15 framing without the continuation marker
+    if (first == 0xFFFFFFFFu) {
+      if (stream_len - at < 8) invalid_stream("truncated Arrow IPC message");
+      memcpy(&msize, stream + at + 4, 4); at += 8;
+    } else { msize = (int32_t)first; at += 4; }   // pre-0.15 framing without the continuation marker
     if (msize == 0) break;   // end of stream
-    if (msize < 0 || at + msize > stream_len) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "truncated Arrow IPC message"};
+    if (msize < 0 || msize > stream_len - at) invalid_stream("truncated Arrow IPC message");
     FlatReader r{stream + at, (size_t)msize};
-    const uint8_t* m = r.root();
+    const size_t m = r.root();
     const uint8_t htype = r.scalar<uint8_t>(m, 1, 0);
-    const uint8_t* h = r.indirect(m, 2);
+    const size_t h = r.indirect(m, 2);
     const int64_t blen = r.scalar<int64_t>(m, 3, 0);
     at += msize;
+    if (blen < 0) invalid_stream("Arrow IPC message with a negative bodyLength");
     if (htype == 1 && h) {   // Schema
+      if (have_schema) invalid_stream("Arrow IPC stream with a second schema");
       if (r.scalar<int16_t>(h, 0, 0) != 0) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "big-endian Arrow IPC streams are not supported"};
-      const uint8_t* fv = r.indirect(h, 1);
-      const uint32_t nf = fv ? r.vec_len(fv) : 0;
+      const size_t fv = r.indirect(h, 1);
+      const uint32_t nf = fv ? r.vec_len(fv, 4) : 0;
       for (uint32_t i = 0; i < nf; ++i) {
-        const uint8_t* slot = fv + 4 + 4 * i;
-        const uint8_t* f = slot + r.rd<uint32_t>(slot);
+        const size_t f = r.follow(fv + 4 + 4 * (size_t)i);
         if (r.field(f, 4)) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "dictionary-encoded fields are outside this build's scope"};
-        const uint8_t* ch = r.indirect(f, 5);
-        if (ch && r.vec_len(ch) != 0) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "nested Arrow types are outside this build's scope"};
+        const size_t ch = r.indirect(f, 5);
+        if (ch && r.vec_len(ch, 4) != 0) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "nested Arrow types are outside this build's scope"};
         FieldInfo fi;
         fi.name = r.str(f, 0); fi.nullable = r.scalar<uint8_t>(f, 1, 0) != 0;
-        const uint8_t* ty = r.indirect(f, 3);
+        const size_t ty = r.indirect(f, 3);
         if (!ty) r.bad();
         fi.format = read_type(r, r.scalar<uint8_t>(f, 2, 0), ty);
+        parse_arrow_format(fi.format.c_str(), &fi.type, &fi.width, true);   // the C-data format parser knows type and width; the decode only places bytes
         ps.fields.push_back(std::move(fi));
       }
       have_schema = true;
     } else if (htype == 3 && h) {   // RecordBatch
-      if (!have_schema) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC record batch before its schema"};
-      if (r.field(h, 3)) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "compressed Arrow IPC bodies are outside this build's scope"};
+      if (!have_schema) invalid_stream("Arrow IPC record batch before its schema");
+      // the reference refuses a second batch too (ExchangeRequestsError::ReceivedMultipleRecordBatches, exchange.rs:259-266)
+      if (have_batch) invalid_stream("Arrow IPC stream with more than one record batch");
+      if (const size_t comp = r.indirect(h, 3)) {
+        const int codec = r.scalar<int8_t>(comp, 0, 0);
+        throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("compressed Arrow IPC bodies (") + (codec == 0 ? "LZ4_FRAME" : codec == 1 ? "ZSTD" : "unknown codec") +
+                                                  ") are outside this build's scope"};
+      }
       ps.n = r.scalar<int64_t>(h, 0, 0);
       auto pairs = [&](int id, std::vector<std::pair<int64_t, int64_t>>& out) {
-        const uint8_t* v = r.indirect(h, id);
-        const uint32_t k = v ? r.vec_len(v) : 0;
-        for (uint32_t i = 0; i < k; ++i) out.push_back({r.rd<int64_t>(v + 4 + 16 * i), r.rd<int64_t>(v + 4 + 16 * i + 8)});
+        const size_t v = r.indirect(h, id);
+        const uint32_t k = v ? r.vec_len(v, 16) : 0;
+        for (uint32_t i = 0; i < k; ++i) out.push_back({r.rd<int64_t>(v + 4 + 16 * (size_t)i), r.rd<int64_t>(v + 4 + 16 * (size_t)i + 8)});
       };
       pairs(1, ps.nodes); pairs(2, ps.buffers);
       ps.body_len = blen;
       ps.body_at = at;
       have_batch = true;
+      if (!separate_body) {
+        if (at == stream_len && blen > 0) ps.header_only = true;
+        else if (blen > stream_len - at) invalid_stream("Arrow IPC body is shorter than its metadata says");
+        else at += blen;
+      }
     } else if (htype == 2) {
       throw ChqError{CHQ_ERR_NOT_SUPPORTED, "dictionary batches are outside this build's scope"};
-    } else {
-      at += blen;   // a message kind we do not need
+    } else {   // a message kind we do not need: step over its body, which must lie inside the stream
+      if (blen > stream_len - at) invalid_stream("truncated Arrow IPC message body");
+      at += blen;
     }
   }
-  if (!have_schema || !have_batch) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC stream without a schema and a record batch"};
-  if (ps.n < 0 || ps.nodes.size() != ps.fields.size()) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC record batch does not match its schema"};
+  if (!have_schema || !have_batch) invalid_stream("Arrow IPC stream without a schema and a record batch");
+  const int64_t n = ps.n, body = ps.body_len;
+  if (n < 0 || ps.nodes.size() != ps.fields.size()) invalid_stream("Arrow IPC record batch does not match its schema");
+  size_t bi = 0;
+  auto take = [&](int64_t need, const char* what) {
+    if (bi >= ps.buffers.size()) invalid_stream("Arrow IPC record batch has too few buffers");
+    const auto [off, len] = ps.buffers[bi++];
+    if (off < 0 || len < 0 || off > body || len > body - off || len < need)
+      invalid_stream(std::string("Arrow IPC buffer (") + what + ") outside the body or too short");
+  };
+  // a column of n rows needs n * width (n / 8, 4 (n + 1)) bytes of the body: n is bounded by division before it is multiplied
+  auto rows_fit = [&](int64_t per_row_num, int64_t per_row_den, const FieldInfo& f) {
+    if (n / per_row_den > body / per_row_num) invalid_stream("Arrow IPC record batch length " + std::to_string(n) + " exceeds what the body can hold for column '" + f.name + "'");
+  };
+  for (size_t c = 0; c < ps.fields.size(); ++c) {
+    const FieldInfo& f = ps.fields[c];
+    const auto [len, nulls] = ps.nodes[c];
+    if (len != n) invalid_stream("Arrow IPC field node length differs from the batch length");
+    if (nulls < 0 || nulls > n) invalid_stream("Arrow IPC field node null count " + std::to_string(nulls) + " outside [0, length]");
+    if (f.type == T_BOOL) rows_fit(1, 8, f);
+    else if (f.type == T_UTF8) rows_fit(4, 1, f);
+    else rows_fit(f.width, 1, f);
+    take(nulls > 0 ? bitmap_bytes(n) : 0, "validity");
+    if (f.type == T_BOOL) take(bitmap_bytes(n), "bitmap");
+    else if (f.type == T_UTF8) {
+      take(n > 0 ? (n + 1) * 4 : 0, "offsets");   // zero rows: older writers emit an empty offsets buffer; arrow-rs and Arrow C++ accept it
+      take(0, "string bytes");
+    } else take(n * f.width, "values");
+  }
   return ps;
 }
 }  // namespace
 
 // host only: what a stream's metadata says (the CPU test tier checks the flatbuffer reader against pyarrow's writer)
 std::string describe_ipc(const uint8_t* stream, int64_t stream_len) {
-  const ParsedStream ps = parse_stream(stream, stream_len);
+  const ParsedStream ps = parse_stream(stream, stream_len, false);
   std::string out = "rows " + std::to_string(ps.n) + " body " + std::to_string(ps.body_len) + " body_at " + std::to_string(ps.body_at) + "\n";
   for (size_t c = 0; c < ps.fields.size(); ++c)
     out += "field " + ps.fields[c].name + " " + ps.fields[c].format + " nullable=" + (ps.fields[c].nullable ? "1" : "0") +
@@ -420,76 +524,96 @@ std::string describe_ipc(const uint8_t* stream, int64_t stream_len) {
 
 Batch record_from_ipc(Context& ctx, const uint8_t* stream, int64_t stream_len, const void* body, int64_t body_len,
                       bool body_on_device, bool out_on_device) {
-  const ParsedStream ps = parse_stream(stream, stream_len);
+  const ParsedStream ps = parse_stream(stream, stream_len, body != nullptr);   // every size below has been validated there
   const std::vector<FieldInfo>& fields = ps.fields;
   const int64_t n = ps.n, meta_body_len = ps.body_len;
   const std::vector<std::pair<int64_t, int64_t>>& nodes = ps.nodes;
   const std::vector<std::pair<int64_t, int64_t>>& buffers = ps.buffers;
-  const uint8_t* inline_body = nullptr;
-  if (!body) {
-    if (ps.body_at + meta_body_len > stream_len) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC body is shorter than its metadata says"};
-    inline_body = stream + ps.body_at;
-  }
-  const void* src_body = body ? body : (const void*)inline_body;
+  if (body ? body_len < meta_body_len : ps.header_only) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC body is shorter than its metadata says"};
+  const void* src_body = body ? body : (const void*)(stream + ps.body_at);
   const bool src_on_device = body ? body_on_device : false;
-  if (body && body_len < meta_body_len) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC body is shorter than its metadata says"};
 
   // ---- the body goes to its destination with ONE copy; the columns are views into it -------------------------------------
   BufferPtr owned = out_on_device ? make_device_buffer((size_t)meta_body_len + 64, ctx.device) : make_host_buffer((size_t)meta_body_len + 64);
+  uint8_t* const base = (uint8_t*)owned->ptr;
   if (meta_body_len > 0) {
-    if (!out_on_device && !src_on_device) memcpy(owned->ptr, src_body, (size_t)meta_body_len);
+    if (!out_on_device && !src_on_device) memcpy(base, src_body, (size_t)meta_body_len);
     else {
       const hipMemcpyKind k = out_on_device ? (src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) : hipMemcpyDeviceToHost;
-      check_hip(hipMemcpyAsync(owned->ptr, src_body, (size_t)meta_body_len, k, ctx.stream), "move Arrow IPC body");
+      check_hip(hipMemcpyAsync(base, src_body, (size_t)meta_body_len, k, ctx.stream), "move Arrow IPC body");
     }
   }
   Batch out;
   out.nrows = n; out.on_device = out_on_device; out.device_id = out_on_device ? ctx.device : -1;
   size_t bi = 0;
-  std::vector<std::pair<const int32_t*, int64_t>> utf8_checks;   // (offsets, data length) to validate after the copy landed
-  auto take = [&](int64_t need, const char* what) -> const uint8_t* {
-    if (bi >= buffers.size()) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC record batch has too few buffers"};
-    const auto [off, len] = buffers[bi++];
-    if (off < 0 || len < 0 || off + len > meta_body_len || len < need)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, std::string("Arrow IPC buffer (") + what + ") outside the body or too short"};
-    return (const uint8_t*)owned->ptr + off;
-  };
+  struct Utf8Check { const int32_t* offs; int64_t data_len; };      // validated after the copy landed
+  struct NullCheck { const uint8_t* validity; int64_t claimed; };   // the bitmap must hold exactly the nulls the node claims
+  std::vector<Utf8Check> utf8_checks;
+  std::vector<NullCheck> null_checks;
+  const uint8_t* zero_offset = nullptr;   // one zero Int32 in the allocation's slack, for zero-row Utf8 columns without offsets
   for (size_t c = 0; c < fields.size(); ++c) {
     Column col;
     col.name = fields[c].name; col.format = fields[c].format; col.nullable = fields[c].nullable;
-    parse_arrow_format(col.format.c_str(), &col.type, &col.width);   // the C-data format parser knows type and width
-    if (nodes[c].first != n) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC field node length differs from the batch length"};
+    col.type = fields[c].type; col.width = fields[c].width;
     col.length = n; col.offset = 0; col.null_count = nodes[c].second;
-    const uint8_t* validity = take(col.null_count > 0 ? (n + 7) / 8 : 0, "validity");
+    // a validity buffer next to null_count 0 is dropped, as Arrow C++ and arrow-rs do: every row is valid
+    const uint8_t* validity = base + buffers[bi++].first;
     col.validity = col.null_count > 0 ? validity : nullptr;
-    if (col.type == T_BOOL) col.values = take((n + 7) / 8, "bitmap");
-    else if (col.type == T_UTF8) {
-      col.values = take((n + 1) * 4, "offsets");
-      const size_t data_idx = bi;
-      col.data = take(0, "string bytes");
-      utf8_checks.push_back({(const int32_t*)col.values, buffers[data_idx].second});
-    } else col.values = take(n * col.width, "values");
+    if (col.validity) null_checks.push_back({col.validity, col.null_count});
+    col.values = base + buffers[bi].first;
+    if (col.type == T_UTF8) {
+      if (buffers[bi].second < 4) {   // only legal with zero rows (parse_stream)
+        if (!zero_offset) {
+          zero_offset = base + (meta_body_len + 7) / 8 * 8;
+          if (out_on_device) check_hip(hipMemsetAsync((void*)zero_offset, 0, 8, ctx.stream), "memset");
+          else memset((void*)zero_offset, 0, 8);
+        }
+        col.values = zero_offset;
+      }
+      ++bi;
+      col.data = base + buffers[bi].first;
+      if (n > 0) utf8_checks.push_back({(const int32_t*)col.values, buffers[bi].second});
+    }
+    ++bi;
     col.owned.push_back(owned);
     out.cols.push_back(std::move(col));
   }
-  // a kernel must never follow offsets out of the data buffer: EVERY offset is checked (0 <= off[i] <= off[i+1] <= data
-  // length), on the device for a device result -- one small kernel per Utf8 column, one flag word read back with the
-  // synchronisation that was needed anyway -- and by a plain loop for a host result
+  // What only the BODY can tell is checked once it has landed.  A kernel must never follow offsets out of the data buffer:
+  // EVERY offset is checked (0 <= off[i] <= off[i+1] <= data length).  A null count that contradicts its bitmap is refused:
+  // consumers size outputs and pick kernels by it.  For a device result these are one small kernel per Utf8 column and per
+  // column with nulls, and one read-back (flag word + counters) with the synchronisation that was needed anyway; for a host
+  // result, plain loops.
   BufferPtr flags;
-  if (out_on_device && !utf8_checks.empty()) {
-    flags = make_device_buffer(16, ctx.device);
-    check_hip(hipMemsetAsync(flags->ptr, 0, 16, ctx.stream), "memset");
+  std::vector<unsigned long long> results(1 + null_checks.size(), 0);   // [0] the offsets flag, then set bits per bitmap
+  if (out_on_device && n > 0 && (!utf8_checks.empty() || !null_checks.empty())) {
+    flags = make_device_buffer(results.size() * 8, ctx.device);
+    unsigned long long* dev = (unsigned long long*)flags->ptr;
+    check_hip(hipMemsetAsync(dev, 0, results.size() * 8, ctx.stream), "memset");
     for (auto& chk : utf8_checks)
-      check_hip(launch_validate_offsets(chk.first, n, chk.second, (uint32_t*)flags->ptr, ctx.stream), "launch validate_offsets_kernel");
+      check_hip(launch_validate_offsets(chk.offs, n, chk.data_len, (uint32_t*)dev, ctx.stream), "launch validate_offsets_kernel");
+    for (size_t k = 0; k < null_checks.size(); ++k)
+      check_hip(launch_count_bits(null_checks[k].validity, 0, n, dev + 1 + k, ctx.stream), "launch count_bits_kernel");
+    check_hip(hipMemcpyAsync(results.data(), dev, results.size() * 8, hipMemcpyDeviceToHost, ctx.stream), "read back");
   }
-  uint32_t bad = 0;
-  if (flags) check_hip(hipMemcpyAsync(&bad, flags->ptr, 4, hipMemcpyDeviceToHost, ctx.stream), "read back");
   check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
   if (!out_on_device) {
+    bool bad = false;
     for (auto& chk : utf8_checks)
-      for (int64_t i = 0; i < n && !bad; ++i) bad |= chk.first[i] < 0 || chk.first[i + 1] < chk.first[i] || (int64_t)chk.first[i + 1] > chk.second;
+      for (int64_t i = 0; i < n && !bad; ++i) bad |= chk.offs[i] < 0 || chk.offs[i + 1] < chk.offs[i] || (int64_t)chk.offs[i + 1] > chk.data_len;
+    results[0] = bad;
+    for (size_t k = 0; k < null_checks.size(); ++k) {
+      const uint8_t* v = null_checks[k].validity;
+      unsigned long long set = 0;
+      for (int64_t i = 0; i < n / 8; ++i) set += (unsigned)__builtin_popcount(v[i]);
+      if (n % 8) set += (unsigned)__builtin_popcount(v[n / 8] & ((1u << (n % 8)) - 1u));
+      results[1 + k] = set;
+    }
   }
-  if (bad) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC Utf8 offsets are not monotonic or point outside the data buffer"};
+  if ((uint32_t)results[0]) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC Utf8 offsets are not monotonic or point outside the data buffer"};
+  for (size_t k = 0; k < null_checks.size(); ++k)
+    if (n - (int64_t)results[1 + k] != null_checks[k].claimed)
+      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "Arrow IPC field node claims " + std::to_string(null_checks[k].claimed) + " nulls, its validity bitmap holds " +
+                                                          std::to_string(n - (int64_t)results[1 + k])};
   return out;
 }
 
