@@ -176,45 +176,14 @@ void export_group(JoinedGroup&& g, int device_type, ArrowDeviceArray* outs, Arro
 // Import of a group.  Batch 0 is imported in full.  A DEVICE-resident group then only gathers its GroupLite -- the checks of
 // import_batch on every record, but no Batch objects: the one-launch path works from the flat arrays, and building and
 // freeing 12 500 Batch objects cost ~0.6 ms of a 2.5 ms call; `gi.materialise` imports them when another path needs them.
-// Host groups (staged and packed from the batches themselves) are imported in full, with their GroupLite on the side.
-void lite_from_arrow(const ArrowDeviceArray* rec, const ArrowSchema* schema, const Batch& first, int device, GroupLite& lite, size_t b) {
-  const ArrowArray& a = rec->array;
-  const size_t nc = lite.ncols;
-  uint8_t f = 0;
-  if (a.offset != 0 || a.n_children != schema->n_children || (size_t)a.n_children != nc || rec->device_type != ARROW_DEVICE_ROCM || rec->sync_event) {
-    lite.flags[b] = GroupLite::GL_SCHEMA_DIFFERS;   // (anything unusual: the full import decides -- and reports)
-    return;
-  }
-  const int64_t rows = a.length;
-  lite.rows[b] = rows;
-  if ((int)rec->device_id == device) f |= GroupLite::GL_ON_DEVICE;
-  if (rows < 2) f |= GroupLite::GL_SHORT;
-  for (size_t i = 0; i < nc; ++i) {
-    const ArrowArray* ca = a.children[i];
-    const Column& c0 = first.cols[i];
-    if (!ca || ca->length < rows || ca->offset < 0 || ca->n_buffers < 2 || !ca->buffers || !ca->buffers[1] ||
-        (ca->null_count > 0 && !ca->buffers[0])) { f |= GroupLite::GL_SCHEMA_DIFFERS; continue; }
-    const uint8_t* validity = (const uint8_t*)ca->buffers[0];
-    const uint8_t* values = (const uint8_t*)ca->buffers[1];
-    if (validity && ca->null_count != 0) { f |= GroupLite::GL_NULLS; lite.validity[b * nc + i] = validity; }
-    lite.offset[b * nc + i] = ca->offset;
-    if (c0.type == T_UTF8) {
-      const uint8_t* data = ca->n_buffers > 2 ? (const uint8_t*)ca->buffers[2] : nullptr;
-      if (!data) f |= GroupLite::GL_NO_UTF8_DATA;
-      lite.values0[b * nc + i] = values + 4 * ca->offset; lite.data[b * nc + i] = data;
-    } else if (c0.type == T_BOOL) lite.values0[b * nc + i] = values;
-    else lite.values0[b * nc + i] = values + (int64_t)c0.width * ca->offset;
-  }
-  lite.flags[b] = f;
-}
-
-void import_group(int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema, int device, std::vector<Batch>& in,
-                  GroupLite& lite, GroupInput& gi) {
+// Host groups are imported in full, and described by their GroupLite like any other.
+void import_group(int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema, int device, GroupInput& gi) {
+  std::vector<Batch>& in = gi.batches;
+  GroupLite& lite = gi.lite;
   in.resize(1);
   in[0] = import_batch(recs[0], schema);
   lite.resize((size_t)n_records, in[0].cols.size());
   lite.set(0, in[0], in[0], device);
-  gi.batches = &in; gi.lite = &lite;
   auto import_rest = [n_records, recs, schema, &in]() {
     if ((int)in.size() == n_records) return;
     in.resize((size_t)n_records);
@@ -222,7 +191,7 @@ void import_group(int n_records, const ArrowDeviceArray* const* recs, const Arro
   };
   if (in[0].on_device && n_records > 1) {
     const Batch& first = in[0];
-    for_each_parallel(n_records - 1, [&](int k) { lite_from_arrow(recs[(size_t)k + 1], schema, first, device, lite, (size_t)k + 1); });
+    for_each_parallel(n_records - 1, [&](int k) { lite.set_from_arrow((size_t)k + 1, recs[(size_t)k + 1], schema, first, device); });
     gi.materialise = import_rest;
     return;
   }
@@ -417,11 +386,9 @@ chq_status chq_filter_records(chq_ctx* ctx, int n_records, const ArrowDeviceArra
       throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_filter_records");
-    std::vector<Batch> in;
-    GroupLite lite;
     GroupInput gi;
     for (int i = 0; i < n_records; ++i) require(recs[i], "record");
-    import_group(n_records, recs, schema, ctx->c.device, in, lite, gi);
+    import_group(n_records, recs, schema, ctx->c.device, gi);
     pt.mark("import");
     GroupResult res = filter_records(ctx->c, gi, table_aliases, expr->e, out_device == ARROW_DEVICE_ROCM);
     pt.mark("filter");
@@ -459,11 +426,9 @@ chq_status chq_filter_records_coalesced(chq_ctx* ctx, int n_records, const Arrow
       throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_filter_records_coalesced");
-    std::vector<Batch> in;
-    GroupLite lite;
     GroupInput gi;
     for (int i = 0; i < n_records; ++i) require(recs[i], "record");
-    import_group(n_records, recs, schema, ctx->c.device, in, lite, gi);
+    import_group(n_records, recs, schema, ctx->c.device, gi);
     pt.mark("import");
     std::vector<int64_t> rows;
     Batch res = filter_records_coalesced(ctx->c, gi, table_aliases, expr->e, out_device == ARROW_DEVICE_ROCM, &rows);

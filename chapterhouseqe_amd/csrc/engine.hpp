@@ -117,6 +117,25 @@ struct Batch {
 };
 
 // ---- context ------------------------------------------------------------------------------------------
+void check_hip(hipError_t e, const char* what);
+// A grow-only block of pinned host memory (staging that the copy engine reads and writes directly).  Every user has its own
+// capacity formula: `reserve` allocates `capacity` bytes when the block holds fewer than `need` (the old contents are lost).
+struct PinnedBlock {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  void reserve(size_t need, size_t capacity, const char* what) {
+    if (bytes >= need) return;
+    if (ptr) (void)hipHostFree(ptr);
+    ptr = nullptr; bytes = 0;
+    check_hip(hipHostMalloc(&ptr, capacity, hipHostMallocDefault), what);
+    bytes = capacity;
+  }
+  PinnedBlock() = default;
+  PinnedBlock(const PinnedBlock&) = delete;
+  PinnedBlock& operator=(const PinnedBlock&) = delete;
+  ~PinnedBlock() { if (ptr) (void)hipHostFree(ptr); }
+};
+
 struct Context {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -161,21 +180,16 @@ struct Context {
   // reusable device scratch
   BufferPtr small;          // [Scratch header (512 B)] [status words of the chained scan]: cleared by ONE memset per call
   size_t small_tiles = 0;   // status words the block has room for
-  void* pinned = nullptr;                  // pinned host staging for small read-backs (256 B)
-  size_t pinned_bytes = 0;
-  void* pinned_tbl = nullptr;              // pinned staging of a batch-group launch (tile table, per-batch prefixes)
-  size_t pinned_tbl_bytes = 0;
-  void* pinned_sizes = nullptr;            // pinned staging of the Utf8 size gather of a group (in flight while the table is built)
-  size_t pinned_sizes_bytes = 0;
-  void* pinned_io = nullptr;               // pinned staging of the small host-batch path: [inputs | outputs]
-  size_t pinned_io_bytes = 0;
+  PinnedBlock pinned;                      // pinned host staging for small read-backs (the Scratch header)
+  PinnedBlock pinned_tbl;                  // pinned staging of a batch-group launch (tile table, per-batch prefixes)
+  PinnedBlock pinned_sizes;                // pinned staging of the Utf8 size gather of a group (in flight while the table is built)
+  PinnedBlock pinned_io;                   // pinned staging of the small host-batch path: [inputs | outputs]
   BufferPtr dev_io;                        // its device twin
   bool opt_small_host = true;              // host batches up to a few MB: one upload, one download, one synchronisation
 
   ~Context();
 };
 
-void check_hip(hipError_t e, const char* what);
 // the auxiliary streams of a context: created on first use (one site), forked off / joined back into ctx.stream with events
 void ensure_aux_streams(Context& ctx);
 void fork_aux_streams(Context& ctx);
@@ -219,9 +233,13 @@ struct GroupLite {
   std::vector<const uint8_t*> validity;    // [nb * ncols] validity bitmap, null when the column has no nulls in that batch
   std::vector<int64_t> offset;             // [nb * ncols] Arrow slice offset: bit position of row 0 in the bitmaps
   std::vector<uint8_t> flags;              // [nb] GL_*
-  enum : uint8_t { GL_NULLS = 1, GL_NO_UTF8_DATA = 2, GL_SCHEMA_DIFFERS = 4, GL_ON_DEVICE = 8, GL_SHORT = 16 };
+  // GL_NULLS: a validity bitmap that may clear a bit (device batch: bitmap present and null_count != 0; host batch: nulls
+  // counted, by the producer or here).  GL_ON_DEVICE: in this context's GPU memory.  GL_ON_HOST: in host memory.
+  enum : uint8_t { GL_NULLS = 1, GL_NO_UTF8_DATA = 2, GL_SCHEMA_DIFFERS = 4, GL_ON_DEVICE = 8, GL_SHORT = 16, GL_ON_HOST = 32 };
   void resize(size_t nb, size_t nc) { ncols = nc; rows.assign(nb, 0); values0.assign(nb * nc, nullptr); data.assign(nb * nc, nullptr); validity.assign(nb * nc, nullptr); offset.assign(nb * nc, 0); flags.assign(nb, 0); }
+  // the facts of batch b from an imported batch / straight from the Arrow structs of a device batch (no Batch object)
   void set(size_t b, const Batch& r, const Batch& first, int device);
+  void set_from_arrow(size_t b, const ArrowDeviceArray* rec, const ArrowSchema* schema, const Batch& first, int device);
   GroupLite slice(size_t b0, size_t b1) const;   // the facts of batches [b0, b1)
 };
 // The joined result of a group call, or of consecutive batches of it: ONE batch holding every surviving row in input order
@@ -243,13 +261,16 @@ struct GroupResult {
     return n;
   }
 };
-// The batches of a group call.  `batches` always holds batch 0; with `lite` the others may be missing until `materialise`
-// (imports every batch; idempotent) has run -- the one-launch path of a device-resident group works from `lite` alone, and
-// 10^4 Batch objects it never looks at cost more to build and free than the rest of the call's host work.
+// The batches of a group call: `lite` describes every batch, `batches` holds batch 0 (schema, names) and -- once
+// `materialise` (imports every batch; idempotent; empty: nothing left to import) has run -- the others.  The one-launch path
+// works from `lite` alone: 10^4 Batch objects it never looks at cost more to build and free than the rest of the call's
+// host work.  `head_only`: a sub-group cut out of a larger call; the other batches cannot be had, and the paths that read
+// Batch objects decline it -- no parts, no per-batch results -- so that the caller goes on with the whole group.
 struct GroupInput {
-  std::vector<Batch>* batches = nullptr;
-  const GroupLite* lite = nullptr;
+  std::vector<Batch> batches;
+  GroupLite lite;
   std::function<void()> materialise;
+  bool head_only = false;
 };
 // one launch for a group of same-schema batches (host or device resident); outputs where `out_on_device` says
 GroupResult filter_records(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases, const Expr& expr,
@@ -257,8 +278,6 @@ GroupResult filter_records(Context& ctx, const GroupInput& in, const chq_table_a
 // the same, but ONE output batch holding every surviving row in input order (+ surviving rows per input batch)
 Batch filter_records_coalesced(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases,
                                const Expr& expr, bool out_on_device, std::vector<int64_t>* rows_per_record);
-// (convenience for callers that hold complete batches)
-inline GroupInput group_of(std::vector<Batch>& batches) { GroupInput g; g.batches = &batches; return g; }
 Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, const Batch& rec_dev,
                      const std::vector<PlanColumn>& pcols);
 // filter_record + project_record in one kernel pass; false = outside its scope (or an error was flagged): run the two steps

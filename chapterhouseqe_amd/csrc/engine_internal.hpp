@@ -45,13 +45,13 @@ inline void ensure_scratch(Context& ctx, int64_t ntiles) {
     ctx.small_tiles = (size_t)ntiles + 64 + (size_t)ntiles / 4;
     ctx.small = make_device_buffer(kHeader + ctx.small_tiles * 8, ctx.device);
   }
-  if (!ctx.pinned) { check_hip(hipHostMalloc(&ctx.pinned, sizeof(Scratch), hipHostMallocDefault), "hipHostMalloc"); ctx.pinned_bytes = sizeof(Scratch); }
+  ctx.pinned.reserve(sizeof(Scratch), sizeof(Scratch), "hipHostMalloc");
 }
 inline Scratch* dev_scratch(Context& ctx) { return (Scratch*)ctx.small->ptr; }
 inline u64* dev_status(Context& ctx) { return (u64*)((uint8_t*)ctx.small->ptr + kHeader); }
 // The header into its pinned mirror, the stream synchronised.  (ensure_scratch may replace ctx.small: looked up per call.)
 inline Scratch* read_scratch(Context& ctx) {
-  Scratch* hs = (Scratch*)ctx.pinned;
+  Scratch* hs = (Scratch*)ctx.pinned.ptr;
   check_hip(hipMemcpyAsync(hs, dev_scratch(ctx), sizeof(Scratch), hipMemcpyDeviceToHost, ctx.stream), "read back");
   check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
   return hs;

@@ -388,7 +388,7 @@ void FilterCall::plan_fold() {
     for (size_t k = 0; k < ncand; ++k) { cap[k] = rec.cols[utf8_cols[k]].data_bytes; unknown |= cap[k] < 0; }
     if (unknown) {
       Scratch* ds = dev_scratch(ctx);
-      Scratch* hs = (Scratch*)ctx.pinned;
+      Scratch* hs = (Scratch*)ctx.pinned.ptr;
       gather_utf8_ends(0, ncand);
       check_hip(hipMemcpyAsync(hs->utf8_ends, ds->utf8_ends, sizeof(hs->utf8_ends), hipMemcpyDeviceToHost, ctx.stream), "read back");
       check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
@@ -521,7 +521,7 @@ void FilterCall::read_main() {
 void FilterCall::follow_ups() {
   if (!need_followup) return;
   Scratch* ds = dev_scratch(ctx);
-  const Scratch* hs = (const Scratch*)ctx.pinned;   // (read back by read_main)
+  const Scratch* hs = (const Scratch*)ctx.pinned.ptr;   // (read back by read_main)
   const int fgrid = (int)std::min<int64_t>((ngroups + 31) / 32, (int64_t)ctx.num_cus * 8);
   const size_t words = (size_t)(total + 31) / 32 + 2;
   auto bit_compact = [&](const uint8_t* in_bits, int64_t bit_off, u64* zero_counter) {
@@ -935,15 +935,12 @@ bool filter_record_small_host(Context& ctx, const Batch& rec, const chq_table_al
   }
   if (!lw.strs.empty()) return false;
 
-  if (ctx.pinned_io_bytes < 2 * block + 64) {
-    if (ctx.pinned_io) (void)hipHostFree(ctx.pinned_io);
-    ctx.pinned_io = nullptr; ctx.pinned_io_bytes = 0;
+  if (ctx.pinned_io.bytes < 2 * block + 64) {
     const size_t cap = std::max<size_t>(2 * block + 64, (size_t)1 << 20);
-    ctx.dev_io = make_device_buffer(cap, ctx.device);   // may throw: the capacity is recorded only once both halves exist
-    check_hip(hipHostMalloc(&ctx.pinned_io, cap, hipHostMallocDefault), "hipHostMalloc (small host path)");
-    ctx.pinned_io_bytes = cap;
+    ctx.dev_io = make_device_buffer(cap, ctx.device);   // may throw: the pinned half grows (and records its capacity) only after it
+    ctx.pinned_io.reserve(2 * block + 64, cap, "hipHostMalloc (small host path)");
   }
-  uint8_t* h_in = (uint8_t*)ctx.pinned_io; uint8_t* h_out = h_in + block;
+  uint8_t* h_in = (uint8_t*)ctx.pinned_io.ptr; uint8_t* h_out = h_in + block;
   uint8_t* d_in = (uint8_t*)ctx.dev_io->ptr; uint8_t* d_out = d_in + block;
   for (size_t i = 0; i < ncols; ++i) memcpy(h_in + at[i], rec.cols[i].values0(), (size_t)nrows * rec.cols[i].width);
   check_hip(hipMemcpyAsync(d_in, h_in, block, hipMemcpyHostToDevice, ctx.stream), "upload packed batch");

@@ -143,12 +143,7 @@ Batch concat_host_batches(const std::vector<Batch>& recs, size_t b0, size_t b1) 
 }
 
 void ensure_pinned_table(Context& ctx, size_t bytes) {
-  if (ctx.pinned_tbl_bytes >= bytes) return;
-  if (ctx.pinned_tbl) (void)hipHostFree(ctx.pinned_tbl);
-  ctx.pinned_tbl = nullptr; ctx.pinned_tbl_bytes = 0;
-  const size_t cap = bytes + bytes / 4 + 4096;
-  check_hip(hipHostMalloc(&ctx.pinned_tbl, cap, hipHostMallocDefault), "hipHostMalloc (group table)");
-  ctx.pinned_tbl_bytes = cap;
+  ctx.pinned_tbl.reserve(bytes, bytes + bytes / 4 + 4096, "hipHostMalloc (group table)");
 }
 
 // ---- device-side concatenation of a group (general column kinds) ----------------------------------------------------
@@ -193,7 +188,7 @@ Batch concat_device_batches(Context& ctx, const std::vector<Batch>& recs, size_t
   }
   pt.mark("scan_batches");
   ensure_pinned_table(ctx, words * 8);
-  u64* h = (u64*)ctx.pinned_tbl;
+  u64* h = (u64*)ctx.pinned_tbl.ptr;
   int64_t total = 0;
   for (size_t k = 0; k < nb; ++k) { h[k] = (u64)total; total += batch_rows[k]; }
   h[nb] = (u64)total;
@@ -293,30 +288,24 @@ struct Utf8Sizes {
   BufferPtr d_tbl;
   int32_t* h_ends = nullptr;   // [cols][2 nb] in ctx.pinned_sizes
 };
-Utf8Sizes device_utf8_bytes_issue(Context& ctx, const std::vector<Batch>& recs, const GroupLite* lite, const std::vector<int>& utf8_cols) {
+Utf8Sizes device_utf8_bytes_issue(Context& ctx, const GroupLite& lite, const std::vector<int>& utf8_cols) {
   Utf8Sizes z;
-  z.cols = utf8_cols; z.nb = lite ? lite->rows.size() : recs.size();
+  z.cols = utf8_cols; z.nb = lite.rows.size();
   const size_t nb = z.nb, nu = utf8_cols.size();
   if (nu == 0) return z;
   const size_t words = (nb + 1) + nu * nb;                 // row_at, then one pointer table per column
   const size_t need = words * 8 + nu * nb * 8;
-  if (ctx.pinned_sizes_bytes < need) {
-    if (ctx.pinned_sizes) (void)hipHostFree(ctx.pinned_sizes);
-    ctx.pinned_sizes = nullptr; ctx.pinned_sizes_bytes = 0;
-    check_hip(hipHostMalloc(&ctx.pinned_sizes, need + need / 4 + 4096, hipHostMallocDefault), "hipHostMalloc (utf8 sizes)");
-    ctx.pinned_sizes_bytes = need + need / 4 + 4096;
-  }
-  u64* h = (u64*)ctx.pinned_sizes;
+  ctx.pinned_sizes.reserve(need, need + need / 4 + 4096, "hipHostMalloc (utf8 sizes)");
+  u64* h = (u64*)ctx.pinned_sizes.ptr;
   int64_t total = 0;
-  for (size_t b = 0; b < nb; ++b) { h[b] = (u64)total; total += lite ? lite->rows[b] : recs[b].nrows; }
+  for (size_t b = 0; b < nb; ++b) { h[b] = (u64)total; total += lite.rows[b]; }
   h[nb] = (u64)total;
   z.d_tbl = make_device_buffer(need + 16, ctx.device);
   z.h_ends = (int32_t*)(h + words);
   for (size_t k = 0; k < nu; ++k) {
     const size_t uc = (size_t)utf8_cols[k];
     u64* tbl = h + nb + 1 + k * nb;
-    if (lite) for (size_t b = 0; b < nb; ++b) tbl[b] = (u64)(uintptr_t)lite->values0[b * lite->ncols + uc];
-    else pool_ranges(nb, 2048, [&](size_t i0, size_t i1) { for (size_t b = i0; b < i1; ++b) tbl[b] = (u64)(uintptr_t)recs[b].cols[uc].values0(); });
+    for (size_t b = 0; b < nb; ++b) tbl[b] = (u64)(uintptr_t)lite.values0[b * lite.ncols + uc];
   }
   check_hip(hipMemcpyAsync(z.d_tbl->ptr, h, words * 8, hipMemcpyHostToDevice, ctx.stream), "upload offsets tables");
   int32_t* d_ends = (int32_t*)((u64*)z.d_tbl->ptr + words);
@@ -338,8 +327,8 @@ std::vector<std::vector<int64_t>> device_utf8_bytes_finish(Context& ctx, const U
   }
   return out;
 }
-std::vector<std::vector<int64_t>> device_utf8_bytes(Context& ctx, const std::vector<Batch>& recs, const std::vector<int>& utf8_cols) {
-  return device_utf8_bytes_finish(ctx, device_utf8_bytes_issue(ctx, recs, nullptr, utf8_cols));
+std::vector<std::vector<int64_t>> device_utf8_bytes(Context& ctx, const GroupLite& lite, const std::vector<int>& utf8_cols) {
+  return device_utf8_bytes_finish(ctx, device_utf8_bytes_issue(ctx, lite, utf8_cols));
 }
 
 // ---- the pieces of a group call ------------------------------------------------------------------------------------------
@@ -359,12 +348,6 @@ std::vector<size_t> chunk_cuts(const std::vector<int64_t>& rows, const std::vect
   }
   cuts.push_back(rows.size());
   return cuts;
-}
-
-std::vector<int64_t> rows_of(const std::vector<Batch>& recs) {
-  std::vector<int64_t> rows;
-  for (const Batch& r : recs) rows.push_back(r.nrows);
-  return rows;
 }
 
 // batch b of a group as a view built from the flat arrays, with the schema of `first` (the head batch of a sub-group)
@@ -406,27 +389,19 @@ struct GroupCall {
   const chq_table_aliases* aliases;
   const Expr& expr;
   bool out_on_device, coalesce;
-  const std::vector<Batch>& recs;   // (batch 0 is always there; the others after need_batches() when `lite` is set)
-  const GroupLite* lite;
-  size_t nb;
-  // a sub-group (the uniform-length rewrite, the short-string split) carries its head batch only: the paths that read Batch
-  // objects decline it -- no parts, no per-batch results -- and the caller goes on with the whole group
-  bool sub_group;
+  const std::vector<Batch>& recs;   // batch 0 (schema, names); the others only after need_batches()
+  const GroupLite& lite;            // every batch
+  const size_t nb;
 
   GroupCall(Context& c, const GroupInput& g, const chq_table_aliases* a, const Expr& e, bool dev, bool co)
-      : ctx(c), gi(g), aliases(a), expr(e), out_on_device(dev), coalesce(co), recs(*g.batches), lite(g.lite) {
-    if (lite && (lite->rows.empty() || recs.empty() || lite->ncols != recs[0].cols.size())) lite = nullptr;
-    if (!lite) need_batches();
-    nb = lite ? lite->rows.size() : recs.size();
-    sub_group = !gi.materialise && recs.size() < nb;
-  }
+      : ctx(c), gi(g), aliases(a), expr(e), out_on_device(dev), coalesce(co), recs(g.batches), lite(g.lite), nb(g.lite.rows.size()) {}
   void need_batches() const { if (gi.materialise) gi.materialise(); }
   GroupResult per_batch_loop() const;
   GroupResult host_concat() const;
   GroupResult device_concat() const;
   // a concat path; a data-dependent error takes the per-batch loop, which reports the earliest failing batch's
   GroupResult concat(bool host) const {
-    if (sub_group) return {};
+    if (gi.head_only) return {};
     try {
       return host ? host_concat() : device_concat();
     } catch (const ChqError& e) {
@@ -437,7 +412,7 @@ struct GroupCall {
 };
 
 GroupResult GroupCall::per_batch_loop() const {
-  if (sub_group) return {};
+  if (gi.head_only) return {};
   need_batches();
   GroupResult r;
   chq_call_stats acc{};
@@ -464,7 +439,7 @@ GroupResult GroupCall::host_concat() const {
       if (c.values && c.length) { const int32_t* o = (const int32_t*)c.values + c.offset; bytes.back()[b] = (int64_t)o[c.length] - o[0]; }
     }
   }
-  const std::vector<size_t> cuts = chunk_cuts(rows_of(recs), bytes, ctx.opt_group_chunk_bytes);
+  const std::vector<size_t> cuts = chunk_cuts(lite.rows, bytes, ctx.opt_group_chunk_bytes);
   GroupResult r;
   chq_call_stats acc{};
   for (size_t k = 0; k + 1 < cuts.size(); ++k) {
@@ -484,9 +459,9 @@ GroupResult GroupCall::device_concat() const {
   std::vector<int> utf8_cols;
   for (size_t i = 0; i < recs[0].cols.size(); ++i) if (recs[0].cols[i].type == T_UTF8) utf8_cols.push_back((int)i);
   PhaseTimer pt("device_concat_path");
-  const std::vector<std::vector<int64_t>> ubytes = device_utf8_bytes(ctx, recs, utf8_cols);
+  const std::vector<std::vector<int64_t>> ubytes = device_utf8_bytes(ctx, lite, utf8_cols);
   pt.mark("utf8_sizes");
-  const std::vector<size_t> cuts = chunk_cuts(rows_of(recs), ubytes, ctx.opt_group_chunk_bytes);
+  const std::vector<size_t> cuts = chunk_cuts(lite.rows, ubytes, ctx.opt_group_chunk_bytes);
   if (coalesce && cuts.size() > 2) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "offset overflow: the joined Utf8 output of this group does not fit int32 offsets; use chq_filter_records"};
   GroupResult r;
   chq_call_stats acc{};
@@ -506,7 +481,7 @@ GroupResult GroupCall::device_concat() const {
 GroupResult filter_group(Context& ctx, const GroupInput& gi, const chq_table_aliases* aliases, const Expr& expr,
                          bool out_on_device, bool coalesce);
 
-// ---- stage 1: eligibility -- one scan of the batches ---------------------------------------------------------------------
+// ---- stage 1: eligibility -- one scan of the per-batch flags -------------------------------------------------------------
 struct GroupPlan {
   bool per_batch = false;    // a batch of fewer than 2 rows, or another schema: the per-batch loop
   bool plain = false;        // fixed-width columns without nulls (wave-packed device groups: bitmaps too): the one-launch path
@@ -514,61 +489,38 @@ struct GroupPlan {
   bool need_bits = false;    // validity bitmaps / Boolean columns ride along (compacted behind the main kernel)
   bool host_in = false, all_host = false;
   bool all_device = false;   // every batch in this GPU's memory
-  bool resident = false;     // every batch where batch 0 is (a device group described by `lite`: in this GPU's memory)
+  bool resident = false;     // every batch where batch 0 is (host memory, or this GPU's)
   int64_t total_rows = 0, max_rows = 0;
   std::vector<int> fold_utf8;
 };
 
+// The facts were gathered per batch at import (GroupLite::set / set_from_arrow, on the pool's threads): here one pass over
+// nb flag bytes and nb row counts, for host and device groups alike.
 GroupPlan plan_group(const GroupCall& g) {
   const Context& ctx = g.ctx;
-  const std::vector<Batch>& recs = g.recs;
-  const size_t ncols = recs[0].cols.size();
+  const Batch& first = g.recs[0];
+  const bool fits = (int)first.cols.size() <= MAX_OUT;
   GroupPlan pl;
-  pl.host_in = pl.all_host = !recs[0].on_device;
-  bool plain = (int)ncols <= MAX_OUT, same_schema = true;
-  // `foldable`: device-resident, non-null, fixed-width or Utf8 columns -- short-string Utf8 columns can then be filtered
-  // straight out of the batches by the one-launch path (their offsets and bytes per batch ride in the group table)
-  bool foldable = (int)ncols <= MAX_OUT && ctx.opt_fold_utf8 && ctx.opt_group_fold;
+  pl.host_in = !first.on_device;
   bool has_bool = false, has_utf8 = false;
-  for (const Column& c : recs[0].cols) { has_bool |= c.type == T_BOOL; has_utf8 |= c.type == T_UTF8; }
-  if (g.lite && !pl.host_in) {
-    // device-resident group: the facts were gathered per batch at import (GroupLite) -- one pass over nb bytes
-    uint8_t any = 0, all = 0xff;
-    for (uint8_t f : g.lite->flags) { any |= f; all &= f; }
-    if (any & (GroupLite::GL_SHORT | GroupLite::GL_SCHEMA_DIFFERS)) { pl.per_batch = true; return pl; }
-    pl.all_host = false;
-    pl.all_device = pl.resident = (all & GroupLite::GL_ON_DEVICE) != 0;
-    // validity bitmaps and Boolean columns ride along in the one-launch path when the group is wave-packed (decided with
-    // the table): their bitmaps are compacted by bit_compact_group_kernel behind the main kernel
-    pl.need_bits = has_bool || (any & GroupLite::GL_NULLS);
-    plain = plain && !has_utf8 && (!pl.need_bits || (pl.all_device && ctx.opt_group_bits));
-    foldable = foldable && pl.all_device && !(any & GroupLite::GL_NO_UTF8_DATA) && (!pl.need_bits || ctx.opt_group_bits);
-    for (int64_t r : g.lite->rows) { pl.total_rows += r; pl.max_rows = std::max(pl.max_rows, r); }
-  } else {
-    g.need_batches();
-    pl.all_device = pl.resident = true;
-    for (const Batch& r : recs) {
-      if (r.cols.size() != ncols || r.nrows < 2) { pl.per_batch = true; return pl; }
-      pl.all_host &= !r.on_device;
-      pl.all_device &= r.on_device && r.device_id == ctx.device;
-      pl.resident &= r.on_device != pl.host_in;
-      for (size_t i = 0; i < ncols; ++i) {
-        const Column& c = r.cols[i];
-        same_schema &= c.type == recs[0].cols[i].type && c.width == recs[0].cols[i].width && c.format == recs[0].cols[i].format;
-        // (not the host fast paths' rule, filter.cpp: plain_host_columns -- a device batch with a bitmap counts as having
-        // nulls, nothing asks for a width, and the scan goes on after a miss, for `same_schema` and `foldable`)
-        plain &= c.type != T_BOOL && c.type != T_UTF8 && !(c.validity && c.null_count != 0 && (r.on_device || c.null_count > 0 ||
-                 count_nulls_host(c.validity, c.offset, c.length) != 0));
-        foldable &= c.type != T_BOOL && !(c.validity && c.null_count != 0) && (c.type != T_UTF8 || c.data != nullptr);
-      }
-      pl.total_rows += r.nrows; pl.max_rows = std::max(pl.max_rows, r.nrows);
-    }
-    foldable &= pl.all_device;
-  }
-  if (!same_schema) { pl.per_batch = true; return pl; }
-  pl.plain = plain;
-  if (!plain && foldable) {
-    for (size_t i = 0; i < ncols; ++i) if (recs[0].cols[i].type == T_UTF8) pl.fold_utf8.push_back((int)i);
+  for (const Column& c : first.cols) { has_bool |= c.type == T_BOOL; has_utf8 |= c.type == T_UTF8; }
+  uint8_t any = 0, all = 0xff;
+  for (uint8_t f : g.lite.flags) { any |= f; all &= f; }
+  if (any & (GroupLite::GL_SHORT | GroupLite::GL_SCHEMA_DIFFERS)) { pl.per_batch = true; return pl; }
+  pl.all_host = (all & GroupLite::GL_ON_HOST) != 0;
+  pl.all_device = (all & GroupLite::GL_ON_DEVICE) != 0;
+  pl.resident = pl.host_in ? pl.all_host : pl.all_device;   // (a mixed group, or a batch on another GPU: the per-batch loop)
+  // validity bitmaps and Boolean columns ride along in the one-launch path when the group is wave-packed (decided with
+  // the table): their bitmaps are compacted by bit_compact_group_kernel behind the main kernel
+  pl.need_bits = has_bool || (any & GroupLite::GL_NULLS);
+  pl.plain = fits && !has_utf8 && (!pl.need_bits || (pl.all_device && ctx.opt_group_bits));
+  // `foldable`: device-resident fixed-width or Utf8 columns -- short-string Utf8 columns can then be filtered straight out
+  // of the batches by the one-launch path (their offsets and bytes per batch ride in the group table)
+  const bool foldable = fits && ctx.opt_fold_utf8 && ctx.opt_group_fold && pl.all_device && !(any & GroupLite::GL_NO_UTF8_DATA) &&
+                        (!pl.need_bits || ctx.opt_group_bits);
+  for (int64_t r : g.lite.rows) { pl.total_rows += r; pl.max_rows = std::max(pl.max_rows, r); }
+  if (!pl.plain && foldable) {
+    for (size_t i = 0; i < first.cols.size(); ++i) if (first.cols[i].type == T_UTF8) pl.fold_utf8.push_back((int)i);
     pl.fold = !pl.fold_utf8.empty() && (int)pl.fold_utf8.size() <= MAX_FOLD_UTF8 && pl.total_rows < (1ll << 31) - 64;
     if (!pl.fold) pl.fold_utf8.clear();
   }
@@ -582,7 +534,7 @@ GroupPlan plan_group(const GroupCall& g) {
 // that the per-batch loop must attribute) -- the caller goes on as before.  `sizes_fit`: the fold's size check.
 bool uniform_group(const GroupCall& g, const GroupPlan& pl, const std::function<bool()>& sizes_fit, GroupResult* out) {
   Context& ctx = g.ctx;
-  const GroupLite& lite = *g.lite;
+  const GroupLite& lite = g.lite;
   const size_t nb = g.nb, ncols = lite.ncols, nu = pl.fold_utf8.size();
   for (int i : pl.fold_utf8) {
     bool bitmap = false;
@@ -606,7 +558,9 @@ bool uniform_group(const GroupCall& g, const GroupPlan& pl, const std::function<
   std::vector<int32_t> h_out(nu * nb * 3);
   check_hip(hipMemcpyAsync(h_out.data(), d_out->ptr, h_out.size() * 4, hipMemcpyDeviceToHost, ctx.stream), "read back");
   check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  GroupLite sub = lite;
+  GroupInput sgi;   // the group with its string columns as FixedSizeBinary(L): pointers into the batches' bytes
+  sgi.head_only = true;
+  GroupLite& sub = sgi.lite = lite;
   Batch first = g.recs[0];
   for (size_t k = 0; k < nu; ++k) {
     const size_t i = (size_t)pl.fold_utf8[k];
@@ -623,8 +577,7 @@ bool uniform_group(const GroupCall& g, const GroupPlan& pl, const std::function<
     c.type = T_FIXED_OPAQUE; c.format = "w:" + std::to_string(L); c.width = L;
   }
   for (uint8_t& f : sub.flags) f &= (uint8_t)~GroupLite::GL_NO_UTF8_DATA;
-  std::vector<Batch> head{lite_head(first, sub, 0)};
-  GroupInput sgi; sgi.batches = &head; sgi.lite = &sub;
+  sgi.batches.push_back(lite_head(first, sub, 0));
   GroupResult r = filter_group(ctx, sgi, g.aliases, g.expr, g.out_on_device, g.coalesce);
   if (r.parts.empty() || r.batches() != nb) return false;
   for (JoinedGroup& part : r.parts)
@@ -657,38 +610,33 @@ constexpr int64_t kWavesPerTile[3] = {16, 4, 4};
 bool build_group_table(const GroupCall& g, const GroupPlan& pl, const Lowered& lw, GroupTable& t) {
   Context& ctx = g.ctx;
   const std::vector<Batch>& recs = g.recs;
-  const GroupLite* lite = g.lite;
+  const GroupLite& lite = g.lite;
   const size_t nb = g.nb, ncols = recs[0].cols.size();
   const int64_t total_rows = pl.total_rows;
   ctx.stats = chq_call_stats{};
   ctx.stats.rows_in = total_rows;
 
-  // ---- inputs: device pointers per batch and column ------------------------------------------------------
-  // host batches are packed column-wise into one staging block per column and uploaded with one copy each
-  struct PtrTable {   // [batch][column], flat: one allocation for 10^5 batches
-    std::vector<const uint8_t*> v; size_t ncols;
-    const uint8_t** operator[](size_t b) { return v.data() + b * ncols; }
-  } in_ptr{std::vector<const uint8_t*>(nb * ncols), ncols};
+  // ---- inputs: device pointers per batch and column, [batch][column] flat --------------------------------------
+  // device batches: where they lie (lite.values0).  Host batches are packed column-wise into one staging block per column
+  // and uploaded with one copy each: `packed` = where every batch's share of it lies in HBM
+  std::vector<const uint8_t*> packed;
   if (pl.host_in) {
+    packed.resize(nb * ncols);
     for (size_t i = 0; i < ncols; ++i) {
       const int64_t w = recs[0].cols[i].width;
       auto pack = make_host_buffer((size_t)(total_rows * w) + 16);   // recycled block: no page faults
       auto db = make_device_buffer((size_t)(total_rows * w) + 16, ctx.device);
       std::vector<int64_t> at(nb + 1, 0);
-      for (size_t b = 0; b < nb; ++b) { at[b + 1] = at[b] + recs[b].nrows * w; in_ptr[b][i] = (const uint8_t*)db->ptr + at[b]; }
+      for (size_t b = 0; b < nb; ++b) { at[b + 1] = at[b] + lite.rows[b] * w; packed[b * ncols + i] = (const uint8_t*)db->ptr + at[b]; }
       parallel_ranges(nb, (size_t)at[nb], [&](size_t k0, size_t k1) {
-        for (size_t b = k0; b < k1; ++b) memcpy((uint8_t*)pack->ptr + at[b], recs[b].cols[i].values0(), (size_t)(recs[b].nrows * w));
+        for (size_t b = k0; b < k1; ++b) memcpy((uint8_t*)pack->ptr + at[b], lite.values0[b * ncols + i], (size_t)(lite.rows[b] * w));
       });
       check_hip(hipMemcpyAsync(db->ptr, pack->ptr, (size_t)at[nb], hipMemcpyHostToDevice, ctx.stream), "upload packed column");
       t.staged.push_back(db); t.staged.push_back(pack);
     }
     check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  } else if (lite) {
-    memcpy(in_ptr.v.data(), lite->values0.data(), nb * ncols * sizeof(const uint8_t*));
-  } else {
-    for (size_t b = 0; b < nb; ++b)
-      for (size_t i = 0; i < ncols; ++i) in_ptr[b][i] = (const uint8_t*)recs[b].cols[i].values0();
   }
+  const uint8_t* const* in_ptr = pl.host_in ? packed.data() : lite.values0.data();
 
   // ---- tiling ------------------------------------------------------------------------------------------------
   // Wave-granular packing when the batches are near-uniform (every batch gets the wave count of the longest one and
@@ -706,16 +654,15 @@ bool build_group_table(const GroupCall& g, const GroupPlan& pl, const Lowered& l
       t.wpb = w; tile_kind = k;
     }
   }
-  auto rows_of_batch = [&](size_t b) { return lite ? lite->rows[b] : recs[b].nrows; };
   if (tile_kind < 0) {   // the large tile unless padding every batch to a multiple of it idles more than a quarter of the lanes
     int64_t padded = 0;
-    for (size_t b = 0; b < nb; ++b) padded += (rows_of_batch(b) + kTileRows[0] - 1) / kTileRows[0] * kTileRows[0];
+    for (size_t b = 0; b < nb; ++b) padded += (lite.rows[b] + kTileRows[0] - 1) / kTileRows[0] * kTileRows[0];
     tile_kind = padded * 4 <= total_rows * 5 ? 0 : 1;
   }
   t.tile_kind = tile_kind;
   const int64_t tile_rows = kTileRows[tile_kind], wpb = t.wpb;
   if (wpb > 0) t.ntiles = (wpb * (int64_t)nb + kWavesPerTile[tile_kind] - 1) / kWavesPerTile[tile_kind];
-  else for (size_t b = 0; b < nb; ++b) t.ntiles += (rows_of_batch(b) + tile_rows - 1) / tile_rows;
+  else for (size_t b = 0; b < nb; ++b) t.ntiles += (lite.rows[b] + tile_rows - 1) / tile_rows;
   ensure_scratch(ctx, t.ntiles);
 
   // ---- bitmaps (validity of any column, values of Boolean columns): wave-packed groups only --------------------------
@@ -727,8 +674,8 @@ bool build_group_table(const GroupCall& g, const GroupPlan& pl, const Lowered& l
     // (the bitmaps' addresses and offsets come from the flat per-batch arrays: no Batch objects, as in the null-free case)
     std::vector<char> col_nulls(ncols, 0);
     for (size_t b = 0; b < nb; ++b) {
-      if (!(lite->flags[b] & GroupLite::GL_NULLS)) continue;
-      for (size_t i = 0; i < ncols; ++i) if (lite->validity[b * ncols + i]) col_nulls[i] = 1;
+      if (!(lite.flags[b] & GroupLite::GL_NULLS)) continue;
+      for (size_t i = 0; i < ncols; ++i) if (lite.validity[b * ncols + i]) col_nulls[i] = 1;
     }
     for (size_t i = 0; i < ncols; ++i) {
       Column& pc = t.proto.cols[i];
@@ -753,35 +700,33 @@ bool build_group_table(const GroupCall& g, const GroupPlan& pl, const Lowered& l
   const size_t tbl_words = (wpb > 0 ? nb : (size_t)t.ntiles) * t.stride;
   t.bytes_tbl = tbl_words * 8; t.bytes_idx = wpb > 0 ? 0 : nb * 8; t.bytes_cnt = nb * 8;
   ensure_pinned_table(ctx, t.bytes_tbl + t.bytes_idx + t.bytes_cnt);
-  u64* w = (u64*)ctx.pinned_tbl;
+  u64* w = (u64*)ctx.pinned_tbl.ptr;
   int64_t* h_idx = (int64_t*)(w + tbl_words);
   int64_t tile = 0;
-  auto utf8_data = [&](size_t b, size_t k) -> u64 {
-    return (u64)(uintptr_t)(lite ? lite->data[b * ncols + (size_t)pl.fold_utf8[k]] : recs[b].cols[(size_t)pl.fold_utf8[k]].data);
-  };
   for (size_t b = 0; b < nb; ++b) {
-    const int64_t rows = rows_of_batch(b);
+    const int64_t rows = lite.rows[b];
+    const size_t at = b * ncols;
+    auto value_ptrs = [&] {   // program refs, output columns, per folded Utf8 column its offsets and bytes
+      for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)in_ptr[at + (size_t)lw.refs[k]];
+      for (size_t k = 0; k < nout; ++k) *w++ = (u64)(uintptr_t)in_ptr[at + (size_t)t.launch_cols[k]];
+      for (size_t k = 0; k < nu; ++k) { *w++ = (u64)(uintptr_t)in_ptr[at + (size_t)pl.fold_utf8[k]]; *w++ = (u64)(uintptr_t)lite.data[at + (size_t)pl.fold_utf8[k]]; }
+    };
     if (wpb > 0) {
       *w++ = (u64)rows;
-      for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][lw.refs[k]];
-      for (size_t k = 0; k < nout; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][t.launch_cols[k]];
-      for (size_t k = 0; k < nu; ++k) { *w++ = (u64)(uintptr_t)in_ptr[b][pl.fold_utf8[k]]; *w++ = utf8_data(b, k); }
+      value_ptrs();
       if (pl.need_bits) {
-        const size_t at = b * ncols;
-        for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)lite->validity[at + (size_t)lw.refs[k]];
-        for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)lite->offset[at + (size_t)lw.refs[k]];
+        for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)lite.validity[at + (size_t)lw.refs[k]];
+        for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)lite.offset[at + (size_t)lw.refs[k]];
         for (const BitCol& q : t.bit_cols) {
-          *w++ = (u64)(uintptr_t)(q.validity ? lite->validity[at + (size_t)q.col] : lite->values0[at + (size_t)q.col]);   // (a Boolean column's values0 is its bitmap)
-          *w++ = (u64)lite->offset[at + (size_t)q.col];
+          *w++ = (u64)(uintptr_t)(q.validity ? lite.validity[at + (size_t)q.col] : lite.values0[at + (size_t)q.col]);   // (a Boolean column's values0 is its bitmap)
+          *w++ = (u64)lite.offset[at + (size_t)q.col];
         }
       }
       continue;
     }
     for (int64_t r0 = 0; r0 < rows; r0 += tile_rows, ++tile) {
       *w++ = (u64)r0; *w++ = (u64)rows;
-      for (size_t k = 0; k < nrefs; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][lw.refs[k]];
-      for (size_t k = 0; k < nout; ++k) *w++ = (u64)(uintptr_t)in_ptr[b][t.launch_cols[k]];
-      for (size_t k = 0; k < nu; ++k) { *w++ = (u64)(uintptr_t)in_ptr[b][pl.fold_utf8[k]]; *w++ = utf8_data(b, k); }
+      value_ptrs();
     }
     h_idx[b] = tile - 1;   // rows >= 2: every batch owns at least one tile
   }
@@ -800,9 +745,9 @@ bool launch_group(const GroupCall& g, const GroupPlan& pl, const Lowered& lw, Gr
   const int tile_kind = t.tile_kind;
   FilterParams& p = t.p;
   PhaseTimer pt("filter_records (launch)");
-  u64* h_cnt = (u64*)((uint8_t*)ctx.pinned_tbl + t.bytes_tbl + t.bytes_idx);
+  u64* h_cnt = (u64*)((uint8_t*)ctx.pinned_tbl.ptr + t.bytes_tbl + t.bytes_idx);
   auto d_tbl = make_device_buffer(t.bytes_tbl + t.bytes_idx + t.bytes_cnt + 16, ctx.device);
-  check_hip(hipMemcpyAsync(d_tbl->ptr, ctx.pinned_tbl, t.bytes_tbl + t.bytes_idx, hipMemcpyHostToDevice, ctx.stream), "upload group table");
+  check_hip(hipMemcpyAsync(d_tbl->ptr, ctx.pinned_tbl.ptr, t.bytes_tbl + t.bytes_idx, hipMemcpyHostToDevice, ctx.stream), "upload group table");
   u64* d_cnt = (u64*)((uint8_t*)d_tbl->ptr + t.bytes_tbl + t.bytes_idx);
   Scratch* ds = dev_scratch(ctx);
 
@@ -924,16 +869,17 @@ bool launch_group(const GroupCall& g, const GroupPlan& pl, const Lowered& lw, Gr
 // chunk) and no Batch objects.  False: a sub-group of ONE batch (it would take the per-batch path: nothing gained -- e.g.
 // ten 1 GB batches), or one that did not run as one launch.
 bool split_short_strings(const GroupCall& g, const std::vector<std::vector<int64_t>>& fold_bytes, GroupResult* out) {
-  const std::vector<size_t> cuts = chunk_cuts(g.lite->rows, fold_bytes, g.ctx.opt_group_chunk_bytes);
+  const std::vector<size_t> cuts = chunk_cuts(g.lite.rows, fold_bytes, g.ctx.opt_group_chunk_bytes);
   bool groups_of_two = cuts.size() > 2;
   for (size_t k = 0; k + 1 < cuts.size(); ++k) groups_of_two = groups_of_two && cuts[k + 1] - cuts[k] >= 2;
   if (!groups_of_two) return false;
   chq_call_stats acc{};
   GroupResult r;
   for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-    GroupLite sub = g.lite->slice(cuts[k], cuts[k + 1]);
-    std::vector<Batch> head{lite_head(g.recs[0], *g.lite, cuts[k])};
-    GroupInput sgi; sgi.batches = &head; sgi.lite = &sub;
+    GroupInput sgi;
+    sgi.head_only = true;
+    sgi.lite = g.lite.slice(cuts[k], cuts[k + 1]);
+    sgi.batches.push_back(lite_head(g.recs[0], g.lite, cuts[k]));
     GroupResult part = filter_group(g.ctx, sgi, g.aliases, g.expr, g.out_on_device, g.coalesce);
     add_stats(acc, g.ctx.stats);
     if (part.parts.size() != 1 || part.batches() != cuts[k + 1] - cuts[k]) return false;
@@ -954,7 +900,7 @@ GroupResult filter_group(Context& ctx, const GroupInput& gi, const chq_table_ali
   // the batches' string sizes are read back from the device: queued here, awaited only after the predicate has been typed
   // and the group table built (`sizes_fit` below)
   Utf8Sizes sizes_in_flight;
-  if (pl.fold) sizes_in_flight = device_utf8_bytes_issue(ctx, g.recs, g.lite, pl.fold_utf8);
+  if (pl.fold) sizes_in_flight = device_utf8_bytes_issue(ctx, g.lite, pl.fold_utf8);
   std::vector<std::vector<int64_t>> fold_bytes;   // bytes of every folded Utf8 column per batch
   std::vector<int64_t> fold_cap;                  // and in all
   bool sizes_done = false, sizes_ok = false;
@@ -1003,7 +949,7 @@ GroupResult filter_group(Context& ctx, const GroupInput& gi, const chq_table_ali
   if (!lw.strs.empty()) return other_path();
   bool reads_utf8 = false;
   for (int r : lw.refs) reads_utf8 |= g.recs[0].cols[(size_t)r].type == T_UTF8;
-  if (pl.fold && g.lite && !pl.host_in && !reads_utf8 && ctx.opt_uniform_utf8_rows > 0 && pl.total_rows >= ctx.opt_uniform_utf8_rows) {
+  if (pl.fold && !reads_utf8 && ctx.opt_uniform_utf8_rows > 0 && pl.total_rows >= ctx.opt_uniform_utf8_rows) {
     GroupResult r;
     if (uniform_group(g, pl, sizes_fit, &r)) return r;
   }
@@ -1014,7 +960,7 @@ GroupResult filter_group(Context& ctx, const GroupInput& gi, const chq_table_ali
   if (!build_group_table(g, pl, lw, t)) return other_path();
   pt.mark("table");
   if (pl.fold && !sizes_fit()) {
-    bool short_strings = g.lite && !pl.host_in && !coalesce;
+    bool short_strings = !coalesce;
     for (int64_t cap : fold_cap) short_strings = short_strings && cap <= pl.total_rows * 24;
     GroupResult r;
     if (short_strings && split_short_strings(g, fold_bytes, &r)) return r;
@@ -1035,7 +981,10 @@ Batch join_group(Context& ctx, const std::vector<Batch>& recs) {
   if (dev.size() == 1) return std::move(dev[0]);
   std::vector<int> utf8_cols;
   for (size_t c = 0; c < dev[0].cols.size(); ++c) if (dev[0].cols[c].type == T_UTF8) utf8_cols.push_back((int)c);
-  const auto bytes = device_utf8_bytes(ctx, dev, utf8_cols);
+  GroupLite lite;
+  lite.resize(dev.size(), dev[0].cols.size());
+  for (size_t b = 0; b < dev.size(); ++b) lite.set(b, dev[b], dev[0], ctx.device);
+  const auto bytes = device_utf8_bytes(ctx, lite, utf8_cols);
   for (size_t k = 0; k < utf8_cols.size(); ++k) {
     int64_t total = 0;
     for (int64_t x : bytes[k]) total += x;
@@ -1053,7 +1002,7 @@ GroupResult filter_records(Context& ctx, const GroupInput& in, const chq_table_a
 
 Batch filter_records_coalesced(Context& ctx, const GroupInput& in, const chq_table_aliases* aliases,
                                const Expr& expr, bool out_on_device, std::vector<int64_t>* rows_per_record) {
-  if (!in.batches || in.batches->empty()) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "no record batches to coalesce"};
+  if (in.batches.empty()) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "no record batches to coalesce"};
   GroupResult r = filter_group(ctx, in, aliases, expr, out_on_device, true);
   std::vector<int64_t> rows;
   for (const JoinedGroup& part : r.parts)
@@ -1074,9 +1023,31 @@ Batch filter_records_coalesced(Context& ctx, const GroupInput& in, const chq_tab
 }
 
 // ---- GroupLite: the per-batch facts of a group (engine.hpp) ----------------------------------------------------------------
+// `set` reads an imported batch, `set_from_arrow` the Arrow structs of a device batch (the checks of import_batch, but no
+// Batch object).  Both run per batch on the pool's threads and allocate nothing.  They must agree on: the residency bits,
+// GL_SHORT below 2 rows, GL_SCHEMA_DIFFERS for anything the group paths cannot take (the full import then decides and
+// reports), and per column what `put_column` stores -- values0 with the slice offset applied (Boolean: the bitmap itself),
+// the Utf8 bytes, the bit offset, and the validity bitmap only where it may clear a bit.
+// One column (type and width of `kind`) of one batch into slot `at`; returns the GL_* bits it contributes.
+static uint8_t put_column(GroupLite& g, size_t at, const Column& kind, bool on_host, const uint8_t* bitmap, int64_t null_count,
+                          int64_t length, const uint8_t* values, const uint8_t* bytes, int64_t off) {
+  uint8_t f = 0;
+  // nulls: a device batch with a bitmap and null_count != 0 counts as having them; a host batch that has not counted
+  // (null_count < 0) is counted here, and a bitmap with every bit set is no bitmap
+  bool nulls = bitmap && null_count != 0;
+  if (nulls && on_host && null_count < 0) nulls = count_nulls_host(bitmap, off, length) != 0;
+  if (nulls) { f |= GroupLite::GL_NULLS; g.validity[at] = bitmap; }
+  if (kind.type == T_UTF8 && !bytes) f |= GroupLite::GL_NO_UTF8_DATA;
+  g.values0[at] = !values || kind.type == T_BOOL ? values : values + (int64_t)(kind.type == T_UTF8 ? 4 : kind.width) * off;
+  g.data[at] = bytes;
+  g.offset[at] = off;
+  return f;
+}
+
 void GroupLite::set(size_t b, const Batch& r, const Batch& first, int device) {
   rows[b] = r.nrows;
   uint8_t f = 0;
+  if (!r.on_device) f |= GL_ON_HOST;
   if (r.on_device && r.device_id == device) f |= GL_ON_DEVICE;
   if (r.nrows < 2) f |= GL_SHORT;
   if (r.cols.size() != ncols) { flags[b] = (uint8_t)(f | GL_SCHEMA_DIFFERS); return; }
@@ -1084,12 +1055,28 @@ void GroupLite::set(size_t b, const Batch& r, const Batch& first, int device) {
     const Column& c = r.cols[i];
     const Column& c0 = first.cols[i];
     if (c.type != c0.type || c.width != c0.width || c.format != c0.format) f |= GL_SCHEMA_DIFFERS;
-    if (c.validity && c.null_count != 0) f |= GL_NULLS;
-    if (c.type == T_UTF8 && c.data == nullptr) f |= GL_NO_UTF8_DATA;
-    values0[b * ncols + i] = c.type == T_BOOL ? c.values : (const uint8_t*)c.values0();
-    data[b * ncols + i] = c.data;
-    validity[b * ncols + i] = (c.validity && c.null_count != 0) ? c.validity : nullptr;
-    offset[b * ncols + i] = c.offset;
+    f |= put_column(*this, b * ncols + i, c, !r.on_device, c.validity, c.null_count, c.length, c.values, c.data, c.offset);
+  }
+  flags[b] = f;
+}
+
+void GroupLite::set_from_arrow(size_t b, const ArrowDeviceArray* rec, const ArrowSchema* schema, const Batch& first, int device) {
+  const ArrowArray& a = rec->array;
+  if (a.offset != 0 || a.n_children != schema->n_children || (size_t)a.n_children != ncols || rec->device_type != ARROW_DEVICE_ROCM || rec->sync_event) {
+    flags[b] = GL_SCHEMA_DIFFERS;   // (anything unusual: the full import decides -- and reports)
+    return;
+  }
+  rows[b] = a.length;
+  uint8_t f = 0;
+  if ((int)rec->device_id == device) f |= GL_ON_DEVICE;
+  if (a.length < 2) f |= GL_SHORT;
+  for (size_t i = 0; i < ncols; ++i) {
+    const ArrowArray* ca = a.children[i];
+    if (!ca || ca->length < a.length || ca->offset < 0 || ca->n_buffers < 2 || !ca->buffers || !ca->buffers[1] ||
+        (ca->null_count > 0 && !ca->buffers[0])) { f |= GL_SCHEMA_DIFFERS; continue; }
+    const Column& c0 = first.cols[i];
+    const uint8_t* bytes = c0.type == T_UTF8 && ca->n_buffers > 2 ? (const uint8_t*)ca->buffers[2] : nullptr;
+    f |= put_column(*this, b * ncols + i, c0, false, (const uint8_t*)ca->buffers[0], ca->null_count, a.length, (const uint8_t*)ca->buffers[1], bytes, ca->offset);
   }
   flags[b] = f;
 }

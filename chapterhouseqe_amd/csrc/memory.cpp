@@ -166,10 +166,6 @@ Context::~Context() {
   if (aux_fork) (void)hipEventDestroy(aux_fork);
   for (hipEvent_t e : upload_events) (void)hipEventDestroy(e);
   for (int i = 0; i < kAuxStreams; ++i) { if (aux_join[i]) (void)hipEventDestroy(aux_join[i]); if (aux[i]) (void)hipStreamDestroy(aux[i]); }
-  if (pinned) (void)hipHostFree(pinned);
-  if (pinned_tbl) (void)hipHostFree(pinned_tbl);
-  if (pinned_sizes) (void)hipHostFree(pinned_sizes);
-  if (pinned_io) (void)hipHostFree(pinned_io);
   if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 

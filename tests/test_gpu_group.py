@@ -1,11 +1,15 @@
 """GPU: chq_filter_records (one launch for a group of same-schema batches) against the CPU oracle and against
 chq_filter_record called batch by batch -- the loop of filter_task.rs:78-126 that the group call replaces.
 Bit-exact: the group call only moves values."""
+import ctypes as C
+
 import numpy as np
 import pyarrow as pa
 import pytest
 
 import chapterhouseqe_amd as chq
+from chapterhouseqe_amd import _lib as L
+from chapterhouseqe_amd import record_utils
 from chapterhouseqe_amd.sqlparse import parse_expr
 from oracle import oracle as O
 
@@ -356,6 +360,54 @@ def test_group_static_errors_and_argument_checks(ctx):
         chq.RecordGroup([], ctx)
     with pytest.raises(ValueError):
         chq.RecordGroup([recs[0], chq.DeviceRecordBatch.from_host(recs[1], ctx)], ctx)
+
+
+def mixed_group(ctx, recs, on_device):
+    """The argument block of a group whose batches lie partly on the host and partly in HBM: RecordGroup refuses to build
+    one, the C ABI takes it -- the same pointer array over the same structs.  Returns (group, the host exports to release)."""
+    cbs = [chq.DeviceRecordBatch.from_host(r, ctx)._cb if dev else record_utils._export_host(r) for r, dev in zip(recs, on_device)]
+    grp = chq.RecordGroup.__new__(chq.RecordGroup)
+    grp.on_device, grp.ctx, grp._cbs, grp._own, grp.n = on_device[0], ctx, cbs, False, len(cbs)
+    grp.ptrs = (C.POINTER(L.ArrowDeviceArray) * grp.n)(*[C.pointer(cb.array) for cb in cbs])
+    grp.schema = cbs[0].schema
+    return grp, [cb for cb, dev in zip(cbs, on_device) if not dev]
+
+
+@pytest.mark.parametrize("device_result", [False, True], ids=["host-out", "device-out"])
+@pytest.mark.parametrize("on_device", [(False, True, False), (True, False, True)], ids=["host-device-host", "device-host-device"])
+def test_mixed_residency_groups_through_the_c_abi(ctx, on_device, device_result):
+    """host and device batches in one call: every output is what chq_filter_record returns for that batch, rows_in covers
+    the whole group, and a static error reports as it does for a single batch"""
+    rows = [3, 64, 1025]
+    recs = [fixed_batch(n, 700 + i, with_wide=False) for i, n in enumerate(rows)]
+    al = empty_aliases(recs[0])
+    for sql in ["value2 > 10.0", "id % 2 = 0 and value1 < 20.0"]:
+        e = parse_expr(sql)
+        single = [chq.filter_record(r, al, e, ctx=ctx, device_result=False) for r in recs]
+        grp, host_cbs = mixed_group(ctx, recs, on_device)
+        try:
+            got = chq.filter_records(grp, al, e, ctx=ctx, device_result=device_result)
+            st = ctx.last_stats()
+        finally:
+            for cb in host_cbs:
+                cb.release()
+        assert len(got) == len(recs)
+        for i, (g, x) in enumerate(zip(got, single)):
+            g = g.to_host() if device_result else g
+            assert batches_identical(g, x), f"{sql}: batch {i} ({rows[i]} rows):\n{explain_diff(g, x)}"
+            assert batches_identical(g, O.filter_record(recs[i], al, e))
+        assert st["rows_in"] == sum(rows), (sql, st)
+    bad = parse_expr("nope > 1")
+    with pytest.raises(chq.ChqError) as one:
+        chq.filter_record(recs[0], al, bad, ctx=ctx)
+    grp, host_cbs = mixed_group(ctx, recs, on_device)
+    try:
+        with pytest.raises(chq.ChqError) as ei:
+            chq.filter_records(grp, al, bad, ctx=ctx, device_result=device_result)
+    finally:
+        for cb in host_cbs:
+            cb.release()
+    assert (ei.value.code, ei.value.message) == (one.value.code, one.value.message)
 
 
 def test_large_group_many_small_batches(ctx):

@@ -110,3 +110,61 @@ def test_large_host_path_takes_only_plain_columns(general, uncounted, kind):
         check(fast, general, batch(n, kind), kind, launches_when_taken=2)   # one launch per chunk; unchunked: one
     finally:
         fast.close()
+
+
+GROUP_ROWS = [2, 65, 2049]
+
+
+def run_group(ctx, recs, where):
+    """chq_filter_records over host batches: (outputs, launches, tiles)"""
+    got = chq.filter_records(recs, chq.get_record_table_aliases(None, recs[0]), parse_expr(where), ctx=ctx)
+    st = ctx.last_stats()
+    print(where, [r.num_rows for r in recs], st)
+    return got, st["launches"], st["tiles"]
+
+
+def test_host_group_with_uncounted_all_valid_bitmaps_is_a_plain_group(uncounted):
+    """every validity bit set, null_count = -1: the group scan counts, finds no null and runs the group as it runs the same
+    batches without the column -- one launch over all of them, the bitmap dropped from the output as the oracle drops it"""
+    uncounted("bitmap_uncounted")
+    recs = [batch(n, "bitmap_uncounted") for n in GROUP_ROWS]
+    bare = [r.select(["id", "v"]) for r in recs]
+    c = chq.Context(0)
+    try:
+        for where in PREDICATES:
+            al, e = chq.get_record_table_aliases(None, recs[0]), parse_expr(where)
+            got, launches, tiles = run_group(c, recs, where)
+            _, bare_launches, bare_tiles = run_group(c, bare, where)
+            assert (launches, tiles) == (bare_launches, bare_tiles), where
+            for r, g in zip(recs, got):
+                exp = O.filter_record(r, al, e)
+                one = chq.filter_record(r, al, e, ctx=c)
+                assert batches_identical(g, exp), f"{where}:\n{explain_diff(g, exp)}"
+                assert batches_identical(g, one), f"{where}:\n{explain_diff(g, one)}"
+                assert [x.null_count for x in g.columns] == [x.null_count for x in exp.columns]
+    finally:
+        c.close()
+
+
+def test_host_group_with_uncounted_nulls_in_one_batch_leaves_the_one_launch_path(uncounted):
+    """the same group with real, uncounted nulls in the middle batch only: the scan must find them -- the group is joined on
+    the host exactly as when the producer had counted them, and is not run as the plain group of the test above"""
+    kinds = ["bitmap_uncounted", "nulls_uncounted", "bitmap_uncounted"]
+    recs = [batch(n, k) for n, k in zip(GROUP_ROWS, kinds)]
+    bare_recs = [r.select(["id", "v"]) for r in recs]
+    c = chq.Context(0)
+    try:
+        counted = {where: run_group(c, recs, where)[1:] for where in PREDICATES}   # (exported by pyarrow: nulls counted)
+        bare = {where: run_group(c, bare_recs, where)[1:] for where in PREDICATES}
+        uncounted("nulls_uncounted")
+        for where in PREDICATES:
+            al, e = chq.get_record_table_aliases(None, recs[0]), parse_expr(where)
+            got, launches, tiles = run_group(c, recs, where)
+            assert (launches, tiles) == counted[where], where
+            assert (launches, tiles) != bare[where], where
+            for r, g in zip(recs, got):
+                exp = O.filter_record(r, al, e)
+                assert batches_identical(g, exp), f"{where}:\n{explain_diff(g, exp)}"
+                assert [x.null_count for x in g.columns] == [x.null_count for x in exp.columns]
+    finally:
+        c.close()
