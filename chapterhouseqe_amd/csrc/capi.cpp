@@ -8,6 +8,7 @@
 #include "engine.hpp"
 #include "parquet.hpp"
 #include "sort.hpp"
+#include "aggregate.hpp"
 #include <atomic>
 
 using namespace chq;
@@ -489,6 +490,64 @@ chq_status chq_sort_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray*
                             const chq_table_aliases* table_aliases, const chq_sort_key* keys, int n_keys, int64_t limit,
                             int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
   return sort_call(ctx, n_records, recs, schema, table_aliases, keys, n_keys, limit, out_device, out, out_schema);
+}
+
+// ---- GROUP BY (aggregate.cpp) ------------------------------------------------------------------------------------------------
+namespace {
+chq_status aggregate_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                          const chq_table_aliases* table_aliases, const chq_expr* const* keys, int n_keys, const chq_agg_item* items,
+                          int n_items, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
+  mark_released(out, out_schema);
+  return guarded(ctx, [&] {
+    require(out, "output array"); require(out_schema, "output schema");
+    if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
+    require(recs, "record array");
+    if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative GROUP BY key count"};
+    if (n_keys > 0) require(keys, "GROUP BY keys");
+    if (n_items <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "GROUP BY needs at least one output item"};
+    require(items, "output items");
+    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
+      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    std::vector<const Expr*> key_args((size_t)n_keys);
+    for (int k = 0; k < n_keys; ++k) {
+      require(keys[k], "GROUP BY key");
+      key_args[(size_t)k] = &keys[k]->e;
+    }
+    std::vector<AggItemArg> item_args((size_t)n_items);
+    for (int i = 0; i < n_items; ++i) {
+      AggItemArg& a = item_args[(size_t)i];
+      a.kind = items[i].kind; a.key_index = items[i].key_index;
+      a.column = items[i].column ? &items[i].column->e : nullptr;
+      require(items[i].name, "output column name");
+      a.name = items[i].name;
+    }
+    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+    PhaseTimer pt("chq_aggregate_records");
+    std::vector<Batch> in((size_t)n_records);
+    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
+    for_each_parallel(n_records, [&](int i) { in[(size_t)i] = import_batch(recs[i], schema); });
+    pt.mark("import");
+    Batch res = aggregate_records(ctx->c, in, table_aliases, key_args, item_args);
+    pt.mark("aggregate");
+    finish(ctx->c, std::move(res), out_device, out, out_schema);
+    pt.mark("export");
+  });
+}
+}  // namespace
+
+chq_status chq_aggregate_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, const chq_table_aliases* table_aliases,
+                                const chq_expr* const* keys, int n_keys, const chq_agg_item* items, int n_items, int out_device,
+                                ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  const ArrowDeviceArray* recs[1] = {rec};
+  if (!rec) { if (!ctx) return CHQ_ERR_INVALID_HANDLE; mark_released(out, out_schema); ctx->c.last_error = "null record"; return CHQ_ERR_INVALID_HANDLE; }
+  return aggregate_call(ctx, 1, recs, schema, table_aliases, keys, n_keys, items, n_items, out_device, out, out_schema);
+}
+
+chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                                 const chq_table_aliases* table_aliases, const chq_expr* const* keys, int n_keys,
+                                 const chq_agg_item* items, int n_items, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  return aggregate_call(ctx, n_records, recs, schema, table_aliases, keys, n_keys, items, n_items, out_device, out, out_schema);
 }
 
 chq_status chq_project_record(chq_ctx* ctx, const chq_select_item* fields, int n_fields, const ArrowDeviceArray* rec,

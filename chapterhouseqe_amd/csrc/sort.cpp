@@ -17,11 +17,6 @@ namespace {
 
 constexpr int64_t kMaxSortRows = (int64_t)1 << 32;   // row ids are u32
 
-// bytes the kernels move, for chq_call_stats (algorithmic: every byte read or written once)
-struct Traffic {
-  int64_t read = 0, written = 0;
-};
-
 // The key words of one sort key, least significant first (buffers and permutation are filled in by the caller).
 std::vector<SortNormParams> key_words(Context& ctx, const Column& c, const SortKeyArg& k, int64_t n) {
   SortNormParams base{};
@@ -81,6 +76,8 @@ std::vector<SortNormParams> key_words(Context& ctx, const Column& c, const SortK
   if (nulls) add(SW_NULL_FLAG);
   return words;
 }
+
+}  // namespace
 
 // the column a sort key names: the resolver of compute_value (plan.cpp), which must come back with a bare column
 int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nrows) {
@@ -207,8 +204,6 @@ BufferPtr sort_permutation(Context& ctx, const Batch& rec, const std::vector<int
   }
   return vb[pv];
 }
-
-}  // namespace
 
 Batch sort_records(Context& ctx, std::vector<Batch>& in, const chq_table_aliases* aliases, const std::vector<SortKeyArg>& keys,
                    int64_t limit) {

@@ -25,6 +25,20 @@ struct SortKeyArg {
   bool nulls_first = false;
 };
 
+// bytes the kernels move, for chq_call_stats (algorithmic: every byte read or written once)
+struct Traffic {
+  int64_t read = 0, written = 0;
+};
+
+// The pieces of the sort that GROUP BY (aggregate.cpp) stands on.
+// the column a sort key names: the resolver of compute_value (plan.cpp), which must come back with a bare column
+int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nrows);
+// out row i = in row perm[i] (perm null: identity) for rows [0, m), on the device; a validity bitmap's set bits are added to
+// *ones and the column's null_count left at -1 for the caller to fill in
+Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_t m, uint64_t* ones, Traffic& t);
+// the permutation of rows [0, n) that orders `rec` by `keys` on the columns `cols` (null: identity -- no key, or fewer than 2 rows)
+BufferPtr sort_permutation(Context& ctx, const Batch& rec, const std::vector<int>& cols, const std::vector<SortKeyArg>& keys, Traffic& t);
+
 // The batches of `in` (one schema, host or device resident) in key order, stable (batch order, then row order), cut to
 // the first `limit` rows (-1: all).  The result is ONE device batch with the schema of the input.  Throws ChqError.
 Batch sort_records(Context& ctx, std::vector<Batch>& in, const chq_table_aliases* aliases, const std::vector<SortKeyArg>& keys,

@@ -8,6 +8,8 @@ Reference (OPS = src/handlers/operator_handler/operators):
   OperatorTask::{Filter{expr}, MaterializeFiles{data_format, fields}}  src/planner/physical_planner.rs:58-65
   OrderByOperatorTask / OrderByTask         not in the reference (its DEV_NOTES.md lists ORDER BY as the next operator):
                                             a blocking single-instance sort over `record_utils.sort_records`
+  AggregateOperatorTask / AggregateTask     not in the reference either: GROUP BY, a blocking single-instance aggregation
+                                            over `record_utils.aggregate_records`
 
 The hot loops call `record_utils.filter_record` / `project_record` exactly where the reference does
 (filter_task.rs:99, materialize_files_task.rs:110); here those are the HIP kernels.  The control plane around
@@ -70,6 +72,17 @@ class OrderByOperatorTask:
         return "order_by"
 
 
+@dataclasses.dataclass(frozen=True)
+class AggregateOperatorTask:
+    """GROUP BY keys with the output items of the SELECT list (`sqlparse.aggregate_plan`); shaped like OrderByOperatorTask"""
+    keys: Sequence[A.Expr]
+    items: Sequence[A.AggItem]
+    max_rows_per_record: int = 10_000
+
+    def task_name(self) -> str:
+        return "aggregate"
+
+
 @dataclasses.dataclass
 class OperatorInstanceConfig:
     """operator_handler_state.rs:28-35 (fields the tasks use)"""
@@ -102,6 +115,7 @@ class OperatorTaskRegistry:
         self.materialize_data_formats: List[str] = []
         self.table_func_tasks: dict = {}
         self.order_by_task: Optional[TaskBuilder] = None
+        self.aggregate_task: Optional[TaskBuilder] = None
 
     def add_filter_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
         if self.filter_task is not None:
@@ -129,6 +143,12 @@ class OperatorTaskRegistry:
         self.order_by_task = builder
         return self
 
+    def add_aggregate_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        if self.aggregate_task is not None:
+            raise OperatorTaskRegistryError("aggregate task builder already set")
+        self.aggregate_task = builder
+        return self
+
     def find_task_builder(self, task) -> Optional[TaskBuilder]:
         if isinstance(task, ReadFilesOperatorTask):
             return self.table_func_tasks.get("read_files")
@@ -136,6 +156,8 @@ class OperatorTaskRegistry:
             return self.filter_task
         if isinstance(task, OrderByOperatorTask):
             return self.order_by_task
+        if isinstance(task, AggregateOperatorTask):
+            return self.aggregate_task
         if isinstance(task, MaterializeFilesOperatorTask):
             if task.data_format in self.materialize_data_formats:
                 return self.materialize_files_task
@@ -328,6 +350,98 @@ class OrderByTaskBuilder(TaskBuilder):
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
         task = OrderByTask(op_in_config, OrderByConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
                            sort_fn=self._sort_fn)
+
+        def run():
+            try:
+                task.async_main()
+                return None
+            except Exception as err:   # noqa: BLE001 -- any error ends the instance
+                return err
+
+        run.task = task
+        return run
+
+
+# ---- group by ---------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class AggregateConfig:
+    keys: Sequence[A.Expr]
+    items: Sequence[A.AggItem]
+    max_rows_per_record: int = 10_000
+
+    @staticmethod
+    def try_from(op_in_config: OperatorInstanceConfig) -> "AggregateConfig":
+        t = op_in_config.task
+        if not isinstance(t, AggregateOperatorTask):
+            raise ValueError("operator instance config is not an aggregate task")
+        if not t.items:
+            raise ValueError("an aggregate task needs at least one output item")
+        if t.max_rows_per_record < 1:
+            raise ValueError("max_rows_per_record must be at least 1")
+        return AggregateConfig(tuple(t.keys), tuple(t.items), t.max_rows_per_record)
+
+
+class AggregateTask:
+    """A blocking, single-instance operator with the protocol of OrderByTask: pulls and holds every inbound record,
+    aggregates them all with ONE `aggregate_records` call, sends the groups (in key order) cut into records of at most
+    `max_rows_per_record` rows with record ids 0, 1, 2, ..., and only then acks its inputs.  When no record came in nothing
+    is sent, also without a GROUP BY key: there is no schema to aggregate over.
+    `aggregate_fn(records, table_aliases, keys, items)` replaces the library call (tests on the CPU)."""
+
+    def __init__(self, op_in_config: OperatorInstanceConfig, config: AggregateConfig, inbound_exchanges, outbound_exchange,
+                 aggregate_fn=None, ctx=None):
+        self.operator_instance_config = op_in_config
+        self.config = config
+        self.inbound_exchanges = inbound_exchanges
+        self.outbound_exchange = outbound_exchange
+        self._aggregate = aggregate_fn
+        self._ctx = ctx
+        self.rows_in = 0
+        self.rows_out = 0
+        self.records_sent = 0
+
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
+        return self._ctx
+
+    def _aggregate_records(self, records, aliases):
+        if self._aggregate is not None:
+            return self._aggregate(records, aliases, self.config.keys, self.config.items)
+        return record_utils.aggregate_records(records, aliases, self.config.keys, self.config.items, ctx=self._context())
+
+    def async_main(self) -> None:
+        rec_handler = RecordHandler.initiate(self.operator_instance_config, self.inbound_exchanges, self.outbound_exchange)
+        try:
+            held = []
+            while True:
+                exchange_rec = rec_handler.next_record_to_hold()
+                if exchange_rec is None:
+                    break
+                held.append(exchange_rec)
+            if not held:
+                return
+            self.rows_in = sum(h.record.num_rows for h in held)
+            result = self._aggregate_records([h.record for h in held], held[0].table_aliases)
+            out_aliases = [[] for _ in range(result.num_columns)]   # the output columns are new: no table prefix reaches them
+            n, step = result.num_rows, self.config.max_rows_per_record
+            for record_id, start in enumerate(range(0, max(n, 1), step)):
+                rec_handler.send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), out_aliases)
+                self.records_sent += 1
+            self.rows_out = n
+            for h in held:
+                rec_handler.complete_record(h)
+        finally:
+            rec_handler.close()
+
+
+class AggregateTaskBuilder(TaskBuilder):
+    def __init__(self, aggregate_fn=None):
+        self._aggregate_fn = aggregate_fn
+
+    def build(self, op_in_config, inbound_exchanges, outbound_exchange):
+        task = AggregateTask(op_in_config, AggregateConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
+                             aggregate_fn=self._aggregate_fn)
 
         def run():
             try:
@@ -545,4 +659,5 @@ def build_default_operator_task_registry(storage_root: str) -> OperatorTaskRegis
             .add_table_func_task_builder("read_files", ReadFilesTaskBuilder(storage_root))
             .add_filter_task_builder(FilterTaskBuilder())
             .add_order_by_task_builder(OrderByTaskBuilder())
+            .add_aggregate_task_builder(AggregateTaskBuilder())
             .add_materialize_files_builder(MaterializeFilesTaskBuilder(storage_root), ["parquet"]))

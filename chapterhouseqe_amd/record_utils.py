@@ -832,6 +832,91 @@ def sort_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], order_b
     return _finish(ctx, rc, out, dev_out)
 
 
+# ------------------------------------------------------------------------------------------ GROUP BY
+class _AggArgs:
+    """the C arguments of one aggregate call: key handles and the item array (expression handles freed by `free`)"""
+
+    def __init__(self, keys: Sequence[A.Expr], items: Sequence[A.AggItem]):
+        self.n_keys, self.n_items = len(keys), len(items)
+        self._handles = []
+        try:
+            self.keys = (C.c_void_p * max(1, self.n_keys))()
+            for i, k in enumerate(keys):
+                self.keys[i] = self._handle(k)
+            self.items = (L.AggItem * max(1, self.n_items))()
+            for i, it in enumerate(items):
+                if not isinstance(it, A.AggItem):
+                    raise TypeError(f"not an AggItem: {it!r}")
+                self.items[i].kind = int(it.kind)
+                self.items[i].key_index = int(it.key_index)
+                self.items[i].column = self._handle(it.column) if it.column is not None else None
+                self.items[i].name = it.name.encode()
+        except Exception:
+            self.free()
+            raise
+
+    def _handle(self, e: A.Expr):
+        h = _expr_to_c(e)
+        self._handles.append(h)
+        return h
+
+    def free(self) -> None:
+        for h in self._handles:
+            L.lib().chq_expr_free(h)
+        self._handles = []
+
+
+def aggregate_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]]], keys: Sequence[A.Expr],
+                     items: Sequence[A.AggItem], *, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
+    """GROUP BY (`chq_aggregate_record`): one row per group of `rec` by the key columns `keys` (none: one group), in key
+    order (ascending, nulls last), one column per `items` entry (`sqlparse.aggregate_plan` builds both from a SELECT).
+    Result residency follows the input unless `device_result` says otherwise."""
+    ctx, src, own_src, on_dev = _prepare(rec, ctx)
+    dev_out = on_dev if device_result is None else device_result
+    al = _Aliases(table_aliases)
+    out = _CBatch()
+    try:
+        args = _AggArgs(keys, items)
+        try:
+            rc = L.lib().chq_aggregate_record(ctx.handle, C.byref(src.array), C.byref(src.schema), al.ptr, args.keys, args.n_keys,
+                                              args.items, args.n_items, L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
+                                              C.byref(out.array), C.byref(out.schema))
+        finally:
+            args.free()
+    finally:
+        if own_src:
+            src.release()
+    return _finish(ctx, rc, out, dev_out)
+
+
+def aggregate_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], keys: Sequence[A.Expr],
+                      items: Sequence[A.AggItem], *, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
+    """GROUP BY over a group (`chq_aggregate_records`): the batches of `recs` (a sequence of same-schema batches or a
+    `RecordGroup`) aggregated as if they were one batch."""
+    if not isinstance(recs, RecordGroup):
+        recs = list(recs)
+        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
+        if any(x != sig[0] for x in sig[1:]):   # (the C call takes ONE schema for the group)
+            raise ChqError(22, "aggregate_records: every record batch must have the schema of the first")
+    grp = recs if isinstance(recs, RecordGroup) else RecordGroup(recs, ctx)
+    ctx = ctx or grp.ctx
+    dev_out = grp.on_device if device_result is None else device_result
+    al = _Aliases(table_aliases)
+    out = _CBatch()
+    try:
+        args = _AggArgs(keys, items)
+        try:
+            rc = L.lib().chq_aggregate_records(ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema), al.ptr, args.keys, args.n_keys,
+                                               args.items, args.n_items, L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
+                                               C.byref(out.array), C.byref(out.schema))
+        finally:
+            args.free()
+    finally:
+        if grp is not recs:
+            grp.release()
+    return _finish(ctx, rc, out, dev_out)
+
+
 def project_record(fields: Sequence[A.SelectItem], record: Record, table_aliases: Optional[Sequence[Sequence[str]]], *,
                    ctx: Optional[Context] = None, device_result: Optional[bool] = None):
     """RU/record_projection.rs:16-76."""

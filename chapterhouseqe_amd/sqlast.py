@@ -110,6 +110,19 @@ class UnsupportedExpr(Expr):
     debug: str
 
 
+@dataclass(frozen=True, repr=False)
+class Function(UnsupportedExpr):
+    """Expr::Function: a call `name(args)` / `name(*)`.  compute_value rejects it like every UnsupportedExpr (its debug text
+    is `Function(name)`); the GROUP BY front-end reads the aggregate calls of a SELECT list from it.  `args` is None when
+    what stands between the parentheses is not a plain expression list (`count(distinct a)`, `cast(a as int)`)."""
+    name: str = ""
+    args: Optional[Tuple[Expr, ...]] = ()
+    star: bool = False
+
+    def __repr__(self) -> str:   # the text an enclosing Unsupported node quotes
+        return f"UnsupportedExpr(debug={self.debug!r})"
+
+
 # ---- sqlparser::ast::SelectItem --------------------------------------------------------------
 class SelectItem:
     pass
@@ -149,6 +162,25 @@ class OrderByExpr:
         """(descending, nulls_first) as the library's sort takes them"""
         asc = True if self.asc is None else self.asc
         return (not asc, (not asc) if self.nulls_first is None else self.nulls_first)
+
+
+# ---- GROUP BY: one output column (include/chq.h: chq_agg_item) -----------------------------------
+class AggKind(enum.IntEnum):
+    KEY = 0
+    COUNT_STAR = 1
+    COUNT = 2
+    SUM = 3
+    MIN = 4
+    MAX = 5
+
+
+@dataclass(frozen=True)
+class AggItem:
+    """`KEY`: `key_index` into the GROUP BY keys; `COUNT_STAR`: nothing else; the others: their argument `column`."""
+    kind: AggKind
+    name: str
+    key_index: int = -1
+    column: Optional[Expr] = None
 
 
 # ---- small constructors used by tests (the reference builds these structs literally) ----------

@@ -7,7 +7,7 @@ grammar -- tokens, operator precedence (Or 5 < And 10 < comparison 20 < +,- 30 <
 associativity, `Nested` for parentheses, `Number` text kept verbatim -- for tests, the bench and the
 sample queries (reference: sample_queries/simple.sql) to be written as SQL text.
 
-    select <items> from <func>('<path>') [[as] alias] [where <expr>]
+    select <items> from <func>('<path>') [[as] alias] [where <expr>] [group by <column> {, ...}]
         [order by <expr> [asc|desc] [nulls first|last] {, ...}] [limit <n>]
 """
 from __future__ import annotations
@@ -69,6 +69,7 @@ class Select:
     selection: Optional[A.Expr]
     order_by: Tuple[A.OrderByExpr, ...] = ()
     limit: Optional[int] = None
+    group_by: Tuple[A.Expr, ...] = ()
 
 
 def _tokenize(text: str) -> List[Tuple[str, str]]:
@@ -172,22 +173,42 @@ class _Parser:
                 inner = self.parse_expr(_PREC_NOT)
                 return A.UnsupportedExpr(f"UnaryOp {{ op: Not, expr: {inner!r} }}")
             if self.peek() == ("op", "("):
-                depth = 0
-                while True:  # skip the call, it is rejected by compute_value anyway
-                    kk, vv = self.next()
-                    if kk == "eof":
-                        raise SqlParseError("unterminated function call")
-                    if (kk, vv) == ("op", "("):
-                        depth += 1
-                    if (kk, vv) == ("op", ")"):
-                        depth -= 1
-                        if depth == 0:
-                            break
-                return A.UnsupportedExpr(f"Function({v})")
+                return self._function_call(v)
             return self._identifier_tail(A.Ident(v))
         if k == "qident":
             return self._identifier_tail(A.Ident(v, '"'))
         raise SqlParseError(f"unexpected token {v!r}")
+
+    def _function_call(self, name: str) -> A.Expr:
+        """`name ( [* | expr {, expr}] )`; anything else between the parentheses is skipped (args None).  compute_value
+        rejects every call, so the evaluator sees `Function(name)` whatever the arguments are."""
+        start = self.i
+        args, star = None, False
+        try:
+            self.expect_op("(")
+            if self.accept_op("*"):
+                star, parsed = True, []
+            elif self.peek() == ("op", ")"):
+                parsed = []
+            else:
+                parsed = [self.parse_expr(0)]
+                while self.accept_op(","):
+                    parsed.append(self.parse_expr(0))
+            self.expect_op(")")
+            args = tuple(parsed)
+        except SqlParseError:
+            self.i, star, depth = start, False, 0
+            while True:
+                kk, vv = self.next()
+                if kk == "eof":
+                    raise SqlParseError("unterminated function call")
+                if (kk, vv) == ("op", "("):
+                    depth += 1
+                if (kk, vv) == ("op", ")"):
+                    depth -= 1
+                    if depth == 0:
+                        break
+        return A.Function(f"Function({name})", name, args, star)
 
     def _identifier_tail(self, first: A.Ident) -> A.Expr:
         parts = [first]
@@ -257,6 +278,13 @@ class _Parser:
         selection = None
         if self.accept_word("WHERE"):
             selection = self.parse_expr(0)
+        group_by: List[A.Expr] = []
+        if self.accept_word("GROUP"):
+            if not self.accept_word("BY"):
+                raise SqlParseError(f"expected BY after GROUP, found {self.peek()[1]!r}")
+            group_by.append(self.parse_expr(0))
+            while self.accept_op(","):
+                group_by.append(self.parse_expr(0))
         order_by: List[A.OrderByExpr] = []
         if self.accept_word("ORDER"):
             if not self.accept_word("BY"):
@@ -271,7 +299,7 @@ class _Parser:
                 raise SqlParseError(f"expected a non-negative integer after LIMIT, found {v!r}")
             limit = int(v)
         self.accept_op(";")
-        return Select(tuple(items), from_, selection, tuple(order_by), limit)
+        return Select(tuple(items), from_, selection, tuple(order_by), limit, tuple(group_by))
 
     def parse_order_by_expr(self) -> A.OrderByExpr:
         """sqlparser Parser::parse_order_by_expr"""
@@ -286,6 +314,58 @@ class _Parser:
             else:
                 raise SqlParseError(f"expected FIRST or LAST after NULLS, found {self.peek()[1]!r}")
         return A.OrderByExpr(expr, asc, nulls_first)
+
+
+# ---- GROUP BY: the SELECT list as keys and output items -----------------------------------------------
+_AGGREGATES = {"count": A.AggKind.COUNT, "sum": A.AggKind.SUM, "min": A.AggKind.MIN, "max": A.AggKind.MAX}
+
+
+def _expr_text(e: A.Expr) -> str:
+    if isinstance(e, A.Identifier):
+        return e.ident.value
+    if isinstance(e, A.CompoundIdentifier):
+        return ".".join(i.value for i in e.idents)
+    if isinstance(e, A.Function):
+        return f"{e.name}({'*' if e.star else ', '.join(_expr_text(a) for a in (e.args or ()))})"
+    return repr(e)
+
+
+def is_aggregate_call(e: A.Expr) -> bool:
+    return isinstance(e, A.Function) and e.name.lower() in _AGGREGATES
+
+
+def aggregate_plan(select: Select):
+    """A `Select` with GROUP BY or aggregate calls -> `(keys, items)` as `record_utils.aggregate_record(s)` takes them
+    (None: the statement has neither).  Every SELECT item must be a GROUP BY key or one of count(*), count(c), sum(c),
+    min(c), max(c) (names case-insensitive); an item is named by its alias, else a key by its column name and an
+    aggregate by its lower-cased call text."""
+    exprs = [(f.expr if isinstance(f, (A.UnnamedExpr, A.ExprWithAlias)) else None) for f in select.projection]
+    if not select.group_by and not any(e is not None and is_aggregate_call(e) for e in exprs):
+        return None
+    keys = tuple(select.group_by)
+    items = []
+    for f, e in zip(select.projection, exprs):
+        if e is None:
+            raise SqlParseError("a wildcard cannot be selected together with GROUP BY or an aggregate")
+        alias = f.alias.value if isinstance(f, A.ExprWithAlias) else None
+        if is_aggregate_call(e):
+            kind = _AGGREGATES[e.name.lower()]
+            name = alias if alias is not None else _expr_text(e).lower()
+            if e.star:
+                if kind != A.AggKind.COUNT:
+                    raise SqlParseError(f"{e.name}(*) is not an aggregate; only count(*) takes '*'")
+                items.append(A.AggItem(A.AggKind.COUNT_STAR, name))
+            elif e.args is None or len(e.args) != 1:
+                raise SqlParseError(f"{e.name} takes exactly one column: {_expr_text(e) if e.args is not None else e.name + '(...)'}")
+            else:
+                items.append(A.AggItem(kind, name, -1, e.args[0]))
+        elif e in keys:
+            name = alias if alias is not None else (e.ident.value if isinstance(e, A.Identifier) else
+                                                    e.idents[-1].value if isinstance(e, A.CompoundIdentifier) else _expr_text(e))
+            items.append(A.AggItem(A.AggKind.KEY, name, keys.index(e)))
+        else:
+            raise SqlParseError(f"SELECT item {_expr_text(e)} is neither a GROUP BY key nor an aggregate")
+    return keys, tuple(items)
 
 
 def parse_expr(text: str) -> A.Expr:

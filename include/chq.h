@@ -385,6 +385,60 @@ chq_status chq_sort_records(chq_ctx* ctx, int n_records, const struct ArrowDevic
                             const chq_sort_key* keys, int n_keys, int64_t limit, int out_device,
                             struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
 
+/* ---- GROUP BY: grouped COUNT / SUM / MIN / MAX on top of the stable sort ---------------------------
+ * The reference has no GROUP BY; these semantics are this library's own (unpinned), chosen so that none of them depends on
+ * the order in which rows are combined:
+ *   - zero or more keys, each a column (Identifier / CompoundIdentifier) resolved exactly like a sort key (a missing
+ *     column: the evaluator's status; any other expression: CHQ_ERR_NOT_SUPPORTED); the key types are those of ORDER BY.
+ *   - two rows are in one group iff for every key both values are null, or both are non-null with EQUAL BIT PATTERNS: for
+ *     floats that is totalOrder equality (-0 and +0 are two groups, so are NaNs with different payloads), for Utf8 equal
+ *     length and equal bytes.  Null is a group of its own.  No key: one group over all rows, which exists even for zero
+ *     rows (COUNT 0, every other aggregate null).  At least one key and zero rows: zero output rows.
+ *   - one output row per group, in a guaranteed order: ascending by the keys in the order given, nulls last.
+ *   - one output column per item, in item order, named `name`:
+ *       CHQ_AGG_KEY         key `key_index`: the input field's type and nullability, the value of the group's first row in
+ *                           input order (for a group of batches: batch order, then row order)
+ *       CHQ_AGG_COUNT_STAR  rows of the group; CHQ_AGG_COUNT: non-null values of `column`.  Int64, not nullable.
+ *       CHQ_AGG_SUM         nulls skipped; Int8..64 -> Int64, UInt8..64 -> UInt64, Float32/64 -> Float64; nullable, null for
+ *                           a group without a non-null value.  Integer overflow is decided on the EXACT total of the group,
+ *                           never on an intermediate ({INT64_MAX, 1, -5} is INT64_MAX - 4); a total outside the result type
+ *                           fails the whole call with CHQ_ERR_ARROW_ARITHMETIC_OVERFLOW naming the output column.  Float
+ *                           sums are IEEE binary64 additions (Float32 widens exactly; NaN and +-inf propagate, +inf with
+ *                           -inf is NaN) combined in an order fixed by the input: bit-identical from run to run.
+ *       CHQ_AGG_MIN / MAX   nulls skipped; the input type, nullable; Int8..64, UInt8..64, Float16/32/64 in totalOrder, and
+ *                           Date, Time, Timestamp, Duration and decimals of up to 8 bytes as signed integers.  The result
+ *                           is the bits of an actual input value.
+ *     CHQ_ERR_NOT_SUPPORTED, naming the column and its type: SUM over Float16, Boolean, temporal types, decimals, Utf8;
+ *     MIN / MAX over Utf8, Boolean, Decimal128.  An empty item list, or a key_index outside the keys:
+ *     CHQ_ERR_ARROW_INVALID_ARGUMENT.
+ *   - fewer than 2^32 rows per call (else CHQ_ERR_NOT_SUPPORTED).
+ * AVG, DISTINCT aggregates, HAVING, expressions as keys or arguments, and partial / merge aggregation across instances are
+ * out of scope.  Inputs may be host or device resident and sliced; `out_device` is ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM.
+ * On failure nothing is returned (release == NULL). */
+typedef enum chq_agg_kind {
+  CHQ_AGG_KEY = 0,
+  CHQ_AGG_COUNT_STAR = 1,
+  CHQ_AGG_COUNT = 2,
+  CHQ_AGG_SUM = 3,
+  CHQ_AGG_MIN = 4,
+  CHQ_AGG_MAX = 5
+} chq_agg_kind;
+typedef struct chq_agg_item {
+  int kind;                /* chq_agg_kind */
+  int key_index;           /* CHQ_AGG_KEY: index into `keys` */
+  const chq_expr* column;  /* COUNT, SUM, MIN, MAX: the argument column; NULL otherwise */
+  const char* name;        /* output column name */
+} chq_agg_item;
+chq_status chq_aggregate_record(chq_ctx* ctx, const struct ArrowDeviceArray* rec, const struct ArrowSchema* schema,
+                                const chq_table_aliases* table_aliases, const chq_expr* const* keys, int n_keys,
+                                const chq_agg_item* items, int n_items, int out_device, struct ArrowDeviceArray* out,
+                                struct ArrowSchema* out_schema);
+/* The same over `n_records` batches of ONE schema, as if they were one batch (the group is joined on the device first). */
+chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const struct ArrowDeviceArray* const* recs,
+                                 const struct ArrowSchema* schema, const chq_table_aliases* table_aliases,
+                                 const chq_expr* const* keys, int n_keys, const chq_agg_item* items, int n_items,
+                                 int out_device, struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
+
 /* Wrap caller-owned device (or host) buffers as a record batch without copying; the buffers must
  * outlive the returned structs, whose release callbacks free only the descriptors. `format` is an
  * Arrow C format string ("i","f","g","l","b","u", ...). */

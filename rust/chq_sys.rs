@@ -52,6 +52,15 @@ pub struct chq_sort_key {
     pub nulls_first: c_int,
 }
 
+/// struct chq_agg_item: one output column of GROUP BY (kind: 0 key, 1 COUNT(*), 2 COUNT, 3 SUM, 4 MIN, 5 MAX)
+#[repr(C)]
+pub struct chq_agg_item {
+    pub kind: c_int,
+    pub key_index: c_int,
+    pub column: *const chq_expr,
+    pub name: *const c_char,
+}
+
 #[repr(C)]
 pub struct chq_alias_list {
     pub aliases: *const *const c_char,
@@ -170,6 +179,20 @@ extern "C" {
         ctx: *mut chq_ctx, n_records: c_int, recs: *const *const ArrowDeviceArray, schema: *const FFI_ArrowSchema,
         table_aliases: *const chq_table_aliases, keys: *const chq_sort_key, n_keys: c_int, limit: i64,
         out_device: c_int, out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
+    ) -> c_int;
+    /// GROUP BY: one row per group in key order (ascending, nulls last), one column per item
+    pub fn chq_aggregate_record(
+        ctx: *mut chq_ctx, rec: *const ArrowDeviceArray, schema: *const FFI_ArrowSchema,
+        table_aliases: *const chq_table_aliases, keys: *const *const chq_expr, n_keys: c_int,
+        items: *const chq_agg_item, n_items: c_int, out_device: c_int,
+        out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
+    ) -> c_int;
+    /// the same over a group of batches of one schema, as if they were one batch
+    pub fn chq_aggregate_records(
+        ctx: *mut chq_ctx, n_records: c_int, recs: *const *const ArrowDeviceArray, schema: *const FFI_ArrowSchema,
+        table_aliases: *const chq_table_aliases, keys: *const *const chq_expr, n_keys: c_int,
+        items: *const chq_agg_item, n_items: c_int, out_device: c_int,
+        out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
     ) -> c_int;
     pub fn chq_project_record(
         ctx: *mut chq_ctx, fields: *const chq_select_item, n_fields: c_int, rec: *const ArrowDeviceArray,
