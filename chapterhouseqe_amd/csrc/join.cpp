@@ -1,0 +1,243 @@
+// join.cpp -- INNER JOIN on the device (chq_join_records): a sort-merge equi-join.
+//
+// The key columns of both sides are concatenated into one key batch, RIGHT rows first, and ordered by the stable sort of
+// sort.cpp; the group-heads kernels of aggregate.hip then number the runs of equal keys.  Because the sort is stable and the
+// right rows come first, a run lies in the sorted positions as [its right rows in input order][its left rows in input order].
+// The kernels of join.hip find where the left rows of every run begin, count the matches of every left row, scan the counts
+// over the left rows in input order and expand them into two row-id lists, which gather_column turns into the output columns.
+// Three read-backs besides the sort's: the number of runs, the number of output rows (it sizes every output), and one block
+// of null counts at the end.  DESIGN.md section 3.8.
+//
+// Out of scope: LEFT / RIGHT / FULL / CROSS joins (the left-major output order is chosen so that LEFT can follow),
+// non-equality conditions, expressions as keys, coercion between key types, partitioned or multi-instance joins.
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#include "join.hpp"
+
+namespace chq {
+namespace {
+
+constexpr int64_t kMaxJoinRows = (int64_t)1 << 32;   // sorted positions, row ids and output rows are u32
+
+int resolve_join_key(const Expr* e, const char* side, const std::vector<PlanColumn>& pcols, int64_t rows) {
+  if (!e) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null ") + side + " join key"};
+  if (e->kind != Expr::IDENT && e->kind != Expr::COMPOUND)
+    throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("a join key must be a column, not ") + (e->text.empty() ? std::string("an expression") : e->text)};
+  return resolve_key(*e, pcols, rows);
+}
+
+// the key types of ORDER BY (sort.cpp: key_words)
+bool sortable(const Column& c) {
+  const std::string& f = c.format;
+  switch (c.type) {
+    case T_BOOL: case T_I8: case T_I16: case T_I32: case T_I64: case T_U8: case T_U16: case T_U32: case T_U64:
+    case T_F16: case T_F32: case T_F64: case T_UTF8:
+      return true;
+    case T_FIXED_OPAQUE:
+      return f == "tdD" || f == "tts" || f == "ttm" || f == "tdm" || f == "ttu" || f == "ttn" || f.rfind("ts", 0) == 0 || f.rfind("tD", 0) == 0 ||
+             (f.rfind("d:", 0) == 0 && (c.width <= 8 || c.width == 16));
+    default: return false;
+  }
+}
+
+// The key columns of one side as batches of their own, appended to `out`: zero-copy views under the names both sides share,
+// cut into slices of rows.  The concat kernels give every batch ONE workgroup: a side handed over in one piece would be
+// copied by a single workgroup, in slices the copy spreads over the device.
+constexpr int64_t kKeySliceRows = 16384;   // at least this many rows per slice ...
+constexpr int64_t kKeySlices = 2048;       // ... and at most about this many slices per side
+
+void key_views(const Batch& side, const std::vector<int>& cols, const std::vector<std::string>& names, std::vector<Batch>& out) {
+  const int64_t step = std::max(kKeySliceRows, (side.nrows + kKeySlices - 1) / kKeySlices);
+  for (int64_t r0 = 0; r0 < side.nrows; r0 += step) {
+    Batch kb;
+    kb.nrows = std::min(step, side.nrows - r0); kb.on_device = side.on_device; kb.device_id = side.device_id;
+    for (size_t k = 0; k < cols.size(); ++k) {
+      Column c = side.cols[(size_t)cols[k]];
+      c.name = names[k];
+      c.nullable = true;
+      if (kb.nrows != side.nrows) {   // a slice: what the column knew about all of its rows no longer holds
+        c.offset += r0; c.length = kb.nrows;
+        if (c.validity && c.null_count != 0) c.null_count = -1;
+        c.data_bytes = -1;
+      }
+      kb.cols.push_back(std::move(c));
+    }
+    out.push_back(std::move(kb));
+  }
+}
+
+}  // namespace
+
+Batch join_records(Context& ctx, std::vector<Batch>& left, const chq_table_aliases* left_aliases, std::vector<Batch>& right,
+                   const chq_table_aliases* right_aliases, const std::vector<JoinKeyArg>& keys) {
+  if (left.empty() || right.empty()) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch per side is needed"};
+  if (keys.empty())
+    throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "INNER JOIN needs at least one pair of key columns (there is no cross join)"};
+  int64_t rows_l = 0, rows_r = 0;
+  for (const Batch& b : left) rows_l += b.nrows;
+  for (const Batch& b : right) rows_r += b.nrows;
+  if (rows_l + rows_r >= kMaxJoinRows)
+    throw ChqError{CHQ_ERR_NOT_SUPPORTED, "a join takes fewer than 2^32 rows per call, both sides together (" + std::to_string(rows_l) + " + " +
+                                          std::to_string(rows_r) + " given)"};
+  // ---- 1. keys resolve and type-check against both schemas before any data moves
+  const auto pcols_l = plan_columns(left[0], left_aliases);
+  const auto pcols_r = plan_columns(right[0], right_aliases);
+  std::vector<int> cols_l, cols_r;
+  std::vector<std::string> key_names;
+  for (const JoinKeyArg& k : keys) {
+    const int cl = resolve_join_key(k.left, "left", pcols_l, rows_l), cr = resolve_join_key(k.right, "right", pcols_r, rows_r);
+    const Column& a = left[0].cols[(size_t)cl];
+    const Column& b = right[0].cols[(size_t)cr];
+    if (a.format != b.format)
+      throw ChqError{CHQ_ERR_NOT_SUPPORTED, "join keys '" + a.name + "' (Arrow type '" + a.format + "') and '" + b.name + "' (Arrow type '" + b.format +
+                                            "') have different types; coercion between key types is not supported in this build"};
+    if (!sortable(a))
+      throw ChqError{CHQ_ERR_NOT_SUPPORTED, "join keys '" + a.name + "' and '" + b.name + "' have Arrow type '" + a.format +
+                                            "', which has no order in this build"};
+    cols_l.push_back(cl); cols_r.push_back(cr);
+    key_names.push_back(a.name + " = " + b.name);   // (what a message about the concatenated keys names)
+  }
+
+  // ---- 2. one device batch per side
+  ctx.stats = chq_call_stats{};
+  const Batch L = join_group(ctx, left);
+  const Batch R = join_group(ctx, right);
+  const int64_t nL = L.nrows, nR = R.nrows, n = nL + nR, ntiles = (n + kJoinTile - 1) / kJoinTile;
+  ctx.stats.rows_in = n; ctx.stats.tiles = ntiles;
+  kernel_span_begin(ctx);
+  Traffic t;
+  int64_t M = 0;
+  BufferPtr lidx, ridx;
+  if (nL > 0 && nR > 0) {
+    // ---- 3. the keys of both sides in one batch, right rows first; 4. their stable order
+    std::vector<Batch> key_batches;
+    key_views(R, cols_r, key_names, key_batches);
+    key_views(L, cols_l, key_names, key_batches);
+    const Batch K = join_group(ctx, key_batches);
+    std::vector<int> key_cols(keys.size());
+    for (size_t k = 0; k < keys.size(); ++k) key_cols[k] = (int)k;
+    const std::vector<SortKeyArg> sort_keys(keys.size(), SortKeyArg{nullptr, false, false});
+    const BufferPtr perm_buf = sort_permutation(ctx, K, key_cols, sort_keys, t);
+    const uint32_t* perm = perm_buf ? (const uint32_t*)perm_buf->ptr : nullptr;
+
+    // ---- 5. the runs of equal keys: heads -> scan -> (read back G) -> ids, starts
+    BufferPtr heads = make_device_buffer((size_t)ntiles * kAggTile + 16, ctx.device);
+    BufferPtr counts = make_device_buffer((size_t)(ntiles + 1) * 4 + 16, ctx.device);
+    AggHeadsParams hp{};
+    hp.perm = perm; hp.n = n; hp.heads = (uint8_t*)heads->ptr; hp.tile_counts = (uint32_t*)counts->ptr; hp.ntiles = ntiles;
+    for (size_t k0 = 0; k0 < key_cols.size(); k0 += (size_t)hp.n_keys) {
+      hp.n_keys = (int32_t)std::min<size_t>(kAggMaxKeys, key_cols.size() - k0);
+      hp.accumulate = k0 ? 1 : 0;
+      for (int q = 0; q < hp.n_keys; ++q) {
+        const Column& c = K.cols[k0 + (size_t)q];
+        AggKey& key = hp.keys[q];
+        key = AggKey{};
+        key.validity = c.validity && c.null_count != 0 ? c.validity : nullptr;
+        key.bit_offset = c.offset;
+        key.values = (const uint8_t*)c.values0();
+        key.data = c.data;
+        key.kind = c.type == T_BOOL ? AK_BOOL : c.type == T_UTF8 ? AK_UTF8 : AK_FIXED;
+        key.width = c.width;
+        t.read += n * (c.type == T_UTF8 ? 8 + (c.length ? std::max<int64_t>(c.data_bytes, 0) / c.length : 0) : std::max(1, c.width));
+      }
+      check_hip(launch_agg_heads(hp, ctx.stream), "launch agg_heads_kernel");
+      ++ctx.stats.launches;
+      t.read += perm ? n * 4 : 0; t.written += n + ntiles * 4;
+    }
+    AggGroupsParams gp{};
+    gp.perm = perm; gp.n = n; gp.heads = (const uint8_t*)heads->ptr; gp.tile_counts = (uint32_t*)counts->ptr; gp.ntiles = ntiles;
+    check_hip(launch_agg_head_scan(gp, ctx.stream), "launch agg_head_scan_kernel");
+    ++ctx.stats.launches;
+    uint32_t g32 = 0;
+    check_hip(hipMemcpyAsync(&g32, gp.tile_counts + ntiles, 4, hipMemcpyDeviceToHost, ctx.stream), "read back the run count");
+    check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+    const int64_t G = (int64_t)g32;
+    if (G < 1 || G > n) throw ChqError{CHQ_ERR_DEVICE, "internal error: " + std::to_string(G) + " key runs over " + std::to_string(n) + " rows"};
+    BufferPtr gids = make_device_buffer((size_t)n * 4 + 16, ctx.device);
+    BufferPtr starts = make_device_buffer((size_t)(G + 1) * 4 + 16, ctx.device);
+    BufferPtr rep = make_device_buffer((size_t)G * 4 + 16, ctx.device);
+    gp.gids = (uint32_t*)gids->ptr; gp.starts = (uint32_t*)starts->ptr; gp.rep = (uint32_t*)rep->ptr; gp.G = G;
+    check_hip(launch_agg_head_write(gp, ctx.stream), "launch agg_head_write_kernel");
+    ++ctx.stats.launches;
+    t.read += ntiles * 8 + n + (perm ? G * 4 : 0); t.written += ntiles * 4 + n * 4 + G * 8;
+
+    // ---- 6. split -> count -> scan (read back M) -> expand
+    BufferPtr split = make_device_buffer((size_t)G * 4 + 16, ctx.device);
+    JoinSplitParams sp{};
+    sp.perm = perm; sp.n = n; sp.n_right = nR; sp.gids = gp.gids; sp.starts = gp.starts; sp.split = (uint32_t*)split->ptr;
+    for (size_t k0 = 0; k0 < key_cols.size(); k0 += (size_t)sp.n_keys) {
+      sp.n_keys = (int32_t)std::min<size_t>(kAggMaxKeys, key_cols.size() - k0);
+      sp.nulls_only = k0 ? 1 : 0;
+      bool any_nulls = false;
+      for (int q = 0; q < sp.n_keys; ++q) {
+        const Column& c = K.cols[k0 + (size_t)q];
+        sp.validity[q] = c.validity && c.null_count != 0 ? c.validity : nullptr;
+        sp.bit_offset[q] = c.offset;
+        any_nulls |= sp.validity[q] != nullptr;
+      }
+      if (k0 && !any_nulls) continue;   // (a later launch only applies the null rule)
+      check_hip(launch_join_split(sp, ctx.stream), "launch join_split_kernel");
+      ++ctx.stats.launches;
+      t.read += n * 8 + G * 4; t.written += G * 4;
+    }
+    const int64_t ltiles = (nL + kJoinTile - 1) / kJoinTile;
+    BufferPtr cnt = make_device_buffer((size_t)nL * 4 + 16, ctx.device);
+    BufferPtr first = make_device_buffer((size_t)nL * 4 + 16, ctx.device);
+    BufferPtr off = make_device_buffer((size_t)nL * 4 + 16, ctx.device);
+    BufferPtr sums = make_device_buffer((size_t)(ltiles + 1) * 8 + 16, ctx.device);
+    JoinCountParams cp{};
+    cp.perm = perm; cp.n = n; cp.n_right = nR; cp.gids = gp.gids; cp.starts = gp.starts; cp.split = sp.split;
+    cp.cnt = (uint32_t*)cnt->ptr; cp.first = (uint32_t*)first->ptr;
+    check_hip(launch_join_count(cp, ctx.stream), "launch join_count_kernel");
+    ++ctx.stats.launches;
+    t.read += n * 8 + nL * 8; t.written += nL * 8;
+    JoinScanParams scp{};
+    scp.cnt = cp.cnt; scp.n_left = nL; scp.ntiles = ltiles; scp.tile_sums = (uint64_t*)sums->ptr; scp.off = (uint32_t*)off->ptr;
+    check_hip(launch_join_scan(scp, ctx.stream), "launch join_tile_sums/scan_sums/offsets_kernel");
+    ctx.stats.launches += 3;
+    t.read += nL * 8 + ltiles * 24; t.written += nL * 4 + ltiles * 16;
+    uint64_t m64 = 0;
+    check_hip(hipMemcpyAsync(&m64, scp.tile_sums + ltiles, 8, hipMemcpyDeviceToHost, ctx.stream), "read back the output row count");
+    check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+    if (m64 >= (uint64_t)kMaxJoinRows)
+      throw ChqError{CHQ_ERR_NOT_SUPPORTED, "the join would produce " + std::to_string(m64) + " rows; a call returns fewer than 2^32"};
+    M = (int64_t)m64;
+    if (M > 0) {
+      lidx = make_device_buffer((size_t)M * 4 + 16, ctx.device);
+      ridx = make_device_buffer((size_t)M * 4 + 16, ctx.device);
+      JoinExpandParams ep{};
+      ep.perm = perm; ep.off = scp.off; ep.first = cp.first; ep.n_left = nL; ep.m = M;
+      ep.lidx = (uint32_t*)lidx->ptr; ep.ridx = (uint32_t*)ridx->ptr;
+      check_hip(launch_join_expand(ep, ctx.stream), "launch join_expand_kernel");
+      ++ctx.stats.launches;
+      t.read += M * 12 + (perm ? M * 4 : 0); t.written += M * 8;
+    }
+  }
+  ctx.stats.rows_out = M;
+
+  // ---- 7. every left column, then every right column, through the row-id lists
+  const size_t nc = L.cols.size() + R.cols.size();
+  BufferPtr ones = make_device_buffer(nc * 8 + 16, ctx.device);
+  check_hip(hipMemsetAsync(ones->ptr, 0, nc * 8 + 16, ctx.stream), "hipMemsetAsync");
+  Batch out;
+  out.nrows = M; out.on_device = true; out.device_id = ctx.device;
+  for (size_t ci = 0; ci < nc; ++ci) {
+    const bool is_left = ci < L.cols.size();
+    const Column& c = is_left ? L.cols[ci] : R.cols[ci - L.cols.size()];
+    const BufferPtr& idx = is_left ? lidx : ridx;
+    out.cols.push_back(gather_column(ctx, c, idx ? (const uint32_t*)idx->ptr : nullptr, M, (uint64_t*)ones->ptr + ci, t));
+  }
+  kernel_span_end(ctx);
+  std::vector<uint64_t> h(nc);
+  if (nc) check_hip(hipMemcpyAsync(h.data(), ones->ptr, nc * 8, hipMemcpyDeviceToHost, ctx.stream), "read back null counts");
+  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  for (size_t ci = 0; ci < nc; ++ci)
+    if (out.cols[ci].null_count < 0) out.cols[ci].null_count = M - (int64_t)h[ci];
+  ctx.stats.kernel_ns += kernel_span_ns(ctx);
+  ctx.stats.bytes_read_alg = t.read; ctx.stats.bytes_written_alg = t.written;
+  return out;
+}
+
+}  // namespace chq

@@ -1,0 +1,198 @@
+// join.hip -- the INNER JOIN kernels (gfx950, wave64).  Host side: join.cpp; in front of them: the sort (sort.hip) and the
+// group heads of GROUP BY (aggregate.hip) over the concatenated keys, right rows first.
+//
+// A run of equal keys lies in the sorted positions as [right rows in input order][left rows in input order]:
+//   split       split[g] = the position where the left rows of group g begin (a group with a null key: no right rows)
+//   count       for every left row l: cnt[l] = right rows of its group, first[l] = their first position
+//   scan        exclusive scan of cnt over the left rows in input order: tile sums, one workgroup over the sums IN 64 BITS
+//               (65 536 x 65 536 equal keys are 2^32 output rows: the total must not wrap), then the offsets per tile
+//   expand      output j -> left row l = the largest l with off[l] <= j, right row perm[first[l] + (j - off[l])]: a binary
+//               search per output, narrowed to the left rows the tile covers -- O(log nL) at worst whatever the skew, and
+//               no thread walks a run or a gap
+// Every hand-off happens at a launch boundary: no workgroup waits for another, nothing spins, no atomics, nothing depends on
+// dispatch order.  The result is bit-identical from run to run.
+#include <hip/hip_runtime.h>
+
+#include "join_device.h"
+
+namespace chq {
+namespace {
+
+constexpr int kWaves = kJoinBlock / 64;
+
+__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
+__device__ __forceinline__ bool bit_at(const uint8_t* bits, int64_t pos) { return (bits[pos >> 3] >> (pos & 7)) & 1; }
+
+// exclusive prefix of `v` over the workgroup (thread order); *total = sum of every thread's v
+template <typename T>
+__device__ __forceinline__ T block_exclusive_scan(T v, T* wave_sums, T* total) {
+  const int lane = lane_id(), w = (int)(threadIdx.x >> 6);
+  T x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T y = __shfl_up(x, (unsigned)o, 64);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) wave_sums[w] = x;
+  __syncthreads();
+  T base = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < kWaves; ++k) {
+    const T s = wave_sums[k];
+    if (k < w) base += s;
+    tot += s;
+  }
+  __syncthreads();   // wave_sums may be reused
+  *total = tot;
+  return base + x - v;
+}
+
+// ---- split ------------------------------------------------------------------------------------------------------------------
+// Exactly one position per group writes: the last right row of the group, or -- a group without right rows -- its head.
+__global__ __launch_bounds__(kJoinBlock) void join_split_kernel(const JoinSplitParams p) {
+  const int64_t p0 = (int64_t)blockIdx.x * kJoinTile + (int64_t)threadIdx.x * kJoinItems;
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k) {
+    const int64_t pos = p0 + k;
+    if (pos >= p.n) continue;
+    const uint32_t row = p.perm ? p.perm[pos] : (uint32_t)pos;
+    const uint32_t g = p.gids[pos];
+    bool writes;
+    if ((int64_t)row < p.n_right) {
+      writes = pos + 1 == p.n || p.gids[pos + 1] != g || (int64_t)(p.perm ? p.perm[pos + 1] : (uint32_t)(pos + 1)) >= p.n_right;
+    } else {
+      writes = pos == 0 || p.gids[pos - 1] != g;
+    }
+    if (!writes) continue;
+    bool null_key = false;
+    for (int q = 0; q < p.n_keys; ++q) null_key |= p.validity[q] && !bit_at(p.validity[q], p.bit_offset[q] + row);
+    if (null_key) p.split[g] = p.starts[g];
+    else if (!p.nulls_only) p.split[g] = (int64_t)row < p.n_right ? (uint32_t)(pos + 1) : p.starts[g];
+  }
+}
+
+// ---- count ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kJoinBlock) void join_count_kernel(const JoinCountParams p) {
+  const int64_t p0 = (int64_t)blockIdx.x * kJoinTile + (int64_t)threadIdx.x * kJoinItems;
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k) {
+    const int64_t pos = p0 + k;
+    if (pos >= p.n) continue;
+    const uint32_t row = p.perm ? p.perm[pos] : (uint32_t)pos;
+    if ((int64_t)row < p.n_right) continue;
+    const uint32_t l = row - (uint32_t)p.n_right;
+    const uint32_t g = p.gids[pos];
+    const uint32_t s = p.starts[g];
+    p.cnt[l] = p.split[g] - s;
+    p.first[l] = s;
+  }
+}
+
+// ---- scan -------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kJoinBlock) void join_tile_sums_kernel(const JoinScanParams p) {
+  __shared__ unsigned long long sums[kWaves];
+  const int64_t l0 = (int64_t)blockIdx.x * kJoinTile + (int64_t)threadIdx.x * kJoinItems;
+  unsigned long long v = 0;
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k)
+    if (l0 + k < p.n_left) v += p.cnt[l0 + k];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if (lane_id() == 0) sums[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long tot = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) tot += sums[k];
+    p.tile_sums[blockIdx.x] = tot;
+  }
+}
+
+// one workgroup: exclusive scan of the tile sums in place, in 64 bits; the total behind them
+__global__ __launch_bounds__(kJoinBlock) void join_scan_sums_kernel(const JoinScanParams p) {
+  __shared__ unsigned long long sums[kWaves];
+  unsigned long long carry = 0, tot;
+  for (int64_t c0 = 0; c0 < p.ntiles; c0 += kJoinBlock) {
+    const int64_t t = c0 + threadIdx.x;
+    const unsigned long long v = t < p.ntiles ? p.tile_sums[t] : 0;
+    const unsigned long long pre = block_exclusive_scan<unsigned long long>(v, sums, &tot) + carry;
+    if (t < p.ntiles) p.tile_sums[t] = pre;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) p.tile_sums[p.ntiles] = carry;
+}
+
+// off[l] = tile prefix + prefix inside the tile (u32: the caller refuses a total of 2^32 or more before it reads them)
+__global__ __launch_bounds__(kJoinBlock) void join_offsets_kernel(const JoinScanParams p) {
+  __shared__ uint32_t sums[kWaves];
+  const int64_t l0 = (int64_t)blockIdx.x * kJoinTile + (int64_t)threadIdx.x * kJoinItems;
+  uint32_t c[kJoinItems];
+  uint32_t v = 0;
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k) {
+    c[k] = l0 + k < p.n_left ? p.cnt[l0 + k] : 0u;
+    v += c[k];
+  }
+  uint32_t tot;
+  uint32_t at = block_exclusive_scan<uint32_t>(v, sums, &tot) + (uint32_t)p.tile_sums[blockIdx.x];
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k) {
+    if (l0 + k < p.n_left) p.off[l0 + k] = at;
+    at += c[k];
+  }
+}
+
+// ---- expand -----------------------------------------------------------------------------------------------------------------
+// the largest l in [lo, hi] with off[l] <= j (off is non-decreasing, off[lo] <= j)
+__device__ __forceinline__ int64_t last_at_most(const uint32_t* off, int64_t lo, int64_t hi, uint32_t j) {
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo + 1) / 2;
+    if (off[mid] <= j) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kJoinBlock) void join_expand_kernel(const JoinExpandParams p) {
+  __shared__ int64_t bounds[2];
+  const int64_t j0 = (int64_t)blockIdx.x * kJoinTile;
+  const int64_t j1 = p.m - j0 < kJoinTile ? p.m : j0 + kJoinTile;   // (j0 < m: the grid covers [0, m))
+  // the left rows of the tile's first and last output bound every search of the tile
+  if (threadIdx.x < 2) bounds[threadIdx.x] = last_at_most(p.off, 0, p.n_left - 1, (uint32_t)(threadIdx.x ? j1 - 1 : j0));
+  __syncthreads();
+  const int64_t lo = bounds[0], hi = bounds[1];
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k) {
+    const int64_t j = j0 + (int64_t)k * kJoinBlock + threadIdx.x;   // consecutive lanes, consecutive outputs
+    if (j >= j1) continue;
+    const int64_t l = last_at_most(p.off, lo, hi, (uint32_t)j);
+    const int64_t pos = (int64_t)p.first[l] + (j - (int64_t)p.off[l]);
+    p.lidx[j] = (uint32_t)l;
+    p.ridx[j] = p.perm ? p.perm[pos] : (uint32_t)pos;
+  }
+}
+
+unsigned tiles_of(int64_t n) { return (unsigned)((n + kJoinTile - 1) / kJoinTile); }
+
+}  // namespace
+
+hipError_t launch_join_split(const JoinSplitParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(join_split_kernel, dim3(tiles_of(p.n)), dim3(kJoinBlock), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_join_count(const JoinCountParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(join_count_kernel, dim3(tiles_of(p.n)), dim3(kJoinBlock), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_join_scan(const JoinScanParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(join_tile_sums_kernel, dim3((unsigned)p.ntiles), dim3(kJoinBlock), 0, stream, p);
+  hipLaunchKernelGGL(join_scan_sums_kernel, dim3(1), dim3(kJoinBlock), 0, stream, p);
+  hipLaunchKernelGGL(join_offsets_kernel, dim3((unsigned)p.ntiles), dim3(kJoinBlock), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_join_expand(const JoinExpandParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(join_expand_kernel, dim3(tiles_of(p.m)), dim3(kJoinBlock), 0, stream, p);
+  return hipGetLastError();
+}
+
+}  // namespace chq

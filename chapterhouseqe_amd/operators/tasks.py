@@ -10,6 +10,8 @@ Reference (OPS = src/handlers/operator_handler/operators):
                                             a blocking single-instance sort over `record_utils.sort_records`
   AggregateOperatorTask / AggregateTask     not in the reference either: GROUP BY, a blocking single-instance aggregation
                                             over `record_utils.aggregate_records`
+  JoinOperatorTask / JoinTask               not in the reference either: INNER JOIN, a blocking single-instance equi-join of
+                                            two inbound exchanges over `record_utils.join_records`
 
 The hot loops call `record_utils.filter_record` / `project_record` exactly where the reference does
 (filter_task.rs:99, materialize_files_task.rs:110); here those are the HIP kernels.  The control plane around
@@ -83,6 +85,17 @@ class AggregateOperatorTask:
         return "aggregate"
 
 
+@dataclasses.dataclass(frozen=True)
+class JoinOperatorTask:
+    """INNER JOIN on the (left column, right column) pairs of the ON condition (`sqlparse.join_plan`); inbound exchange 0
+    is the left input, 1 the right; shaped like AggregateOperatorTask"""
+    keys: Sequence[Any]
+    max_rows_per_record: int = 10_000
+
+    def task_name(self) -> str:
+        return "join"
+
+
 @dataclasses.dataclass
 class OperatorInstanceConfig:
     """operator_handler_state.rs:28-35 (fields the tasks use)"""
@@ -116,6 +129,7 @@ class OperatorTaskRegistry:
         self.table_func_tasks: dict = {}
         self.order_by_task: Optional[TaskBuilder] = None
         self.aggregate_task: Optional[TaskBuilder] = None
+        self.join_task: Optional[TaskBuilder] = None
 
     def add_filter_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
         if self.filter_task is not None:
@@ -149,6 +163,12 @@ class OperatorTaskRegistry:
         self.aggregate_task = builder
         return self
 
+    def add_join_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        if self.join_task is not None:
+            raise OperatorTaskRegistryError("join task builder already set")
+        self.join_task = builder
+        return self
+
     def find_task_builder(self, task) -> Optional[TaskBuilder]:
         if isinstance(task, ReadFilesOperatorTask):
             return self.table_func_tasks.get("read_files")
@@ -158,6 +178,8 @@ class OperatorTaskRegistry:
             return self.order_by_task
         if isinstance(task, AggregateOperatorTask):
             return self.aggregate_task
+        if isinstance(task, JoinOperatorTask):
+            return self.join_task
         if isinstance(task, MaterializeFilesOperatorTask):
             if task.data_format in self.materialize_data_formats:
                 return self.materialize_files_task
@@ -454,6 +476,104 @@ class AggregateTaskBuilder(TaskBuilder):
         return run
 
 
+# ---- inner join ---------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class JoinConfig:
+    keys: Sequence[Any]
+    max_rows_per_record: int = 10_000
+
+    @staticmethod
+    def try_from(op_in_config: OperatorInstanceConfig) -> "JoinConfig":
+        t = op_in_config.task
+        if not isinstance(t, JoinOperatorTask):
+            raise ValueError("operator instance config is not a join task")
+        if not t.keys:
+            raise ValueError("a join task needs at least one pair of key columns")
+        if t.max_rows_per_record < 1:
+            raise ValueError("max_rows_per_record must be at least 1")
+        return JoinConfig(tuple((l, r) for l, r in t.keys), t.max_rows_per_record)
+
+
+class JoinTask:
+    """A blocking, single-instance operator with the protocol of AggregateTask over TWO inbound exchanges (0: the left input,
+    1: the right): pulls and holds every record of both sides, joins them with ONE `join_records` call, sends the result
+    (ascending by left row, then by right row) cut into records of at most `max_rows_per_record` rows with record ids 0, 1,
+    2, ... under the table aliases of the left columns followed by those of the right columns, and only then acks both
+    sides.  When either side delivered no record nothing is sent: there is no schema to join with.
+    Each side has a RecordHandler of its own: a handler reads only its first exchange and tracks by record id, which the two
+    exchanges may share.
+    `join_fn(left_records, left_aliases, right_records, right_aliases, keys)` replaces the library call (tests on the CPU)."""
+
+    def __init__(self, op_in_config: OperatorInstanceConfig, config: JoinConfig, inbound_exchanges, outbound_exchange,
+                 join_fn=None, ctx=None):
+        if len(inbound_exchanges) != 2:
+            raise ValueError(f"a join task takes two inbound exchanges (left, right), not {len(inbound_exchanges)}")
+        self.operator_instance_config = op_in_config
+        self.config = config
+        self.inbound_exchanges = inbound_exchanges
+        self.outbound_exchange = outbound_exchange
+        self._join = join_fn
+        self._ctx = ctx
+        self.rows_in = 0
+        self.rows_out = 0
+        self.records_sent = 0
+
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
+        return self._ctx
+
+    def _join_records(self, left, left_aliases, right, right_aliases):
+        if self._join is not None:
+            return self._join(left, left_aliases, right, right_aliases, self.config.keys)
+        return record_utils.join_records(left, left_aliases, right, right_aliases, self.config.keys, ctx=self._context())
+
+    def async_main(self) -> None:
+        handlers = [RecordHandler.initiate(self.operator_instance_config, [ex], self.outbound_exchange) for ex in self.inbound_exchanges]
+        try:
+            held = [[], []]
+            for side, handler in enumerate(handlers):
+                while True:
+                    exchange_rec = handler.next_record_to_hold()
+                    if exchange_rec is None:
+                        break
+                    held[side].append(exchange_rec)
+            self.rows_in = sum(h.record.num_rows for side in held for h in side)
+            if held[0] and held[1]:
+                left_aliases, right_aliases = held[0][0].table_aliases, held[1][0].table_aliases
+                result = self._join_records([h.record for h in held[0]], left_aliases, [h.record for h in held[1]], right_aliases)
+                out_aliases = [list(a) for a in left_aliases] + [list(a) for a in right_aliases]
+                n, step = result.num_rows, self.config.max_rows_per_record
+                for record_id, start in enumerate(range(0, max(n, 1), step)):
+                    handlers[0].send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), out_aliases)
+                    self.records_sent += 1
+                self.rows_out = n
+            for side, handler in enumerate(handlers):
+                for h in held[side]:
+                    handler.complete_record(h)
+        finally:
+            for handler in handlers:
+                handler.close()
+
+
+class JoinTaskBuilder(TaskBuilder):
+    def __init__(self, join_fn=None):
+        self._join_fn = join_fn
+
+    def build(self, op_in_config, inbound_exchanges, outbound_exchange):
+        task = JoinTask(op_in_config, JoinConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange, join_fn=self._join_fn)
+
+        def run():
+            try:
+                task.async_main()
+                return None
+            except Exception as err:   # noqa: BLE001 -- any error ends the instance
+                return err
+
+        run.task = task
+        return run
+
+
 # ---- read_files (the table function in front of the path) -----------------------------------------------------
 class ReadFilesTask:
     """read_files_task.rs:129-291 with `read_records` (:233-282) on the GPU: every matching Parquet file is opened through a
@@ -660,4 +780,5 @@ def build_default_operator_task_registry(storage_root: str) -> OperatorTaskRegis
             .add_filter_task_builder(FilterTaskBuilder())
             .add_order_by_task_builder(OrderByTaskBuilder())
             .add_aggregate_task_builder(AggregateTaskBuilder())
+            .add_join_task_builder(JoinTaskBuilder())
             .add_materialize_files_builder(MaterializeFilesTaskBuilder(storage_root), ["parquet"]))

@@ -917,6 +917,87 @@ def aggregate_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], ke
     return _finish(ctx, rc, out, dev_out)
 
 
+# ------------------------------------------------------------------------------------------ INNER JOIN
+class _JoinSide:
+    """one side of a join as the C call takes it: a pointer array over its batches and their one schema.  `recs` is a
+    record, a sequence of records (host and device batches may be mixed) or a prepared `RecordGroup`."""
+
+    def __init__(self, recs, ctx: Optional[Context], what: str):
+        self._own = []
+        if isinstance(recs, RecordGroup):
+            self.ctx, self.n, self.ptrs, self.schema, self.on_device = recs.ctx, recs.n, recs.ptrs, recs.schema, recs.on_device
+            return
+        recs = [recs] if isinstance(recs, (pa.RecordBatch, DeviceRecordBatch)) else list(recs)
+        if not recs:
+            raise ValueError(f"join_records: the {what} side needs at least one record batch")
+        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
+        host_sig = [x for x in sig if isinstance(x, pa.Schema)]
+        dev_sig = [x for x in sig if not isinstance(x, pa.Schema)]
+        if any(x != host_sig[0] for x in host_sig[1:]) or any(x != dev_sig[0] for x in dev_sig[1:]) or \
+                (host_sig and dev_sig and tuple(host_sig[0].names) != dev_sig[0][0]):   # (the C call takes ONE schema per side)
+            raise ChqError(22, f"join_records: every record batch of the {what} side must have the schema of the first")
+        self.ctx = ctx or next((r.ctx for r in recs if isinstance(r, DeviceRecordBatch)), None) or default_context()
+        cbs = []
+        try:
+            for r in recs:
+                _c, src, own, _ = _prepare(r, self.ctx)
+                cbs.append(src)
+                if own:
+                    self._own.append(src)
+        except Exception:
+            self.release()
+            raise
+        self.n = len(cbs)
+        self.ptrs = (C.POINTER(L.ArrowDeviceArray) * self.n)(*[C.pointer(cb.array) for cb in cbs])
+        self.schema = cbs[0].schema
+        self.on_device = all(isinstance(r, DeviceRecordBatch) for r in recs)
+
+    def release(self) -> None:
+        for cb in self._own:
+            cb.release()
+        self._own = []
+
+
+def join_records(left, left_aliases: Optional[Sequence[Sequence[str]]], right, right_aliases: Optional[Sequence[Sequence[str]]],
+                 keys: Sequence[Tuple[A.Expr, A.Expr]], *, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
+    """INNER JOIN (`chq_join_records`): one row per pair (left row, right row) whose key columns are all non-null and equal
+    by bits, ascending by left row, then by right row; every left column, then every right column.  `left` and `right` are
+    each a record, a sequence of same-schema records or a `RecordGroup`; `keys` is a sequence of (left column, right column)
+    expressions (`sqlparse.join_plan` builds it from a SELECT).  The result is device resident when every input is, unless
+    `device_result` says otherwise."""
+    keys = list(keys)
+    for pair in keys:
+        if not (isinstance(pair, (tuple, list)) and len(pair) == 2):
+            raise TypeError(f"not a (left, right) key pair: {pair!r}")
+    ls = _JoinSide(left, ctx, "left")
+    try:
+        rs = _JoinSide(right, ctx or ls.ctx, "right")
+    except Exception:
+        ls.release()
+        raise
+    ctx = ctx or ls.ctx
+    dev_out = (ls.on_device and rs.on_device) if device_result is None else device_result
+    lal, ral = _Aliases(left_aliases), _Aliases(right_aliases)
+    ckeys = (L.JoinKey * max(1, len(keys)))()
+    handles = []
+    out = _CBatch()
+    try:
+        for i, (lk, rk) in enumerate(keys):
+            for side, e in (("left", lk), ("right", rk)):
+                h = _expr_to_c(e)
+                handles.append(h)
+                setattr(ckeys[i], side, h)
+        rc = L.lib().chq_join_records(ctx.handle, ls.n, ls.ptrs, C.byref(ls.schema), lal.ptr, rs.n, rs.ptrs, C.byref(rs.schema), ral.ptr,
+                                      ckeys, len(keys), L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
+                                      C.byref(out.array), C.byref(out.schema))
+    finally:
+        for h in handles:
+            L.lib().chq_expr_free(h)
+        ls.release()
+        rs.release()
+    return _finish(ctx, rc, out, dev_out)
+
+
 def project_record(fields: Sequence[A.SelectItem], record: Record, table_aliases: Optional[Sequence[Sequence[str]]], *,
                    ctx: Optional[Context] = None, device_result: Optional[bool] = None):
     """RU/record_projection.rs:16-76."""

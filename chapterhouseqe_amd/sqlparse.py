@@ -7,7 +7,8 @@ grammar -- tokens, operator precedence (Or 5 < And 10 < comparison 20 < +,- 30 <
 associativity, `Nested` for parentheses, `Number` text kept verbatim -- for tests, the bench and the
 sample queries (reference: sample_queries/simple.sql) to be written as SQL text.
 
-    select <items> from <func>('<path>') [[as] alias] [where <expr>] [group by <column> {, ...}]
+    select <items> from <func>('<path>') [[as] alias] {[inner] join <func>('<path>') [[as] alias] on <expr>}
+        [where <expr>] [group by <column> {, ...}]
         [order by <expr> [asc|desc] [nulls first|last] {, ...}] [limit <n>]
 """
 from __future__ import annotations
@@ -47,7 +48,8 @@ _BINOPS = {
 }
 _WORD_BINOPS = {"OR": (A.BinaryOperator.Or, _PREC_OR), "AND": (A.BinaryOperator.And, _PREC_AND),
                 "XOR": (A.BinaryOperator.Xor, _PREC_XOR)}
-_STOP_WORDS = {"FROM", "WHERE", "AS", "GROUP", "ORDER", "LIMIT"}
+_STOP_WORDS = {"FROM", "WHERE", "AS", "GROUP", "ORDER", "LIMIT", "JOIN", "INNER", "ON"}
+_OTHER_JOINS = {"LEFT", "RIGHT", "FULL", "OUTER", "CROSS"}
 
 
 class SqlParseError(ValueError):
@@ -63,6 +65,13 @@ class TableFunc:
 
 
 @dataclass(frozen=True)
+class Join:
+    """`[inner] join read_files('glob') alias on <cond>`"""
+    table: TableFunc
+    on: A.Expr
+
+
+@dataclass(frozen=True)
 class Select:
     projection: Tuple[A.SelectItem, ...]
     from_: Optional[TableFunc]
@@ -70,6 +79,7 @@ class Select:
     order_by: Tuple[A.OrderByExpr, ...] = ()
     limit: Optional[int] = None
     group_by: Tuple[A.Expr, ...] = ()
+    joins: Tuple[Join, ...] = ()
 
 
 def _tokenize(text: str) -> List[Tuple[str, str]]:
@@ -248,6 +258,37 @@ class _Parser:
             return A.ExprWithAlias(expr, A.Ident(v))
         return A.UnnamedExpr(expr)
 
+    def reject_other_joins(self) -> None:
+        """LEFT / RIGHT / FULL / OUTER / CROSS in front of JOIN (as an alias elsewhere they are ordinary words)"""
+        j = self.i
+        while j < len(self.toks) and self.toks[j][0] == "word" and self.toks[j][1].upper() in _OTHER_JOINS:
+            j += 1
+        if j > self.i and j < len(self.toks) and self.toks[j][0] == "word" and self.toks[j][1].upper() == "JOIN":
+            kind = " ".join(t[1].upper() for t in self.toks[self.i:j])
+            raise SqlParseError(f"{kind} JOIN is not supported: only INNER JOIN is supported")
+
+    def parse_table_func(self, after: str) -> TableFunc:
+        k, name = self.next()
+        if k != "word":
+            raise SqlParseError(f"expected table function or table name after {after}")
+        args: List[str] = []
+        if self.accept_op("("):
+            while not self.accept_op(")"):
+                kk, vv = self.next()
+                if kk == "eof":
+                    raise SqlParseError("unterminated table function")
+                if kk == "string":
+                    args.append(vv)
+        self.reject_other_joins()
+        alias = None
+        if self.accept_word("AS"):
+            alias = self.next()[1]
+        else:
+            k2, v2 = self.peek()
+            if k2 == "word" and v2.upper() not in _STOP_WORDS:
+                alias = self.next()[1]
+        return TableFunc(name, tuple(args), alias)
+
     def parse_select(self) -> Select:
         if not self.accept_word("SELECT"):
             raise SqlParseError("expected SELECT")
@@ -255,26 +296,20 @@ class _Parser:
         while self.accept_op(","):
             items.append(self.parse_select_item())
         from_ = None
+        joins: List[Join] = []
         if self.accept_word("FROM"):
-            k, name = self.next()
-            if k != "word":
-                raise SqlParseError("expected table function or table name after FROM")
-            args: List[str] = []
-            if self.accept_op("("):
-                while not self.accept_op(")"):
-                    kk, vv = self.next()
-                    if kk == "eof":
-                        raise SqlParseError("unterminated table function")
-                    if kk == "string":
-                        args.append(vv)
-            alias = None
-            if self.accept_word("AS"):
-                alias = self.next()[1]
-            else:
-                k2, v2 = self.peek()
-                if k2 == "word" and v2.upper() not in _STOP_WORDS:
-                    alias = self.next()[1]
-            from_ = TableFunc(name, tuple(args), alias)
+            from_ = self.parse_table_func("FROM")
+            while True:
+                self.reject_other_joins()
+                inner = self.accept_word("INNER")
+                if not self.accept_word("JOIN"):
+                    if inner:
+                        raise SqlParseError(f"expected JOIN after INNER, found {self.peek()[1]!r}")
+                    break
+                table = self.parse_table_func("JOIN")
+                if not self.accept_word("ON"):
+                    raise SqlParseError(f"expected ON after the joined table, found {self.peek()[1]!r}")
+                joins.append(Join(table, self.parse_expr(0)))
         selection = None
         if self.accept_word("WHERE"):
             selection = self.parse_expr(0)
@@ -299,7 +334,7 @@ class _Parser:
                 raise SqlParseError(f"expected a non-negative integer after LIMIT, found {v!r}")
             limit = int(v)
         self.accept_op(";")
-        return Select(tuple(items), from_, selection, tuple(order_by), limit, tuple(group_by))
+        return Select(tuple(items), from_, selection, tuple(order_by), limit, tuple(group_by), tuple(joins))
 
     def parse_order_by_expr(self) -> A.OrderByExpr:
         """sqlparser Parser::parse_order_by_expr"""
@@ -366,6 +401,58 @@ def aggregate_plan(select: Select):
         else:
             raise SqlParseError(f"SELECT item {_expr_text(e)} is neither a GROUP BY key nor an aggregate")
     return keys, tuple(items)
+
+
+# ---- INNER JOIN: the ON condition as key pairs -------------------------------------------------------------
+def join_plan(select: Select):
+    """A `Select` with one `[inner] join ... on <cond>` -> the key pairs `((left column, right column), ...)` as
+    `record_utils.join_records` takes them (None: the statement has no join).  `<cond>` must be a conjunction (AND,
+    parentheses allowed) of `=` between one column qualified with the left table's alias and one qualified with the right
+    table's alias, in either order; the pairs come out as (left, right)."""
+    if not select.joins:
+        return None
+    if len(select.joins) != 1:
+        raise SqlParseError(f"one JOIN per statement is supported, {len(select.joins)} are written")
+    join = select.joins[0]
+    la = select.from_.alias if select.from_ is not None else None
+    ra = join.table.alias
+    if la is None or ra is None:
+        raise SqlParseError("both tables of a JOIN need an alias: the ON condition names its columns through them")
+    if la == ra:
+        raise SqlParseError(f"both tables of the JOIN have the alias {la!r}")
+
+    def side(e: A.Expr) -> Optional[str]:
+        if isinstance(e, A.CompoundIdentifier) and len(e.idents) == 2 and e.idents[0].value in (la, ra):
+            return e.idents[0].value
+        return None
+
+    pairs: List[Tuple[A.Expr, A.Expr]] = []
+
+    def walk(e: A.Expr) -> None:
+        if isinstance(e, A.Nested):
+            walk(e.expr)
+        elif isinstance(e, A.BinaryOp) and e.op == A.BinaryOperator.And:
+            walk(e.left)
+            walk(e.right)
+        elif isinstance(e, A.BinaryOp) and e.op == A.BinaryOperator.Eq and {side(e.left), side(e.right)} == {la, ra}:
+            pairs.append((e.left, e.right) if side(e.left) == la else (e.right, e.left))
+        else:
+            raise SqlParseError(f"the ON condition of an INNER JOIN must be a conjunction of {la}.<column> = {ra}.<column>; "
+                                f"found {_term_text(e)}")
+
+    walk(join.on)
+    return tuple(pairs)
+
+
+def _term_text(e: A.Expr) -> str:
+    if isinstance(e, A.Nested):
+        return f"({_term_text(e.expr)})"
+    if isinstance(e, A.BinaryOp):
+        return f"{_term_text(e.left)} {e.op.value} {_term_text(e.right)}"
+    if isinstance(e, A.ValueExpr):
+        v = e.value
+        return v.text if isinstance(v, A.Number) else repr(v.value) if hasattr(v, "value") else repr(v)
+    return _expr_text(e)
 
 
 def parse_expr(text: str) -> A.Expr:

@@ -439,6 +439,43 @@ chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const struct Arrow
                                  const chq_expr* const* keys, int n_keys, const chq_agg_item* items, int n_items,
                                  int out_device, struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
 
+/* ---- INNER JOIN: sort-merge equi-join of two groups of record batches -----------------------------
+ * The reference has no join; the semantics are derived from what it has: THE RESULT IS EXACTLY WHAT THE REFERENCE'S
+ * filter_record RETURNS ON THE CROSS PRODUCT OF THE TWO INPUTS, LEFT-MAJOR, UNDER `l.k0 = r.k0 AND l.k1 = r.k1 ...`
+ * (whenever the two sides of every key have one type).
+ *   - keys: one or more (left column, right column) pairs, each side a column (Identifier / CompoundIdentifier) resolved
+ *     against its own side's schema and table aliases exactly like a sort key (a missing column: the evaluator's status; any
+ *     other expression: CHQ_ERR_NOT_SUPPORTED).  No key: CHQ_ERR_ARROW_INVALID_ARGUMENT -- there is no cross join.
+ *   - key types: those of ORDER BY, and the two columns of a pair must have the IDENTICAL Arrow C format string (the rule
+ *     the comparisons of temporal and decimal types follow).  Different types (Int32 with Int64, ...): CHQ_ERR_NOT_SUPPORTED
+ *     naming both columns and both types -- the reference would coerce, this build does not.  FixedSizeBinary and other
+ *     types without an order: CHQ_ERR_NOT_SUPPORTED.
+ *   - equality: two non-null values are equal iff their BIT PATTERNS are equal: for floats totalOrder equality (-0 and +0
+ *     differ, NaNs are equal iff their payloads are), for Utf8 equal length and equal bytes, likewise Boolean and Decimal128.
+ *     A NULL KEY NEVER MATCHES ANYTHING, a null included (`=` yields null and the filter drops the row).
+ *   - rows: one per matching (left row, right row) pair, in a guaranteed order: ascending by left row, then by right row;
+ *     the row order of a side is batch order, then row order inside the batch.  Bit-identical from run to run.
+ *   - columns: every left column, then every right column, key columns of both sides included, each with its input field's
+ *     name, type and nullability (duplicate names are allowed: lookups are first-match, aliases disambiguate).  Null counts
+ *     are exact.  Output conventions are those of chq_sort_records: ONE batch, `out_device` ARROW_DEVICE_CPU or
+ *     ARROW_DEVICE_ROCM; on failure nothing is returned (release == NULL).
+ *   - inputs: each side a group of n >= 1 batches of one schema, host or device resident, sliced or empty; each side is
+ *     joined into one batch on the device first.  An empty side: zero rows with the full schema.
+ *   - limits: left rows + right rows < 2^32 and output rows < 2^32 (counted in 64 bits: 65 536 x 65 536 equal keys are
+ *     refused), else CHQ_ERR_NOT_SUPPORTED with the count; a Utf8 column past int32 offsets:
+ *     CHQ_ERR_ARROW_INVALID_ARGUMENT naming it (for the concatenated keys: both key columns).
+ * Out of scope: LEFT / RIGHT / FULL / CROSS joins (the left-major order is chosen so that LEFT can follow), non-equality
+ * conditions, expressions as keys, coercion between key types, partitioned or multi-instance joins. */
+typedef struct chq_join_key {
+  const chq_expr* left;    /* column of the left schema */
+  const chq_expr* right;   /* column of the right schema */
+} chq_join_key;
+chq_status chq_join_records(chq_ctx* ctx, int n_left, const struct ArrowDeviceArray* const* left,
+                            const struct ArrowSchema* left_schema, const chq_table_aliases* left_aliases, int n_right,
+                            const struct ArrowDeviceArray* const* right, const struct ArrowSchema* right_schema,
+                            const chq_table_aliases* right_aliases, const chq_join_key* keys, int n_keys, int out_device,
+                            struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
+
 /* Wrap caller-owned device (or host) buffers as a record batch without copying; the buffers must
  * outlive the returned structs, whose release callbacks free only the descriptors. `format` is an
  * Arrow C format string ("i","f","g","l","b","u", ...). */

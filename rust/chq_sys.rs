@@ -61,6 +61,13 @@ pub struct chq_agg_item {
     pub name: *const c_char,
 }
 
+/// struct chq_join_key: one `left = right` pair of INNER JOIN key columns
+#[repr(C)]
+pub struct chq_join_key {
+    pub left: *const chq_expr,
+    pub right: *const chq_expr,
+}
+
 #[repr(C)]
 pub struct chq_alias_list {
     pub aliases: *const *const c_char,
@@ -193,6 +200,14 @@ extern "C" {
         table_aliases: *const chq_table_aliases, keys: *const *const chq_expr, n_keys: c_int,
         items: *const chq_agg_item, n_items: c_int, out_device: c_int,
         out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
+    ) -> c_int;
+    /// INNER JOIN (sort-merge equi-join) of two groups of batches: one row per matching pair, ascending by left row, then by
+    /// right row; every left column, then every right column
+    pub fn chq_join_records(
+        ctx: *mut chq_ctx, n_left: c_int, left: *const *const ArrowDeviceArray, left_schema: *const FFI_ArrowSchema,
+        left_aliases: *const chq_table_aliases, n_right: c_int, right: *const *const ArrowDeviceArray,
+        right_schema: *const FFI_ArrowSchema, right_aliases: *const chq_table_aliases, keys: *const chq_join_key,
+        n_keys: c_int, out_device: c_int, out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
     ) -> c_int;
     pub fn chq_project_record(
         ctx: *mut chq_ctx, fields: *const chq_select_item, n_fields: c_int, rec: *const ArrowDeviceArray,

@@ -1,0 +1,108 @@
+"""Host reference of INNER JOIN (tests only), plain Python.
+
+A dict from the tuple of the right rows' key BIT PATTERNS to the list of those rows, in input order; then a loop over the
+left rows in input order.  A row with a null in any key is neither entered nor looked up: a null key matches nothing.  The
+bit patterns are read from the raw buffers (as tests/sort_reference.py reads them), so -0 and +0 differ and two NaNs are
+equal iff their payloads are; Utf8 keys are their bytes, Boolean keys their bit.
+
+Keys are `(left column name, right column name)` pairs.  The result rows are ascending by left row, then by right row.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import pyarrow as pa
+
+from . import sort_reference as R
+
+KeyPair = Tuple[str, str]
+
+
+def key_bits(arr: pa.Array) -> List[Optional[object]]:
+    """per row: a hashable holding the value's bits, None for a null"""
+    n = len(arr)
+    if n == 0:
+        return []
+    t = arr.type
+    valid = np.asarray(arr.is_valid().to_numpy(zero_copy_only=False), dtype=bool).tolist()
+    if pa.types.is_boolean(t):
+        bits = np.unpackbits(np.frombuffer(arr.buffers()[1], dtype=np.uint8), bitorder="little")[arr.offset:arr.offset + n].tolist()
+    elif pa.types.is_string(t):
+        offs = np.frombuffer(arr.buffers()[1], dtype=np.int32, count=arr.offset + n + 1)[arr.offset:].tolist()
+        data = arr.buffers()[2].to_pybytes() if arr.buffers()[2] is not None else b""
+        bits = [data[offs[i]:offs[i + 1]] for i in range(n)]
+    elif pa.types.is_decimal(t):
+        assert t.bit_width == 128
+        w = np.frombuffer(arr.buffers()[1], dtype=np.uint64, count=2 * (arr.offset + n))[2 * arr.offset:].reshape(n, 2)
+        bits = [tuple(x) for x in w.tolist()]
+    elif pa.types.is_fixed_size_binary(t) or t.bit_width not in (8, 16, 32, 64):
+        raise TypeError(f"no join key of type {t}")
+    else:
+        bits = R._fixed_raw(arr, t.bit_width // 8).tolist()
+    return [b if v else None for b, v in zip(bits, valid)]
+
+
+def _row_keys(batch: pa.RecordBatch, names: Sequence[str]) -> List[Optional[tuple]]:
+    cols = [key_bits(batch.column(batch.schema.get_field_index(n))) for n in names]
+    out = []
+    for row in zip(*cols):
+        out.append(None if any(x is None for x in row) else tuple(row))
+    return out if cols else [() for _ in range(batch.num_rows)]
+
+
+def join_indices(left: pa.RecordBatch, right: pa.RecordBatch, keys: Sequence[KeyPair]) -> Tuple[List[int], List[int]]:
+    assert keys, "there is no cross join"
+    for lk, rk in keys:
+        lt, rt = left.schema.field(lk).type, right.schema.field(rk).type
+        assert lt == rt, f"key types differ: {lt} vs {rt}"
+    table = {}
+    for j, k in enumerate(_row_keys(right, [rk for _, rk in keys])):
+        if k is not None:
+            table.setdefault(k, []).append(j)
+    lidx, ridx = [], []
+    for i, k in enumerate(_row_keys(left, [lk for lk, _ in keys])):
+        if k is None:
+            continue
+        for j in table.get(k, ()):
+            lidx.append(i)
+            ridx.append(j)
+    return lidx, ridx
+
+
+def take_pairs(left: pa.RecordBatch, right: pa.RecordBatch, lidx: Sequence[int], ridx: Sequence[int]) -> pa.RecordBatch:
+    """every left column at rows `lidx`, then every right column at rows `ridx`; the input fields as they are"""
+    li, ri = pa.array(lidx, type=pa.int64()), pa.array(ridx, type=pa.int64())
+    arrays = [c.take(li) for c in left.columns] + [c.take(ri) for c in right.columns]
+    return pa.RecordBatch.from_arrays(arrays, schema=pa.schema(list(left.schema) + list(right.schema)))
+
+
+def join(left, right, keys: Sequence[KeyPair]):
+    """`left` / `right`: a batch or a sequence of batches -> (lidx, ridx, the joined batch)"""
+    lb = left if isinstance(left, pa.RecordBatch) else R.join(list(left))
+    rb = right if isinstance(right, pa.RecordBatch) else R.join(list(right))
+    lidx, ridx = join_indices(lb, rb, keys)
+    return lidx, ridx, take_pairs(lb, rb, lidx, ridx)
+
+
+def cross_product(left: pa.RecordBatch, right: pa.RecordBatch) -> pa.RecordBatch:
+    """every (left row, right row) pair, left-major"""
+    nl, nr = left.num_rows, right.num_rows
+    return take_pairs(left, right, np.repeat(np.arange(nl), nr).tolist(), np.tile(np.arange(nr), nl).tolist())
+
+
+# ---- the library's argument types <-> the reference's ------------------------------------------------------------------
+def _column_name(e) -> str:
+    from chapterhouseqe_amd import sqlast as A
+    return e.ident.value if isinstance(e, A.Identifier) else e.idents[-1].value
+
+
+def from_plan(keys) -> List[KeyPair]:
+    """`sqlparse.join_plan` output (pairs of column expressions) -> reference keys"""
+    return [(_column_name(l), _column_name(r)) for l, r in keys]
+
+
+def to_plan(keys: Sequence[KeyPair]):
+    """reference keys -> what `record_utils.join_records` takes"""
+    from chapterhouseqe_amd import sqlast as A
+    return [(A.ident(l), A.ident(r)) for l, r in keys]
