@@ -10,6 +10,7 @@
 #include "sort.hpp"
 #include "aggregate.hpp"
 #include "join.hpp"
+#include "partition.hpp"
 #include <atomic>
 
 using namespace chq;
@@ -584,6 +585,45 @@ chq_status chq_join_records(chq_ctx* ctx, int n_left, const ArrowDeviceArray* co
     Batch res = join_records(ctx->c, in_l, left_aliases, in_r, right_aliases, args);
     pt.mark("join");
     finish(ctx->c, std::move(res), out_device, out, out_schema);
+    pt.mark("export");
+  });
+}
+
+// ---- hash partitioning (partition.cpp) -------------------------------------------------------------------------------------
+chq_status chq_partition_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                                 const chq_table_aliases* table_aliases, const chq_expr* const* keys, int n_keys, int n_partitions,
+                                 int out_device, ArrowDeviceArray* outs, ArrowSchema* out_schemas) {
+  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
+  const bool p_ok = n_partitions >= 1 && n_partitions <= kPartMaxPartitions;   // (else the caller's arrays have no known length)
+  if (p_ok) for (int p = 0; p < n_partitions; ++p) mark_released(outs ? &outs[p] : nullptr, out_schemas ? &out_schemas[p] : nullptr);
+  return guarded(ctx, [&] {
+    if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
+    require(recs, "record array");
+    if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative partition key count"};
+    if (n_keys > 0) require(keys, "partition keys");
+    if (!p_ok)
+      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "n_partitions must be in [1, " + std::to_string(kPartMaxPartitions) + "] (" +
+                                                     std::to_string(n_partitions) + " given)"};
+    require(outs, "output arrays"); require(out_schemas, "output schemas");
+    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
+      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    std::vector<const Expr*> key_args((size_t)n_keys);
+    for (int k = 0; k < n_keys; ++k) {
+      require(keys[k], "partition key");
+      key_args[(size_t)k] = &keys[k]->e;
+    }
+    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+    PhaseTimer pt("chq_partition_records");
+    std::vector<Batch> in((size_t)n_records);
+    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
+    for_each_parallel(n_records, [&](int i) { in[(size_t)i] = import_batch(recs[i], schema); });
+    pt.mark("import");
+    JoinedGroup res = partition_records(ctx->c, in, table_aliases, key_args, n_partitions);
+    pt.mark("partition");
+    if (res.ends.size() != (size_t)n_partitions)
+      throw ChqError{CHQ_ERR_DEVICE, "internal error: " + std::to_string(res.ends.size()) + " of " + std::to_string(n_partitions) + " partitions"};
+    if (out_device == ARROW_DEVICE_CPU) res.joined = to_host(ctx->c, res.joined);
+    export_group(std::move(res), out_device, outs, out_schemas);   // every output or none
     pt.mark("export");
   });
 }

@@ -9,7 +9,8 @@
 // of null counts at the end.  DESIGN.md section 3.8.
 //
 // Out of scope: LEFT / RIGHT / FULL / CROSS joins (the left-major output order is chosen so that LEFT can follow),
-// non-equality conditions, expressions as keys, coercion between key types, partitioned or multi-instance joins.
+// non-equality conditions, expressions as keys, coercion between key types.  A call is single-instance: a partitioned or
+// multi-instance join partitions both sides by the keys first (partition.cpp) and makes one call per partition.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -26,20 +27,6 @@ int resolve_join_key(const Expr* e, const char* side, const std::vector<PlanColu
   if (e->kind != Expr::IDENT && e->kind != Expr::COMPOUND)
     throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("a join key must be a column, not ") + (e->text.empty() ? std::string("an expression") : e->text)};
   return resolve_key(*e, pcols, rows);
-}
-
-// the key types of ORDER BY (sort.cpp: key_words)
-bool sortable(const Column& c) {
-  const std::string& f = c.format;
-  switch (c.type) {
-    case T_BOOL: case T_I8: case T_I16: case T_I32: case T_I64: case T_U8: case T_U16: case T_U32: case T_U64:
-    case T_F16: case T_F32: case T_F64: case T_UTF8:
-      return true;
-    case T_FIXED_OPAQUE:
-      return f == "tdD" || f == "tts" || f == "ttm" || f == "tdm" || f == "ttu" || f == "ttn" || f.rfind("ts", 0) == 0 || f.rfind("tD", 0) == 0 ||
-             (f.rfind("d:", 0) == 0 && (c.width <= 8 || c.width == 16));
-    default: return false;
-  }
 }
 
 // The key columns of one side as batches of their own, appended to `out`: zero-copy views under the names both sides share,

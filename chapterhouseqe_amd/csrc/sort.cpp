@@ -79,6 +79,20 @@ std::vector<SortNormParams> key_words(Context& ctx, const Column& c, const SortK
 
 }  // namespace
 
+// the key types of ORDER BY (key_words above), which JOIN and the hash partitioning share
+bool sortable(const Column& c) {
+  const std::string& f = c.format;
+  switch (c.type) {
+    case T_BOOL: case T_I8: case T_I16: case T_I32: case T_I64: case T_U8: case T_U16: case T_U32: case T_U64:
+    case T_F16: case T_F32: case T_F64: case T_UTF8:
+      return true;
+    case T_FIXED_OPAQUE:
+      return f == "tdD" || f == "tts" || f == "ttm" || f == "tdm" || f == "ttu" || f == "ttn" || f.rfind("ts", 0) == 0 || f.rfind("tD", 0) == 0 ||
+             (f.rfind("d:", 0) == 0 && (c.width <= 8 || c.width == 16));
+    default: return false;
+  }
+}
+
 // the column a sort key names: the resolver of compute_value (plan.cpp), which must come back with a bare column
 int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nrows) {
   if (e.kind != Expr::IDENT && e.kind != Expr::COMPOUND)

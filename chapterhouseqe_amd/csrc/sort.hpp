@@ -33,6 +33,8 @@ struct Traffic {
 // The pieces of the sort that GROUP BY (aggregate.cpp) stands on.
 // the column a sort key names: the resolver of compute_value (plan.cpp), which must come back with a bare column
 int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nrows);
+// does the column's type have an order here?  The key types of ORDER BY, JOIN (join.cpp) and the hash partitioning (partition.cpp)
+bool sortable(const Column& c);
 // out row i = in row perm[i] (perm null: identity) for rows [0, m), on the device; a validity bitmap's set bits are added to
 // *ones and the column's null_count left at -1 for the caller to fill in
 Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_t m, uint64_t* ones, Traffic& t);

@@ -216,6 +216,69 @@ def receive_into_exchange(ex, srcs: Sequence[int], ctx=None, device=None) -> int
     return added
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Hash repartition: the one exchange a keyed operator (join, GROUP BY) needs to run on more than one rank.  Every rank cuts
+# its local records into world_size parts by the pinned hash of the key columns (`chq_partition_records`, DESIGN.md section
+# 3.9: the same function of the key bits on every rank and on both sides of a join) and ships part q to rank q.  Afterwards
+# rank p owns every row of the key ranges hashed to p: it joins its left rows with its right rows, or aggregates its rows,
+# and nothing else crosses ranks.
+# ---------------------------------------------------------------------------------------------------------------
+def repartition_records(records, table_aliases, keys, *, ctx=None, partition_fn=None, device=None) -> list:
+    """Every rank calls this with its local `records` (same-schema batches); returns the records this rank now owns, one
+    per source rank, ordered by source rank: all rows whose keys hash to this rank, in (source rank, input order) order.
+
+    `partition_fn(records, table_aliases, keys, n) -> n batches` replaces `record_utils.partition_records` (CPU tests).  A
+    host batch travels by `send_record`, a batch in HBM by `send_device_record`; part `rank` stays local.  With one rank
+    (or no process group) the single part is returned and nothing is sent.
+
+    Schedule (the module's `dist.send` / `dist.recv` are blocking): every rank walks its peers in ASCENDING rank order, and
+    in each pair the LOWER rank sends first and then receives, the higher rank receives first and then sends.  It cannot
+    deadlock: a rank waiting for peer p waits because p is still busy with a peer q that comes before it in p's walk, so
+    following the chain of waits the ranks two steps apart strictly decrease -- no cycle."""
+    import torch.distributed as dist
+    from ..record_utils import DeviceRecordBatch
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    rank = dist.get_rank() if world > 1 else 0
+    if partition_fn is not None:
+        parts = list(partition_fn(records, table_aliases, keys, world))
+    else:
+        from ..record_utils import partition_records
+        parts = partition_records(records, table_aliases, keys, world, ctx=ctx)
+    if len(parts) != world:
+        raise ValueError(f"the partitioning returned {len(parts)} parts for {world} ranks")
+    if world == 1:
+        return parts
+    device = _default_device(device)
+
+    def ship(part, dst):
+        if isinstance(part, DeviceRecordBatch):
+            _send_kind(1, dst, device)
+            send_device_record(part, rank, dst, table_aliases)
+        else:
+            _send_kind(0, dst, device)
+            send_record(part, rank, dst, device, table_aliases)
+
+    def take(src):
+        if _recv_kind(src, device) == 1:
+            if ctx is None:
+                raise ValueError("repartition_records: a batch in HBM arrived and there is no ctx to own it")
+            return recv_device_record(src, ctx)[1]
+        return recv_record(src, device)[1]
+
+    owned = [None] * world
+    owned[rank] = parts[rank]
+    for peer in range(world):
+        if peer == rank:
+            continue
+        if rank < peer:
+            ship(parts[peer], peer)
+            owned[peer] = take(peer)
+        else:
+            owned[peer] = take(peer)
+            ship(parts[peer], peer)
+    return owned
+
+
 def _default_device(device):
     """control tensors must live where the backend can reach them: HBM for nccl (= RCCL), host memory for gloo"""
     import torch

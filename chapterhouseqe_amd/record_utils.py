@@ -998,6 +998,60 @@ def join_records(left, left_aliases: Optional[Sequence[Sequence[str]]], right, r
     return _finish(ctx, rc, out, dev_out)
 
 
+# ------------------------------------------------------------------------------------------ hash partitioning
+def partition_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], keys: Sequence[A.Expr], n_partitions: int, *,
+                      ctx: Optional[Context] = None, device_result: Optional[bool] = None) -> list:
+    """Hash partitioning (`chq_partition_records`): the rows of `recs` (a record, a sequence of same-schema records or a
+    `RecordGroup`) cut into `n_partitions` batches by the pinned hash of the key columns `keys`, so
+    that all rows with equal keys land in the same output.  Output p holds its rows in input order (batch order, then row
+    order); an empty partition is an empty batch with the full schema.  The results are device resident when every input
+    is, unless `device_result` says otherwise."""
+    if isinstance(n_partitions, bool) or not isinstance(n_partitions, int):
+        raise TypeError(f"n_partitions must be an int, not {n_partitions!r}")
+    keys = list(keys)
+    for k in keys:
+        if not isinstance(k, A.Expr):
+            raise TypeError(f"not a key expression: {k!r}")
+    if not isinstance(recs, RecordGroup):
+        recs = [recs] if isinstance(recs, (pa.RecordBatch, DeviceRecordBatch)) else list(recs)
+        if not recs:
+            raise ValueError("partition_records needs at least one record batch")
+        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
+        host_sig = [x for x in sig if isinstance(x, pa.Schema)]
+        dev_sig = [x for x in sig if not isinstance(x, pa.Schema)]
+        if any(x != host_sig[0] for x in host_sig[1:]) or any(x != dev_sig[0] for x in dev_sig[1:]) or \
+                (host_sig and dev_sig and tuple(host_sig[0].names) != dev_sig[0][0]):   # (the C call takes ONE schema for the group)
+            raise ChqError(22, "partition_records: every record batch must have the schema of the first")
+    grp = _JoinSide(recs, ctx, "partitioned")
+    ctx = ctx or grp.ctx
+    dev_out = grp.on_device if device_result is None else device_result
+    al = _Aliases(table_aliases)
+    n_out = max(1, n_partitions)
+    outs = (L.ArrowDeviceArray * n_out)()
+    schemas = (L.ArrowSchema * n_out)()
+    ckeys = (C.c_void_p * max(1, len(keys)))()
+    handles = []
+    try:
+        for i, k in enumerate(keys):
+            handles.append(_expr_to_c(k))
+            ckeys[i] = handles[-1]
+        rc = L.lib().chq_partition_records(ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema), al.ptr, ckeys, len(keys), n_partitions,
+                                           L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, outs, schemas)
+    finally:
+        for h in handles:
+            L.lib().chq_expr_free(h)
+        grp.release()
+    if rc:
+        raise ChqError(rc, ctx.last_error())
+    results = []
+    for i in range(n_partitions):
+        cb = _CBatch()   # struct copy = Arrow "move": the slots of the call arrays are never touched again
+        C.memmove(C.addressof(cb.array), C.addressof(outs[i]), C.sizeof(L.ArrowDeviceArray))
+        C.memmove(C.addressof(cb.schema), C.addressof(schemas[i]), C.sizeof(L.ArrowSchema))
+        results.append(DeviceRecordBatch(ctx, cb) if dev_out else _import_host(cb))
+    return results
+
+
 def project_record(fields: Sequence[A.SelectItem], record: Record, table_aliases: Optional[Sequence[Sequence[str]]], *,
                    ctx: Optional[Context] = None, device_result: Optional[bool] = None):
     """RU/record_projection.rs:16-76."""

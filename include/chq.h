@@ -413,7 +413,7 @@ chq_status chq_sort_records(chq_ctx* ctx, int n_records, const struct ArrowDevic
  *     CHQ_ERR_ARROW_INVALID_ARGUMENT.
  *   - fewer than 2^32 rows per call (else CHQ_ERR_NOT_SUPPORTED).
  * AVG, DISTINCT aggregates, HAVING, expressions as keys or arguments, and partial / merge aggregation across instances are
- * out of scope.  Inputs may be host or device resident and sliced; `out_device` is ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM.
+ * out of scope (the route to several instances is chq_partition_records by the keys: a group lies wholly inside one partition).  Inputs may be host or device resident and sliced; `out_device` is ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM.
  * On failure nothing is returned (release == NULL). */
 typedef enum chq_agg_kind {
   CHQ_AGG_KEY = 0,
@@ -465,7 +465,8 @@ chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const struct Arrow
  *     refused), else CHQ_ERR_NOT_SUPPORTED with the count; a Utf8 column past int32 offsets:
  *     CHQ_ERR_ARROW_INVALID_ARGUMENT naming it (for the concatenated keys: both key columns).
  * Out of scope: LEFT / RIGHT / FULL / CROSS joins (the left-major order is chosen so that LEFT can follow), non-equality
- * conditions, expressions as keys, coercion between key types, partitioned or multi-instance joins. */
+ * conditions, expressions as keys, coercion between key types.  A call is single-instance; the route to a partitioned or
+ * multi-instance join is chq_partition_records on both sides, then one call per partition. */
 typedef struct chq_join_key {
   const chq_expr* left;    /* column of the left schema */
   const chq_expr* right;   /* column of the right schema */
@@ -475,6 +476,45 @@ chq_status chq_join_records(chq_ctx* ctx, int n_left, const struct ArrowDeviceAr
                             const struct ArrowDeviceArray* const* right, const struct ArrowSchema* right_schema,
                             const chq_table_aliases* right_aliases, const chq_join_key* keys, int n_keys, int out_device,
                             struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
+
+/* ---- Hash partitioning of a group of record batches by key columns --------------------------------
+ * The primitive that lets a keyed operator run on more than one instance: the rows of the group are cut into `n_partitions`
+ * batches so that ALL ROWS WITH EQUAL KEYS LAND IN THE SAME OUTPUT.  Rank p then joins partition p of the left input with
+ * partition p of the right, and a GROUP BY group lies wholly inside one partition.
+ *   - input: a group of n >= 1 batches of one schema, host or device resident, sliced or empty; it is joined into one batch
+ *     on the device first, as chq_sort_records does.
+ *   - keys: one or more columns (Identifier / CompoundIdentifier) resolved exactly like a sort key (a missing column: the
+ *     evaluator's status; any other expression: CHQ_ERR_NOT_SUPPORTED).  The key types are those of ORDER BY and JOIN; a type
+ *     without an order (FixedSizeBinary, ...): CHQ_ERR_NOT_SUPPORTED naming the column and its Arrow type.  No key:
+ *     CHQ_ERR_ARROW_INVALID_ARGUMENT.
+ *   - `n_partitions` in [1, 256], else CHQ_ERR_ARROW_INVALID_ARGUMENT (and `outs` is not touched); 2^32 rows or more:
+ *     CHQ_ERR_NOT_SUPPORTED.
+ *   - output: exactly `n_partitions` batches with the input schema (names, types, nullability).  Output p holds the rows
+ *     whose partition id is p, IN INPUT ORDER (batch order, then row order): the split is stable, every row appears exactly
+ *     once, an empty partition is an empty batch with the full schema, and the result is bit-identical from run to run.  All
+ *     outputs are slices of ONE gathered batch and share its buffers (null counts as chq_filter_records gives them: exact for
+ *     a host result, -1 for a device result's nullable columns).  `out_device` is ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM.  On
+ *     failure nothing is returned (release == NULL for every output).
+ *   - THE PARTITION ID IS A PINNED FUNCTION OF THE KEY BITS: every rank, and both sides of a join, compute the same one.
+ *     All arithmetic is mod 2^64.
+ *       fmix64(x):   x ^= x >> 33; x *= 0xFF51AFD7ED558CCD; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53; x ^= x >> 33
+ *       V(null)    = 0
+ *       V(value):    acc = fmix64(L + 1), L the value's byte length (the width of a fixed-width type; 1 for a Boolean, whose
+ *                    value is one byte holding 0 or 1; the string's length for Utf8); then for every 8-byte chunk of the
+ *                    value's bytes (little-endian, the last chunk zero-padded) acc = fmix64(acc ^ chunk).  Decimal128 is two
+ *                    chunks, low word first.  Values are taken BY BITS, as join and group equality take them: -0 and +0 may
+ *                    part, and so may NaNs with different payloads.
+ *       row hash:    h = 0x9E3779B97F4A7C15; for each key in the order given h = fmix64(h * 0x9E3779B97F4A7C15 + V)
+ *       partition id = ((h >> 32) * n_partitions) >> 32
+ *     The Int32 5 and the Int64 5 hash differently: join keys must have identical formats anyway.  Pins (one-key rows, h):
+ *     Int32 0 -> 0092d4ed7de0c088, Int32 1 -> 94e150e41a43b226 (partition 4 of 8, 148 of 256), Utf8 "a" ->
+ *     8fdebbde62f89937, null -> 3836f0681055a942; the full table is in DESIGN.md section 3.9 and tests/test_partition_host.py.
+ *   - chq_ctx_last_stats: rows_in = rows_out = the rows of the group, launches, algorithmic bytes, kernel_ns.
+ * Out of scope: expressions as keys, range partitioning, more than 256 partitions per call. */
+chq_status chq_partition_records(chq_ctx* ctx, int n_records, const struct ArrowDeviceArray* const* recs,
+                                 const struct ArrowSchema* schema, const chq_table_aliases* table_aliases,
+                                 const chq_expr* const* keys, int n_keys, int n_partitions, int out_device,
+                                 struct ArrowDeviceArray* outs, struct ArrowSchema* out_schemas);
 
 /* Wrap caller-owned device (or host) buffers as a record batch without copying; the buffers must
  * outlive the returned structs, whose release callbacks free only the descriptors. `format` is an

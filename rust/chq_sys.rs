@@ -209,6 +209,13 @@ extern "C" {
         right_schema: *const FFI_ArrowSchema, right_aliases: *const chq_table_aliases, keys: *const chq_join_key,
         n_keys: c_int, out_device: c_int, out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
     ) -> c_int;
+    /// hash partitioning by key columns: `n_partitions` (1..=256) batches, equal keys in one output, rows in input order;
+    /// the partition id is the pinned hash of include/chq.h, the same on every rank and on both sides of a join
+    pub fn chq_partition_records(
+        ctx: *mut chq_ctx, n_records: c_int, recs: *const *const ArrowDeviceArray, schema: *const FFI_ArrowSchema,
+        table_aliases: *const chq_table_aliases, keys: *const *const chq_expr, n_keys: c_int, n_partitions: c_int,
+        out_device: c_int, outs: *mut ArrowDeviceArray, out_schemas: *mut FFI_ArrowSchema,
+    ) -> c_int;
     pub fn chq_project_record(
         ctx: *mut chq_ctx, fields: *const chq_select_item, n_fields: c_int, rec: *const ArrowDeviceArray,
         schema: *const FFI_ArrowSchema, table_aliases: *const chq_table_aliases, out_device: c_int,
