@@ -154,7 +154,9 @@ RULES = [
     # numeric::rem says "Overflow or division by zero will result in an error".  The alternative reading (the pre-numeric
     # arithmetic::modulus kernel: zero check + mod_wrapping => MIN % -1 = 0) is what the round-1 review recalled; if a
     # maintainer shows arrow 53.x does that, flip these four `rem` rows to a "value" row with 0 and change
-    # kernels.hip `Interp::arith` / chq_oracle.c INT_ARITH together.
+    # kernels.hip `Interp::arith` / chq_oracle.c INT_ARITH together -- and MIN_REM_NEG1_OVERFLOWS in tests/int_reference.py,
+    # the one constant the exact integer reference and the range-edge suites built on it (tests/test_int_reference.py,
+    # tests/test_gpu_int_edges.py) take this decision from.
     ("i8_min_div_neg1_overflows", batch_min, "error", "m8 / n8", 20),
     ("i16_min_div_neg1_overflows", batch_min, "error", "m16 / n16", 20),
     ("i32_min_div_neg1_overflows", batch_min, "error", "m32 / n32", 20),
