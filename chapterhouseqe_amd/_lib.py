@@ -106,7 +106,7 @@ EXPORTED_SYMBOLS = [
     "chq_parquet_close", "chq_parquet_num_row_groups", "chq_parquet_row_group_num_rows",
     "chq_parquet_describe", "chq_parquet_read_row_group", "chq_parquet_read_row_groups", "chq_record_to_parquet", "chq_records_to_parquet",
     "chq_sort_record", "chq_sort_records", "chq_aggregate_record", "chq_aggregate_records",
-    "chq_join_records", "chq_partition_records",
+    "chq_join_records", "chq_join_records_kind", "chq_partition_records",
 ]
 
 
@@ -197,6 +197,7 @@ def lib():
         "chq_aggregate_record": (ci, [vp, PDA, PS, PTA, C.POINTER(vp), ci, C.POINTER(AggItem), ci, ci, PDA, PS]),
         "chq_aggregate_records": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, C.POINTER(vp), ci, C.POINTER(AggItem), ci, ci, PDA, PS]),
         "chq_join_records": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, ci, C.POINTER(PDA), PS, PTA, C.POINTER(JoinKey), ci, ci, PDA, PS]),
+        "chq_join_records_kind": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, ci, C.POINTER(PDA), PS, PTA, C.POINTER(JoinKey), ci, ci, ci, PDA, PS]),
         "chq_partition_records": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, C.POINTER(vp), ci, ci, ci, PDA, PS]),
     }
     for name, (res, args) in sig.items():

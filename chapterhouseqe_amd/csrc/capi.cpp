@@ -552,11 +552,19 @@ chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const ArrowDeviceA
   return aggregate_call(ctx, n_records, recs, schema, table_aliases, keys, n_keys, items, n_items, out_device, out, out_schema);
 }
 
-// ---- INNER JOIN (join.cpp) ---------------------------------------------------------------------------------------------------
+// ---- JOIN (join.cpp) ---------------------------------------------------------------------------------------------------------
 chq_status chq_join_records(chq_ctx* ctx, int n_left, const ArrowDeviceArray* const* left, const ArrowSchema* left_schema,
                             const chq_table_aliases* left_aliases, int n_right, const ArrowDeviceArray* const* right,
                             const ArrowSchema* right_schema, const chq_table_aliases* right_aliases, const chq_join_key* keys, int n_keys,
                             int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  return chq_join_records_kind(ctx, n_left, left, left_schema, left_aliases, n_right, right, right_schema, right_aliases, keys, n_keys,
+                               CHQ_JOIN_INNER, out_device, out, out_schema);
+}
+
+chq_status chq_join_records_kind(chq_ctx* ctx, int n_left, const ArrowDeviceArray* const* left, const ArrowSchema* left_schema,
+                                 const chq_table_aliases* left_aliases, int n_right, const ArrowDeviceArray* const* right,
+                                 const ArrowSchema* right_schema, const chq_table_aliases* right_aliases, const chq_join_key* keys, int n_keys,
+                                 int kind, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
   if (!ctx) return CHQ_ERR_INVALID_HANDLE;
   mark_released(out, out_schema);
   return guarded(ctx, [&] {
@@ -564,6 +572,8 @@ chq_status chq_join_records(chq_ctx* ctx, int n_left, const ArrowDeviceArray* co
     if (n_left <= 0 || n_right <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch per side is needed"};
     require(left, "left record array"); require(right, "right record array");
     require(left_schema, "left schema"); require(right_schema, "right schema");
+    if (kind < CHQ_JOIN_INNER || kind > CHQ_JOIN_LEFT_ANTI)
+      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "unknown join kind " + std::to_string(kind) + " (a chq_join_kind is expected)"};
     if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative join key count"};
     if (n_keys > 0) require(keys, "join keys");
     if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
@@ -575,14 +585,14 @@ chq_status chq_join_records(chq_ctx* ctx, int n_left, const ArrowDeviceArray* co
       args[(size_t)k].right = &keys[k].right->e;
     }
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    PhaseTimer pt("chq_join_records");
+    PhaseTimer pt("chq_join_records_kind");
     std::vector<Batch> in_l((size_t)n_left), in_r((size_t)n_right);
     for (int i = 0; i < n_left; ++i) require(left[i], "left record");
     for (int i = 0; i < n_right; ++i) require(right[i], "right record");
     for_each_parallel(n_left, [&](int i) { in_l[(size_t)i] = import_batch(left[i], left_schema); });
     for_each_parallel(n_right, [&](int i) { in_r[(size_t)i] = import_batch(right[i], right_schema); });
     pt.mark("import");
-    Batch res = join_records(ctx->c, in_l, left_aliases, in_r, right_aliases, args);
+    Batch res = join_records(ctx->c, in_l, left_aliases, in_r, right_aliases, args, kind);
     pt.mark("join");
     finish(ctx->c, std::move(res), out_device, out, out_schema);
     pt.mark("export");

@@ -1,4 +1,4 @@
-// join.hip -- the INNER JOIN kernels (gfx950, wave64).  Host side: join.cpp; in front of them: the sort (sort.hip) and the
+// join.hip -- the join kernels (gfx950, wave64): INNER, and what LEFT / FULL / LEFT_SEMI / LEFT_ANTI add to it.  Host side: join.cpp; in front of them: the sort (sort.hip) and the
 // group heads of GROUP BY (aggregate.hip) over the concatenated keys, right rows first.
 //
 // A run of equal keys lies in the sorted positions as [right rows in input order][left rows in input order]:
@@ -9,6 +9,14 @@
 //   expand      output j -> left row l = the largest l with off[l] <= j, right row perm[first[l] + (j - off[l])]: a binary
 //               search per output, narrowed to the left rows the tile covers -- O(log nL) at worst whatever the skew, and
 //               no thread walks a run or a gap
+// The other kinds run the same split and scan and replace count and expand by their siblings:
+//   count_kind  the count rule of the kind over c = cnt[l]: max(c, 1) (LEFT, FULL; an unmatched row: first[l] = "no row"),
+//               c > 0 (SEMI), c == 0 (ANTI)
+//   expand_kind as expand; a left row marked "no row" writes ridx[j] = "no row"; SEMI and ANTI write lidx only
+//   tail        FULL: flag[r] = right row r lies in a run with a null key or without left rows (one pass over the sorted
+//               positions), the same scan over the flags, then lidx[M_left + off[r]] = "no row", ridx[...] = r: one writer
+//               per slot
+// INNER launches exactly the kernels it launched before the other kinds existed.
 // Every hand-off happens at a launch boundary: no workgroup waits for another, nothing spins, no atomics, nothing depends on
 // dispatch order.  The result is bit-identical from run to run.
 #include <hip/hip_runtime.h>
@@ -85,6 +93,29 @@ __global__ __launch_bounds__(kJoinBlock) void join_count_kernel(const JoinCountP
     const uint32_t s = p.starts[g];
     p.cnt[l] = p.split[g] - s;
     p.first[l] = s;
+  }
+}
+
+// the same pass with the count rule of an outer, semi or anti join
+__global__ __launch_bounds__(kJoinBlock) void join_count_kind_kernel(const JoinCountKindParams q) {
+  const JoinCountParams& p = q.base;
+  const int64_t p0 = (int64_t)blockIdx.x * kJoinTile + (int64_t)threadIdx.x * kJoinItems;
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k) {
+    const int64_t pos = p0 + k;
+    if (pos >= p.n) continue;
+    const uint32_t row = p.perm ? p.perm[pos] : (uint32_t)pos;
+    if ((int64_t)row < p.n_right) continue;
+    const uint32_t l = row - (uint32_t)p.n_right;
+    const uint32_t g = p.gids[pos];
+    const uint32_t s = p.starts[g];
+    const uint32_t c = p.split[g] - s;
+    if (q.rule == JOIN_COUNT_PADDED) {
+      p.cnt[l] = c ? c : 1u;
+      p.first[l] = c ? s : kJoinNoRow;
+    } else {
+      p.cnt[l] = q.rule == JOIN_COUNT_SEMI ? (c != 0) : (c == 0);
+    }
   }
 }
 
@@ -172,6 +203,61 @@ __global__ __launch_bounds__(kJoinBlock) void join_expand_kernel(const JoinExpan
   }
 }
 
+// kRight: the kinds with right rows (LEFT, FULL); else SEMI and ANTI, whose counts are 0 or 1
+template <bool kRight>
+__global__ __launch_bounds__(kJoinBlock) void join_expand_kind_kernel(const JoinExpandParams p) {
+  __shared__ int64_t bounds[2];
+  const int64_t j0 = (int64_t)blockIdx.x * kJoinTile;
+  const int64_t j1 = p.m - j0 < kJoinTile ? p.m : j0 + kJoinTile;
+  if (threadIdx.x < 2) bounds[threadIdx.x] = last_at_most(p.off, 0, p.n_left - 1, (uint32_t)(threadIdx.x ? j1 - 1 : j0));
+  __syncthreads();
+  const int64_t lo = bounds[0], hi = bounds[1];
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k) {
+    const int64_t j = j0 + (int64_t)k * kJoinBlock + threadIdx.x;
+    if (j >= j1) continue;
+    const int64_t l = last_at_most(p.off, lo, hi, (uint32_t)j);
+    p.lidx[j] = (uint32_t)l;
+    if constexpr (kRight) {
+      const uint32_t f = p.first[l];
+      uint32_t r = kJoinNoRow;
+      if (f != kJoinNoRow) {
+        const int64_t pos = (int64_t)f + (j - (int64_t)p.off[l]);
+        r = p.perm ? p.perm[pos] : (uint32_t)pos;
+      }
+      p.ridx[j] = r;
+    }
+  }
+}
+
+// ---- FULL's tail ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kJoinBlock) void join_tail_flag_kernel(const JoinTailParams p) {
+  const int64_t p0 = (int64_t)blockIdx.x * kJoinTile + (int64_t)threadIdx.x * kJoinItems;
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k) {
+    const int64_t pos = p0 + k;
+    if (pos >= p.n) continue;
+    const uint32_t row = p.perm ? p.perm[pos] : (uint32_t)pos;
+    if ((int64_t)row >= p.n_right) continue;
+    const uint32_t g = p.gids[pos];
+    const uint32_t sp = p.split[g];
+    p.flag[row] = sp == p.starts[g] || sp == p.starts[g + 1];
+  }
+}
+
+__global__ __launch_bounds__(kJoinBlock) void join_tail_write_kernel(const JoinTailParams p) {
+  const int64_t r0 = (int64_t)blockIdx.x * kJoinTile + (int64_t)threadIdx.x * kJoinItems;
+#pragma unroll
+  for (int k = 0; k < kJoinItems; ++k) {
+    const int64_t r = r0 + k;
+    if (r >= p.n_right || !p.flag[r]) continue;
+    const int64_t j = p.m_left + (int64_t)p.off[r];
+    if (j >= p.m) continue;   // (never taken: off[r] < the tail's length)
+    p.lidx[j] = kJoinNoRow;
+    p.ridx[j] = (uint32_t)r;
+  }
+}
+
 unsigned tiles_of(int64_t n) { return (unsigned)((n + kJoinTile - 1) / kJoinTile); }
 
 }  // namespace
@@ -184,6 +270,10 @@ hipError_t launch_join_count(const JoinCountParams& p, hipStream_t stream) {
   hipLaunchKernelGGL(join_count_kernel, dim3(tiles_of(p.n)), dim3(kJoinBlock), 0, stream, p);
   return hipGetLastError();
 }
+hipError_t launch_join_count_kind(const JoinCountKindParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(join_count_kind_kernel, dim3(tiles_of(p.base.n)), dim3(kJoinBlock), 0, stream, p);
+  return hipGetLastError();
+}
 hipError_t launch_join_scan(const JoinScanParams& p, hipStream_t stream) {
   hipLaunchKernelGGL(join_tile_sums_kernel, dim3((unsigned)p.ntiles), dim3(kJoinBlock), 0, stream, p);
   hipLaunchKernelGGL(join_scan_sums_kernel, dim3(1), dim3(kJoinBlock), 0, stream, p);
@@ -192,6 +282,19 @@ hipError_t launch_join_scan(const JoinScanParams& p, hipStream_t stream) {
 }
 hipError_t launch_join_expand(const JoinExpandParams& p, hipStream_t stream) {
   hipLaunchKernelGGL(join_expand_kernel, dim3(tiles_of(p.m)), dim3(kJoinBlock), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_join_expand_kind(const JoinExpandParams& p, bool right, hipStream_t stream) {
+  if (right) hipLaunchKernelGGL(join_expand_kind_kernel<true>, dim3(tiles_of(p.m)), dim3(kJoinBlock), 0, stream, p);
+  else hipLaunchKernelGGL(join_expand_kind_kernel<false>, dim3(tiles_of(p.m)), dim3(kJoinBlock), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_join_tail_flag(const JoinTailParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(join_tail_flag_kernel, dim3(tiles_of(p.n)), dim3(kJoinBlock), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_join_tail_write(const JoinTailParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(join_tail_write_kernel, dim3(tiles_of(p.n_right)), dim3(kJoinBlock), 0, stream, p);
   return hipGetLastError();
 }
 

@@ -104,22 +104,22 @@ int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nro
   return root.col;
 }
 
-// out row i = in row perm[i] (perm null: identity) for rows [0, m), on the device
-Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_t m, uint64_t* ones, Traffic& t) {
+// out row i = in row perm[i] (perm null: identity) for rows [0, m), on the device; pad: perm[i] may be kSortNoRow (a null row)
+Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_t m, uint64_t* ones, Traffic& t, bool pad) {
   Column o;
-  o.name = c.name; o.format = c.format; o.type = c.type; o.width = c.width; o.nullable = c.nullable;
+  o.name = c.name; o.format = c.format; o.type = c.type; o.width = c.width; o.nullable = c.nullable || pad;
   o.length = m; o.offset = 0; o.null_count = 0;
   auto bits = [&](const uint8_t* in, int64_t bit_offset, uint64_t* count) {
     BufferPtr b = make_device_buffer((size_t)((m + 31) / 32) * 4 + 16, ctx.device);
     SortGatherParams g{};
     g.perm = perm; g.m = m; g.in = in; g.in_bit_offset = bit_offset; g.out = (uint8_t*)b->ptr; g.ones = count;
-    if (m > 0) { check_hip(launch_sort_gather_bits(g, ctx.stream), "launch sort_gather_bits_kernel"); ++ctx.stats.launches; }
+    if (m > 0) { check_hip(launch_sort_gather_bits(g, ctx.stream, pad), "launch sort_gather_bits_kernel"); ++ctx.stats.launches; }
     t.read += m * 4 + (m + 7) / 8; t.written += (m + 7) / 8;
     o.owned.push_back(b);
     return (const uint8_t*)b->ptr;
   };
-  if (c.validity && c.null_count != 0) {
-    o.validity = bits(c.validity, c.offset, ones);
+  if (pad || (c.validity && c.null_count != 0)) {   // (pad: the source's bitmap, if it has one, and the padding)
+    o.validity = bits(c.validity && c.null_count != 0 ? c.validity : nullptr, c.offset, ones);
     o.null_count = -1;   // set from `ones` once read back
   }
   if (c.type == T_BOOL) {
@@ -136,7 +136,7 @@ Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_
     } else {
       BufferPtr sums = make_device_buffer((size_t)(g.ntiles + 1) * 8 + 16, ctx.device);
       g.tile_sums = (uint64_t*)sums->ptr;
-      check_hip(launch_sort_utf8_sizes(g, ctx.stream), "launch sort_utf8_tile_sums_kernel");
+      check_hip(launch_sort_utf8_sizes(g, ctx.stream, pad), "launch sort_utf8_tile_sums_kernel");
       ctx.stats.launches += 2;
       uint64_t tot = 0;
       check_hip(hipMemcpyAsync(&tot, g.tile_sums + g.ntiles, 8, hipMemcpyDeviceToHost, ctx.stream), "read back Utf8 bytes");
@@ -148,7 +148,7 @@ Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_
       BufferPtr data = make_device_buffer((size_t)total + 16, ctx.device);
       g.out_data = (uint8_t*)data->ptr;
       o.data = (const uint8_t*)data->ptr; o.owned.push_back(data);
-      check_hip(launch_sort_utf8_copy(g, ctx.stream), "launch sort_utf8_copy_kernel");
+      check_hip(launch_sort_utf8_copy(g, ctx.stream, pad), "launch sort_utf8_copy_kernel");
       ctx.stats.launches += 2;
       t.read += m * 4 * 3 + total; t.written += (m + 1) * 4 + total;
     }
@@ -161,7 +161,7 @@ Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_
     BufferPtr v = make_device_buffer((size_t)(m * c.width) + 16, ctx.device);
     SortGatherParams g{};
     g.perm = perm; g.m = m; g.in = (const uint8_t*)c.values0(); g.out = (uint8_t*)v->ptr; g.width = c.width;
-    if (m > 0) { check_hip(launch_sort_gather_fixed(g, ctx.stream), "launch sort_gather_fixed_kernel"); ++ctx.stats.launches; }
+    if (m > 0) { check_hip(launch_sort_gather_fixed(g, ctx.stream, pad), "launch sort_gather_fixed_kernel"); ++ctx.stats.launches; }
     t.read += m * (4 + c.width); t.written += m * c.width;
     o.values = (const uint8_t*)v->ptr; o.owned.push_back(v);
   }

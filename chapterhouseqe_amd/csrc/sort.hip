@@ -272,6 +272,10 @@ __global__ __launch_bounds__(kSortBlock) void sort_utf8_maxlen_kernel(const Sort
 }
 
 // ---- gathers ---------------------------------------------------------------------------------------------------------------
+// Every gather kernel that reads the row-id list exists in two compile-time variants.  kPad = false: the list holds rows only
+// (ORDER BY, GROUP BY, partitioning, INNER JOIN).  kPad = true: the list may hold kSortNoRow, "no row" (the padded side of an
+// outer join): such an output row is null -- validity bit 0, zero value bytes, Boolean bit 0, Utf8 length 0 -- and nothing of
+// the source is read for it.
 __device__ __forceinline__ uint32_t src_row(const SortGatherParams& p, int64_t i) { return p.perm ? p.perm[i] : (uint32_t)i; }
 
 template <int W>
@@ -279,23 +283,39 @@ struct Word { uint8_t b[W]; };
 template <>
 struct Word<16> { uint64_t lo, hi; };
 
-template <int W>
+template <int W, bool kPad>
 __global__ __launch_bounds__(kSortBlock) void sort_gather_fixed_kernel(const SortGatherParams p) {
   using T = typename std::conditional<W == 1, uint8_t, typename std::conditional<W == 2, uint16_t,
             typename std::conditional<W == 4, uint32_t, typename std::conditional<W == 8, uint64_t, Word<16>>::type>::type>::type>::type;
   const int64_t i = (int64_t)blockIdx.x * kSortBlock + threadIdx.x;
   if (i >= p.m) return;
-  ((T*)p.out)[i] = ((const T*)p.in)[src_row(p, i)];
+  if constexpr (kPad) {
+    const uint32_t r = src_row(p, i);
+    T v{};
+    if (r != kSortNoRow) v = ((const T*)p.in)[r];
+    ((T*)p.out)[i] = v;
+  } else {
+    ((T*)p.out)[i] = ((const T*)p.in)[src_row(p, i)];
+  }
 }
 
-// one output word of 32 bits per thread; set bits counted (null count of a validity bitmap)
+// one output word of 32 bits per thread; set bits counted (null count of a validity bitmap).  kPad: a missing source bitmap
+// (p.in null) is all ones, and "no row" gives a 0 bit.
+template <bool kPad>
 __global__ __launch_bounds__(kSortBlock) void sort_gather_bits_kernel(const SortGatherParams p) {
   const int64_t wi = (int64_t)blockIdx.x * kSortBlock + threadIdx.x;
   uint32_t word = 0;
   if (wi * 32 < p.m) {
     const int64_t i0 = wi * 32;
     const int n = p.m - i0 < 32 ? (int)(p.m - i0) : 32;
-    for (int b = 0; b < n; ++b) word |= (uint32_t)bit_at(p.in, p.in_bit_offset + src_row(p, i0 + b)) << b;
+    if constexpr (kPad) {
+      for (int b = 0; b < n; ++b) {
+        const uint32_t r = src_row(p, i0 + b);
+        word |= (uint32_t)(r != kSortNoRow && (!p.in || bit_at(p.in, p.in_bit_offset + r))) << b;
+      }
+    } else {
+      for (int b = 0; b < n; ++b) word |= (uint32_t)bit_at(p.in, p.in_bit_offset + src_row(p, i0 + b)) << b;
+    }
     ((uint32_t*)p.out)[wi] = word;
   }
   uint64_t ones = (uint64_t)__popc(word);
@@ -304,20 +324,25 @@ __global__ __launch_bounds__(kSortBlock) void sort_gather_bits_kernel(const Sort
   if (p.ones && lane_id() == 0 && ones) atomicAdd((unsigned long long*)p.ones, (unsigned long long)ones);
 }
 
+template <bool kPad>
 __device__ __forceinline__ uint64_t gathered_len(const SortGatherParams& p, int64_t i) {
   if (i >= p.m) return 0;
   const int32_t* offs = (const int32_t*)p.in;
   const uint32_t r = src_row(p, i);
+  if constexpr (kPad) {
+    if (r == kSortNoRow) return 0;
+  }
   return (uint64_t)(uint32_t)(offs[r + 1] - offs[r]);
 }
 
 // Utf8 step 1: bytes of every output tile
+template <bool kPad>
 __global__ __launch_bounds__(kSortBlock) void sort_utf8_tile_sums_kernel(const SortGatherParams p) {
   __shared__ uint64_t sums[kWaves];
   const int64_t at = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kSortItems;
   uint64_t s = 0;
 #pragma unroll
-  for (int k = 0; k < kSortItems; ++k) s += gathered_len(p, at + k);
+  for (int k = 0; k < kSortItems; ++k) s += gathered_len<kPad>(p, at + k);
   uint64_t tot;
   (void)block_exclusive_scan<uint64_t>(s, sums, &tot);
   if (threadIdx.x == 0) p.tile_sums[blockIdx.x] = tot;
@@ -338,12 +363,13 @@ __global__ __launch_bounds__(kSortBlock) void sort_utf8_scan_sums_kernel(const S
 }
 
 // Utf8 step 3: output offsets (the host has checked that the grand total fits int32)
+template <bool kPad>
 __global__ __launch_bounds__(kSortBlock) void sort_utf8_offsets_kernel(const SortGatherParams p) {
   __shared__ uint64_t sums[kWaves];
   const int64_t at = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kSortItems;
   uint64_t len[kSortItems], s = 0;
 #pragma unroll
-  for (int k = 0; k < kSortItems; ++k) { len[k] = gathered_len(p, at + k); s += len[k]; }
+  for (int k = 0; k < kSortItems; ++k) { len[k] = gathered_len<kPad>(p, at + k); s += len[k]; }
   uint64_t tot;
   uint64_t pre = block_exclusive_scan<uint64_t>(s, sums, &tot) + p.tile_sums[blockIdx.x];
   int32_t* out = (int32_t*)p.out;
@@ -356,6 +382,8 @@ __global__ __launch_bounds__(kSortBlock) void sort_utf8_offsets_kernel(const Sor
 }
 
 // Utf8 step 4: bytes.  A lane copies a short string alone; the wave copies each long one together, 64 bytes a step.
+// kPad: "no row" is a string of length 0 and copies nothing.
+template <bool kPad>
 __global__ __launch_bounds__(kSortBlock) void sort_utf8_copy_kernel(const SortGatherParams p) {
   constexpr int kShort = 32;
   const int64_t i = (int64_t)blockIdx.x * kSortBlock + threadIdx.x;
@@ -365,9 +393,17 @@ __global__ __launch_bounds__(kSortBlock) void sort_utf8_copy_kernel(const SortGa
   int64_t src = 0, dst = 0, len = 0;
   if (valid) {
     const uint32_t r = src_row(p, i);
-    src = in_offs[r];
-    len = in_offs[r + 1] - src;
-    dst = out_offs[i];
+    if constexpr (kPad) {
+      if (r != kSortNoRow) {
+        src = in_offs[r];
+        len = in_offs[r + 1] - src;
+        dst = out_offs[i];
+      }
+    } else {
+      src = in_offs[r];
+      len = in_offs[r + 1] - src;
+      dst = out_offs[i];
+    }
   }
   if (valid && len <= kShort)
     for (int64_t b = 0; b < len; ++b) p.out_data[dst + b] = p.in_data[src + b];
@@ -404,30 +440,44 @@ hipError_t launch_sort_utf8_maxlen(const SortMaxLenParams& p, int grid, hipStrea
   hipLaunchKernelGGL(sort_utf8_maxlen_kernel, dim3(g < (unsigned)grid ? g : (unsigned)grid), dim3(kSortBlock), 0, stream, p);
   return hipGetLastError();
 }
-hipError_t launch_sort_gather_fixed(const SortGatherParams& p, hipStream_t stream) {
+template <bool kPad>
+void gather_fixed(const SortGatherParams& p, hipStream_t stream) {
   const dim3 g(blocks_for(p.m, kSortBlock)), b(kSortBlock);
   switch (p.width) {
-    case 1: hipLaunchKernelGGL(sort_gather_fixed_kernel<1>, g, b, 0, stream, p); break;
-    case 2: hipLaunchKernelGGL(sort_gather_fixed_kernel<2>, g, b, 0, stream, p); break;
-    case 4: hipLaunchKernelGGL(sort_gather_fixed_kernel<4>, g, b, 0, stream, p); break;
-    case 8: hipLaunchKernelGGL(sort_gather_fixed_kernel<8>, g, b, 0, stream, p); break;
-    case 16: hipLaunchKernelGGL(sort_gather_fixed_kernel<16>, g, b, 0, stream, p); break;
-    default: return hipErrorInvalidValue;
+    case 1: hipLaunchKernelGGL((sort_gather_fixed_kernel<1, kPad>), g, b, 0, stream, p); break;
+    case 2: hipLaunchKernelGGL((sort_gather_fixed_kernel<2, kPad>), g, b, 0, stream, p); break;
+    case 4: hipLaunchKernelGGL((sort_gather_fixed_kernel<4, kPad>), g, b, 0, stream, p); break;
+    case 8: hipLaunchKernelGGL((sort_gather_fixed_kernel<8, kPad>), g, b, 0, stream, p); break;
+    default: hipLaunchKernelGGL((sort_gather_fixed_kernel<16, kPad>), g, b, 0, stream, p); break;
   }
+}
+hipError_t launch_sort_gather_fixed(const SortGatherParams& p, hipStream_t stream, bool pad) {
+  if (p.width != 1 && p.width != 2 && p.width != 4 && p.width != 8 && p.width != 16) return hipErrorInvalidValue;
+  if (pad) gather_fixed<true>(p, stream);
+  else gather_fixed<false>(p, stream);
   return hipGetLastError();
 }
-hipError_t launch_sort_gather_bits(const SortGatherParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(sort_gather_bits_kernel, dim3(blocks_for(blocks_for(p.m, 32), kSortBlock)), dim3(kSortBlock), 0, stream, p);
+hipError_t launch_sort_gather_bits(const SortGatherParams& p, hipStream_t stream, bool pad) {
+  const dim3 g(blocks_for(blocks_for(p.m, 32), kSortBlock)), b(kSortBlock);
+  if (pad) hipLaunchKernelGGL(sort_gather_bits_kernel<true>, g, b, 0, stream, p);
+  else hipLaunchKernelGGL(sort_gather_bits_kernel<false>, g, b, 0, stream, p);
   return hipGetLastError();
 }
-hipError_t launch_sort_utf8_sizes(const SortGatherParams& p, hipStream_t stream) {   // steps 1 and 2
-  hipLaunchKernelGGL(sort_utf8_tile_sums_kernel, dim3((unsigned)p.ntiles), dim3(kSortBlock), 0, stream, p);
+hipError_t launch_sort_utf8_sizes(const SortGatherParams& p, hipStream_t stream, bool pad) {   // steps 1 and 2
+  if (pad) hipLaunchKernelGGL(sort_utf8_tile_sums_kernel<true>, dim3((unsigned)p.ntiles), dim3(kSortBlock), 0, stream, p);
+  else hipLaunchKernelGGL(sort_utf8_tile_sums_kernel<false>, dim3((unsigned)p.ntiles), dim3(kSortBlock), 0, stream, p);
   hipLaunchKernelGGL(sort_utf8_scan_sums_kernel, dim3(1), dim3(kSortBlock), 0, stream, p);
   return hipGetLastError();
 }
-hipError_t launch_sort_utf8_copy(const SortGatherParams& p, hipStream_t stream) {    // steps 3 and 4
-  hipLaunchKernelGGL(sort_utf8_offsets_kernel, dim3((unsigned)p.ntiles), dim3(kSortBlock), 0, stream, p);
-  hipLaunchKernelGGL(sort_utf8_copy_kernel, dim3(blocks_for(p.m, kSortBlock)), dim3(kSortBlock), 0, stream, p);
+hipError_t launch_sort_utf8_copy(const SortGatherParams& p, hipStream_t stream, bool pad) {    // steps 3 and 4
+  const dim3 g(blocks_for(p.m, kSortBlock)), b(kSortBlock);
+  if (pad) {
+    hipLaunchKernelGGL(sort_utf8_offsets_kernel<true>, dim3((unsigned)p.ntiles), b, 0, stream, p);
+    hipLaunchKernelGGL(sort_utf8_copy_kernel<true>, g, b, 0, stream, p);
+  } else {
+    hipLaunchKernelGGL(sort_utf8_offsets_kernel<false>, dim3((unsigned)p.ntiles), b, 0, stream, p);
+    hipLaunchKernelGGL(sort_utf8_copy_kernel<false>, g, b, 0, stream, p);
+  }
   return hipGetLastError();
 }
 

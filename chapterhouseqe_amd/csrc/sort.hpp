@@ -13,10 +13,10 @@ hipError_t launch_sort_norm(const SortNormParams& p, hipStream_t stream);
 hipError_t launch_sort_hist(const SortHistParams& p, int grid, hipStream_t stream);
 hipError_t launch_sort_pass(const SortPassParams& p, hipStream_t stream);   // count, scan, scatter: 3 launches
 hipError_t launch_sort_utf8_maxlen(const SortMaxLenParams& p, int grid, hipStream_t stream);
-hipError_t launch_sort_gather_fixed(const SortGatherParams& p, hipStream_t stream);
-hipError_t launch_sort_gather_bits(const SortGatherParams& p, hipStream_t stream);
-hipError_t launch_sort_utf8_sizes(const SortGatherParams& p, hipStream_t stream);   // 2 launches
-hipError_t launch_sort_utf8_copy(const SortGatherParams& p, hipStream_t stream);    // 2 launches
+hipError_t launch_sort_gather_fixed(const SortGatherParams& p, hipStream_t stream, bool pad = false);
+hipError_t launch_sort_gather_bits(const SortGatherParams& p, hipStream_t stream, bool pad = false);
+hipError_t launch_sort_utf8_sizes(const SortGatherParams& p, hipStream_t stream, bool pad = false);   // 2 launches
+hipError_t launch_sort_utf8_copy(const SortGatherParams& p, hipStream_t stream, bool pad = false);    // 2 launches
 
 // one ORDER BY key as the C ABI hands it over (chq_sort_key)
 struct SortKeyArg {
@@ -36,8 +36,10 @@ int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nro
 // does the column's type have an order here?  The key types of ORDER BY, JOIN (join.cpp) and the hash partitioning (partition.cpp)
 bool sortable(const Column& c);
 // out row i = in row perm[i] (perm null: identity) for rows [0, m), on the device; a validity bitmap's set bits are added to
-// *ones and the column's null_count left at -1 for the caller to fill in
-Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_t m, uint64_t* ones, Traffic& t);
+// *ones and the column's null_count left at -1 for the caller to fill in.  `pad`: perm may hold kSortNoRow ("no row", the
+// padded side of an outer join): such a row comes out null over zeroed value bytes, and the column nullable with a bitmap,
+// through the padded variants of the kernels -- the kernels of a call with pad = false are the ones without the test.
+Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_t m, uint64_t* ones, Traffic& t, bool pad = false);
 // the permutation of rows [0, n) that orders `rec` by `keys` on the columns `cols` (null: identity -- no key, or fewer than 2 rows)
 BufferPtr sort_permutation(Context& ctx, const Batch& rec, const std::vector<int>& cols, const std::vector<SortKeyArg>& keys, Traffic& t);
 

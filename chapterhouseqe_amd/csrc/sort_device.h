@@ -70,8 +70,10 @@ struct SortMaxLenParams {   // sort_utf8_maxlen_kernel: *out = max byte length o
   uint32_t* out;               // zeroed by the caller
 };
 
+constexpr uint32_t kSortNoRow = 0xFFFFFFFFu;   // "no row" in a row-id list (the padded variants of the gathers; never a row: a call takes fewer than 2^32 - 1)
+
 struct SortGatherParams {   // the final permutation applied to one column: out row i = in row perm[i]
-  const uint32_t* perm;
+  const uint32_t* perm;        // padded variants: an entry may be kSortNoRow, and the output row is then null
   int64_t m;                   // output rows
   const uint8_t* in;           // fixed width: values of row 0; bits: bitmap; Utf8: int32 offsets of row 0
   int64_t in_bit_offset;       // bits: position of row 0

@@ -10,8 +10,8 @@ Reference (OPS = src/handlers/operator_handler/operators):
                                             a blocking single-instance sort over `record_utils.sort_records`
   AggregateOperatorTask / AggregateTask     not in the reference either: GROUP BY, a blocking single-instance aggregation
                                             over `record_utils.aggregate_records`
-  JoinOperatorTask / JoinTask               not in the reference either: INNER JOIN, a blocking single-instance equi-join of
-                                            two inbound exchanges over `record_utils.join_records`
+  JoinOperatorTask / JoinTask               not in the reference either: JOIN (inner, left, right, full, semi, anti), a blocking
+                                            single-instance equi-join of two inbound exchanges over `record_utils.join_records`
 
 The hot loops call `record_utils.filter_record` / `project_record` exactly where the reference does
 (filter_task.rs:99, materialize_files_task.rs:110); here those are the HIP kernels.  The control plane around
@@ -87,10 +87,11 @@ class AggregateOperatorTask:
 
 @dataclasses.dataclass(frozen=True)
 class JoinOperatorTask:
-    """INNER JOIN on the (left column, right column) pairs of the ON condition (`sqlparse.join_plan`); inbound exchange 0
-    is the left input, 1 the right; shaped like AggregateOperatorTask"""
+    """JOIN on the (left column, right column) pairs of the ON condition (`sqlparse.join_plan`); inbound exchange 0
+    is the left input, 1 the right; shaped like AggregateOperatorTask.  `kind` is the `how` of `record_utils.join_records`."""
     keys: Sequence[Any]
     max_rows_per_record: int = 10_000
+    kind: str = "inner"
 
     def task_name(self) -> str:
         return "join"
@@ -476,11 +477,15 @@ class AggregateTaskBuilder(TaskBuilder):
         return run
 
 
-# ---- inner join ---------------------------------------------------------------------------------------------------------
+# ---- join ---------------------------------------------------------------------------------------------------------------
+JOIN_KINDS = ("inner", "left", "right", "full", "semi", "anti")
+
+
 @dataclasses.dataclass(frozen=True)
 class JoinConfig:
     keys: Sequence[Any]
     max_rows_per_record: int = 10_000
+    kind: str = "inner"
 
     @staticmethod
     def try_from(op_in_config: OperatorInstanceConfig) -> "JoinConfig":
@@ -491,18 +496,22 @@ class JoinConfig:
             raise ValueError("a join task needs at least one pair of key columns")
         if t.max_rows_per_record < 1:
             raise ValueError("max_rows_per_record must be at least 1")
-        return JoinConfig(tuple((l, r) for l, r in t.keys), t.max_rows_per_record)
+        if t.kind not in JOIN_KINDS:
+            raise ValueError(f"a join task's kind must be one of {', '.join(JOIN_KINDS)}, not {t.kind!r}")
+        return JoinConfig(tuple((l, r) for l, r in t.keys), t.max_rows_per_record, t.kind)
 
 
 class JoinTask:
     """A blocking, single-instance operator with the protocol of AggregateTask over TWO inbound exchanges (0: the left input,
     1: the right): pulls and holds every record of both sides, joins them with ONE `join_records` call, sends the result
-    (ascending by left row, then by right row) cut into records of at most `max_rows_per_record` rows with record ids 0, 1,
-    2, ... under the table aliases of the left columns followed by those of the right columns, and only then acks both
-    sides.  When either side delivered no record nothing is sent: there is no schema to join with.
+    (in the row order of its kind; inner: ascending by left row, then by right row) cut into records of at most
+    `max_rows_per_record` rows with record ids 0, 1, 2, ... under the table aliases of the left columns followed by those of
+    the right columns (semi and anti: the left columns only), and only then acks both sides.  When either side delivered no
+    record nothing is sent, whatever the kind: there is no schema to join or to pad with.
     Each side has a RecordHandler of its own: a handler reads only its first exchange and tracks by record id, which the two
     exchanges may share.
-    `join_fn(left_records, left_aliases, right_records, right_aliases, keys)` replaces the library call (tests on the CPU)."""
+    `join_fn(left_records, left_aliases, right_records, right_aliases, keys)` replaces the library call (tests on the CPU);
+    for a kind other than "inner" it is called with `kind=` as a keyword on top."""
 
     def __init__(self, op_in_config: OperatorInstanceConfig, config: JoinConfig, inbound_exchanges, outbound_exchange,
                  join_fn=None, ctx=None):
@@ -524,9 +533,12 @@ class JoinTask:
         return self._ctx
 
     def _join_records(self, left, left_aliases, right, right_aliases):
+        kind = self.config.kind
         if self._join is not None:
-            return self._join(left, left_aliases, right, right_aliases, self.config.keys)
-        return record_utils.join_records(left, left_aliases, right, right_aliases, self.config.keys, ctx=self._context())
+            if kind == "inner":
+                return self._join(left, left_aliases, right, right_aliases, self.config.keys)
+            return self._join(left, left_aliases, right, right_aliases, self.config.keys, kind=kind)
+        return record_utils.join_records(left, left_aliases, right, right_aliases, self.config.keys, ctx=self._context(), how=kind)
 
     def async_main(self) -> None:
         handlers = [RecordHandler.initiate(self.operator_instance_config, [ex], self.outbound_exchange) for ex in self.inbound_exchanges]
@@ -542,7 +554,9 @@ class JoinTask:
             if held[0] and held[1]:
                 left_aliases, right_aliases = held[0][0].table_aliases, held[1][0].table_aliases
                 result = self._join_records([h.record for h in held[0]], left_aliases, [h.record for h in held[1]], right_aliases)
-                out_aliases = [list(a) for a in left_aliases] + [list(a) for a in right_aliases]
+                out_aliases = [list(a) for a in left_aliases]
+                if self.config.kind not in ("semi", "anti"):
+                    out_aliases += [list(a) for a in right_aliases]
                 n, step = result.num_rows, self.config.max_rows_per_record
                 for record_id, start in enumerate(range(0, max(n, 1), step)):
                     handlers[0].send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), out_aliases)

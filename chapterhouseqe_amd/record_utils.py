@@ -917,7 +917,10 @@ def aggregate_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], ke
     return _finish(ctx, rc, out, dev_out)
 
 
-# ------------------------------------------------------------------------------------------ INNER JOIN
+# ------------------------------------------------------------------------------------------ JOIN
+_JOIN_KINDS = {"inner": 0, "left": 1, "right": 2, "full": 3, "semi": 4, "anti": 5}   # enum chq_join_kind
+
+
 class _JoinSide:
     """one side of a join as the C call takes it: a pointer array over its batches and their one schema.  `recs` is a
     record, a sequence of records (host and device batches may be mixed) or a prepared `RecordGroup`."""
@@ -959,12 +962,19 @@ class _JoinSide:
 
 
 def join_records(left, left_aliases: Optional[Sequence[Sequence[str]]], right, right_aliases: Optional[Sequence[Sequence[str]]],
-                 keys: Sequence[Tuple[A.Expr, A.Expr]], *, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
-    """INNER JOIN (`chq_join_records`): one row per pair (left row, right row) whose key columns are all non-null and equal
-    by bits, ascending by left row, then by right row; every left column, then every right column.  `left` and `right` are
-    each a record, a sequence of same-schema records or a `RecordGroup`; `keys` is a sequence of (left column, right column)
-    expressions (`sqlparse.join_plan` builds it from a SELECT).  The result is device resident when every input is, unless
-    `device_result` says otherwise."""
+                 keys: Sequence[Tuple[A.Expr, A.Expr]], *, ctx: Optional[Context] = None, device_result: Optional[bool] = None,
+                 how: str = "inner"):
+    """JOIN (`chq_join_records_kind`).  `how="inner"`: one row per pair (left row, right row) whose key columns are all
+    non-null and equal by bits, ascending by left row, then by right row; every left column, then every right column.
+    `"left"`: the same, and a left row without a pair gives one row whose right columns are null; `"right"`: that with the
+    sides exchanged (ascending by right row, then by left row; columns still left, then right); `"full"`: the rows of
+    `"left"`, then the right rows without a pair, ascending, under null left columns; `"semi"` / `"anti"`: the left rows with
+    / without a pair (a null key has none), once, ascending, left columns only.  The fields of a padded side come out
+    nullable.  Any other `how`: ValueError.  `left` and `right` are each a record, a sequence of same-schema records or a
+    `RecordGroup`; `keys` is a sequence of (left column, right column) expressions (`sqlparse.join_plan` builds it from a
+    SELECT).  The result is device resident when every input is, unless `device_result` says otherwise."""
+    if not isinstance(how, str) or how not in _JOIN_KINDS:
+        raise ValueError(f"join_records: how must be one of {', '.join(map(repr, _JOIN_KINDS))}, not {how!r}")
     keys = list(keys)
     for pair in keys:
         if not (isinstance(pair, (tuple, list)) and len(pair) == 2):
@@ -987,9 +997,9 @@ def join_records(left, left_aliases: Optional[Sequence[Sequence[str]]], right, r
                 h = _expr_to_c(e)
                 handles.append(h)
                 setattr(ckeys[i], side, h)
-        rc = L.lib().chq_join_records(ctx.handle, ls.n, ls.ptrs, C.byref(ls.schema), lal.ptr, rs.n, rs.ptrs, C.byref(rs.schema), ral.ptr,
-                                      ckeys, len(keys), L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
-                                      C.byref(out.array), C.byref(out.schema))
+        rc = L.lib().chq_join_records_kind(ctx.handle, ls.n, ls.ptrs, C.byref(ls.schema), lal.ptr, rs.n, rs.ptrs, C.byref(rs.schema),
+                                           ral.ptr, ckeys, len(keys), _JOIN_KINDS[how],
+                                           L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, C.byref(out.array), C.byref(out.schema))
     finally:
         for h in handles:
             L.lib().chq_expr_free(h)

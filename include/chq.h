@@ -439,34 +439,60 @@ chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const struct Arrow
                                  const chq_expr* const* keys, int n_keys, const chq_agg_item* items, int n_items,
                                  int out_device, struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
 
-/* ---- INNER JOIN: sort-merge equi-join of two groups of record batches -----------------------------
- * The reference has no join; the semantics are derived from what it has: THE RESULT IS EXACTLY WHAT THE REFERENCE'S
- * filter_record RETURNS ON THE CROSS PRODUCT OF THE TWO INPUTS, LEFT-MAJOR, UNDER `l.k0 = r.k0 AND l.k1 = r.k1 ...`
- * (whenever the two sides of every key have one type).
+/* ---- JOIN: sort-merge equi-join of two groups of record batches -----------------------------------
+ * The reference has no join; the semantics of INNER are derived from what it has: THE RESULT IS EXACTLY WHAT THE
+ * REFERENCE'S filter_record RETURNS ON THE CROSS PRODUCT OF THE TWO INPUTS, LEFT-MAJOR, UNDER
+ * `l.k0 = r.k0 AND l.k1 = r.k1 ...` (whenever the two sides of every key have one type).  The other kinds are defined on
+ * top of INNER.  For every kind:
  *   - keys: one or more (left column, right column) pairs, each side a column (Identifier / CompoundIdentifier) resolved
  *     against its own side's schema and table aliases exactly like a sort key (a missing column: the evaluator's status; any
  *     other expression: CHQ_ERR_NOT_SUPPORTED).  No key: CHQ_ERR_ARROW_INVALID_ARGUMENT -- there is no cross join.
  *   - key types: those of ORDER BY, and the two columns of a pair must have the IDENTICAL Arrow C format string (the rule
  *     the comparisons of temporal and decimal types follow).  Different types (Int32 with Int64, ...): CHQ_ERR_NOT_SUPPORTED
- *     naming both columns and both types -- the reference would coerce, this build does not.  FixedSizeBinary and other
- *     types without an order: CHQ_ERR_NOT_SUPPORTED.
+ *     naming both columns and both types, the caller's left first -- the reference would coerce, this build does not.
+ *     FixedSizeBinary and other types without an order: CHQ_ERR_NOT_SUPPORTED.
  *   - equality: two non-null values are equal iff their BIT PATTERNS are equal: for floats totalOrder equality (-0 and +0
  *     differ, NaNs are equal iff their payloads are), for Utf8 equal length and equal bytes, likewise Boolean and Decimal128.
  *     A NULL KEY NEVER MATCHES ANYTHING, a null included (`=` yields null and the filter drops the row).
- *   - rows: one per matching (left row, right row) pair, in a guaranteed order: ascending by left row, then by right row;
- *     the row order of a side is batch order, then row order inside the batch.  Bit-identical from run to run.
- *   - columns: every left column, then every right column, key columns of both sides included, each with its input field's
- *     name, type and nullability (duplicate names are allowed: lookups are first-match, aliases disambiguate).  Null counts
- *     are exact.  Output conventions are those of chq_sort_records: ONE batch, `out_device` ARROW_DEVICE_CPU or
- *     ARROW_DEVICE_ROCM; on failure nothing is returned (release == NULL).
  *   - inputs: each side a group of n >= 1 batches of one schema, host or device resident, sliced or empty; each side is
- *     joined into one batch on the device first.  An empty side: zero rows with the full schema.
+ *     joined into one batch on the device first.  The row order of a side is batch order, then row order inside the batch.
  *   - limits: left rows + right rows < 2^32 and output rows < 2^32 (counted in 64 bits: 65 536 x 65 536 equal keys are
  *     refused), else CHQ_ERR_NOT_SUPPORTED with the count; a Utf8 column past int32 offsets:
  *     CHQ_ERR_ARROW_INVALID_ARGUMENT naming it (for the concatenated keys: both key columns).
- * Out of scope: LEFT / RIGHT / FULL / CROSS joins (the left-major order is chosen so that LEFT can follow), non-equality
- * conditions, expressions as keys, coercion between key types.  A call is single-instance; the route to a partitioned or
- * multi-instance join is chq_partition_records on both sides, then one call per partition. */
+ *   - output conventions are those of chq_sort_records: ONE batch, `out_device` ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM; on
+ *     failure nothing is returned (release == NULL).  The result is bit-identical from run to run.  Every result has the
+ *     full schema of its kind, a result of zero rows too.  chq_ctx_last_stats: rows_in = left rows + right rows, rows_out =
+ *     the rows returned.
+ * The rows and columns per kind; matches(l) = the right rows whose keys all equal those of left row l, ascending (none for a
+ * left row with a null key):
+ *   CHQ_JOIN_INNER      one row per pair (l, r), r in matches(l), ascending by left row, then by right row.  Every left
+ *                       column, then every right column, key columns of both sides included, each with its input field's
+ *                       name, type and nullability (duplicate names are allowed: lookups are first-match, aliases
+ *                       disambiguate).  An empty side: zero rows.
+ *   CHQ_JOIN_LEFT       for each left row ascending: its pairs ascending by right row, or -- it has none -- ONE row whose
+ *                       right columns are all null.  Columns as INNER.  No right rows: every left row padded.
+ *   CHQ_JOIN_RIGHT      exactly LEFT with the sides exchanged: ascending by right row, then by left row; an unmatched right
+ *                       row carries null left columns.  The columns are still left, then right.
+ *   CHQ_JOIN_FULL       the rows of LEFT, then every right row that matches no left row, ascending by right row, with every
+ *                       left column null.  An empty left side: every right row padded.
+ *   CHQ_JOIN_LEFT_SEMI  every left row with at least one match, once, ascending.  Left columns only.
+ *   CHQ_JOIN_LEFT_ANTI  every left row with no match, once, ascending -- a left row with a null key among them: this is
+ *                       NOT EXISTS, not NOT IN.  Left columns only.  No right rows: every left row.
+ *   - padding: the fields of a padded side (the right of LEFT, the left of RIGHT, both of FULL) come out NULLABLE whatever
+ *     the input field said; all other fields keep their input nullability.  The slot under a padded null is deterministic:
+ *     zero bytes for a fixed width, a 0 bit for Boolean, length 0 for Utf8.  Null counts are exact for every column: the
+ *     source's own nulls plus the padding.
+ * Out of scope: CROSS joins, non-equality conditions, expressions as keys, coercion between key types.  A call is
+ * single-instance; the route to a partitioned or multi-instance join is chq_partition_records on both sides, then one call
+ * per partition (for every kind: equal keys share a partition, and a row without a match has none in any other). */
+typedef enum chq_join_kind {
+  CHQ_JOIN_INNER = 0,
+  CHQ_JOIN_LEFT = 1,
+  CHQ_JOIN_RIGHT = 2,
+  CHQ_JOIN_FULL = 3,
+  CHQ_JOIN_LEFT_SEMI = 4,
+  CHQ_JOIN_LEFT_ANTI = 5
+} chq_join_kind;
 typedef struct chq_join_key {
   const chq_expr* left;    /* column of the left schema */
   const chq_expr* right;   /* column of the right schema */
@@ -475,7 +501,13 @@ chq_status chq_join_records(chq_ctx* ctx, int n_left, const struct ArrowDeviceAr
                             const struct ArrowSchema* left_schema, const chq_table_aliases* left_aliases, int n_right,
                             const struct ArrowDeviceArray* const* right, const struct ArrowSchema* right_schema,
                             const chq_table_aliases* right_aliases, const chq_join_key* keys, int n_keys, int out_device,
-                            struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
+                            struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);   /* kind CHQ_JOIN_INNER */
+/* `kind`: a chq_join_kind; any other value: CHQ_ERR_ARROW_INVALID_ARGUMENT */
+chq_status chq_join_records_kind(chq_ctx* ctx, int n_left, const struct ArrowDeviceArray* const* left,
+                                 const struct ArrowSchema* left_schema, const chq_table_aliases* left_aliases, int n_right,
+                                 const struct ArrowDeviceArray* const* right, const struct ArrowSchema* right_schema,
+                                 const chq_table_aliases* right_aliases, const chq_join_key* keys, int n_keys, int kind,
+                                 int out_device, struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
 
 /* ---- Hash partitioning of a group of record batches by key columns --------------------------------
  * The primitive that lets a keyed operator run on more than one instance: the rows of the group are cut into `n_partitions`

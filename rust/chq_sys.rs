@@ -61,7 +61,7 @@ pub struct chq_agg_item {
     pub name: *const c_char,
 }
 
-/// struct chq_join_key: one `left = right` pair of INNER JOIN key columns
+/// struct chq_join_key: one `left = right` pair of JOIN key columns
 #[repr(C)]
 pub struct chq_join_key {
     pub left: *const chq_expr,
@@ -208,6 +208,14 @@ extern "C" {
         left_aliases: *const chq_table_aliases, n_right: c_int, right: *const *const ArrowDeviceArray,
         right_schema: *const FFI_ArrowSchema, right_aliases: *const chq_table_aliases, keys: *const chq_join_key,
         n_keys: c_int, out_device: c_int, out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
+    ) -> c_int;
+    /// the same with a join kind (enum chq_join_kind: 0 INNER, 1 LEFT, 2 RIGHT, 3 FULL, 4 LEFT_SEMI, 5 LEFT_ANTI): the fields
+    /// of a padded side come out nullable; LEFT_SEMI and LEFT_ANTI return the left columns only
+    pub fn chq_join_records_kind(
+        ctx: *mut chq_ctx, n_left: c_int, left: *const *const ArrowDeviceArray, left_schema: *const FFI_ArrowSchema,
+        left_aliases: *const chq_table_aliases, n_right: c_int, right: *const *const ArrowDeviceArray,
+        right_schema: *const FFI_ArrowSchema, right_aliases: *const chq_table_aliases, keys: *const chq_join_key,
+        n_keys: c_int, kind: c_int, out_device: c_int, out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
     ) -> c_int;
     /// hash partitioning by key columns: `n_partitions` (1..=256) batches, equal keys in one output, rows in input order;
     /// the partition id is the pinned hash of include/chq.h, the same on every rank and on both sides of a join
