@@ -85,6 +85,10 @@ class AggItem(C.Structure):
     _fields_ = [("kind", C.c_int), ("key_index", C.c_int), ("column", C.c_void_p), ("name", C.c_char_p)]
 
 
+class WindowItem(C.Structure):
+    _fields_ = [("kind", C.c_int), ("frame", C.c_int), ("offset", C.c_int64), ("column", C.c_void_p), ("name", C.c_char_p)]
+
+
 class JoinKey(C.Structure):
     _fields_ = [("left", C.c_void_p), ("right", C.c_void_p)]
 
@@ -106,6 +110,7 @@ EXPORTED_SYMBOLS = [
     "chq_parquet_close", "chq_parquet_num_row_groups", "chq_parquet_row_group_num_rows",
     "chq_parquet_describe", "chq_parquet_read_row_group", "chq_parquet_read_row_groups", "chq_record_to_parquet", "chq_records_to_parquet",
     "chq_sort_record", "chq_sort_records", "chq_aggregate_record", "chq_aggregate_records",
+    "chq_window_record", "chq_window_records",
     "chq_join_records", "chq_join_records_kind", "chq_partition_records",
 ]
 
@@ -196,6 +201,9 @@ def lib():
         "chq_sort_records": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, C.POINTER(SortKey), ci, i64, ci, PDA, PS]),
         "chq_aggregate_record": (ci, [vp, PDA, PS, PTA, C.POINTER(vp), ci, C.POINTER(AggItem), ci, ci, PDA, PS]),
         "chq_aggregate_records": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, C.POINTER(vp), ci, C.POINTER(AggItem), ci, ci, PDA, PS]),
+        "chq_window_record": (ci, [vp, PDA, PS, PTA, C.POINTER(vp), ci, C.POINTER(SortKey), ci, C.POINTER(WindowItem), ci, ci, PDA, PS]),
+        "chq_window_records": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, C.POINTER(vp), ci, C.POINTER(SortKey), ci, C.POINTER(WindowItem), ci, ci,
+                               PDA, PS]),
         "chq_join_records": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, ci, C.POINTER(PDA), PS, PTA, C.POINTER(JoinKey), ci, ci, PDA, PS]),
         "chq_join_records_kind": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, ci, C.POINTER(PDA), PS, PTA, C.POINTER(JoinKey), ci, ci, ci, PDA, PS]),
         "chq_partition_records": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, C.POINTER(vp), ci, ci, ci, PDA, PS]),

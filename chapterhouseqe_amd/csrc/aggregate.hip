@@ -13,32 +13,13 @@
 // order.  No float atomics: a float sum is combined in an order fixed by the sorted positions, bit-identical from run to run.
 #include <hip/hip_runtime.h>
 
+#include "aggregate_acc.h"
 #include "aggregate_device.h"
 
 namespace chq {
 namespace {
 
 constexpr int kWaves = kAggBlock / 64;
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
-__device__ __forceinline__ bool bit_at(const uint8_t* bits, int64_t pos) { return (bits[pos >> 3] >> (pos & 7)) & 1; }
-
-__device__ __forceinline__ uint64_t load_uint(const uint8_t* values, uint32_t r, int width) {
-  switch (width) {
-    case 1: return values[r];
-    case 2: return ((const uint16_t*)values)[r];
-    case 4: return ((const uint32_t*)values)[r];
-    default: return ((const uint64_t*)values)[r];
-  }
-}
-__device__ __forceinline__ int64_t load_int(const uint8_t* values, uint32_t r, int width) {
-  switch (width) {
-    case 1: return ((const int8_t*)values)[r];
-    case 2: return ((const int16_t*)values)[r];
-    case 4: return ((const int32_t*)values)[r];
-    default: return ((const int64_t*)values)[r];
-  }
-}
 
 // sum of every thread's v over the workgroup (256 threads)
 __device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* wave_sums) {
@@ -164,120 +145,6 @@ __global__ __launch_bounds__(kAggBlock) void agg_head_write_kernel(const AggGrou
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) p.starts[p.G] = (uint32_t)p.n;
-}
-
-// ---- accumulators ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double as_double(uint64_t u) { return __longlong_as_double((long long)u); }
-__device__ __forceinline__ uint64_t as_bits(double d) { return (uint64_t)__double_as_longlong(d); }
-
-template <int OP>
-__device__ __forceinline__ AggAcc acc_identity() {
-  AggAcc x{0, 0, 0};
-  if (OP == AO_SUM_FLOAT) x.a = 1ull << 63;   // -0.0: v + -0.0 == v for every v, -0.0 and +0.0 included
-  if (OP == AO_MIN) x.a = ~0ull;
-  return x;
-}
-
-// x covers earlier sorted positions than y
-template <int OP>
-__device__ __forceinline__ AggAcc acc_combine(const AggAcc& x, const AggAcc& y) {
-  AggAcc r;
-  r.cnt = x.cnt + y.cnt;
-  r.b = 0;
-  if (OP == AO_SUM_INT) {
-    r.a = x.a + y.a;
-    r.b = x.b + y.b + (r.a < x.a ? 1 : 0);
-  } else if (OP == AO_SUM_FLOAT) {
-    r.a = as_bits(as_double(x.a) + as_double(y.a));
-  } else if (OP == AO_MIN) {
-    r.a = x.a < y.a ? x.a : y.a;
-  } else if (OP == AO_MAX) {
-    r.a = x.a > y.a ? x.a : y.a;
-  } else {
-    r.a = 0;
-  }
-  return r;
-}
-
-template <int OP>
-__device__ __forceinline__ AggAcc acc_load(const AggReduceParams& p, int64_t pos) {
-  const uint32_t r = p.perm ? p.perm[pos] : (uint32_t)pos;
-  if (p.validity && !bit_at(p.validity, p.bit_offset + r)) return acc_identity<OP>();
-  AggAcc x{0, 0, 1};
-  if (OP == AO_SUM_INT) {
-    if (p.value_kind == AV_SIGNED) {
-      const int64_t v = load_int(p.values, r, p.width);
-      x.a = (uint64_t)v;
-      x.b = v < 0 ? ~0ull : 0ull;
-    } else {
-      x.a = load_uint(p.values, r, p.width);
-    }
-  } else if (OP == AO_SUM_FLOAT) {
-    x.a = as_bits(p.width == 4 ? (double)((const float*)p.values)[r] : ((const double*)p.values)[r]);   // Float32 widens exactly
-  } else if (OP == AO_MIN || OP == AO_MAX) {
-    if (p.value_kind == AV_SIGNED) {
-      x.a = (uint64_t)load_int(p.values, r, p.width) ^ (1ull << 63);
-    } else if (p.value_kind == AV_UNSIGNED) {
-      x.a = load_uint(p.values, r, p.width);
-    } else {   // totalOrder: sign set -> every bit inverted, else the sign bit set
-      const int bits = 8 * p.width;
-      const uint64_t u = load_uint(p.values, r, p.width);
-      const uint64_t sign = 1ull << (bits - 1), mask = bits == 64 ? ~0ull : (1ull << bits) - 1;
-      x.a = (u & sign) ? (~u & mask) : (u | sign);
-    }
-  }
-  return x;
-}
-
-// the finished accumulator of group g -> its output value
-template <int OP>
-__device__ __forceinline__ void acc_finalize(const AggReduceParams& p, uint32_t g, const AggAcc& acc) {
-  if (OP == AO_COUNT) {
-    ((int64_t*)p.out)[g] = (int64_t)acc.cnt;
-    return;
-  }
-  p.cnt_out[g] = acc.cnt;
-  if (OP == AO_SUM_INT) {
-    const bool fits = p.value_kind == AV_SIGNED ? acc.b == ((acc.a >> 63) ? ~0ull : 0ull) : acc.b == 0;
-    if (!fits) atomicOr(p.overflow, 1u);
-    ((uint64_t*)p.out)[g] = acc.a;
-  } else if (OP == AO_SUM_FLOAT) {
-    ((uint64_t*)p.out)[g] = acc.cnt ? acc.a : 0;
-  } else {
-    uint64_t u = 0;
-    if (acc.cnt) {
-      if (p.value_kind == AV_SIGNED) {
-        u = acc.a ^ (1ull << 63);
-      } else if (p.value_kind == AV_UNSIGNED) {
-        u = acc.a;
-      } else {
-        const int bits = 8 * p.width;
-        const uint64_t sign = 1ull << (bits - 1), mask = bits == 64 ? ~0ull : (1ull << bits) - 1;
-        u = (acc.a & sign) ? (acc.a & ~sign) : (~acc.a & mask);
-      }
-    }
-    switch (p.width) {
-      case 1: p.out[g] = (uint8_t)u; break;
-      case 2: ((uint16_t*)p.out)[g] = (uint16_t)u; break;
-      case 4: ((uint32_t*)p.out)[g] = (uint32_t)u; break;
-      default: ((uint64_t*)p.out)[g] = u; break;
-    }
-  }
-}
-
-__device__ __forceinline__ AggAcc shfl_up_acc(const AggAcc& x, int o) {
-  AggAcc y;
-  y.a = __shfl_up((unsigned long long)x.a, (unsigned)o, 64);
-  y.b = __shfl_up((unsigned long long)x.b, (unsigned)o, 64);
-  y.cnt = __shfl_up((unsigned long long)x.cnt, (unsigned)o, 64);
-  return y;
-}
-__device__ __forceinline__ AggAcc shfl_down_acc(const AggAcc& x, int o) {
-  AggAcc y;
-  y.a = __shfl_down((unsigned long long)x.a, (unsigned)o, 64);
-  y.b = __shfl_down((unsigned long long)x.b, (unsigned)o, 64);
-  y.cnt = __shfl_down((unsigned long long)x.cnt, (unsigned)o, 64);
-  return y;
 }
 
 // ---- segmented reduce -------------------------------------------------------------------------------------------------------

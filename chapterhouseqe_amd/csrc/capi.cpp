@@ -9,6 +9,7 @@
 #include "parquet.hpp"
 #include "sort.hpp"
 #include "aggregate.hpp"
+#include "window.hpp"
 #include "join.hpp"
 #include "partition.hpp"
 #include <atomic>
@@ -550,6 +551,77 @@ chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const ArrowDeviceA
                                  const chq_table_aliases* table_aliases, const chq_expr* const* keys, int n_keys,
                                  const chq_agg_item* items, int n_items, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
   return aggregate_call(ctx, n_records, recs, schema, table_aliases, keys, n_keys, items, n_items, out_device, out, out_schema);
+}
+
+// ---- window functions (window.cpp) -----------------------------------------------------------------------------------------
+namespace {
+chq_status window_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                       const chq_table_aliases* table_aliases, const chq_expr* const* partition_by, int n_partition_by,
+                       const chq_sort_key* order_by, int n_order_by, const chq_window_item* items, int n_items, int out_device,
+                       ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
+  mark_released(out, out_schema);
+  return guarded(ctx, [&] {
+    require(out, "output array"); require(out_schema, "output schema");
+    if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
+    require(recs, "record array");
+    if (n_partition_by < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative PARTITION BY key count"};
+    if (n_partition_by > 0) require(partition_by, "PARTITION BY keys");
+    if (n_order_by < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative ORDER BY key count"};
+    if (n_order_by > 0) require(order_by, "ORDER BY keys");
+    if (n_items <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "a window call needs at least one item"};
+    require(items, "window items");
+    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
+      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    std::vector<const Expr*> part_args((size_t)n_partition_by);
+    for (int k = 0; k < n_partition_by; ++k) {
+      require(partition_by[k], "PARTITION BY key");
+      part_args[(size_t)k] = &partition_by[k]->e;
+    }
+    std::vector<SortKeyArg> order_args((size_t)n_order_by);
+    for (int k = 0; k < n_order_by; ++k) {
+      require(order_by[k].column, "ORDER BY key column");
+      order_args[(size_t)k].column = &order_by[k].column->e;
+      order_args[(size_t)k].descending = order_by[k].descending != 0;
+      order_args[(size_t)k].nulls_first = order_by[k].nulls_first != 0;
+    }
+    std::vector<WinItemArg> item_args((size_t)n_items);
+    for (int i = 0; i < n_items; ++i) {
+      WinItemArg& a = item_args[(size_t)i];
+      a.kind = items[i].kind; a.frame = items[i].frame; a.offset = items[i].offset;
+      a.column = items[i].column ? &items[i].column->e : nullptr;
+      require(items[i].name, "output column name");
+      a.name = items[i].name;
+    }
+    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+    PhaseTimer pt("chq_window_records");
+    std::vector<Batch> in((size_t)n_records);
+    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
+    for_each_parallel(n_records, [&](int i) { in[(size_t)i] = import_batch(recs[i], schema); });
+    pt.mark("import");
+    Batch res = window_records(ctx->c, in, table_aliases, part_args, order_args, item_args);
+    pt.mark("window");
+    finish(ctx->c, std::move(res), out_device, out, out_schema);
+    pt.mark("export");
+  });
+}
+}  // namespace
+
+chq_status chq_window_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, const chq_table_aliases* table_aliases,
+                             const chq_expr* const* partition_by, int n_partition_by, const chq_sort_key* order_by, int n_order_by,
+                             const chq_window_item* items, int n_items, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  const ArrowDeviceArray* recs[1] = {rec};
+  if (!rec) { if (!ctx) return CHQ_ERR_INVALID_HANDLE; mark_released(out, out_schema); ctx->c.last_error = "null record"; return CHQ_ERR_INVALID_HANDLE; }
+  return window_call(ctx, 1, recs, schema, table_aliases, partition_by, n_partition_by, order_by, n_order_by, items, n_items, out_device, out,
+                     out_schema);
+}
+
+chq_status chq_window_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                              const chq_table_aliases* table_aliases, const chq_expr* const* partition_by, int n_partition_by,
+                              const chq_sort_key* order_by, int n_order_by, const chq_window_item* items, int n_items, int out_device,
+                              ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  return window_call(ctx, n_records, recs, schema, table_aliases, partition_by, n_partition_by, order_by, n_order_by, items, n_items,
+                     out_device, out, out_schema);
 }
 
 // ---- JOIN (join.cpp) ---------------------------------------------------------------------------------------------------------

@@ -4,4 +4,5 @@ from .record_handler import ExchangeRecord, RecordHandler, RecordHandlerError  #
 from .tasks import (AggregateConfig, AggregateOperatorTask, AggregateTask, AggregateTaskBuilder, FilterConfig, FilterOperatorTask, FilterTask, FilterTaskBuilder, JoinConfig, JoinOperatorTask, JoinTask, JoinTaskBuilder, MaterializeFilesConfig,  # noqa: F401
                     MaterializeFilesOperatorTask, MaterializeFilesTask, MaterializeFilesTaskBuilder,
                     OperatorInstanceConfig, OperatorTaskRegistry, OperatorTaskRegistryError, OrderByConfig,
-                    OrderByOperatorTask, OrderByTask, OrderByTaskBuilder, TaskBuilder, build_default_operator_task_registry)
+                    OrderByOperatorTask, OrderByTask, OrderByTaskBuilder, TaskBuilder, WindowConfig, WindowOperatorTask, WindowTask,
+                    WindowTaskBuilder, build_default_operator_task_registry)

@@ -10,6 +10,8 @@ Reference (OPS = src/handlers/operator_handler/operators):
                                             a blocking single-instance sort over `record_utils.sort_records`
   AggregateOperatorTask / AggregateTask     not in the reference either: GROUP BY, a blocking single-instance aggregation
                                             over `record_utils.aggregate_records`
+  WindowOperatorTask / WindowTask           not in the reference either: window functions (fn(...) OVER (...)), a blocking
+                                            single-instance operator over `record_utils.window_records` + `project_record`
   JoinOperatorTask / JoinTask               not in the reference either: JOIN (inner, left, right, full, semi, anti), a blocking
                                             single-instance equi-join of two inbound exchanges over `record_utils.join_records`
 
@@ -86,6 +88,20 @@ class AggregateOperatorTask:
 
 
 @dataclasses.dataclass(frozen=True)
+class WindowOperatorTask:
+    """One window specification with the items and the final projection of the SELECT list (`sqlparse.window_plan`); shaped
+    like AggregateOperatorTask"""
+    partition_by: Sequence[A.Expr]
+    order_by: Sequence[A.OrderByExpr]
+    items: Sequence[A.WindowItem]
+    projection: Sequence[A.SelectItem]
+    max_rows_per_record: int = 10_000
+
+    def task_name(self) -> str:
+        return "window"
+
+
+@dataclasses.dataclass(frozen=True)
 class JoinOperatorTask:
     """JOIN on the (left column, right column) pairs of the ON condition (`sqlparse.join_plan`); inbound exchange 0
     is the left input, 1 the right; shaped like AggregateOperatorTask.  `kind` is the `how` of `record_utils.join_records`."""
@@ -131,6 +147,7 @@ class OperatorTaskRegistry:
         self.order_by_task: Optional[TaskBuilder] = None
         self.aggregate_task: Optional[TaskBuilder] = None
         self.join_task: Optional[TaskBuilder] = None
+        self.window_task: Optional[TaskBuilder] = None
 
     def add_filter_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
         if self.filter_task is not None:
@@ -164,6 +181,12 @@ class OperatorTaskRegistry:
         self.aggregate_task = builder
         return self
 
+    def add_window_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        if self.window_task is not None:
+            raise OperatorTaskRegistryError("window task builder already set")
+        self.window_task = builder
+        return self
+
     def add_join_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
         if self.join_task is not None:
             raise OperatorTaskRegistryError("join task builder already set")
@@ -181,6 +204,8 @@ class OperatorTaskRegistry:
             return self.aggregate_task
         if isinstance(task, JoinOperatorTask):
             return self.join_task
+        if isinstance(task, WindowOperatorTask):
+            return self.window_task
         if isinstance(task, MaterializeFilesOperatorTask):
             if task.data_format in self.materialize_data_formats:
                 return self.materialize_files_task
@@ -465,6 +490,115 @@ class AggregateTaskBuilder(TaskBuilder):
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
         task = AggregateTask(op_in_config, AggregateConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
                              aggregate_fn=self._aggregate_fn)
+
+        def run():
+            try:
+                task.async_main()
+                return None
+            except Exception as err:   # noqa: BLE001 -- any error ends the instance
+                return err
+
+        run.task = task
+        return run
+
+
+# ---- window functions -----------------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class WindowConfig:
+    partition_by: Sequence[A.Expr]
+    order_by: Sequence[A.OrderByExpr]
+    items: Sequence[A.WindowItem]
+    projection: Sequence[A.SelectItem]
+    max_rows_per_record: int = 10_000
+
+    @staticmethod
+    def try_from(op_in_config: OperatorInstanceConfig) -> "WindowConfig":
+        t = op_in_config.task
+        if not isinstance(t, WindowOperatorTask):
+            raise ValueError("operator instance config is not a window task")
+        if not t.items:
+            raise ValueError("a window task needs at least one item")
+        if not t.projection:
+            raise ValueError("a window task needs at least one projected field")
+        if t.max_rows_per_record < 1:
+            raise ValueError("max_rows_per_record must be at least 1")
+        return WindowConfig(tuple(t.partition_by), tuple(t.order_by), tuple(t.items), tuple(t.projection), t.max_rows_per_record)
+
+
+class WindowTask:
+    """A blocking, single-instance operator with the protocol of AggregateTask: pulls and holds every inbound record,
+    evaluates every window item with ONE `window_records` call (the rows come back in input order: record order, then row
+    order), finishes the SELECT list with ONE `project_record` over that result, sends it cut into records of at most
+    `max_rows_per_record` rows with record ids 0, 1, 2, ..., and only then acks its inputs.  When no record came in nothing
+    is sent.  `window_fn(records, table_aliases, partition_by, order_by, items)` and `project_fn(fields, record,
+    table_aliases)` replace the library calls (tests on the CPU)."""
+
+    def __init__(self, op_in_config: OperatorInstanceConfig, config: WindowConfig, inbound_exchanges, outbound_exchange,
+                 window_fn=None, project_fn=None, ctx=None):
+        self.operator_instance_config = op_in_config
+        self.config = config
+        self.inbound_exchanges = inbound_exchanges
+        self.outbound_exchange = outbound_exchange
+        self._window = window_fn
+        self._project = project_fn
+        self._ctx = ctx
+        self.rows_in = 0
+        self.rows_out = 0
+        self.records_sent = 0
+
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
+        return self._ctx
+
+    def _window_records(self, records, aliases):
+        c = self.config
+        if self._window is not None:
+            return self._window(records, aliases, c.partition_by, c.order_by, c.items)
+        return record_utils.window_records(records, aliases, c.partition_by, c.order_by, c.items, ctx=self._context())
+
+    def _project_record(self, rec, aliases):
+        if self._project is not None:
+            return self._project(self.config.projection, rec, aliases)
+        return record_utils.project_record(self.config.projection, rec, aliases, ctx=self._context())
+
+    def async_main(self) -> None:
+        rec_handler = RecordHandler.initiate(self.operator_instance_config, self.inbound_exchanges, self.outbound_exchange)
+        try:
+            held = []
+            while True:
+                exchange_rec = rec_handler.next_record_to_hold()
+                if exchange_rec is None:
+                    break
+                held.append(exchange_rec)
+            if not held:
+                return
+            self.rows_in = sum(h.record.num_rows for h in held)
+            aliases = held[0].table_aliases
+            windowed = self._window_records([h.record for h in held], aliases)
+            # the item columns are new: no table prefix reaches them
+            win_aliases = None if aliases is None else list(aliases) + [[] for _ in range(windowed.num_columns - len(aliases))]
+            result = self._project_record(windowed, win_aliases)
+            out_aliases = [[] for _ in range(result.num_columns)]
+            n, step = result.num_rows, self.config.max_rows_per_record
+            for record_id, start in enumerate(range(0, max(n, 1), step)):
+                rec_handler.send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), out_aliases)
+                self.records_sent += 1
+            self.rows_out = n
+            for h in held:
+                rec_handler.complete_record(h)
+        finally:
+            rec_handler.close()
+
+
+class WindowTaskBuilder(TaskBuilder):
+    def __init__(self, window_fn=None, project_fn=None):
+        self._window_fn = window_fn
+        self._project_fn = project_fn
+
+    def build(self, op_in_config, inbound_exchanges, outbound_exchange):
+        task = WindowTask(op_in_config, WindowConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
+                          window_fn=self._window_fn, project_fn=self._project_fn)
 
         def run():
             try:
@@ -794,5 +928,6 @@ def build_default_operator_task_registry(storage_root: str) -> OperatorTaskRegis
             .add_filter_task_builder(FilterTaskBuilder())
             .add_order_by_task_builder(OrderByTaskBuilder())
             .add_aggregate_task_builder(AggregateTaskBuilder())
+            .add_window_task_builder(WindowTaskBuilder())
             .add_join_task_builder(JoinTaskBuilder())
             .add_materialize_files_builder(MaterializeFilesTaskBuilder(storage_root), ["parquet"]))

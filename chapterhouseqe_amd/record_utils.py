@@ -917,6 +917,101 @@ def aggregate_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], ke
     return _finish(ctx, rc, out, dev_out)
 
 
+# ------------------------------------------------------------------------------------------ window functions
+class _WindowArgs:
+    """the C arguments of one window call: partition key handles, sort keys and the item array (handles freed by `free`)"""
+
+    def __init__(self, partition_by: Sequence[A.Expr], order_by: Sequence[A.OrderByExpr], items: Sequence[A.WindowItem]):
+        self.n_partition_by, self.n_order_by, self.n_items = len(partition_by), len(order_by), len(items)
+        self._handles = []
+        self.order_by = None
+        try:
+            self.partition_by = (C.c_void_p * max(1, self.n_partition_by))()
+            for i, k in enumerate(partition_by):
+                self.partition_by[i] = self._handle(k)
+            self.items = (L.WindowItem * max(1, self.n_items))()
+            for i, it in enumerate(items):
+                if not isinstance(it, A.WindowItem):
+                    raise TypeError(f"not a WindowItem: {it!r}")
+                self.items[i].kind = int(it.kind)
+                self.items[i].frame = int(it.frame)
+                self.items[i].offset = int(it.offset)
+                self.items[i].column = self._handle(it.column) if it.column is not None else None
+                self.items[i].name = it.name.encode()
+            self.order_by = _sort_keys_to_c(order_by)
+        except Exception:
+            self.free()
+            raise
+
+    def _handle(self, e: A.Expr):
+        h = _expr_to_c(e)
+        self._handles.append(h)
+        return h
+
+    def free(self) -> None:
+        for h in self._handles:
+            L.lib().chq_expr_free(h)
+        self._handles = []
+        if self.order_by is not None:
+            _free_sort_keys(self.order_by, self.n_order_by)
+            self.order_by = None
+
+
+def window_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]]], partition_by: Sequence[A.Expr],
+                  order_by: Sequence[A.OrderByExpr], items: Sequence[A.WindowItem], *, ctx: Optional[Context] = None,
+                  device_result: Optional[bool] = None):
+    """Window functions (`chq_window_record`): every row of `rec` in input order, its columns followed by one column per
+    `items` entry evaluated over (PARTITION BY `partition_by` ORDER BY `order_by`) (`sqlparse.window_plan` builds all three
+    from a SELECT).  Result residency follows the input unless `device_result` says otherwise."""
+    ctx, src, own_src, on_dev = _prepare(rec, ctx)
+    dev_out = on_dev if device_result is None else device_result
+    al = _Aliases(table_aliases)
+    out = _CBatch()
+    try:
+        args = _WindowArgs(partition_by, order_by, items)
+        try:
+            rc = L.lib().chq_window_record(ctx.handle, C.byref(src.array), C.byref(src.schema), al.ptr, args.partition_by,
+                                           args.n_partition_by, args.order_by, args.n_order_by, args.items, args.n_items,
+                                           L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, C.byref(out.array),
+                                           C.byref(out.schema))
+        finally:
+            args.free()
+    finally:
+        if own_src:
+            src.release()
+    return _finish(ctx, rc, out, dev_out)
+
+
+def window_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], partition_by: Sequence[A.Expr],
+                   order_by: Sequence[A.OrderByExpr], items: Sequence[A.WindowItem], *, ctx: Optional[Context] = None,
+                   device_result: Optional[bool] = None):
+    """Window functions over a group (`chq_window_records`): the batches of `recs` (a sequence of same-schema batches or a
+    `RecordGroup`) as if they were one batch; ONE batch comes back, in batch order, then row order."""
+    if not isinstance(recs, RecordGroup):
+        recs = list(recs)
+        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
+        if any(x != sig[0] for x in sig[1:]):   # (the C call takes ONE schema for the group)
+            raise ChqError(22, "window_records: every record batch must have the schema of the first")
+    grp = recs if isinstance(recs, RecordGroup) else RecordGroup(recs, ctx)
+    ctx = ctx or grp.ctx
+    dev_out = grp.on_device if device_result is None else device_result
+    al = _Aliases(table_aliases)
+    out = _CBatch()
+    try:
+        args = _WindowArgs(partition_by, order_by, items)
+        try:
+            rc = L.lib().chq_window_records(ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema), al.ptr, args.partition_by,
+                                            args.n_partition_by, args.order_by, args.n_order_by, args.items, args.n_items,
+                                            L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, C.byref(out.array),
+                                            C.byref(out.schema))
+        finally:
+            args.free()
+    finally:
+        if grp is not recs:
+            grp.release()
+    return _finish(ctx, rc, out, dev_out)
+
+
 # ------------------------------------------------------------------------------------------ JOIN
 _JOIN_KINDS = {"inner": 0, "left": 1, "right": 2, "full": 3, "semi": 4, "anti": 5}   # enum chq_join_kind
 

@@ -110,14 +110,25 @@ class UnsupportedExpr(Expr):
     debug: str
 
 
+@dataclass(frozen=True)
+class WindowSpec:
+    """`OVER ( [PARTITION BY e {, e}] [ORDER BY o {, o}] [frame] )`.  `frame` is a `WindowFrame`, resolved by the parser:
+    written, or the SQL default (RANGE_TO_CURRENT with ORDER BY, PARTITION without)."""
+    partition_by: Tuple["Expr", ...] = ()
+    order_by: Tuple["OrderByExpr", ...] = ()
+    frame: int = 0
+
+
 @dataclass(frozen=True, repr=False)
 class Function(UnsupportedExpr):
     """Expr::Function: a call `name(args)` / `name(*)`.  compute_value rejects it like every UnsupportedExpr (its debug text
     is `Function(name)`); the GROUP BY front-end reads the aggregate calls of a SELECT list from it.  `args` is None when
-    what stands between the parentheses is not a plain expression list (`count(distinct a)`, `cast(a as int)`)."""
+    what stands between the parentheses is not a plain expression list (`count(distinct a)`, `cast(a as int)`).  `over`:
+    the window the call is evaluated over (`name(args) OVER (...)`), read by `sqlparse.window_plan`."""
     name: str = ""
     args: Optional[Tuple[Expr, ...]] = ()
     star: bool = False
+    over: Optional[WindowSpec] = None
 
     def __repr__(self) -> str:   # the text an enclosing Unsupported node quotes
         return f"UnsupportedExpr(debug={self.debug!r})"
@@ -181,6 +192,37 @@ class AggItem:
     name: str
     key_index: int = -1
     column: Optional[Expr] = None
+
+
+# ---- window functions: one output column (include/chq.h: chq_window_item) ------------------------
+class WindowKind(enum.IntEnum):
+    ROW_NUMBER = 0
+    RANK = 1
+    DENSE_RANK = 2
+    LAG = 3
+    LEAD = 4
+    COUNT_STAR = 5
+    COUNT = 6
+    SUM = 7
+    MIN = 8
+    MAX = 9
+
+
+class WindowFrame(enum.IntEnum):
+    PARTITION = 0           # the whole partition
+    ROWS_TO_CURRENT = 1     # ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW
+    RANGE_TO_CURRENT = 2    # RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW: through the row's last peer
+
+
+@dataclass(frozen=True)
+class WindowItem:
+    """ROW_NUMBER / RANK / DENSE_RANK: nothing else; LAG / LEAD: `column` and `offset`; COUNT_STAR: `frame`; COUNT / SUM /
+    MIN / MAX: `column` and `frame`."""
+    kind: WindowKind
+    name: str
+    column: Optional[Expr] = None
+    frame: WindowFrame = WindowFrame.PARTITION
+    offset: int = 0
 
 
 # ---- small constructors used by tests (the reference builds these structs literally) ----------

@@ -9,6 +9,8 @@ sample queries (reference: sample_queries/simple.sql) to be written as SQL text.
 
     select <items> from <func>('<path>') [[as] alias] {[inner] join <func>('<path>') [[as] alias] on <expr>}
         [where <expr>] [group by <column> {, ...}]
+    a select item may be a window call: <name>(<args>) over ([partition by <column> {, ...}] [order by ...]
+        [rows|range between unbounded preceding and current row|unbounded following])
         [order by <expr> [asc|desc] [nulls first|last] {, ...}] [limit <n>]
 """
 from __future__ import annotations
@@ -218,7 +220,45 @@ class _Parser:
                     depth -= 1
                     if depth == 0:
                         break
-        return A.Function(f"Function({name})", name, args, star)
+        over = self._window_spec() if self.accept_word("OVER") else None
+        return A.Function(f"Function({name})", name, args, star, over)
+
+    def _window_spec(self) -> A.WindowSpec:
+        """`( [PARTITION BY e {, e}] [ORDER BY o {, o}] [ROWS | RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW |
+        UNBOUNDED FOLLOWING] )`; the default frame is SQL's: RANGE ... CURRENT ROW with ORDER BY, the partition without."""
+        self.expect_op("(")
+        partition_by: List[A.Expr] = []
+        order_by: List[A.OrderByExpr] = []
+        if self.accept_word("PARTITION"):
+            if not self.accept_word("BY"):
+                raise SqlParseError(f"expected BY after PARTITION, found {self.peek()[1]!r}")
+            partition_by.append(self.parse_expr(0))
+            while self.accept_op(","):
+                partition_by.append(self.parse_expr(0))
+        if self.accept_word("ORDER"):
+            if not self.accept_word("BY"):
+                raise SqlParseError(f"expected BY after ORDER, found {self.peek()[1]!r}")
+            order_by.append(self.parse_order_by_expr())
+            while self.accept_op(","):
+                order_by.append(self.parse_order_by_expr())
+        frame = A.WindowFrame.RANGE_TO_CURRENT if order_by else A.WindowFrame.PARTITION
+        k, v = self.peek()
+        if k == "word" and v.upper() in ("ROWS", "RANGE", "GROUPS"):
+            unit = self.next()[1].upper()
+            words = []
+            while self.peek()[0] not in ("eof",) and self.peek() != ("op", ")"):
+                words.append(self.next()[1].upper())
+            text = " ".join(words)
+            if unit != "GROUPS" and text == "BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW":
+                frame = A.WindowFrame.ROWS_TO_CURRENT if unit == "ROWS" else A.WindowFrame.RANGE_TO_CURRENT
+            elif unit != "GROUPS" and text == "BETWEEN UNBOUNDED PRECEDING AND UNBOUNDED FOLLOWING":
+                frame = A.WindowFrame.PARTITION
+            else:
+                raise SqlParseError(f"window frame {unit} {text} is not supported: only BETWEEN UNBOUNDED PRECEDING AND "
+                                    "CURRENT ROW | UNBOUNDED FOLLOWING")
+        if not self.accept_op(")"):
+            raise SqlParseError(f"expected ')' to close OVER (...), found {self.peek()[1]!r}")
+        return A.WindowSpec(tuple(partition_by), tuple(order_by), frame)
 
     def _identifier_tail(self, first: A.Ident) -> A.Expr:
         parts = [first]
@@ -361,12 +401,15 @@ def _expr_text(e: A.Expr) -> str:
     if isinstance(e, A.CompoundIdentifier):
         return ".".join(i.value for i in e.idents)
     if isinstance(e, A.Function):
-        return f"{e.name}({'*' if e.star else ', '.join(_expr_text(a) for a in (e.args or ()))})"
+        call = f"{e.name}({'*' if e.star else ', '.join(_expr_text(a) for a in (e.args or ()))})"
+        return call if e.over is None else f"{call} over ({_window_text(e.over)})"
+    if isinstance(e, A.ValueExpr) and isinstance(e.value, A.Number):
+        return e.value.text
     return repr(e)
 
 
 def is_aggregate_call(e: A.Expr) -> bool:
-    return isinstance(e, A.Function) and e.name.lower() in _AGGREGATES
+    return isinstance(e, A.Function) and e.name.lower() in _AGGREGATES and e.over is None
 
 
 def aggregate_plan(select: Select):
@@ -401,6 +444,102 @@ def aggregate_plan(select: Select):
         else:
             raise SqlParseError(f"SELECT item {_expr_text(e)} is neither a GROUP BY key nor an aggregate")
     return keys, tuple(items)
+
+
+# ---- window functions: the SELECT list as one window call's items ------------------------------------------------------
+_WINDOW_KINDS = {"row_number": A.WindowKind.ROW_NUMBER, "rank": A.WindowKind.RANK, "dense_rank": A.WindowKind.DENSE_RANK,
+                 "lag": A.WindowKind.LAG, "lead": A.WindowKind.LEAD, "count": A.WindowKind.COUNT, "sum": A.WindowKind.SUM,
+                 "min": A.WindowKind.MIN, "max": A.WindowKind.MAX}
+_FRAME_TEXT = {A.WindowFrame.PARTITION: "range between unbounded preceding and unbounded following",
+               A.WindowFrame.ROWS_TO_CURRENT: "rows between unbounded preceding and current row",
+               A.WindowFrame.RANGE_TO_CURRENT: "range between unbounded preceding and current row"}
+
+
+def _window_text(w: A.WindowSpec) -> str:
+    parts = []
+    if w.partition_by:
+        parts.append("partition by " + ", ".join(_expr_text(e) for e in w.partition_by))
+    if w.order_by:
+        def key(o: A.OrderByExpr) -> str:
+            return _expr_text(o.expr) + ("" if o.asc is None else " asc" if o.asc else " desc") + \
+                ("" if o.nulls_first is None else " nulls first" if o.nulls_first else " nulls last")
+        parts.append("order by " + ", ".join(key(o) for o in w.order_by))
+    parts.append(_FRAME_TEXT[A.WindowFrame(w.frame)])
+    return " ".join(parts)
+
+
+def _has_window_call(e) -> bool:
+    if isinstance(e, A.Function):
+        return e.over is not None or any(_has_window_call(a) for a in (e.args or ()))
+    if isinstance(e, A.BinaryOp):
+        return _has_window_call(e.left) or _has_window_call(e.right)
+    if isinstance(e, A.Nested):
+        return _has_window_call(e.expr)
+    return False
+
+
+def window_plan(select: Select):
+    """A `Select` whose SELECT list holds window calls (`fn(...) over (...)`) -> `(partition_by, order_by, items, projection)`:
+    the first three as `record_utils.window_record(s)` takes them, `projection` the SELECT list with every window call
+    replaced by an identifier of its output column (its alias, else its lower-cased call text without the OVER clause) for `project_record` to
+    finish the statement on the window call's result.  None: no call has OVER.  Every window call must be a whole SELECT
+    item, all of them must share PARTITION BY and ORDER BY (their frames may differ), and they cannot be mixed with
+    GROUP BY or plain aggregates.  row_number() / rank() / dense_rank() take no argument, lag / lead a column and an
+    optional integer literal (default 1), count(*) / count / sum / min / max one column."""
+    exprs = [(f.expr if isinstance(f, (A.UnnamedExpr, A.ExprWithAlias)) else None) for f in select.projection]
+    if not any(e is not None and _has_window_call(e) for e in exprs):
+        return None
+    if select.group_by or any(e is not None and is_aggregate_call(e) for e in exprs):
+        raise SqlParseError("window calls cannot be selected together with GROUP BY or plain aggregates")
+    spec = None
+    items, projection = [], []
+    for f, e in zip(select.projection, exprs):
+        if e is None or not _has_window_call(e):
+            projection.append(f)
+            continue
+        if not (isinstance(e, A.Function) and e.over is not None) or any(_has_window_call(a) for a in (e.args or ())):
+            raise SqlParseError(f"a window call must be a whole SELECT item: {_term_text(e)}")
+        if spec is None:
+            spec = e.over
+        elif (e.over.partition_by, e.over.order_by) != (spec.partition_by, spec.order_by):
+            raise SqlParseError("all window calls of a statement must share PARTITION BY and ORDER BY: "
+                                f"({_window_text(e.over)}) differs from ({_window_text(spec)})")
+        call = f"{e.name}({'*' if e.star else ', '.join(_expr_text(a) for a in (e.args or ()))})"
+        kind = _WINDOW_KINDS.get(e.name.lower())
+        if kind is None:
+            raise SqlParseError(f"{e.name} is not a window function of this build")
+        if e.args is None:
+            raise SqlParseError(f"{e.name}(...) over: the arguments must be plain columns")
+        alias = f.alias.value if isinstance(f, A.ExprWithAlias) else None
+        name = alias if alias is not None else call.lower()
+        if any(it.name == name for it in items):
+            raise SqlParseError(f"two window calls would both be named {name!r}: give one an alias")
+        frame = A.WindowFrame(e.over.frame)
+        if e.star:
+            if kind != A.WindowKind.COUNT:
+                raise SqlParseError(f"{e.name}(*) is not a window function; only count(*) takes '*'")
+            items.append(A.WindowItem(A.WindowKind.COUNT_STAR, name, None, frame))
+        elif kind in (A.WindowKind.ROW_NUMBER, A.WindowKind.RANK, A.WindowKind.DENSE_RANK):
+            if e.args:
+                raise SqlParseError(f"{e.name} takes no argument: {call}")
+            items.append(A.WindowItem(kind, name))
+        elif kind in (A.WindowKind.LAG, A.WindowKind.LEAD):
+            if len(e.args) not in (1, 2):
+                raise SqlParseError(f"{e.name} takes a column and an optional offset: {call}")
+            offset = 1
+            if len(e.args) == 2:
+                k = e.args[1]
+                if not (isinstance(k, A.ValueExpr) and isinstance(k.value, A.Number) and k.value.text.isdigit()):
+                    raise SqlParseError(f"the offset of {e.name} must be a non-negative integer literal: {call}")
+                offset = int(k.value.text)
+            items.append(A.WindowItem(kind, name, e.args[0], A.WindowFrame.PARTITION, offset))
+        elif len(e.args) != 1:
+            raise SqlParseError(f"{e.name} takes exactly one column: {call}")
+        else:
+            items.append(A.WindowItem(kind, name, e.args[0], frame))
+        ident = A.Identifier(A.Ident(name))
+        projection.append(A.ExprWithAlias(ident, f.alias) if isinstance(f, A.ExprWithAlias) else A.UnnamedExpr(ident))
+    return tuple(spec.partition_by), tuple(spec.order_by), tuple(items), tuple(projection)
 
 
 # ---- INNER JOIN: the ON condition as key pairs -------------------------------------------------------------

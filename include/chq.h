@@ -439,6 +439,86 @@ chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const struct Arrow
                                  const chq_expr* const* keys, int n_keys, const chq_agg_item* items, int n_items,
                                  int out_device, struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
 
+/* ---- Window functions: fn(...) OVER (PARTITION BY ... ORDER BY ...) -----------------------------
+ * The reference has no window functions; these semantics are this library's own (unpinned).  One call takes a group of
+ * n >= 1 batches of one schema (host or device resident, sliced or empty; joined on the device first, as chq_sort_records
+ * does), zero or more PARTITION BY keys, zero or more ORDER BY keys (chq_sort_key: each with `descending` / `nulls_first`)
+ * and one or more items, and returns EVERY INPUT ROW IN INPUT ORDER (batch order, then row order) with one more column
+ * per item:
+ *   - keys are columns (Identifier / CompoundIdentifier) resolved exactly like a sort key (a missing column: the
+ *     evaluator's status; any other expression: CHQ_ERR_NOT_SUPPORTED); the key types are those of ORDER BY, any other
+ *     type: CHQ_ERR_NOT_SUPPORTED naming the column and its Arrow type.
+ *   - the rows are ordered by the partition keys (ascending, nulls last; the order AMONG partitions cannot be observed),
+ *     then by the order keys with their flags; the order is stable, ties keep input order.
+ *   - two rows are in one PARTITION iff for every partition key both values are null, or both are non-null with EQUAL BIT
+ *     PATTERNS (GROUP BY's rule: -0 and +0 differ, so do NaNs with different payloads; Utf8: length, then bytes).  No
+ *     partition key: one partition.  Two rows of a partition are PEERS iff the same holds for every order key; no order
+ *     key: the whole partition is one peer group.
+ *   - output: ONE batch.  First every input column (same fields, same values, exact null counts), then one column per
+ *     item, in item order, named `name`.  Zero rows in: zero rows out with the full schema.
+ *   - items, by `kind`:
+ *       CHQ_WIN_ROW_NUMBER / RANK / DENSE_RANK   Int64, not nullable, 1-based inside the partition: the row's sorted position;
+ *                            the row number of its first peer; the number of peer groups up to and including its own.
+ *       CHQ_WIN_LAG / LEAD   the value of `column` in the row `offset` (>= 0) sorted positions before / behind inside the
+ *                            partition, null where there is none (no default-value argument); offset 0: the row's own
+ *                            value; a negative offset: CHQ_ERR_ARROW_INVALID_ARGUMENT.  Every column type is accepted (Utf8,
+ *                            Boolean, Decimal128, ...); the output field has the input's type and is nullable.
+ *       CHQ_WIN_COUNT_STAR / COUNT / SUM / MIN / MAX   input types, result types, null skipping and the
+ *                            CHQ_ERR_NOT_SUPPORTED cases are EXACTLY those of chq_aggregate_records, evaluated over `frame`:
+ *                              CHQ_FRAME_PARTITION          the whole partition
+ *                              CHQ_FRAME_ROWS_TO_CURRENT    the partition's first row through this row
+ *                              CHQ_FRAME_RANGE_TO_CURRENT   the partition's first row through this row's LAST PEER (SQL's
+ *                                                           default when ORDER BY is written)
+ *                            COUNTs are Int64, not nullable; SUM / MIN / MAX are nullable and null where the frame holds no
+ *                            non-null value.  Integer SUM accumulates in 128 bits; if the exact total of ANY ROW'S FRAME is
+ *                            outside the result type the whole call fails with CHQ_ERR_ARROW_ARITHMETIC_OVERFLOW naming the
+ *                            output column ({INT64_MAX, 1, -5} in that sorted order succeeds under PARTITION and fails under
+ *                            ROWS_TO_CURRENT).  Float SUM: IEEE binary64 additions (Float32 widens exactly; NaN and +-inf
+ *                            propagate) combined in an order fixed by the sorted positions alone: bit-identical from run to
+ *                            run, and all rows of one peer group under RANGE, all rows of one partition under PARTITION,
+ *                            carry the same bits.
+ *     `frame` is ignored for the ranking kinds and LAG / LEAD.  An empty item list, an unknown kind or frame, or a missing
+ *     `column` where one is needed: CHQ_ERR_ARROW_INVALID_ARGUMENT.
+ *   - fewer than 2^32 rows per call (else CHQ_ERR_NOT_SUPPORTED).  `out_device` is ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM.
+ *     On failure nothing is returned (release == NULL).  chq_ctx_last_stats: rows_in = rows_out = the rows of the group.
+ * Out of scope: bounded frames (n PRECEDING / FOLLOWING), FIRST_VALUE / LAST_VALUE / NTILE, AVG, expressions as keys or
+ * arguments, several window specifications in one call, and multi-instance execution (the route is chq_partition_records by
+ * the PARTITION BY keys: a partition lies wholly inside one hash partition). */
+typedef enum chq_window_kind {
+  CHQ_WIN_ROW_NUMBER = 0,
+  CHQ_WIN_RANK = 1,
+  CHQ_WIN_DENSE_RANK = 2,
+  CHQ_WIN_LAG = 3,
+  CHQ_WIN_LEAD = 4,
+  CHQ_WIN_COUNT_STAR = 5,
+  CHQ_WIN_COUNT = 6,
+  CHQ_WIN_SUM = 7,
+  CHQ_WIN_MIN = 8,
+  CHQ_WIN_MAX = 9
+} chq_window_kind;
+typedef enum chq_window_frame {
+  CHQ_FRAME_PARTITION = 0,
+  CHQ_FRAME_ROWS_TO_CURRENT = 1,
+  CHQ_FRAME_RANGE_TO_CURRENT = 2
+} chq_window_frame;
+typedef struct chq_window_item {
+  int kind;                /* chq_window_kind */
+  int frame;               /* chq_window_frame: the aggregates */
+  int64_t offset;          /* LAG, LEAD */
+  const chq_expr* column;  /* LAG, LEAD, COUNT, SUM, MIN, MAX: the argument column; NULL otherwise */
+  const char* name;        /* output column name */
+} chq_window_item;
+chq_status chq_window_record(chq_ctx* ctx, const struct ArrowDeviceArray* rec, const struct ArrowSchema* schema,
+                             const chq_table_aliases* table_aliases, const chq_expr* const* partition_by, int n_partition_by,
+                             const chq_sort_key* order_by, int n_order_by, const chq_window_item* items, int n_items,
+                             int out_device, struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
+/* The same over `n_records` batches of ONE schema, as if they were one batch (the group is joined on the device first). */
+chq_status chq_window_records(chq_ctx* ctx, int n_records, const struct ArrowDeviceArray* const* recs,
+                              const struct ArrowSchema* schema, const chq_table_aliases* table_aliases,
+                              const chq_expr* const* partition_by, int n_partition_by, const chq_sort_key* order_by,
+                              int n_order_by, const chq_window_item* items, int n_items, int out_device,
+                              struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
+
 /* ---- JOIN: sort-merge equi-join of two groups of record batches -----------------------------------
  * The reference has no join; the semantics of INNER are derived from what it has: THE RESULT IS EXACTLY WHAT THE
  * REFERENCE'S filter_record RETURNS ON THE CROSS PRODUCT OF THE TWO INPUTS, LEFT-MAJOR, UNDER

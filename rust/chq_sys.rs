@@ -61,6 +61,17 @@ pub struct chq_agg_item {
     pub name: *const c_char,
 }
 
+/// struct chq_window_item: one output column of a window call (kind: 0 ROW_NUMBER, 1 RANK, 2 DENSE_RANK, 3 LAG, 4 LEAD,
+/// 5 COUNT(*), 6 COUNT, 7 SUM, 8 MIN, 9 MAX; frame: 0 PARTITION, 1 ROWS_TO_CURRENT, 2 RANGE_TO_CURRENT)
+#[repr(C)]
+pub struct chq_window_item {
+    pub kind: c_int,
+    pub frame: c_int,
+    pub offset: i64,
+    pub column: *const chq_expr,
+    pub name: *const c_char,
+}
+
 /// struct chq_join_key: one `left = right` pair of JOIN key columns
 #[repr(C)]
 pub struct chq_join_key {
@@ -200,6 +211,20 @@ extern "C" {
         table_aliases: *const chq_table_aliases, keys: *const *const chq_expr, n_keys: c_int,
         items: *const chq_agg_item, n_items: c_int, out_device: c_int,
         out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
+    ) -> c_int;
+    /// window functions: every input row in input order, the input columns and one more column per item
+    pub fn chq_window_record(
+        ctx: *mut chq_ctx, rec: *const ArrowDeviceArray, schema: *const FFI_ArrowSchema,
+        table_aliases: *const chq_table_aliases, partition_by: *const *const chq_expr, n_partition_by: c_int,
+        order_by: *const chq_sort_key, n_order_by: c_int, items: *const chq_window_item, n_items: c_int,
+        out_device: c_int, out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
+    ) -> c_int;
+    /// the same over a group of batches of one schema, as if they were one batch
+    pub fn chq_window_records(
+        ctx: *mut chq_ctx, n_records: c_int, recs: *const *const ArrowDeviceArray, schema: *const FFI_ArrowSchema,
+        table_aliases: *const chq_table_aliases, partition_by: *const *const chq_expr, n_partition_by: c_int,
+        order_by: *const chq_sort_key, n_order_by: c_int, items: *const chq_window_item, n_items: c_int,
+        out_device: c_int, out: *mut ArrowDeviceArray, out_schema: *mut FFI_ArrowSchema,
     ) -> c_int;
     /// INNER JOIN (sort-merge equi-join) of two groups of batches: one row per matching pair, ascending by left row, then by
     /// right row; every left column, then every right column
