@@ -5,6 +5,9 @@
 // number the runs and reduce every aggregate over them, reading the values through the permutation -- no column is gathered
 // but the key columns, and those only at one representative row per group.  Two read-backs besides the sort's: the number
 // of groups (it sizes the outputs), and one block of null counts and overflow flags at the end.  DESIGN.md section 3.7.
+//
+// The run finder (find_runs) and the typing of the aggregates (plan_aggregate) are defined here for JOIN (join.cpp) and the
+// window functions (window.cpp) as well: aggregate.hpp declares them.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -26,62 +29,8 @@ const char* kind_name(int kind) {
   }
 }
 
-// temporal types and decimals of up to 8 bytes: MIN / MAX order them as their signed integers (sort.cpp: key_words)
-bool orders_as_signed(const Column& c) {
-  const std::string& f = c.format;
-  return c.type == T_FIXED_OPAQUE &&
-         (f == "tdD" || f == "tts" || f == "ttm" || f == "tdm" || f == "ttu" || f == "ttn" || f.rfind("ts", 0) == 0 ||
-          f.rfind("tD", 0) == 0 || (f.rfind("d:", 0) == 0 && c.width <= 8));
-}
-
-// what one output item does, decided against the schema before any data moves
-struct ItemPlan {
-  int col = -1;                 // input column (key column for CHQ_AGG_KEY)
-  int op = AO_COUNT;
-  int value_kind = AV_SIGNED;
-  std::string format;           // output type
-  DType type = T_I64;
-  int width = 8;
-};
-
-ItemPlan plan_aggregate(const AggItemArg& it, const Column& c) {
-  ItemPlan pl;
-  const bool is_signed = c.type >= T_I8 && c.type <= T_I64, is_unsigned = c.type >= T_U8 && c.type <= T_U64;
-  const bool is_float = c.type == T_F16 || c.type == T_F32 || c.type == T_F64;
-  auto unsupported = [&]() {
-    return ChqError{CHQ_ERR_NOT_SUPPORTED, std::string(kind_name(it.kind)) + " over column '" + c.name + "' of Arrow type '" + c.format +
-                                           "' is not supported in this build"};
-  };
-  pl.value_kind = is_unsigned ? AV_UNSIGNED : is_float ? AV_FLOAT : AV_SIGNED;
-  switch (it.kind) {
-    case CHQ_AGG_COUNT:
-      pl.op = AO_COUNT; pl.format = "l"; pl.type = T_I64; pl.width = 8;
-      break;
-    case CHQ_AGG_SUM:
-      if (is_signed) { pl.op = AO_SUM_INT; pl.format = "l"; pl.type = T_I64; }
-      else if (is_unsigned) { pl.op = AO_SUM_INT; pl.format = "L"; pl.type = T_U64; }
-      else if (c.type == T_F32 || c.type == T_F64) { pl.op = AO_SUM_FLOAT; pl.format = "g"; pl.type = T_F64; }
-      else throw unsupported();
-      pl.width = 8;
-      break;
-    case CHQ_AGG_MIN: case CHQ_AGG_MAX:
-      if (!(is_signed || is_unsigned || is_float || orders_as_signed(c))) throw unsupported();
-      pl.op = it.kind == CHQ_AGG_MIN ? AO_MIN : AO_MAX;
-      pl.format = c.format; pl.type = c.type; pl.width = c.width;
-      break;
-    default: throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "unknown aggregate kind " + std::to_string(it.kind)};
-  }
-  return pl;
-}
-
-int resolve_argument(const AggItemArg& it, const std::vector<PlanColumn>& pcols, int64_t rows) {
-  if (!it.column) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null column of ") + kind_name(it.kind)};
-  const Expr& e = *it.column;
-  if (e.kind != Expr::IDENT && e.kind != Expr::COMPOUND)
-    throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("the argument of ") + kind_name(it.kind) + " must be a column, not " +
-                                          (e.text.empty() ? std::string("an expression") : e.text)};
-  return resolve_key(e, pcols, rows);
-}
+static_assert(CHQ_AGG_SUM - CHQ_AGG_COUNT == AGG_FN_SUM && CHQ_AGG_MIN - CHQ_AGG_COUNT == AGG_FN_MIN && CHQ_AGG_MAX - CHQ_AGG_COUNT == AGG_FN_MAX,
+              "chq_agg_kind numbers COUNT, SUM, MIN, MAX like AggFn");
 
 AggKey key_of(const Column& c) {
   AggKey k{};
@@ -94,16 +43,95 @@ AggKey key_of(const Column& c) {
   return k;
 }
 
-Column fixed_column(const std::string& name, const ItemPlan& pl, bool nullable, int64_t G, const BufferPtr& values) {
+}  // namespace
+
+AggPlan plan_aggregate(AggFn fn, const char* name, const Column& c) {
+  AggPlan pl;
+  const bool is_signed = c.type >= T_I8 && c.type <= T_I64, is_unsigned = c.type >= T_U8 && c.type <= T_U64;
+  const bool is_float = c.type == T_F16 || c.type == T_F32 || c.type == T_F64;
+  auto unsupported = [&]() {
+    return ChqError{CHQ_ERR_NOT_SUPPORTED, std::string(name) + " over column '" + c.name + "' of Arrow type '" + c.format +
+                                           "' is not supported in this build"};
+  };
+  pl.value_kind = is_unsigned ? AV_UNSIGNED : is_float ? AV_FLOAT : AV_SIGNED;
+  switch (fn) {
+    case AGG_FN_COUNT:
+      pl.op = AO_COUNT;
+      break;
+    case AGG_FN_SUM:
+      if (is_signed) { pl.op = AO_SUM_INT; }
+      else if (is_unsigned) { pl.op = AO_SUM_INT; pl.format = "L"; pl.type = T_U64; }
+      else if (c.type == T_F32 || c.type == T_F64) { pl.op = AO_SUM_FLOAT; pl.format = "g"; pl.type = T_F64; }
+      else throw unsupported();
+      break;
+    case AGG_FN_MIN: case AGG_FN_MAX:
+      if (!(is_signed || is_unsigned || is_float || orders_as_signed(c))) throw unsupported();
+      pl.op = fn == AGG_FN_MIN ? AO_MIN : AO_MAX;
+      pl.format = c.format; pl.type = c.type; pl.width = c.width;
+      break;
+  }
+  return pl;
+}
+
+Column fixed_column(const std::string& name, const AggPlan& pl, bool nullable, int64_t m, const BufferPtr& values) {
   Column o;
   o.name = name; o.format = pl.format; o.type = pl.type; o.width = pl.width; o.nullable = nullable;
-  o.length = G; o.offset = 0; o.null_count = 0;
+  o.length = m; o.offset = 0; o.null_count = 0;
   o.values = (const uint8_t*)values->ptr;
   o.owned.push_back(values);
   return o;
 }
 
-}  // namespace
+void validity_from_counts(Context& ctx, Column& o, const BufferPtr& counts, int64_t m, uint64_t* ones, Traffic& t) {
+  BufferPtr bits = make_device_buffer((size_t)((m + 31) / 32) * 4 + 16, ctx.device);
+  AggValidityParams vp{(const uint64_t*)counts->ptr, m, (uint8_t*)bits->ptr, ones};
+  if (m > 0) { check_hip(launch_agg_validity(vp, ctx.stream), "launch agg_validity_kernel"); ++ctx.stats.launches; }
+  t.read += m * 8; t.written += (m + 7) / 8;
+  o.validity = (const uint8_t*)bits->ptr;
+  o.owned.push_back(bits);
+  o.null_count = -1;   // set from `ones` once read back
+}
+
+Runs find_runs(Context& ctx, const Batch& rec, const uint32_t* perm, const std::vector<int>& cols, Traffic& t) {
+  const int64_t n = rec.nrows, ntiles = (n + kAggTile - 1) / kAggTile;
+  Runs r;
+  BufferPtr heads = make_device_buffer((size_t)ntiles * kAggTile + 16, ctx.device);
+  BufferPtr counts = make_device_buffer((size_t)(ntiles + 1) * 4 + 16, ctx.device);
+  AggHeadsParams hp{};
+  hp.perm = perm; hp.n = n; hp.heads = (uint8_t*)heads->ptr; hp.tile_counts = (uint32_t*)counts->ptr; hp.ntiles = ntiles;
+  size_t k0 = 0;
+  do {   // (no key: one launch that marks position 0)
+    hp.n_keys = (int32_t)std::min<size_t>(kAggMaxKeys, cols.size() - k0);
+    hp.accumulate = k0 ? 1 : 0;
+    for (int q = 0; q < hp.n_keys; ++q) {
+      const Column& c = rec.cols[(size_t)cols[k0 + (size_t)q]];
+      hp.keys[q] = key_of(c);
+      t.read += n * (c.type == T_UTF8 ? 8 + (c.length ? std::max<int64_t>(c.data_bytes, 0) / c.length : 0) : std::max(1, c.width));
+    }
+    check_hip(launch_agg_heads(hp, ctx.stream), "launch agg_heads_kernel");
+    ++ctx.stats.launches;
+    t.read += perm ? n * 4 : 0; t.written += n + ntiles * 4;
+    k0 += (size_t)hp.n_keys;
+  } while (k0 < cols.size());
+  AggGroupsParams gp{};
+  gp.perm = perm; gp.n = n; gp.heads = (const uint8_t*)heads->ptr; gp.tile_counts = (uint32_t*)counts->ptr; gp.ntiles = ntiles;
+  check_hip(launch_agg_head_scan(gp, ctx.stream), "launch agg_head_scan_kernel");
+  ++ctx.stats.launches;
+  uint32_t g32 = 0;
+  check_hip(hipMemcpyAsync(&g32, gp.tile_counts + ntiles, 4, hipMemcpyDeviceToHost, ctx.stream), "read back the run count");
+  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
+  r.G = (int64_t)g32;
+  if (r.G < 1 || r.G > n) throw ChqError{CHQ_ERR_DEVICE, "internal error: " + std::to_string(r.G) + " runs over " + std::to_string(n) + " rows"};
+  r.gids = make_device_buffer((size_t)n * 4 + 16, ctx.device);
+  r.starts = make_device_buffer((size_t)(r.G + 1) * 4 + 16, ctx.device);
+  // agg_head_write_kernel writes rep[] without a test: it is allocated for every caller, whether or not that caller reads it
+  r.rep = make_device_buffer((size_t)r.G * 4 + 16, ctx.device);
+  gp.gids = (uint32_t*)r.gids->ptr; gp.starts = (uint32_t*)r.starts->ptr; gp.rep = (uint32_t*)r.rep->ptr; gp.G = r.G;
+  check_hip(launch_agg_head_write(gp, ctx.stream), "launch agg_head_write_kernel");
+  ++ctx.stats.launches;
+  t.read += ntiles * 8 + n + (perm ? r.G * 4 : 0); t.written += ntiles * 4 + n * 4 + r.G * 8;
+  return r;
+}
 
 Batch aggregate_records(Context& ctx, std::vector<Batch>& in, const chq_table_aliases* aliases, const std::vector<const Expr*>& keys,
                         const std::vector<AggItemArg>& items) {
@@ -122,7 +150,7 @@ Batch aggregate_records(Context& ctx, std::vector<Batch>& in, const chq_table_al
     key_cols.push_back(resolve_key(*k, pcols, rows));
     sort_keys.push_back(SortKeyArg{k, false, false});
   }
-  std::vector<ItemPlan> plans(items.size());
+  std::vector<AggPlan> plans(items.size());
   for (size_t i = 0; i < items.size(); ++i) {
     const AggItemArg& it = items[i];
     if (it.kind == CHQ_AGG_KEY) {
@@ -130,13 +158,12 @@ Batch aggregate_records(Context& ctx, std::vector<Batch>& in, const chq_table_al
         throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "output column '" + it.name + "' names key " + std::to_string(it.key_index) + " of " +
                                                        std::to_string(keys.size())};
       plans[i].col = key_cols[(size_t)it.key_index];
-    } else if (it.kind == CHQ_AGG_COUNT_STAR) {
-      plans[i].format = "l";
-    } else {
+    } else if (it.kind != CHQ_AGG_COUNT_STAR) {
       if (it.kind < CHQ_AGG_COUNT || it.kind > CHQ_AGG_MAX)
         throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "unknown aggregate kind " + std::to_string(it.kind)};
-      const int col = resolve_argument(it, pcols, rows);
-      plans[i] = plan_aggregate(it, in[0].cols[(size_t)col]);
+      if (!it.column) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null column of ") + kind_name(it.kind)};
+      const int col = resolve_key(*it.column, pcols, rows, std::string("the argument of ") + kind_name(it.kind));
+      plans[i] = plan_aggregate((AggFn)(it.kind - CHQ_AGG_COUNT), kind_name(it.kind), in[0].cols[(size_t)col]);
       plans[i].col = col;
     }
   }
@@ -150,49 +177,17 @@ Batch aggregate_records(Context& ctx, std::vector<Batch>& in, const chq_table_al
   const BufferPtr perm_buf = sort_permutation(ctx, rec, key_cols, sort_keys, t);
   const uint32_t* perm = perm_buf ? (const uint32_t*)perm_buf->ptr : nullptr;
 
-  // ---- the groups: heads -> scan -> (read back G) -> ids, starts, representatives
-  int64_t G = 0;
-  BufferPtr gids, starts, rep;
+  // ---- the groups: ids, starts, representatives
+  Runs runs;
   if (n == 0) {
-    G = keys.empty() ? 1 : 0;   // no key: one group over no rows
-    starts = make_device_buffer((size_t)(G + 1) * 4 + 16, ctx.device);
-    check_hip(hipMemsetAsync(starts->ptr, 0, (size_t)(G + 1) * 4, ctx.stream), "hipMemsetAsync");
+    runs.G = keys.empty() ? 1 : 0;   // no key: one group over no rows
+    runs.starts = make_device_buffer((size_t)(runs.G + 1) * 4 + 16, ctx.device);
+    check_hip(hipMemsetAsync(runs.starts->ptr, 0, (size_t)(runs.G + 1) * 4, ctx.stream), "hipMemsetAsync");
   } else {
-    BufferPtr heads = make_device_buffer((size_t)ntiles * kAggTile + 16, ctx.device);
-    BufferPtr counts = make_device_buffer((size_t)(ntiles + 1) * 4 + 16, ctx.device);
-    AggHeadsParams hp{};
-    hp.perm = perm; hp.n = n; hp.heads = (uint8_t*)heads->ptr; hp.tile_counts = (uint32_t*)counts->ptr; hp.ntiles = ntiles;
-    size_t k0 = 0;
-    do {   // (no key: one launch that marks position 0)
-      hp.n_keys = (int32_t)std::min<size_t>(kAggMaxKeys, key_cols.size() - k0);
-      hp.accumulate = k0 ? 1 : 0;
-      for (int q = 0; q < hp.n_keys; ++q) {
-        const Column& c = rec.cols[(size_t)key_cols[k0 + (size_t)q]];
-        hp.keys[q] = key_of(c);
-        t.read += n * (c.type == T_UTF8 ? 8 + (c.length ? std::max<int64_t>(c.data_bytes, 0) / c.length : 0) : std::max(1, c.width));
-      }
-      check_hip(launch_agg_heads(hp, ctx.stream), "launch agg_heads_kernel");
-      ++ctx.stats.launches;
-      t.read += perm ? n * 4 : 0; t.written += n + ntiles * 4;
-      k0 += (size_t)hp.n_keys;
-    } while (k0 < key_cols.size());
-    AggGroupsParams gp{};
-    gp.perm = perm; gp.n = n; gp.heads = (const uint8_t*)heads->ptr; gp.tile_counts = (uint32_t*)counts->ptr; gp.ntiles = ntiles;
-    check_hip(launch_agg_head_scan(gp, ctx.stream), "launch agg_head_scan_kernel");
-    ++ctx.stats.launches;
-    uint32_t g32 = 0;
-    check_hip(hipMemcpyAsync(&g32, gp.tile_counts + ntiles, 4, hipMemcpyDeviceToHost, ctx.stream), "read back the group count");
-    check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-    G = (int64_t)g32;
-    if (G < 1 || G > n) throw ChqError{CHQ_ERR_DEVICE, "internal error: " + std::to_string(G) + " groups over " + std::to_string(n) + " rows"};
-    gids = make_device_buffer((size_t)n * 4 + 16, ctx.device);
-    starts = make_device_buffer((size_t)(G + 1) * 4 + 16, ctx.device);
-    rep = make_device_buffer((size_t)G * 4 + 16, ctx.device);
-    gp.gids = (uint32_t*)gids->ptr; gp.starts = (uint32_t*)starts->ptr; gp.rep = (uint32_t*)rep->ptr; gp.G = G;
-    check_hip(launch_agg_head_write(gp, ctx.stream), "launch agg_head_write_kernel");
-    ++ctx.stats.launches;
-    t.read += ntiles * 8 + n + (perm ? G * 4 : 0); t.written += ntiles * 4 + n * 4 + G * 8;
+    runs = find_runs(ctx, rec, perm, key_cols, t);
   }
+  const int64_t G = runs.G;
+  const BufferPtr &gids = runs.gids, &starts = runs.starts, &rep = runs.rep;
   ctx.stats.rows_out = G;
 
   // ---- one output column per item
@@ -205,7 +200,7 @@ Batch aggregate_records(Context& ctx, std::vector<Batch>& in, const chq_table_al
   out.nrows = G; out.on_device = true; out.device_id = ctx.device;
   for (size_t i = 0; i < ni; ++i) {
     const AggItemArg& it = items[i];
-    const ItemPlan& pl = plans[i];
+    const AggPlan& pl = plans[i];
     uint64_t* ones = (uint64_t*)words->ptr + i;
     if (it.kind == CHQ_AGG_KEY) {
       Column o = gather_column(ctx, rec.cols[(size_t)pl.col], rep ? (const uint32_t*)rep->ptr : nullptr, G, ones, t);
@@ -251,27 +246,15 @@ Batch aggregate_records(Context& ctx, std::vector<Batch>& in, const chq_table_al
       continue;
     }
     Column o = fixed_column(it.name, pl, true, G, values);
-    BufferPtr bits = make_device_buffer((size_t)((G + 31) / 32) * 4 + 16, ctx.device);
-    AggValidityParams vp{(const uint64_t*)cnt->ptr, G, (uint8_t*)bits->ptr, ones};
-    if (G > 0) { check_hip(launch_agg_validity(vp, ctx.stream), "launch agg_validity_kernel"); ++ctx.stats.launches; }
-    t.read += G * 8; t.written += (G + 7) / 8;
-    o.validity = (const uint8_t*)bits->ptr;
-    o.owned.push_back(bits);
-    o.null_count = -1;   // set from `ones` once read back
+    validity_from_counts(ctx, o, cnt, G, ones, t);
     out.cols.push_back(std::move(o));
   }
-  kernel_span_end(ctx);
-  std::vector<uint64_t> h(ni * 2);
-  check_hip(hipMemcpyAsync(h.data(), words->ptr, ni * 16, hipMemcpyDeviceToHost, ctx.stream), "read back null counts and overflow flags");
-  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  ctx.stats.kernel_ns += kernel_span_ns(ctx);
-  ctx.stats.bytes_read_alg = t.read; ctx.stats.bytes_written_alg = t.written;
-  for (size_t i = 0; i < ni; ++i) {
+  const std::vector<uint64_t> h = finish_call(ctx, words->ptr, ni * 2, t, "read back null counts and overflow flags");
+  for (size_t i = 0; i < ni; ++i)
     if (h[ni + i])
       throw ChqError{CHQ_ERR_ARROW_ARITHMETIC_OVERFLOW, "SUM over column '" + rec.cols[(size_t)plans[i].col].name + "' for output column '" +
                                                         items[i].name + "' overflows " + (plans[i].type == T_U64 ? "UInt64" : "Int64")};
-    if (out.cols[i].null_count < 0) out.cols[i].null_count = G - (int64_t)h[i];
-  }
+  fill_null_counts(out.cols, G, h);
   return out;
 }
 

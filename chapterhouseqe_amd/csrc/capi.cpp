@@ -44,13 +44,47 @@ void mark_released(ArrowDeviceArray* out, ArrowSchema* out_schema) {
   if (out_schema) { memset(out_schema, 0, sizeof(*out_schema)); }
 }
 
+void require_out_device(int out_device) {
+  if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
+    throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+}
+
 void finish(Context& c, Batch&& result_dev, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  require_out_device(out_device);
   if (out_device == ARROW_DEVICE_ROCM) export_batch(std::move(result_dev), ARROW_DEVICE_ROCM, out, out_schema);
-  else if (out_device == ARROW_DEVICE_CPU) { Batch h = to_host(c, result_dev); export_batch(std::move(h), ARROW_DEVICE_CPU, out, out_schema); }
-  else throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+  else { Batch h = to_host(c, result_dev); export_batch(std::move(h), ARROW_DEVICE_CPU, out, out_schema); }
 }
 
 void require(const void* p, const char* what) { if (!p) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null ") + what}; }
+
+// the *_record entries, handed no record (before the shared call, which takes the record in an array of one)
+chq_status null_record(chq_ctx* ctx, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
+  mark_released(out, out_schema);
+  ctx->c.last_error = "null record";
+  return CHQ_ERR_INVALID_HANDLE;
+}
+
+// the C arrays of a call as the engine takes them; a null element is CHQ_ERR_INVALID_HANDLE "null <what>"
+std::vector<const Expr*> expr_args(const chq_expr* const* keys, int n, const char* what) {
+  std::vector<const Expr*> args((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    require(keys[k], what);
+    args[(size_t)k] = &keys[k]->e;
+  }
+  return args;
+}
+
+std::vector<SortKeyArg> sort_key_args(const chq_sort_key* keys, int n, const char* what) {
+  std::vector<SortKeyArg> args((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    require(keys[k].column, what);
+    args[(size_t)k].column = &keys[k].column->e;
+    args[(size_t)k].descending = keys[k].descending != 0;
+    args[(size_t)k].nulls_first = keys[k].nulls_first != 0;
+  }
+  return args;
+}
 
 // f(i) for i in [0, n) on a few host threads when the group is large: importing / exporting 10^5 Arrow structs one after
 // the other (~0.3 + 0.4 us each) used to be 93 % of a group call (round 1).  The first error, if any, is rethrown.
@@ -58,6 +92,16 @@ template <class F>
 void for_each_parallel(int n, F&& f) {
   if (n < 2048) { for (int i = 0; i < n; ++i) f(i); return; }
   pool_ranges((size_t)n, 1024, [&](size_t i0, size_t i1) { for (size_t i = i0; i < i1; ++i) f((int)i); });
+}
+
+void require_each(int n, const ArrowDeviceArray* const* recs, const char* what) { for (int i = 0; i < n; ++i) require(recs[i], what); }
+
+// the batches of one group: every record is required before the first is imported
+std::vector<Batch> import_records(int n, const ArrowDeviceArray* const* recs, const ArrowSchema* schema, const char* what = "record") {
+  require_each(n, recs, what);
+  std::vector<Batch> in((size_t)n);
+  for_each_parallel(n, [&](int i) { in[(size_t)i] = import_batch(recs[i], schema); });
+  return in;
 }
 
 // ---- the outputs of a joined group call, exported from ONE block --------------------------------------------------------
@@ -386,8 +430,7 @@ chq_status chq_filter_records(chq_ctx* ctx, int n_records, const ArrowDeviceArra
     if (n_records < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative record count"};
     if (n_records == 0) return;
     require(recs, "record array"); require(outs, "output arrays"); require(out_schemas, "output schemas");
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    require_out_device(out_device);
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_filter_records");
     GroupInput gi;
@@ -426,8 +469,7 @@ chq_status chq_filter_records_coalesced(chq_ctx* ctx, int n_records, const Arrow
     require(expr, "expression"); require(out, "output array"); require(out_schema, "output schema");
     if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
     require(recs, "record array");
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    require_out_device(out_device);
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_filter_records_coalesced");
     GroupInput gi;
@@ -458,20 +500,11 @@ chq_status sort_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const*
     require(recs, "record array");
     if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative sort key count"};
     if (n_keys > 0) require(keys, "sort keys");
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
-    std::vector<SortKeyArg> args((size_t)n_keys);
-    for (int k = 0; k < n_keys; ++k) {
-      require(keys[k].column, "sort key column");
-      args[(size_t)k].column = &keys[k].column->e;
-      args[(size_t)k].descending = keys[k].descending != 0;
-      args[(size_t)k].nulls_first = keys[k].nulls_first != 0;
-    }
+    require_out_device(out_device);
+    const std::vector<SortKeyArg> args = sort_key_args(keys, n_keys, "sort key column");
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_sort_records");
-    std::vector<Batch> in((size_t)n_records);
-    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
-    for_each_parallel(n_records, [&](int i) { in[(size_t)i] = import_batch(recs[i], schema); });
+    std::vector<Batch> in = import_records(n_records, recs, schema);
     pt.mark("import");
     Batch res = sort_records(ctx->c, in, table_aliases, args, limit);
     pt.mark("sort");
@@ -485,7 +518,7 @@ chq_status chq_sort_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const Arro
                            const chq_sort_key* keys, int n_keys, int64_t limit, int out_device, ArrowDeviceArray* out,
                            ArrowSchema* out_schema) {
   const ArrowDeviceArray* recs[1] = {rec};
-  if (!rec) { if (!ctx) return CHQ_ERR_INVALID_HANDLE; mark_released(out, out_schema); ctx->c.last_error = "null record"; return CHQ_ERR_INVALID_HANDLE; }
+  if (!rec) return null_record(ctx, out, out_schema);
   return sort_call(ctx, 1, recs, schema, table_aliases, keys, n_keys, limit, out_device, out, out_schema);
 }
 
@@ -510,13 +543,8 @@ chq_status aggregate_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* c
     if (n_keys > 0) require(keys, "GROUP BY keys");
     if (n_items <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "GROUP BY needs at least one output item"};
     require(items, "output items");
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
-    std::vector<const Expr*> key_args((size_t)n_keys);
-    for (int k = 0; k < n_keys; ++k) {
-      require(keys[k], "GROUP BY key");
-      key_args[(size_t)k] = &keys[k]->e;
-    }
+    require_out_device(out_device);
+    const std::vector<const Expr*> key_args = expr_args(keys, n_keys, "GROUP BY key");
     std::vector<AggItemArg> item_args((size_t)n_items);
     for (int i = 0; i < n_items; ++i) {
       AggItemArg& a = item_args[(size_t)i];
@@ -527,9 +555,7 @@ chq_status aggregate_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* c
     }
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_aggregate_records");
-    std::vector<Batch> in((size_t)n_records);
-    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
-    for_each_parallel(n_records, [&](int i) { in[(size_t)i] = import_batch(recs[i], schema); });
+    std::vector<Batch> in = import_records(n_records, recs, schema);
     pt.mark("import");
     Batch res = aggregate_records(ctx->c, in, table_aliases, key_args, item_args);
     pt.mark("aggregate");
@@ -543,7 +569,7 @@ chq_status chq_aggregate_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const
                                 const chq_expr* const* keys, int n_keys, const chq_agg_item* items, int n_items, int out_device,
                                 ArrowDeviceArray* out, ArrowSchema* out_schema) {
   const ArrowDeviceArray* recs[1] = {rec};
-  if (!rec) { if (!ctx) return CHQ_ERR_INVALID_HANDLE; mark_released(out, out_schema); ctx->c.last_error = "null record"; return CHQ_ERR_INVALID_HANDLE; }
+  if (!rec) return null_record(ctx, out, out_schema);
   return aggregate_call(ctx, 1, recs, schema, table_aliases, keys, n_keys, items, n_items, out_device, out, out_schema);
 }
 
@@ -571,20 +597,9 @@ chq_status window_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* cons
     if (n_order_by > 0) require(order_by, "ORDER BY keys");
     if (n_items <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "a window call needs at least one item"};
     require(items, "window items");
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
-    std::vector<const Expr*> part_args((size_t)n_partition_by);
-    for (int k = 0; k < n_partition_by; ++k) {
-      require(partition_by[k], "PARTITION BY key");
-      part_args[(size_t)k] = &partition_by[k]->e;
-    }
-    std::vector<SortKeyArg> order_args((size_t)n_order_by);
-    for (int k = 0; k < n_order_by; ++k) {
-      require(order_by[k].column, "ORDER BY key column");
-      order_args[(size_t)k].column = &order_by[k].column->e;
-      order_args[(size_t)k].descending = order_by[k].descending != 0;
-      order_args[(size_t)k].nulls_first = order_by[k].nulls_first != 0;
-    }
+    require_out_device(out_device);
+    const std::vector<const Expr*> part_args = expr_args(partition_by, n_partition_by, "PARTITION BY key");
+    const std::vector<SortKeyArg> order_args = sort_key_args(order_by, n_order_by, "ORDER BY key column");
     std::vector<WinItemArg> item_args((size_t)n_items);
     for (int i = 0; i < n_items; ++i) {
       WinItemArg& a = item_args[(size_t)i];
@@ -595,9 +610,7 @@ chq_status window_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* cons
     }
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_window_records");
-    std::vector<Batch> in((size_t)n_records);
-    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
-    for_each_parallel(n_records, [&](int i) { in[(size_t)i] = import_batch(recs[i], schema); });
+    std::vector<Batch> in = import_records(n_records, recs, schema);
     pt.mark("import");
     Batch res = window_records(ctx->c, in, table_aliases, part_args, order_args, item_args);
     pt.mark("window");
@@ -611,7 +624,7 @@ chq_status chq_window_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const Ar
                              const chq_expr* const* partition_by, int n_partition_by, const chq_sort_key* order_by, int n_order_by,
                              const chq_window_item* items, int n_items, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
   const ArrowDeviceArray* recs[1] = {rec};
-  if (!rec) { if (!ctx) return CHQ_ERR_INVALID_HANDLE; mark_released(out, out_schema); ctx->c.last_error = "null record"; return CHQ_ERR_INVALID_HANDLE; }
+  if (!rec) return null_record(ctx, out, out_schema);
   return window_call(ctx, 1, recs, schema, table_aliases, partition_by, n_partition_by, order_by, n_order_by, items, n_items, out_device, out,
                      out_schema);
 }
@@ -648,8 +661,7 @@ chq_status chq_join_records_kind(chq_ctx* ctx, int n_left, const ArrowDeviceArra
       throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "unknown join kind " + std::to_string(kind) + " (a chq_join_kind is expected)"};
     if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative join key count"};
     if (n_keys > 0) require(keys, "join keys");
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    require_out_device(out_device);
     std::vector<JoinKeyArg> args((size_t)n_keys);
     for (int k = 0; k < n_keys; ++k) {
       require(keys[k].left, "left join key"); require(keys[k].right, "right join key");
@@ -658,11 +670,9 @@ chq_status chq_join_records_kind(chq_ctx* ctx, int n_left, const ArrowDeviceArra
     }
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_join_records_kind");
-    std::vector<Batch> in_l((size_t)n_left), in_r((size_t)n_right);
-    for (int i = 0; i < n_left; ++i) require(left[i], "left record");
-    for (int i = 0; i < n_right; ++i) require(right[i], "right record");
-    for_each_parallel(n_left, [&](int i) { in_l[(size_t)i] = import_batch(left[i], left_schema); });
-    for_each_parallel(n_right, [&](int i) { in_r[(size_t)i] = import_batch(right[i], right_schema); });
+    require_each(n_left, left, "left record"); require_each(n_right, right, "right record");   // (both sides before either is imported)
+    std::vector<Batch> in_l = import_records(n_left, left, left_schema, "left record");
+    std::vector<Batch> in_r = import_records(n_right, right, right_schema, "right record");
     pt.mark("import");
     Batch res = join_records(ctx->c, in_l, left_aliases, in_r, right_aliases, args, kind);
     pt.mark("join");
@@ -687,18 +697,11 @@ chq_status chq_partition_records(chq_ctx* ctx, int n_records, const ArrowDeviceA
       throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "n_partitions must be in [1, " + std::to_string(kPartMaxPartitions) + "] (" +
                                                      std::to_string(n_partitions) + " given)"};
     require(outs, "output arrays"); require(out_schemas, "output schemas");
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
-    std::vector<const Expr*> key_args((size_t)n_keys);
-    for (int k = 0; k < n_keys; ++k) {
-      require(keys[k], "partition key");
-      key_args[(size_t)k] = &keys[k]->e;
-    }
+    require_out_device(out_device);
+    const std::vector<const Expr*> key_args = expr_args(keys, n_keys, "partition key");
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_partition_records");
-    std::vector<Batch> in((size_t)n_records);
-    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
-    for_each_parallel(n_records, [&](int i) { in[(size_t)i] = import_batch(recs[i], schema); });
+    std::vector<Batch> in = import_records(n_records, recs, schema);
     pt.mark("import");
     JoinedGroup res = partition_records(ctx->c, in, table_aliases, key_args, n_partitions);
     pt.mark("partition");
@@ -752,9 +755,9 @@ chq_status chq_compute_value(chq_ctx* ctx, const ArrowDeviceArray* rec, const Ar
     // reuse the batch path for the host copy
     Batch one; one.nrows = col.length; one.on_device = true; one.device_id = ctx->c.device;
     one.cols.push_back(std::move(col));
+    require_out_device(out_device);
     if (out_device == ARROW_DEVICE_CPU) { Batch h = to_host(ctx->c, one); export_single_column(std::move(h.cols[0]), false, -1, out, out_schema); }
-    else if (out_device == ARROW_DEVICE_ROCM) export_single_column(std::move(one.cols[0]), true, ctx->c.device, out, out_schema);
-    else throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    else export_single_column(std::move(one.cols[0]), true, ctx->c.device, out, out_schema);
   });
 }
 
@@ -858,8 +861,7 @@ chq_status chq_record_from_ipc(chq_ctx* ctx, const uint8_t* stream, int64_t stre
   mark_released(out, out_schema);
   return guarded(ctx, [&] {
     require(out, "output array"); require(out_schema, "output schema"); require(stream, "stream");
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    require_out_device(out_device);
     if (body && body_device_type != ARROW_DEVICE_ROCM && body_device_type != ARROW_DEVICE_CPU)
       throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "body_device_type must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
@@ -942,8 +944,7 @@ chq_status chq_parquet_read_row_group(chq_ctx* ctx, const chq_parquet* pq, int32
   mark_released(out, out_schema);
   return guarded(ctx, [&] {
     require(out, "output array"); require(out_schema, "output schema");
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    require_out_device(out_device);
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     Batch res = parquet_read_row_group(ctx->c, pq->file, row_group);
     if (out_device == ARROW_DEVICE_CPU) res = to_host(ctx->c, res);
@@ -962,8 +963,7 @@ chq_status chq_parquet_read_columns(chq_ctx* ctx, const chq_parquet* pq, int32_t
   if (outs && out_schemas) for (int32_t i = 0; i < count; ++i) mark_released(&outs[i], &out_schemas[i]);
   return guarded(ctx, [&] {
     if (count > 0) { require(outs, "output arrays"); require(out_schemas, "output schemas"); }
-    if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
+    require_out_device(out_device);
     check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     if (!columns) n_columns = -1;
     std::vector<Batch> res = parquet_read_row_groups(ctx->c, pq->file, first, count, columns, n_columns);

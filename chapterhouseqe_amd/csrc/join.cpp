@@ -2,7 +2,7 @@
 // LEFT_SEMI and LEFT_ANTI.
 //
 // The key columns of both sides are concatenated into one key batch, RIGHT rows first, and ordered by the stable sort of
-// sort.cpp; the group-heads kernels of aggregate.hip then number the runs of equal keys.  Because the sort is stable and the
+// sort.cpp; GROUP BY's run finder (aggregate.hpp: find_runs) then numbers the runs of equal keys.  Because the sort is stable and the
 // right rows come first, a run lies in the sorted positions as [its right rows in input order][its left rows in input order].
 // The kernels of join.hip find where the left rows of every run begin, count the matches of every left row, scan the counts
 // over the left rows in input order and expand them into two row-id lists, which gather_column turns into the output columns.
@@ -32,9 +32,7 @@ constexpr int64_t kMaxJoinRows = (int64_t)1 << 32;   // sorted positions, row id
 
 int resolve_join_key(const Expr* e, const char* side, const std::vector<PlanColumn>& pcols, int64_t rows) {
   if (!e) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null ") + side + " join key"};
-  if (e->kind != Expr::IDENT && e->kind != Expr::COMPOUND)
-    throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("a join key must be a column, not ") + (e->text.empty() ? std::string("an expression") : e->text)};
-  return resolve_key(*e, pcols, rows);
+  return resolve_key(*e, pcols, rows, "a join key");
 }
 
 // The key columns of one side as batches of their own, appended to `out`: zero-copy views under the names both sides share,
@@ -103,51 +101,16 @@ Batch join_resolved(Context& ctx, std::vector<Batch>& left, std::vector<Batch>& 
     const BufferPtr perm_buf = sort_permutation(ctx, K, key_cols, sort_keys, t);
     const uint32_t* perm = perm_buf ? (const uint32_t*)perm_buf->ptr : nullptr;
 
-    // ---- 5. the runs of equal keys: heads -> scan -> (read back G) -> ids, starts
-    BufferPtr heads = make_device_buffer((size_t)ntiles * kAggTile + 16, ctx.device);
-    BufferPtr counts = make_device_buffer((size_t)(ntiles + 1) * 4 + 16, ctx.device);
-    AggHeadsParams hp{};
-    hp.perm = perm; hp.n = n; hp.heads = (uint8_t*)heads->ptr; hp.tile_counts = (uint32_t*)counts->ptr; hp.ntiles = ntiles;
-    for (size_t k0 = 0; k0 < key_cols.size(); k0 += (size_t)hp.n_keys) {
-      hp.n_keys = (int32_t)std::min<size_t>(kAggMaxKeys, key_cols.size() - k0);
-      hp.accumulate = k0 ? 1 : 0;
-      for (int q = 0; q < hp.n_keys; ++q) {
-        const Column& c = K.cols[k0 + (size_t)q];
-        AggKey& key = hp.keys[q];
-        key = AggKey{};
-        key.validity = c.validity && c.null_count != 0 ? c.validity : nullptr;
-        key.bit_offset = c.offset;
-        key.values = (const uint8_t*)c.values0();
-        key.data = c.data;
-        key.kind = c.type == T_BOOL ? AK_BOOL : c.type == T_UTF8 ? AK_UTF8 : AK_FIXED;
-        key.width = c.width;
-        t.read += n * (c.type == T_UTF8 ? 8 + (c.length ? std::max<int64_t>(c.data_bytes, 0) / c.length : 0) : std::max(1, c.width));
-      }
-      check_hip(launch_agg_heads(hp, ctx.stream), "launch agg_heads_kernel");
-      ++ctx.stats.launches;
-      t.read += perm ? n * 4 : 0; t.written += n + ntiles * 4;
-    }
-    AggGroupsParams gp{};
-    gp.perm = perm; gp.n = n; gp.heads = (const uint8_t*)heads->ptr; gp.tile_counts = (uint32_t*)counts->ptr; gp.ntiles = ntiles;
-    check_hip(launch_agg_head_scan(gp, ctx.stream), "launch agg_head_scan_kernel");
-    ++ctx.stats.launches;
-    uint32_t g32 = 0;
-    check_hip(hipMemcpyAsync(&g32, gp.tile_counts + ntiles, 4, hipMemcpyDeviceToHost, ctx.stream), "read back the run count");
-    check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-    const int64_t G = (int64_t)g32;
-    if (G < 1 || G > n) throw ChqError{CHQ_ERR_DEVICE, "internal error: " + std::to_string(G) + " key runs over " + std::to_string(n) + " rows"};
-    BufferPtr gids = make_device_buffer((size_t)n * 4 + 16, ctx.device);
-    BufferPtr starts = make_device_buffer((size_t)(G + 1) * 4 + 16, ctx.device);
-    BufferPtr rep = make_device_buffer((size_t)G * 4 + 16, ctx.device);
-    gp.gids = (uint32_t*)gids->ptr; gp.starts = (uint32_t*)starts->ptr; gp.rep = (uint32_t*)rep->ptr; gp.G = G;
-    check_hip(launch_agg_head_write(gp, ctx.stream), "launch agg_head_write_kernel");
-    ++ctx.stats.launches;
-    t.read += ntiles * 8 + n + (perm ? G * 4 : 0); t.written += ntiles * 4 + n * 4 + G * 8;
+    // ---- 5. the runs of equal keys: ids, starts
+    const Runs runs = find_runs(ctx, K, perm, key_cols, t);
+    const int64_t G = runs.G;
+    const uint32_t* const gids = (const uint32_t*)runs.gids->ptr;
+    const uint32_t* const starts = (const uint32_t*)runs.starts->ptr;
 
     // ---- 6. split -> count -> scan (read back M) -> expand
     BufferPtr split = make_device_buffer((size_t)G * 4 + 16, ctx.device);
     JoinSplitParams sp{};
-    sp.perm = perm; sp.n = n; sp.n_right = nR; sp.gids = gp.gids; sp.starts = gp.starts; sp.split = (uint32_t*)split->ptr;
+    sp.perm = perm; sp.n = n; sp.n_right = nR; sp.gids = gids; sp.starts = starts; sp.split = (uint32_t*)split->ptr;
     for (size_t k0 = 0; k0 < key_cols.size(); k0 += (size_t)sp.n_keys) {
       sp.n_keys = (int32_t)std::min<size_t>(kAggMaxKeys, key_cols.size() - k0);
       sp.nulls_only = k0 ? 1 : 0;
@@ -169,7 +132,7 @@ Batch join_resolved(Context& ctx, std::vector<Batch>& left, std::vector<Batch>& 
     BufferPtr off = make_device_buffer((size_t)nL * 4 + 16, ctx.device);
     BufferPtr sums = make_device_buffer((size_t)(ltiles + 1) * 8 + 16, ctx.device);
     JoinCountParams cp{};
-    cp.perm = perm; cp.n = n; cp.n_right = nR; cp.gids = gp.gids; cp.starts = gp.starts; cp.split = sp.split;
+    cp.perm = perm; cp.n = n; cp.n_right = nR; cp.gids = gids; cp.starts = starts; cp.split = sp.split;
     cp.cnt = (uint32_t*)cnt->ptr; cp.first = (uint32_t*)first->ptr;
     if (kind == CHQ_JOIN_INNER) {
       check_hip(launch_join_count(cp, ctx.stream), "launch join_count_kernel");
@@ -194,7 +157,7 @@ Batch join_resolved(Context& ctx, std::vector<Batch>& left, std::vector<Batch>& 
       flag = make_device_buffer((size_t)nR * 4 + 16, ctx.device);
       roff = make_device_buffer((size_t)nR * 4 + 16, ctx.device);
       rsums = make_device_buffer((size_t)(rtiles + 1) * 8 + 16, ctx.device);
-      tp.perm = perm; tp.n = n; tp.n_right = nR; tp.gids = gp.gids; tp.starts = gp.starts; tp.split = sp.split;
+      tp.perm = perm; tp.n = n; tp.n_right = nR; tp.gids = gids; tp.starts = starts; tp.split = sp.split;
       tp.flag = (uint32_t*)flag->ptr; tp.off = (const uint32_t*)roff->ptr;
       check_hip(launch_join_tail_flag(tp, ctx.stream), "launch join_tail_flag_kernel");
       ++ctx.stats.launches;
@@ -250,14 +213,7 @@ Batch join_resolved(Context& ctx, std::vector<Batch>& left, std::vector<Batch>& 
     const BufferPtr& idx = is_left ? lidx : ridx;
     out.cols.push_back(gather_column(ctx, c, idx ? (const uint32_t*)idx->ptr : nullptr, M, (uint64_t*)ones->ptr + ci, t, is_left ? pad_left : pad_right));
   }
-  kernel_span_end(ctx);
-  std::vector<uint64_t> h(nc);
-  if (nc) check_hip(hipMemcpyAsync(h.data(), ones->ptr, nc * 8, hipMemcpyDeviceToHost, ctx.stream), "read back null counts");
-  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  for (size_t ci = 0; ci < nc; ++ci)
-    if (out.cols[ci].null_count < 0) out.cols[ci].null_count = M - (int64_t)h[ci];
-  ctx.stats.kernel_ns += kernel_span_ns(ctx);
-  ctx.stats.bytes_read_alg = t.read; ctx.stats.bytes_written_alg = t.written;
+  fill_null_counts(out.cols, M, finish_call(ctx, ones->ptr, nc, t));
   return out;
 }
 

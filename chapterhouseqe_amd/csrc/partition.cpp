@@ -36,9 +36,7 @@ JoinedGroup partition_records(Context& ctx, std::vector<Batch>& in, const chq_ta
   std::vector<int> cols;
   for (const Expr* e : keys) {
     if (!e) throw ChqError{CHQ_ERR_INVALID_HANDLE, "null partition key"};
-    if (e->kind != Expr::IDENT && e->kind != Expr::COMPOUND)
-      throw ChqError{CHQ_ERR_NOT_SUPPORTED, "a partition key must be a column, not " + (e->text.empty() ? std::string("an expression") : e->text)};
-    const int c = resolve_key(*e, pcols, rows);
+    const int c = resolve_key(*e, pcols, rows, "a partition key");
     const Column& col = in[0].cols[(size_t)c];
     if (!sortable(col))
       throw ChqError{CHQ_ERR_NOT_SUPPORTED, "partition key '" + col.name + "' has Arrow type '" + col.format + "', which has no order in this build"};
@@ -110,14 +108,7 @@ JoinedGroup partition_records(Context& ctx, std::vector<Batch>& in, const chq_ta
   check_hip(hipMemsetAsync(ones->ptr, 0, nc * 8 + 16, ctx.stream), "hipMemsetAsync");
   out.joined.nrows = n; out.joined.on_device = true; out.joined.device_id = ctx.device;
   for (size_t ci = 0; ci < nc; ++ci) out.joined.cols.push_back(gather_column(ctx, rec.cols[ci], perm, n, (uint64_t*)ones->ptr + ci, t));
-  kernel_span_end(ctx);
-  std::vector<uint64_t> h(nc);
-  if (nc) check_hip(hipMemcpyAsync(h.data(), ones->ptr, nc * 8, hipMemcpyDeviceToHost, ctx.stream), "read back null counts");
-  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  for (size_t ci = 0; ci < nc; ++ci)
-    if (out.joined.cols[ci].null_count < 0) out.joined.cols[ci].null_count = n - (int64_t)h[ci];
-  ctx.stats.kernel_ns += kernel_span_ns(ctx);
-  ctx.stats.bytes_read_alg = t.read; ctx.stats.bytes_written_alg = t.written;
+  fill_null_counts(out.joined.cols, n, finish_call(ctx, ones->ptr, nc, t));
   return out;
 }
 

@@ -61,9 +61,7 @@ std::vector<SortNormParams> key_words(Context& ctx, const Column& c, const SortK
       break;
     }
     case T_FIXED_OPAQUE:
-      // temporal types order as their signed integers, decimals as signed integers of their width
-      if (f == "tdD" || f == "tts" || f == "ttm" || f == "tdm" || f == "ttu" || f == "ttn" || f.rfind("ts", 0) == 0 ||
-          f.rfind("tD", 0) == 0 || (f.rfind("d:", 0) == 0 && c.width <= 8)) {
+      if (orders_as_signed(c)) {
         add(SW_SIGNED);
       } else if (f.rfind("d:", 0) == 0 && c.width == 16) {
         add(SW_DEC_LO, 8); add(SW_DEC_HI, 8);
@@ -79,24 +77,29 @@ std::vector<SortNormParams> key_words(Context& ctx, const Column& c, const SortK
 
 }  // namespace
 
+// temporal types order as their signed integers, decimals of up to 8 bytes as signed integers of their width
+bool orders_as_signed(const Column& c) {
+  const std::string& f = c.format;
+  return c.type == T_FIXED_OPAQUE &&
+         (f == "tdD" || f == "tts" || f == "ttm" || f == "tdm" || f == "ttu" || f == "ttn" || f.rfind("ts", 0) == 0 ||
+          f.rfind("tD", 0) == 0 || (f.rfind("d:", 0) == 0 && c.width <= 8));
+}
+
 // the key types of ORDER BY (key_words above), which JOIN and the hash partitioning share
 bool sortable(const Column& c) {
-  const std::string& f = c.format;
   switch (c.type) {
     case T_BOOL: case T_I8: case T_I16: case T_I32: case T_I64: case T_U8: case T_U16: case T_U32: case T_U64:
     case T_F16: case T_F32: case T_F64: case T_UTF8:
       return true;
-    case T_FIXED_OPAQUE:
-      return f == "tdD" || f == "tts" || f == "ttm" || f == "tdm" || f == "ttu" || f == "ttn" || f.rfind("ts", 0) == 0 || f.rfind("tD", 0) == 0 ||
-             (f.rfind("d:", 0) == 0 && (c.width <= 8 || c.width == 16));
+    case T_FIXED_OPAQUE: return orders_as_signed(c) || (c.format.rfind("d:", 0) == 0 && c.width == 16);
     default: return false;
   }
 }
 
-// the column a sort key names: the resolver of compute_value (plan.cpp), which must come back with a bare column
-int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nrows) {
+// the column an argument names: the resolver of compute_value (plan.cpp), which must come back with a bare column
+int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nrows, const std::string& what) {
   if (e.kind != Expr::IDENT && e.kind != Expr::COMPOUND)
-    throw ChqError{CHQ_ERR_NOT_SUPPORTED, "a sort key must be a column, not " + (e.text.empty() ? std::string("an expression") : e.text)};
+    throw ChqError{CHQ_ERR_NOT_SUPPORTED, what + " must be a column, not " + (e.text.empty() ? std::string("an expression") : e.text)};
   TypedExpr te = type_expr(e, pcols, std::max<int64_t>(nrows, 2), false);
   if (te.pending_code) throw ChqError{te.pending_code, te.pending_msg};
   const Node& root = te.at(te.root);
@@ -247,15 +250,23 @@ Batch sort_records(Context& ctx, std::vector<Batch>& in, const chq_table_aliases
   check_hip(hipMemsetAsync(ones->ptr, 0, rec.cols.size() * 8, ctx.stream), "hipMemsetAsync");
   for (size_t ci = 0; ci < rec.cols.size(); ++ci)
     out.cols.push_back(gather_column(ctx, rec.cols[ci], perm, m, (uint64_t*)ones->ptr + ci, t));
+  fill_null_counts(out.cols, m, finish_call(ctx, ones->ptr, rec.cols.size(), t));
+  return out;
+}
+
+std::vector<uint64_t> finish_call(Context& ctx, const void* words, size_t n, const Traffic& t, const char* what) {
   kernel_span_end(ctx);
-  std::vector<uint64_t> h(rec.cols.size());
-  if (!h.empty()) check_hip(hipMemcpyAsync(h.data(), ones->ptr, h.size() * 8, hipMemcpyDeviceToHost, ctx.stream), "read back null counts");
+  std::vector<uint64_t> h(n);
+  if (n) check_hip(hipMemcpyAsync(h.data(), words, n * 8, hipMemcpyDeviceToHost, ctx.stream), what);
   check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  for (size_t ci = 0; ci < out.cols.size(); ++ci)
-    if (out.cols[ci].null_count < 0) out.cols[ci].null_count = m - (int64_t)h[ci];
   ctx.stats.kernel_ns += kernel_span_ns(ctx);
   ctx.stats.bytes_read_alg = t.read; ctx.stats.bytes_written_alg = t.written;
-  return out;
+  return h;
+}
+
+void fill_null_counts(std::vector<Column>& cols, int64_t rows, const std::vector<uint64_t>& ones) {
+  for (size_t ci = 0; ci < cols.size(); ++ci)
+    if (cols[ci].null_count < 0) cols[ci].null_count = rows - (int64_t)ones[ci];
 }
 
 }  // namespace chq

@@ -1,6 +1,7 @@
 // sort.hpp -- ORDER BY: the stable multi-key sort of a record batch, or of a group of them joined into one (sort.cpp).
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "engine.hpp"
@@ -30,9 +31,13 @@ struct Traffic {
   int64_t read = 0, written = 0;
 };
 
-// The pieces of the sort that GROUP BY (aggregate.cpp) stands on.
-// the column a sort key names: the resolver of compute_value (plan.cpp), which must come back with a bare column
-int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nrows);
+// The pieces of the sort that the operators on top of it (aggregate.cpp, join.cpp, window.cpp, partition.cpp) stand on.
+// the column an argument names: the resolver of compute_value (plan.cpp), which must come back with a bare column.  `what`
+// says which argument in "<what> must be a column, not <text>"
+int resolve_key(const Expr& e, const std::vector<PlanColumn>& pcols, int64_t nrows, const std::string& what = "a sort key");
+// temporal types and decimals of up to 8 bytes: they order, and MIN / MAX compare them, as their signed integers.  The ONE
+// place the list of their formats stands: the key words, sortable() and the typing of the aggregates all ask here.
+bool orders_as_signed(const Column& c);
 // does the column's type have an order here?  The key types of ORDER BY, JOIN (join.cpp) and the hash partitioning (partition.cpp)
 bool sortable(const Column& c);
 // out row i = in row perm[i] (perm null: identity) for rows [0, m), on the device; a validity bitmap's set bits are added to
@@ -42,6 +47,12 @@ bool sortable(const Column& c);
 Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_t m, uint64_t* ones, Traffic& t, bool pad = false);
 // the permutation of rows [0, n) that orders `rec` by `keys` on the columns `cols` (null: identity -- no key, or fewer than 2 rows)
 BufferPtr sort_permutation(Context& ctx, const Batch& rec, const std::vector<int>& cols, const std::vector<SortKeyArg>& keys, Traffic& t);
+
+// The end of an operator's call: closes the kernel span, copies the call's `n` counter words (u64: set validity bits, overflow
+// flags) back -- nothing when n is 0 --, synchronises the stream and sets kernel_ns and the two byte counters of ctx.stats.
+std::vector<uint64_t> finish_call(Context& ctx, const void* words, size_t n, const Traffic& t, const char* what = "read back null counts");
+// every null_count that gather_column (or validity_from_counts, aggregate.hpp) left at -1: rows - ones[i] for column i
+void fill_null_counts(std::vector<Column>& cols, int64_t rows, const std::vector<uint64_t>& ones);
 
 // The batches of `in` (one schema, host or device resident) in key order, stable (batch order, then row order), cut to
 // the first `limit` rows (-1: all).  The result is ONE device batch with the schema of the input.  Throws ChqError.

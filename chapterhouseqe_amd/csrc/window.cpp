@@ -8,7 +8,7 @@
 // Read-backs besides the sort's and the gathers': the partitions, the peer groups when needed, and ONE block of null
 // counts and overflow flags at the end.  DESIGN.md section 3.10.
 //
-// The run finder and the aggregate typing restate aggregate.cpp's: GROUP BY's code and launch sequence stay what they are.
+// The run finder (find_runs) and the typing of the aggregates (plan_aggregate) are GROUP BY's own: aggregate.hpp.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -39,125 +39,8 @@ bool is_ranking(int kind) { return kind >= CHQ_WIN_ROW_NUMBER && kind <= CHQ_WIN
 bool is_shift(int kind) { return kind == CHQ_WIN_LAG || kind == CHQ_WIN_LEAD; }
 bool needs_column(int kind) { return is_shift(kind) || (kind >= CHQ_WIN_COUNT && kind <= CHQ_WIN_MAX); }
 
-// temporal types and decimals of up to 8 bytes: MIN / MAX order them as their signed integers (aggregate.cpp)
-bool orders_as_signed(const Column& c) {
-  const std::string& f = c.format;
-  return c.type == T_FIXED_OPAQUE &&
-         (f == "tdD" || f == "tts" || f == "ttm" || f == "tdm" || f == "ttu" || f == "ttn" || f.rfind("ts", 0) == 0 ||
-          f.rfind("tD", 0) == 0 || (f.rfind("d:", 0) == 0 && c.width <= 8));
-}
-
-// what one output item does, decided against the schema before any data moves
-struct ItemPlan {
-  int col = -1;                 // argument column
-  int op = AO_COUNT;
-  int value_kind = AV_SIGNED;
-  std::string format = "l";     // output type of the ranking kinds and the aggregates
-  DType type = T_I64;
-  int width = 8;
-};
-
-// the typing of chq_aggregate_records (aggregate.cpp: plan_aggregate)
-ItemPlan plan_aggregate(const WinItemArg& it, const Column& c) {
-  ItemPlan pl;
-  const bool is_signed = c.type >= T_I8 && c.type <= T_I64, is_unsigned = c.type >= T_U8 && c.type <= T_U64;
-  const bool is_float = c.type == T_F16 || c.type == T_F32 || c.type == T_F64;
-  auto unsupported = [&]() {
-    return ChqError{CHQ_ERR_NOT_SUPPORTED, std::string(kind_name(it.kind)) + " over column '" + c.name + "' of Arrow type '" + c.format +
-                                           "' is not supported in this build"};
-  };
-  pl.value_kind = is_unsigned ? AV_UNSIGNED : is_float ? AV_FLOAT : AV_SIGNED;
-  switch (it.kind) {
-    case CHQ_WIN_COUNT:
-      pl.op = AO_COUNT;
-      break;
-    case CHQ_WIN_SUM:
-      if (is_signed) { pl.op = AO_SUM_INT; }
-      else if (is_unsigned) { pl.op = AO_SUM_INT; pl.format = "L"; pl.type = T_U64; }
-      else if (c.type == T_F32 || c.type == T_F64) { pl.op = AO_SUM_FLOAT; pl.format = "g"; pl.type = T_F64; }
-      else throw unsupported();
-      break;
-    default:   // CHQ_WIN_MIN, CHQ_WIN_MAX
-      if (!(is_signed || is_unsigned || is_float || orders_as_signed(c))) throw unsupported();
-      pl.op = it.kind == CHQ_WIN_MIN ? AO_MIN : AO_MAX;
-      pl.format = c.format; pl.type = c.type; pl.width = c.width;
-      break;
-  }
-  return pl;
-}
-
-int resolve_column(const Expr* e, const char* what, const std::vector<PlanColumn>& pcols, int64_t rows) {
-  if (e->kind != Expr::IDENT && e->kind != Expr::COMPOUND)
-    throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string(what) + " must be a column, not " + (e->text.empty() ? std::string("an expression") : e->text)};
-  return resolve_key(*e, pcols, rows);
-}
-
-AggKey key_of(const Column& c) {
-  AggKey k{};
-  k.validity = c.validity && c.null_count != 0 ? c.validity : nullptr;
-  k.bit_offset = c.offset;
-  k.values = (const uint8_t*)c.values0();
-  k.data = c.data;
-  k.kind = c.type == T_BOOL ? AK_BOOL : c.type == T_UTF8 ? AK_UTF8 : AK_FIXED;
-  k.width = c.width;
-  return k;
-}
-
-// the runs of equal keys among the sorted positions
-struct Runs {
-  BufferPtr gids, starts;   // [n], [G + 1]
-  int64_t G = 0;
-};
-
-// GROUP BY's heads -> scan -> (read back G) -> write over `cols` (aggregate.cpp); n >= 1
-Runs find_runs(Context& ctx, const Batch& rec, const uint32_t* perm, const std::vector<int>& cols, Traffic& t) {
-  const int64_t n = rec.nrows, ntiles = (n + kAggTile - 1) / kAggTile;
-  Runs r;
-  BufferPtr heads = make_device_buffer((size_t)ntiles * kAggTile + 16, ctx.device);
-  BufferPtr counts = make_device_buffer((size_t)(ntiles + 1) * 4 + 16, ctx.device);
-  AggHeadsParams hp{};
-  hp.perm = perm; hp.n = n; hp.heads = (uint8_t*)heads->ptr; hp.tile_counts = (uint32_t*)counts->ptr; hp.ntiles = ntiles;
-  size_t k0 = 0;
-  do {   // (no key: one launch that marks position 0)
-    hp.n_keys = (int32_t)std::min<size_t>(kAggMaxKeys, cols.size() - k0);
-    hp.accumulate = k0 ? 1 : 0;
-    for (int q = 0; q < hp.n_keys; ++q) {
-      const Column& c = rec.cols[(size_t)cols[k0 + (size_t)q]];
-      hp.keys[q] = key_of(c);
-      t.read += n * (c.type == T_UTF8 ? 8 + (c.length ? std::max<int64_t>(c.data_bytes, 0) / c.length : 0) : std::max(1, c.width));
-    }
-    check_hip(launch_agg_heads(hp, ctx.stream), "launch agg_heads_kernel");
-    ++ctx.stats.launches;
-    t.read += perm ? n * 4 : 0; t.written += n + ntiles * 4;
-    k0 += (size_t)hp.n_keys;
-  } while (k0 < cols.size());
-  AggGroupsParams gp{};
-  gp.perm = perm; gp.n = n; gp.heads = (const uint8_t*)heads->ptr; gp.tile_counts = (uint32_t*)counts->ptr; gp.ntiles = ntiles;
-  check_hip(launch_agg_head_scan(gp, ctx.stream), "launch agg_head_scan_kernel");
-  ++ctx.stats.launches;
-  uint32_t g32 = 0;
-  check_hip(hipMemcpyAsync(&g32, gp.tile_counts + ntiles, 4, hipMemcpyDeviceToHost, ctx.stream), "read back the run count");
-  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  r.G = (int64_t)g32;
-  if (r.G < 1 || r.G > n) throw ChqError{CHQ_ERR_DEVICE, "internal error: " + std::to_string(r.G) + " runs over " + std::to_string(n) + " rows"};
-  r.gids = make_device_buffer((size_t)n * 4 + 16, ctx.device);
-  r.starts = make_device_buffer((size_t)(r.G + 1) * 4 + 16, ctx.device);
-  BufferPtr rep = make_device_buffer((size_t)r.G * 4 + 16, ctx.device);
-  gp.gids = (uint32_t*)r.gids->ptr; gp.starts = (uint32_t*)r.starts->ptr; gp.rep = (uint32_t*)rep->ptr; gp.G = r.G;
-  check_hip(launch_agg_head_write(gp, ctx.stream), "launch agg_head_write_kernel");
-  ++ctx.stats.launches;
-  t.read += ntiles * 8 + n + (perm ? r.G * 4 : 0); t.written += ntiles * 4 + n * 4 + r.G * 8;
-  return r;
-}
-
-Column fixed_column(const std::string& name, const ItemPlan& pl, bool nullable, int64_t n, const BufferPtr& values) {
-  Column o;
-  o.name = name; o.format = pl.format; o.type = pl.type; o.width = pl.width; o.nullable = nullable;
-  o.length = n; o.offset = 0; o.null_count = 0;
-  o.values = (const uint8_t*)values->ptr;
-  o.owned.push_back(values);
-  return o;
-}
+static_assert(CHQ_WIN_SUM - CHQ_WIN_COUNT == AGG_FN_SUM && CHQ_WIN_MIN - CHQ_WIN_COUNT == AGG_FN_MIN && CHQ_WIN_MAX - CHQ_WIN_COUNT == AGG_FN_MAX,
+              "chq_window_kind numbers COUNT, SUM, MIN, MAX like AggFn");
 
 }  // namespace
 
@@ -175,7 +58,7 @@ Batch window_records(Context& ctx, std::vector<Batch>& in, const chq_table_alias
   std::vector<SortKeyArg> sort_keys;
   auto add_key = [&](const Expr* e, const char* what, bool descending, bool nulls_first) {
     if (!e) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null ") + what};
-    const int c = resolve_column(e, what, pcols, rows);
+    const int c = resolve_key(*e, pcols, rows, what);
     const Column& col = in[0].cols[(size_t)c];
     if (!sortable(col))
       throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string(what) + " '" + col.name + "' has Arrow type '" + col.format + "', which has no order in this build"};
@@ -187,7 +70,7 @@ Batch window_records(Context& ctx, std::vector<Batch>& in, const chq_table_alias
   const std::vector<int> part_cols(key_cols.begin(), key_cols.begin() + (std::ptrdiff_t)partition_by.size());
 
   const size_t ni = items.size();
-  std::vector<ItemPlan> plans(ni);
+  std::vector<AggPlan> plans(ni);
   bool need_peers = false;
   for (size_t i = 0; i < ni; ++i) {
     const WinItemArg& it = items[i];
@@ -203,15 +86,15 @@ Batch window_records(Context& ctx, std::vector<Batch>& in, const chq_table_alias
       if (it.offset < 0)
         throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, std::string(kind_name(it.kind)) + " for output column '" + it.name + "' has the negative offset " +
                                                        std::to_string(it.offset)};
-      plans[i].col = resolve_column(it.column, (std::string("the argument of ") + kind_name(it.kind)).c_str(), pcols, rows);
+      plans[i].col = resolve_key(*it.column, pcols, rows, std::string("the argument of ") + kind_name(it.kind));
       continue;
     }
     if (it.frame < CHQ_FRAME_PARTITION || it.frame > CHQ_FRAME_RANGE_TO_CURRENT)
       throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "unknown window frame " + std::to_string(it.frame) + " of output column '" + it.name + "'"};
     need_peers |= it.frame == CHQ_FRAME_RANGE_TO_CURRENT;
     if (it.kind == CHQ_WIN_COUNT_STAR) continue;
-    const int col = resolve_column(it.column, (std::string("the argument of ") + kind_name(it.kind)).c_str(), pcols, rows);
-    plans[i] = plan_aggregate(it, in[0].cols[(size_t)col]);
+    const int col = resolve_key(*it.column, pcols, rows, std::string("the argument of ") + kind_name(it.kind));
+    plans[i] = plan_aggregate((AggFn)(it.kind - CHQ_WIN_COUNT), kind_name(it.kind), in[0].cols[(size_t)col]);
     plans[i].col = col;
   }
 
@@ -269,7 +152,7 @@ Batch window_records(Context& ctx, std::vector<Batch>& in, const chq_table_alias
   BufferPtr scan_a, scan_b, scan_cnt, tile_tot, tile_carry;   // the scan's scratch, shared by the items (one stream: one at a time)
   for (size_t i = 0; i < ni; ++i) {
     const WinItemArg& it = items[i];
-    const ItemPlan& pl = plans[i];
+    const AggPlan& pl = plans[i];
     if (is_ranking(it.kind)) {
       const BufferPtr values = n > 0 ? rank_values[it.kind] : make_device_buffer(16, ctx.device);
       out.cols.push_back(fixed_column(it.name, pl, false, n, values));
@@ -337,29 +220,17 @@ Batch window_records(Context& ctx, std::vector<Batch>& in, const chq_table_alias
     }
     // validity: the per-row counts were scattered in input order; the bitmap is packed from them contiguously
     Column o = fixed_column(it.name, pl, true, n, values);
-    BufferPtr bits = make_device_buffer((size_t)((n + 31) / 32) * 4 + 16, ctx.device);
-    AggValidityParams vp{(const uint64_t*)cnt->ptr, n, (uint8_t*)bits->ptr, ones + nc + i};
-    if (n > 0) { check_hip(launch_agg_validity(vp, ctx.stream), "launch agg_validity_kernel"); ++ctx.stats.launches; }
-    t.read += n * 8; t.written += (n + 7) / 8;
-    o.validity = (const uint8_t*)bits->ptr;
-    o.owned.push_back(bits);
-    o.null_count = -1;   // set from `ones` once read back
+    validity_from_counts(ctx, o, cnt, n, ones + nc + i, t);
     out.cols.push_back(std::move(o));
   }
-  kernel_span_end(ctx);
   // ---- 6. ONE read-back: null counts and overflow flags
-  std::vector<uint64_t> h(nc + 2 * ni);
-  check_hip(hipMemcpyAsync(h.data(), words->ptr, h.size() * 8, hipMemcpyDeviceToHost, ctx.stream), "read back null counts and overflow flags");
-  check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
-  ctx.stats.kernel_ns += kernel_span_ns(ctx);
-  ctx.stats.bytes_read_alg = t.read; ctx.stats.bytes_written_alg = t.written;
+  const std::vector<uint64_t> h = finish_call(ctx, words->ptr, nc + 2 * ni, t, "read back null counts and overflow flags");
   for (size_t i = 0; i < ni; ++i)
     if (h[nc + ni + i])
       throw ChqError{CHQ_ERR_ARROW_ARITHMETIC_OVERFLOW, "SUM over column '" + rec.cols[(size_t)plans[i].col].name + "' for output column '" +
                                                         items[i].name + "' overflows " + (plans[i].type == T_U64 ? "UInt64" : "Int64") +
                                                         " in the frame of some row"};
-  for (size_t ci = 0; ci < out.cols.size(); ++ci)
-    if (out.cols[ci].null_count < 0) out.cols[ci].null_count = n - (int64_t)h[ci];
+  fill_null_counts(out.cols, n, h);
   return out;
 }
 

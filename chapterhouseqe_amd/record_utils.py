@@ -376,6 +376,45 @@ def _finish(ctx: Context, rc: int, out: _CBatch, device_result: bool):
     return _import_host(out)
 
 
+class _ExprHandles:
+    """owner of the expression handles of one C call: `add` makes one, leaving the `with` block (or `free`) releases them all"""
+
+    def __init__(self):
+        self._handles = []
+
+    def add(self, e: A.Expr):
+        h = _expr_to_c(e)
+        self._handles.append(h)
+        return h
+
+    def free(self) -> None:
+        for h in self._handles:
+            L.lib().chq_expr_free(h)
+        self._handles = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.free()
+
+
+def _call_record(rec: Record, ctx: Optional[Context], device_result: Optional[bool], call):
+    """The frame of a call on ONE record with ONE result.  `call(head, tail)` makes the C call: `head` is the context and the
+    record's array and schema, `tail` the output device and the output's array and schema; the operator's own arguments go
+    in between.  Result residency follows the input unless `device_result` says otherwise."""
+    ctx, src, own_src, on_dev = _prepare(rec, ctx)
+    dev_out = on_dev if device_result is None else device_result
+    out = _CBatch()
+    try:
+        rc = call((ctx.handle, C.byref(src.array), C.byref(src.schema)),
+                  (L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, C.byref(out.array), C.byref(out.schema)))
+    finally:
+        if own_src:
+            src.release()
+    return _finish(ctx, rc, out, dev_out)
+
+
 # ------------------------------------------------------------------------------------------ the path
 def filter_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]]], expr: A.Expr, *,
                   ctx: Optional[Context] = None, device_result: Optional[bool] = None):
@@ -702,6 +741,49 @@ class RecordGroup:
         self._cbs = []
 
 
+def _require_one_schema(recs: Sequence[Record], op: str, side: Optional[str] = None, mixed: bool = False) -> None:
+    """The C calls take ONE schema for a group: ChqError unless every batch of `recs` has the schema of the first.  `mixed`:
+    host and device batches may stand side by side; each kind must then agree in itself, and the two in their column names."""
+    sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
+    if mixed:
+        host_sig = [x for x in sig if isinstance(x, pa.Schema)]
+        dev_sig = [x for x in sig if not isinstance(x, pa.Schema)]
+        bad = any(x != host_sig[0] for x in host_sig[1:]) or any(x != dev_sig[0] for x in dev_sig[1:]) or \
+            bool(host_sig and dev_sig and tuple(host_sig[0].names) != dev_sig[0][0])
+    else:
+        bad = any(x != sig[0] for x in sig[1:])
+    if bad and side is None:
+        raise ChqError(22, f"{op}: every record batch must have the schema of the first")
+    if bad:
+        raise ChqError(22, f"{op}: every record batch of the {side} side must have the schema of the first")
+
+
+def _as_group(recs, ctx: Optional[Context], op: str) -> Tuple[RecordGroup, bool]:
+    """`recs` as (group, owned): a prepared `RecordGroup` as it is, a sequence of same-schema batches as a group of its own,
+    which the caller releases after the call.  `op` names the wrapper in the schema error."""
+    if isinstance(recs, RecordGroup):
+        return recs, False
+    recs = list(recs)
+    _require_one_schema(recs, op)
+    return RecordGroup(recs, ctx), True
+
+
+def _call_group(recs, ctx: Optional[Context], device_result: Optional[bool], op: str, call):
+    """`_call_record` for a group (`_as_group`) with ONE result: `head` is the context, the number of batches, their pointer
+    array and their one schema."""
+    grp, owned = _as_group(recs, ctx, op)
+    ctx = ctx or grp.ctx
+    dev_out = grp.on_device if device_result is None else device_result
+    out = _CBatch()
+    try:
+        rc = call((ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema)),
+                  (L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, C.byref(out.array), C.byref(out.schema)))
+    finally:
+        if owned:
+            grp.release()
+    return _finish(ctx, rc, out, dev_out)
+
+
 def filter_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], expr: A.Expr, *,
                    ctx: Optional[Context] = None, device_result: Optional[bool] = None, wrap: bool = True):
     """`[filter_record(r, table_aliases, expr) for r in recs]` in one call (`chq_filter_records`): the loop of
@@ -760,22 +842,16 @@ def filter_records_coalesced(recs, table_aliases: Optional[Sequence[Sequence[str
 
 
 # ------------------------------------------------------------------------------------------ ORDER BY
-def _sort_keys_to_c(order_by: Sequence[A.OrderByExpr]):
+def _sort_keys_to_c(order_by: Sequence[A.OrderByExpr], handles: _ExprHandles):
     keys = (L.SortKey * max(1, len(order_by)))()
     for i, o in enumerate(order_by):
         if not isinstance(o, A.OrderByExpr):
             raise TypeError(f"not an OrderByExpr: {o!r}")
         desc, nulls_first = o.sort_options()
-        keys[i].column = _expr_to_c(o.expr)
+        keys[i].column = handles.add(o.expr)
         keys[i].descending = int(desc)
         keys[i].nulls_first = int(nulls_first)
     return keys
-
-
-def _free_sort_keys(keys, n: int) -> None:
-    for i in range(n):
-        if keys[i].column:
-            L.lib().chq_expr_free(keys[i].column)
 
 
 def _limit_arg(limit: Optional[int]) -> int:
@@ -786,84 +862,61 @@ def _limit_arg(limit: Optional[int]) -> int:
     return int(limit)
 
 
+def _sort_call(c_fn, table_aliases, order_by, limit):
+    """the C call of sort_record / sort_records between the head and the tail of the frame"""
+    def call(head, tail):
+        al = _Aliases(table_aliases)
+        with _ExprHandles() as handles:
+            keys = _sort_keys_to_c(order_by, handles)
+            return c_fn(*head, al.ptr, keys, len(order_by), _limit_arg(limit), *tail)
+    return call
+
+
 def sort_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]]], order_by: Sequence[A.OrderByExpr], *,
                 limit: Optional[int] = None, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
     """ORDER BY (`chq_sort_record`): every column of `rec` permuted into the order of `order_by`, stable, cut to the
     first `limit` rows.  Result residency follows the input unless `device_result` says otherwise."""
-    ctx, src, own_src, on_dev = _prepare(rec, ctx)
-    dev_out = on_dev if device_result is None else device_result
-    al = _Aliases(table_aliases)
-    keys = _sort_keys_to_c(order_by)
-    out = _CBatch()
-    try:
-        rc = L.lib().chq_sort_record(ctx.handle, C.byref(src.array), C.byref(src.schema), al.ptr, keys, len(order_by),
-                                     _limit_arg(limit), L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
-                                     C.byref(out.array), C.byref(out.schema))
-    finally:
-        _free_sort_keys(keys, len(order_by))
-        if own_src:
-            src.release()
-    return _finish(ctx, rc, out, dev_out)
+    return _call_record(rec, ctx, device_result, _sort_call(L.lib().chq_sort_record, table_aliases, order_by, limit))
 
 
 def sort_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], order_by: Sequence[A.OrderByExpr], *,
                  limit: Optional[int] = None, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
     """ORDER BY over a group (`chq_sort_records`): ONE batch holding the rows of every batch of `recs` (a sequence of
     same-schema batches or a `RecordGroup`) in sorted order; ties keep batch order, then row order."""
-    if not isinstance(recs, RecordGroup):
-        recs = list(recs)
-        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
-        if any(x != sig[0] for x in sig[1:]):   # (the C call takes ONE schema for the group)
-            raise ChqError(22, "sort_records: every record batch must have the schema of the first")
-    grp = recs if isinstance(recs, RecordGroup) else RecordGroup(recs, ctx)
-    ctx = ctx or grp.ctx
-    dev_out = grp.on_device if device_result is None else device_result
-    al = _Aliases(table_aliases)
-    keys = _sort_keys_to_c(order_by)
-    out = _CBatch()
-    try:
-        rc = L.lib().chq_sort_records(ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema), al.ptr, keys, len(order_by),
-                                      _limit_arg(limit), L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
-                                      C.byref(out.array), C.byref(out.schema))
-    finally:
-        _free_sort_keys(keys, len(order_by))
-        if grp is not recs:
-            grp.release()
-    return _finish(ctx, rc, out, dev_out)
+    return _call_group(recs, ctx, device_result, "sort_records", _sort_call(L.lib().chq_sort_records, table_aliases, order_by, limit))
 
 
 # ------------------------------------------------------------------------------------------ GROUP BY
-class _AggArgs:
-    """the C arguments of one aggregate call: key handles and the item array (expression handles freed by `free`)"""
+class _AggArgs(_ExprHandles):
+    """the C arguments of one aggregate call: key handles and the item array"""
 
     def __init__(self, keys: Sequence[A.Expr], items: Sequence[A.AggItem]):
+        super().__init__()
         self.n_keys, self.n_items = len(keys), len(items)
-        self._handles = []
         try:
             self.keys = (C.c_void_p * max(1, self.n_keys))()
             for i, k in enumerate(keys):
-                self.keys[i] = self._handle(k)
+                self.keys[i] = self.add(k)
             self.items = (L.AggItem * max(1, self.n_items))()
             for i, it in enumerate(items):
                 if not isinstance(it, A.AggItem):
                     raise TypeError(f"not an AggItem: {it!r}")
                 self.items[i].kind = int(it.kind)
                 self.items[i].key_index = int(it.key_index)
-                self.items[i].column = self._handle(it.column) if it.column is not None else None
+                self.items[i].column = self.add(it.column) if it.column is not None else None
                 self.items[i].name = it.name.encode()
         except Exception:
             self.free()
             raise
 
-    def _handle(self, e: A.Expr):
-        h = _expr_to_c(e)
-        self._handles.append(h)
-        return h
 
-    def free(self) -> None:
-        for h in self._handles:
-            L.lib().chq_expr_free(h)
-        self._handles = []
+def _aggregate_call(c_fn, table_aliases, keys, items):
+    """the C call of aggregate_record / aggregate_records between the head and the tail of the frame"""
+    def call(head, tail):
+        al = _Aliases(table_aliases)
+        with _AggArgs(keys, items) as a:
+            return c_fn(*head, al.ptr, a.keys, a.n_keys, a.items, a.n_items, *tail)
+    return call
 
 
 def aggregate_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]]], keys: Sequence[A.Expr],
@@ -871,64 +924,28 @@ def aggregate_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]
     """GROUP BY (`chq_aggregate_record`): one row per group of `rec` by the key columns `keys` (none: one group), in key
     order (ascending, nulls last), one column per `items` entry (`sqlparse.aggregate_plan` builds both from a SELECT).
     Result residency follows the input unless `device_result` says otherwise."""
-    ctx, src, own_src, on_dev = _prepare(rec, ctx)
-    dev_out = on_dev if device_result is None else device_result
-    al = _Aliases(table_aliases)
-    out = _CBatch()
-    try:
-        args = _AggArgs(keys, items)
-        try:
-            rc = L.lib().chq_aggregate_record(ctx.handle, C.byref(src.array), C.byref(src.schema), al.ptr, args.keys, args.n_keys,
-                                              args.items, args.n_items, L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
-                                              C.byref(out.array), C.byref(out.schema))
-        finally:
-            args.free()
-    finally:
-        if own_src:
-            src.release()
-    return _finish(ctx, rc, out, dev_out)
+    return _call_record(rec, ctx, device_result, _aggregate_call(L.lib().chq_aggregate_record, table_aliases, keys, items))
 
 
 def aggregate_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], keys: Sequence[A.Expr],
                       items: Sequence[A.AggItem], *, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
     """GROUP BY over a group (`chq_aggregate_records`): the batches of `recs` (a sequence of same-schema batches or a
     `RecordGroup`) aggregated as if they were one batch."""
-    if not isinstance(recs, RecordGroup):
-        recs = list(recs)
-        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
-        if any(x != sig[0] for x in sig[1:]):   # (the C call takes ONE schema for the group)
-            raise ChqError(22, "aggregate_records: every record batch must have the schema of the first")
-    grp = recs if isinstance(recs, RecordGroup) else RecordGroup(recs, ctx)
-    ctx = ctx or grp.ctx
-    dev_out = grp.on_device if device_result is None else device_result
-    al = _Aliases(table_aliases)
-    out = _CBatch()
-    try:
-        args = _AggArgs(keys, items)
-        try:
-            rc = L.lib().chq_aggregate_records(ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema), al.ptr, args.keys, args.n_keys,
-                                               args.items, args.n_items, L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU,
-                                               C.byref(out.array), C.byref(out.schema))
-        finally:
-            args.free()
-    finally:
-        if grp is not recs:
-            grp.release()
-    return _finish(ctx, rc, out, dev_out)
+    return _call_group(recs, ctx, device_result, "aggregate_records",
+                       _aggregate_call(L.lib().chq_aggregate_records, table_aliases, keys, items))
 
 
 # ------------------------------------------------------------------------------------------ window functions
-class _WindowArgs:
-    """the C arguments of one window call: partition key handles, sort keys and the item array (handles freed by `free`)"""
+class _WindowArgs(_ExprHandles):
+    """the C arguments of one window call: partition key handles, sort keys and the item array"""
 
     def __init__(self, partition_by: Sequence[A.Expr], order_by: Sequence[A.OrderByExpr], items: Sequence[A.WindowItem]):
+        super().__init__()
         self.n_partition_by, self.n_order_by, self.n_items = len(partition_by), len(order_by), len(items)
-        self._handles = []
-        self.order_by = None
         try:
             self.partition_by = (C.c_void_p * max(1, self.n_partition_by))()
             for i, k in enumerate(partition_by):
-                self.partition_by[i] = self._handle(k)
+                self.partition_by[i] = self.add(k)
             self.items = (L.WindowItem * max(1, self.n_items))()
             for i, it in enumerate(items):
                 if not isinstance(it, A.WindowItem):
@@ -936,25 +953,21 @@ class _WindowArgs:
                 self.items[i].kind = int(it.kind)
                 self.items[i].frame = int(it.frame)
                 self.items[i].offset = int(it.offset)
-                self.items[i].column = self._handle(it.column) if it.column is not None else None
+                self.items[i].column = self.add(it.column) if it.column is not None else None
                 self.items[i].name = it.name.encode()
-            self.order_by = _sort_keys_to_c(order_by)
+            self.order_by = _sort_keys_to_c(order_by, self)
         except Exception:
             self.free()
             raise
 
-    def _handle(self, e: A.Expr):
-        h = _expr_to_c(e)
-        self._handles.append(h)
-        return h
 
-    def free(self) -> None:
-        for h in self._handles:
-            L.lib().chq_expr_free(h)
-        self._handles = []
-        if self.order_by is not None:
-            _free_sort_keys(self.order_by, self.n_order_by)
-            self.order_by = None
+def _window_call(c_fn, table_aliases, partition_by, order_by, items):
+    """the C call of window_record / window_records between the head and the tail of the frame"""
+    def call(head, tail):
+        al = _Aliases(table_aliases)
+        with _WindowArgs(partition_by, order_by, items) as a:
+            return c_fn(*head, al.ptr, a.partition_by, a.n_partition_by, a.order_by, a.n_order_by, a.items, a.n_items, *tail)
+    return call
 
 
 def window_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]]], partition_by: Sequence[A.Expr],
@@ -963,23 +976,8 @@ def window_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]]],
     """Window functions (`chq_window_record`): every row of `rec` in input order, its columns followed by one column per
     `items` entry evaluated over (PARTITION BY `partition_by` ORDER BY `order_by`) (`sqlparse.window_plan` builds all three
     from a SELECT).  Result residency follows the input unless `device_result` says otherwise."""
-    ctx, src, own_src, on_dev = _prepare(rec, ctx)
-    dev_out = on_dev if device_result is None else device_result
-    al = _Aliases(table_aliases)
-    out = _CBatch()
-    try:
-        args = _WindowArgs(partition_by, order_by, items)
-        try:
-            rc = L.lib().chq_window_record(ctx.handle, C.byref(src.array), C.byref(src.schema), al.ptr, args.partition_by,
-                                           args.n_partition_by, args.order_by, args.n_order_by, args.items, args.n_items,
-                                           L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, C.byref(out.array),
-                                           C.byref(out.schema))
-        finally:
-            args.free()
-    finally:
-        if own_src:
-            src.release()
-    return _finish(ctx, rc, out, dev_out)
+    return _call_record(rec, ctx, device_result,
+                        _window_call(L.lib().chq_window_record, table_aliases, partition_by, order_by, items))
 
 
 def window_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], partition_by: Sequence[A.Expr],
@@ -987,29 +985,8 @@ def window_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], parti
                    device_result: Optional[bool] = None):
     """Window functions over a group (`chq_window_records`): the batches of `recs` (a sequence of same-schema batches or a
     `RecordGroup`) as if they were one batch; ONE batch comes back, in batch order, then row order."""
-    if not isinstance(recs, RecordGroup):
-        recs = list(recs)
-        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
-        if any(x != sig[0] for x in sig[1:]):   # (the C call takes ONE schema for the group)
-            raise ChqError(22, "window_records: every record batch must have the schema of the first")
-    grp = recs if isinstance(recs, RecordGroup) else RecordGroup(recs, ctx)
-    ctx = ctx or grp.ctx
-    dev_out = grp.on_device if device_result is None else device_result
-    al = _Aliases(table_aliases)
-    out = _CBatch()
-    try:
-        args = _WindowArgs(partition_by, order_by, items)
-        try:
-            rc = L.lib().chq_window_records(ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema), al.ptr, args.partition_by,
-                                            args.n_partition_by, args.order_by, args.n_order_by, args.items, args.n_items,
-                                            L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, C.byref(out.array),
-                                            C.byref(out.schema))
-        finally:
-            args.free()
-    finally:
-        if grp is not recs:
-            grp.release()
-    return _finish(ctx, rc, out, dev_out)
+    return _call_group(recs, ctx, device_result, "window_records",
+                       _window_call(L.lib().chq_window_records, table_aliases, partition_by, order_by, items))
 
 
 # ------------------------------------------------------------------------------------------ JOIN
@@ -1017,23 +994,19 @@ _JOIN_KINDS = {"inner": 0, "left": 1, "right": 2, "full": 3, "semi": 4, "anti": 
 
 
 class _JoinSide:
-    """one side of a join as the C call takes it: a pointer array over its batches and their one schema.  `recs` is a
-    record, a sequence of records (host and device batches may be mixed) or a prepared `RecordGroup`."""
+    """one side of a join, or the input of the hash partitioning, as the C call takes it: a pointer array over its batches and
+    their one schema.  `recs` is a record, a sequence of records (host and device batches may be mixed) or a prepared
+    `RecordGroup`; `op` (and `side`, for an operator with two) name the caller in the errors."""
 
-    def __init__(self, recs, ctx: Optional[Context], what: str):
+    def __init__(self, recs, ctx: Optional[Context], op: str, side: Optional[str] = None):
         self._own = []
         if isinstance(recs, RecordGroup):
             self.ctx, self.n, self.ptrs, self.schema, self.on_device = recs.ctx, recs.n, recs.ptrs, recs.schema, recs.on_device
             return
         recs = [recs] if isinstance(recs, (pa.RecordBatch, DeviceRecordBatch)) else list(recs)
         if not recs:
-            raise ValueError(f"join_records: the {what} side needs at least one record batch")
-        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
-        host_sig = [x for x in sig if isinstance(x, pa.Schema)]
-        dev_sig = [x for x in sig if not isinstance(x, pa.Schema)]
-        if any(x != host_sig[0] for x in host_sig[1:]) or any(x != dev_sig[0] for x in dev_sig[1:]) or \
-                (host_sig and dev_sig and tuple(host_sig[0].names) != dev_sig[0][0]):   # (the C call takes ONE schema per side)
-            raise ChqError(22, f"join_records: every record batch of the {what} side must have the schema of the first")
+            raise ValueError(f"{op}: the {side} side needs at least one record batch" if side else f"{op} needs at least one record batch")
+        _require_one_schema(recs, op, side, mixed=True)
         self.ctx = ctx or next((r.ctx for r in recs if isinstance(r, DeviceRecordBatch)), None) or default_context()
         cbs = []
         try:
@@ -1074,9 +1047,9 @@ def join_records(left, left_aliases: Optional[Sequence[Sequence[str]]], right, r
     for pair in keys:
         if not (isinstance(pair, (tuple, list)) and len(pair) == 2):
             raise TypeError(f"not a (left, right) key pair: {pair!r}")
-    ls = _JoinSide(left, ctx, "left")
+    ls = _JoinSide(left, ctx, "join_records", "left")
     try:
-        rs = _JoinSide(right, ctx or ls.ctx, "right")
+        rs = _JoinSide(right, ctx or ls.ctx, "join_records", "right")
     except Exception:
         ls.release()
         raise
@@ -1084,20 +1057,15 @@ def join_records(left, left_aliases: Optional[Sequence[Sequence[str]]], right, r
     dev_out = (ls.on_device and rs.on_device) if device_result is None else device_result
     lal, ral = _Aliases(left_aliases), _Aliases(right_aliases)
     ckeys = (L.JoinKey * max(1, len(keys)))()
-    handles = []
     out = _CBatch()
     try:
-        for i, (lk, rk) in enumerate(keys):
-            for side, e in (("left", lk), ("right", rk)):
-                h = _expr_to_c(e)
-                handles.append(h)
-                setattr(ckeys[i], side, h)
-        rc = L.lib().chq_join_records_kind(ctx.handle, ls.n, ls.ptrs, C.byref(ls.schema), lal.ptr, rs.n, rs.ptrs, C.byref(rs.schema),
-                                           ral.ptr, ckeys, len(keys), _JOIN_KINDS[how],
-                                           L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, C.byref(out.array), C.byref(out.schema))
+        with _ExprHandles() as handles:
+            for i, (lk, rk) in enumerate(keys):
+                ckeys[i].left, ckeys[i].right = handles.add(lk), handles.add(rk)
+            rc = L.lib().chq_join_records_kind(ctx.handle, ls.n, ls.ptrs, C.byref(ls.schema), lal.ptr, rs.n, rs.ptrs, C.byref(rs.schema),
+                                               ral.ptr, ckeys, len(keys), _JOIN_KINDS[how],
+                                               L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, C.byref(out.array), C.byref(out.schema))
     finally:
-        for h in handles:
-            L.lib().chq_expr_free(h)
         ls.release()
         rs.release()
     return _finish(ctx, rc, out, dev_out)
@@ -1117,17 +1085,7 @@ def partition_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], ke
     for k in keys:
         if not isinstance(k, A.Expr):
             raise TypeError(f"not a key expression: {k!r}")
-    if not isinstance(recs, RecordGroup):
-        recs = [recs] if isinstance(recs, (pa.RecordBatch, DeviceRecordBatch)) else list(recs)
-        if not recs:
-            raise ValueError("partition_records needs at least one record batch")
-        sig = [(tuple(r.column_names), tuple(r.column_formats)) if isinstance(r, DeviceRecordBatch) else r.schema for r in recs]
-        host_sig = [x for x in sig if isinstance(x, pa.Schema)]
-        dev_sig = [x for x in sig if not isinstance(x, pa.Schema)]
-        if any(x != host_sig[0] for x in host_sig[1:]) or any(x != dev_sig[0] for x in dev_sig[1:]) or \
-                (host_sig and dev_sig and tuple(host_sig[0].names) != dev_sig[0][0]):   # (the C call takes ONE schema for the group)
-            raise ChqError(22, "partition_records: every record batch must have the schema of the first")
-    grp = _JoinSide(recs, ctx, "partitioned")
+    grp = _JoinSide(recs, ctx, "partition_records")
     ctx = ctx or grp.ctx
     dev_out = grp.on_device if device_result is None else device_result
     al = _Aliases(table_aliases)
@@ -1135,16 +1093,13 @@ def partition_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], ke
     outs = (L.ArrowDeviceArray * n_out)()
     schemas = (L.ArrowSchema * n_out)()
     ckeys = (C.c_void_p * max(1, len(keys)))()
-    handles = []
     try:
-        for i, k in enumerate(keys):
-            handles.append(_expr_to_c(k))
-            ckeys[i] = handles[-1]
-        rc = L.lib().chq_partition_records(ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema), al.ptr, ckeys, len(keys), n_partitions,
-                                           L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, outs, schemas)
+        with _ExprHandles() as handles:
+            for i, k in enumerate(keys):
+                ckeys[i] = handles.add(k)
+            rc = L.lib().chq_partition_records(ctx.handle, grp.n, grp.ptrs, C.byref(grp.schema), al.ptr, ckeys, len(keys), n_partitions,
+                                               L.ARROW_DEVICE_ROCM if dev_out else L.ARROW_DEVICE_CPU, outs, schemas)
     finally:
-        for h in handles:
-            L.lib().chq_expr_free(h)
         grp.release()
     if rc:
         raise ChqError(rc, ctx.last_error())
