@@ -453,7 +453,7 @@ def test_written_chunks_carry_the_statistics_a_cpu_writer_records(ctx):
     f32 = (rng.standard_normal(n) * 50).astype(np.float32)
     f32[::97] = np.nan; f32[5] = 0.0; f32[6] = -0.0
     zeros = np.zeros(n, dtype=np.float64); zeros[::2] = -0.0
-    words = np.array(["", "a", "ab", "zeta", "Zulu", "\u00e9t\u00e9", "\U0001F600", "a" * 300])
+    words = np.array(["", "a", "ab", "zeta", "Zulu", "\u00e9t\u00e9", "\U0001F600", "".join(chr(0x61 + (7 * i + i // 26) % 26) for i in range(300))])   # (300 bytes that depend on their position)
     cases = [pa.table({
         "i32": pa.array(rng.integers(-2**31, 2**31, n).astype(np.int32), mask=rng.random(n) < 0.1),
         "i64": pa.array(rng.integers(-2**62, 2**62, n).astype(np.int64)),
