@@ -88,62 +88,43 @@ class RecordHandler:
     def initiate(op_in_config, inbound_exchanges: List[ExchangeOperator], outbound_exchange: Optional[ExchangeOperator]) -> "RecordHandler":
         return RecordHandler(op_in_config.operator_id, op_in_config.instance_id, inbound_exchanges, outbound_exchange)
 
-    def next_record(self, max_wait_s: Optional[float] = None) -> Optional[ExchangeRecord]:
-        """Pull the next record from the FIRST inbound exchange (a producer reads only its first inbound
-        exchange, record_handler.rs:133-138). Returns None when the exchange has nothing left."""
+    def _pull(self, give_up, recheck_heartbeats: bool = False) -> Optional[ExchangeRecord]:
+        """Pull the next record from the FIRST inbound exchange (a producer reads only its first inbound exchange,
+        record_handler.rs:133-138), track it and start its heartbeat.  None when the exchange has nothing left, or when it
+        has nothing available and `give_up(exchange)` says to stop asking; otherwise sleep and ask again."""
         self._check_heartbeats()
         if not self.inbound_exchanges:
             raise RecordHandlerError("inbound exchanges is empty")
         ex = self.inbound_exchanges[0]
-        deadline = None if max_wait_s is None else time.monotonic() + max_wait_s
         while True:
             got = ex.get_next_record(self.operator_id, self.operator_instance_id)
-            if got == NONE_LEFT:
+            if got == NONE_LEFT or (got == NONE_AVAILABLE and give_up(ex)):
                 return None
             if got == NONE_AVAILABLE:
-                if deadline is not None and time.monotonic() > deadline:
-                    return None
                 time.sleep(self.none_available_wait_time_s)
+                if recheck_heartbeats:
+                    self._check_heartbeats()
                 continue
             record_id, record, aliases = got
             self._track(record_id, 0)
             return ExchangeRecord(record_id, record, aliases)
 
+    def next_record(self, max_wait_s: Optional[float] = None) -> Optional[ExchangeRecord]:
+        """record_handler.rs:127-214: wait for the next record, for at most `max_wait_s` if that is given."""
+        deadline = None if max_wait_s is None else time.monotonic() + max_wait_s
+        return self._pull(lambda ex: deadline is not None and time.monotonic() > deadline)
+
     def next_record_to_hold(self) -> Optional[ExchangeRecord]:
-        """next_record for a blocking operator (order by) that holds every record it pulls until it has them all.  The
-        exchange reports NoneLeft only once nothing is reserved either, so "producers done, nothing queued" ends the
-        pull instead.  Not in the reference."""
-        self._check_heartbeats()
-        if not self.inbound_exchanges:
-            raise RecordHandlerError("inbound exchanges is empty")
-        ex = self.inbound_exchanges[0]
-        while True:
-            got = ex.get_next_record(self.operator_id, self.operator_instance_id)
-            if got == NONE_LEFT:
-                return None
-            if got == NONE_AVAILABLE:
-                if ex.nothing_left_to_reserve(self.operator_id):
-                    return None
-                time.sleep(self.none_available_wait_time_s)
-                self._check_heartbeats()
-                continue
-            record_id, record, aliases = got
-            self._track(record_id, 0)
-            return ExchangeRecord(record_id, record, aliases)
+        """next_record for a blocking operator that holds every record it pulls until it has them all.  The exchange
+        reports NoneLeft only once nothing is reserved either, so "producers done, nothing queued" ends the pull
+        instead.  The records held so far keep beating while this waits, so a failed heartbeat ends the wait.  Not in the
+        reference."""
+        return self._pull(lambda ex: ex.nothing_left_to_reserve(self.operator_id), recheck_heartbeats=True)
 
     def try_next_record(self) -> Optional[ExchangeRecord]:
         """Non-blocking pull: a record that is queued right now, else None (nothing available yet, or nothing left).
         Not in the reference -- the GPU filter task uses it to drain the queue into one batch-group launch."""
-        self._check_heartbeats()
-        if not self.inbound_exchanges:
-            raise RecordHandlerError("inbound exchanges is empty")
-        ex = self.inbound_exchanges[0]
-        got = ex.get_next_record(self.operator_id, self.operator_instance_id)
-        if got == NONE_LEFT or got == NONE_AVAILABLE:
-            return None
-        record_id, record, aliases = got
-        self._track(record_id, 0)
-        return ExchangeRecord(record_id, record, aliases)
+        return self._pull(lambda ex: True)
 
     def send_record_to_outbound_exchange(self, record_id: int, record: Any, table_aliases: List[List[str]]) -> None:
         self._check_heartbeats()

@@ -6,18 +6,23 @@ Reference (OPS = src/handlers/operator_handler/operators):
   FilterConfig / FilterTask / FilterTaskBuilder        OPS/filter_tasks/{config.rs, filter_task.rs:30-199}
   MaterializeFilesConfig / MaterializeFilesTask / ...  OPS/materialize_tasks/{config.rs, materialize_files_task.rs:30-230}
   OperatorTask::{Filter{expr}, MaterializeFiles{data_format, fields}}  src/planner/physical_planner.rs:58-65
+  BlockingTask                              not in the reference: the protocol of the four operators below, which need every
+                                            input row before they can send one (hold all / compute once / send / ack all)
   OrderByOperatorTask / OrderByTask         not in the reference (its DEV_NOTES.md lists ORDER BY as the next operator):
-                                            a blocking single-instance sort over `record_utils.sort_records`
-  AggregateOperatorTask / AggregateTask     not in the reference either: GROUP BY, a blocking single-instance aggregation
-                                            over `record_utils.aggregate_records`
-  WindowOperatorTask / WindowTask           not in the reference either: window functions (fn(...) OVER (...)), a blocking
-                                            single-instance operator over `record_utils.window_records` + `project_record`
-  JoinOperatorTask / JoinTask               not in the reference either: JOIN (inner, left, right, full, semi, anti), a blocking
-                                            single-instance equi-join of two inbound exchanges over `record_utils.join_records`
+                                            `record_utils.sort_records`
+  AggregateOperatorTask / AggregateTask     not in the reference either: GROUP BY, `record_utils.aggregate_records`
+  WindowOperatorTask / WindowTask           not in the reference either: window functions (fn(...) OVER (...)),
+                                            `record_utils.window_records` + `project_record`
+  JoinOperatorTask / JoinTask               not in the reference either: JOIN (inner, left, right, full, semi, anti) of two
+                                            inbound exchanges, `record_utils.join_records`
 
 The hot loops call `record_utils.filter_record` / `project_record` exactly where the reference does
 (filter_task.rs:99, materialize_files_task.rs:110); here those are the HIP kernels.  The control plane around
 them (message router, pipes, TCP) is out of scope: `build` receives the exchanges directly.
+
+What every task shares is written once: `_task_of` and `_max_rows_per_record` (the checks of the `try_from` methods),
+`_LazyContext` (the library context, made on first use), `_runner` (what `TaskBuilder.build` returns) and, for the blocking
+operators, `BlockingTask.async_main` -- the one place that says "ack only after every send, so a failure requeues the inputs".
 """
 from __future__ import annotations
 
@@ -134,31 +139,95 @@ class TaskBuilder(abc.ABC):
         ...
 
 
+def _runner(task) -> Callable[[], Optional[Exception]]:
+    """what every `TaskBuilder.build` returns: run `task` to completion; None, or the error that ended it.  The task is
+    reachable as `run.task` (its counters are what the callers and the tests read)."""
+
+    def run():
+        try:
+            task.async_main()
+            return None
+        except Exception as err:   # noqa: BLE001 -- any error ends the instance (producer_operator.rs:179-183)
+            return err
+
+    run.task = task
+    return run
+
+
+def _task_of(op_in_config: "OperatorInstanceConfig", task_type: type, a_name: str):
+    """the operator task of `op_in_config`, which must be a `task_type` (`a_name`: "a filter", "an order by", ...)"""
+    if not isinstance(op_in_config.task, task_type):
+        raise ValueError(f"operator instance config is not {a_name} task")
+    return op_in_config.task
+
+
+def _max_rows_per_record(task) -> int:
+    if task.max_rows_per_record < 1:
+        raise ValueError("max_rows_per_record must be at least 1")
+    return task.max_rows_per_record
+
+
+class _LazyContext:
+    """mixin of the tasks that call the library: `_ctx` is the context they were given, or the one `_context()` makes on
+    the instance's device the first time the library is needed (never, when the compute functions are injected)"""
+    _ctx = None
+
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
+        return self._ctx
+
+
 class OperatorTaskRegistryError(Exception):
     pass
 
 
 class OperatorTaskRegistry:
+    # operator-task type -> (the attribute that holds its one builder, its name in the "already set" message)
+    _SLOTS = {
+        FilterOperatorTask: ("filter_task", "filter"),
+        OrderByOperatorTask: ("order_by_task", "order by"),
+        AggregateOperatorTask: ("aggregate_task", "aggregate"),
+        JoinOperatorTask: ("join_task", "join"),
+        WindowOperatorTask: ("window_task", "window"),
+        MaterializeFilesOperatorTask: ("materialize_files_task", "materialize file"),
+    }
+
     def __init__(self):
         self.filter_task: Optional[TaskBuilder] = None
-        self.materialize_files_task: Optional[TaskBuilder] = None
-        self.materialize_data_formats: List[str] = []
-        self.table_func_tasks: dict = {}
         self.order_by_task: Optional[TaskBuilder] = None
         self.aggregate_task: Optional[TaskBuilder] = None
         self.join_task: Optional[TaskBuilder] = None
         self.window_task: Optional[TaskBuilder] = None
+        self.materialize_files_task: Optional[TaskBuilder] = None
+        self.materialize_data_formats: List[str] = []
+        self.table_func_tasks: dict = {}
 
-    def add_filter_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
-        if self.filter_task is not None:
-            raise OperatorTaskRegistryError("filter task builder already set")
-        self.filter_task = builder
+    def _set(self, task_type: type, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        """operator_task_registry.rs:51-57: exactly one builder per operator task"""
+        slot, name = self._SLOTS[task_type]
+        if getattr(self, slot) is not None:
+            raise OperatorTaskRegistryError(f"{name} task builder already set")
+        setattr(self, slot, builder)
         return self
 
+    def add_filter_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        return self._set(FilterOperatorTask, builder)
+
+    def add_order_by_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        return self._set(OrderByOperatorTask, builder)
+
+    def add_aggregate_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        return self._set(AggregateOperatorTask, builder)
+
+    def add_window_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        return self._set(WindowOperatorTask, builder)
+
+    def add_join_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
+        return self._set(JoinOperatorTask, builder)
+
     def add_materialize_files_builder(self, builder: TaskBuilder, data_formats: List[str]) -> "OperatorTaskRegistry":
-        if self.materialize_files_task is not None:
-            raise OperatorTaskRegistryError("materialize file task builder already set")
-        self.materialize_files_task = builder
+        self._set(MaterializeFilesOperatorTask, builder)
         self.materialize_data_formats = list(data_formats)
         return self
 
@@ -169,46 +238,14 @@ class OperatorTaskRegistry:
         self.table_func_tasks[func_name] = builder
         return self
 
-    def add_order_by_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
-        if self.order_by_task is not None:
-            raise OperatorTaskRegistryError("order by task builder already set")
-        self.order_by_task = builder
-        return self
-
-    def add_aggregate_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
-        if self.aggregate_task is not None:
-            raise OperatorTaskRegistryError("aggregate task builder already set")
-        self.aggregate_task = builder
-        return self
-
-    def add_window_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
-        if self.window_task is not None:
-            raise OperatorTaskRegistryError("window task builder already set")
-        self.window_task = builder
-        return self
-
-    def add_join_task_builder(self, builder: TaskBuilder) -> "OperatorTaskRegistry":
-        if self.join_task is not None:
-            raise OperatorTaskRegistryError("join task builder already set")
-        self.join_task = builder
-        return self
-
     def find_task_builder(self, task) -> Optional[TaskBuilder]:
         if isinstance(task, ReadFilesOperatorTask):
             return self.table_func_tasks.get("read_files")
-        if isinstance(task, FilterOperatorTask):
-            return self.filter_task
-        if isinstance(task, OrderByOperatorTask):
-            return self.order_by_task
-        if isinstance(task, AggregateOperatorTask):
-            return self.aggregate_task
-        if isinstance(task, JoinOperatorTask):
-            return self.join_task
-        if isinstance(task, WindowOperatorTask):
-            return self.window_task
-        if isinstance(task, MaterializeFilesOperatorTask):
-            if task.data_format in self.materialize_data_formats:
-                return self.materialize_files_task
+        if isinstance(task, MaterializeFilesOperatorTask) and task.data_format not in self.materialize_data_formats:
+            return None
+        for task_type, (slot, _) in self._SLOTS.items():
+            if isinstance(task, task_type):
+                return getattr(self, slot)
         return None
 
 
@@ -219,12 +256,10 @@ class FilterConfig:
 
     @staticmethod
     def try_from(op_in_config: OperatorInstanceConfig) -> "FilterConfig":
-        if not isinstance(op_in_config.task, FilterOperatorTask):
-            raise ValueError("operator instance config is not a filter task")
-        return FilterConfig(op_in_config.task.expr)
+        return FilterConfig(_task_of(op_in_config, FilterOperatorTask, "a filter").expr)
 
 
-class FilterTask:
+class FilterTask(_LazyContext):
     """filter_task.rs:65-142.  `group_size` > 1 is the GPU extension: the task drains up to that many queued records
     of one schema and filters them with ONE kernel launch (`record_utils.filter_records`); every output still
     carries its input record id and is acked individually, so the exchange protocol is unchanged."""
@@ -242,11 +277,6 @@ class FilterTask:
         self.rows_in = 0
         self.rows_out = 0
         self.group_calls = 0
-
-    def _context(self):
-        if self._ctx is None:
-            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
-        return self._ctx
 
     def _filter_record(self, rec, aliases):
         if self._filter is not None:
@@ -304,18 +334,71 @@ class FilterTaskBuilder(TaskBuilder):
         self._group_size = group_size
 
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
-        task = FilterTask(op_in_config, FilterConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
-                          filter_fn=self._filter_fn, group_size=self._group_size)
+        return _runner(FilterTask(op_in_config, FilterConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
+                                  filter_fn=self._filter_fn, group_size=self._group_size))
 
-        def run():
-            try:
-                task.async_main()
-                return None
-            except Exception as err:   # noqa: BLE001 -- any error ends the instance (producer_operator.rs:179-183)
-                return err
 
-        run.task = task
-        return run
+# ---- the blocking operators: order by, group by, window functions, join ----------------------------------------------
+class BlockingTask(_LazyContext):
+    """A blocking, single-instance operator: one that needs every input row before it can send the first output row.
+
+    `async_main` is its whole protocol.  It pulls every record of every inbound side and holds them all (each tracked and
+    heart-beaten by the side's RecordHandler meanwhile), hands them to `_compute` in ONE call, sends the result cut into
+    records of at most `config.max_rows_per_record` rows with record ids 0, 1, 2, ... in result order -- a result without
+    rows as one empty record, which carries the schema -- and only then acks its inputs: if the compute step or a send fails,
+    nothing is acked, the handlers close, the heartbeats stop and the exchange requeues every input for another attempt
+    (the ack-after-send rule of FilterTask, over the whole input instead of one record).  When a side delivered no record
+    there is no schema to compute over: nothing is sent, and what the other sides delivered is acked.
+
+    A subclass is a constructor and `_compute`.  `rows_in` counts the rows of every side, `rows_out` and `records_sent`
+    what went out."""
+
+    def __init__(self, op_in_config: OperatorInstanceConfig, config, inbound_exchanges, outbound_exchange, ctx=None):
+        self.operator_instance_config = op_in_config
+        self.config = config
+        self.inbound_exchanges = inbound_exchanges
+        self.outbound_exchange = outbound_exchange
+        self._ctx = ctx
+        self.rows_in = 0
+        self.rows_out = 0
+        self.records_sent = 0
+
+    def _inbound_sides(self) -> List[list]:
+        """the inbound exchanges of each side's RecordHandler.  One side, unless a subclass says otherwise (a handler reads
+        only the first of its exchanges)."""
+        return [self.inbound_exchanges]
+
+    def _compute(self, *records_and_aliases):
+        """-> (result, table aliases of the result's columns).  The arguments are, for each side in turn, the list of its
+        records and the table aliases they came in under (those of the side's first record)."""
+        raise NotImplementedError
+
+    def async_main(self) -> None:
+        handlers = [RecordHandler.initiate(self.operator_instance_config, exchanges, self.outbound_exchange)
+                    for exchanges in self._inbound_sides()]
+        try:
+            held = [[] for _ in handlers]
+            for handler, side in zip(handlers, held):
+                while (exchange_rec := handler.next_record_to_hold()) is not None:
+                    side.append(exchange_rec)
+            self.rows_in = sum(h.record.num_rows for side in held for h in side)
+            if all(held):
+                args = []
+                for side in held:
+                    args += [[h.record for h in side], side[0].table_aliases]
+                result, out_aliases = self._compute(*args)
+                n, step = result.num_rows, self.config.max_rows_per_record
+                # the first side's handler sends: they all share the outbound exchange
+                for record_id, start in enumerate(range(0, max(n, 1), step)):
+                    handlers[0].send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), out_aliases)
+                    self.records_sent += 1
+                self.rows_out = n
+            for handler, side in zip(handlers, held):   # every send is out: now, and only now, the inputs are done with
+                for h in side:
+                    handler.complete_record(h)
+        finally:
+            for handler in handlers:
+                handler.close()
 
 
 # ---- order by ---------------------------------------------------------------------------------------------------------
@@ -327,68 +410,26 @@ class OrderByConfig:
 
     @staticmethod
     def try_from(op_in_config: OperatorInstanceConfig) -> "OrderByConfig":
-        t = op_in_config.task
-        if not isinstance(t, OrderByOperatorTask):
-            raise ValueError("operator instance config is not an order by task")
+        t = _task_of(op_in_config, OrderByOperatorTask, "an order by")
         if not t.order_by:
             raise ValueError("an order by task needs at least one key")
-        if t.max_rows_per_record < 1:
-            raise ValueError("max_rows_per_record must be at least 1")
-        return OrderByConfig(tuple(t.order_by), t.limit, t.max_rows_per_record)
+        return OrderByConfig(tuple(t.order_by), t.limit, _max_rows_per_record(t))
 
 
-class OrderByTask:
-    """A blocking, single-instance operator: pulls every inbound record (each tracked and heart-beaten by the
-    RecordHandler while it is held), sorts them all with ONE `sort_records` call, sends the result cut into records of
-    at most `max_rows_per_record` rows with record ids 0, 1, 2, ... in sorted order, and only then acks its inputs --
-    if anything fails before that, the exchange requeues them (the ack-after-send rule of FilterTask).  `sort_fn(records,
-    table_aliases, order_by, limit)` replaces the library call (tests on the CPU)."""
+class OrderByTask(BlockingTask):
+    """Sorts every inbound record with ONE `sort_records` call; the result goes out in sorted order under the table aliases
+    of the input.  `sort_fn(records, table_aliases, order_by, limit)` replaces the library call (tests on the CPU)."""
 
     def __init__(self, op_in_config: OperatorInstanceConfig, config: OrderByConfig, inbound_exchanges, outbound_exchange,
                  sort_fn=None, ctx=None):
-        self.operator_instance_config = op_in_config
-        self.config = config
-        self.inbound_exchanges = inbound_exchanges
-        self.outbound_exchange = outbound_exchange
+        super().__init__(op_in_config, config, inbound_exchanges, outbound_exchange, ctx)
         self._sort = sort_fn
-        self._ctx = ctx
-        self.rows_in = 0
-        self.rows_out = 0
-        self.records_sent = 0
 
-    def _context(self):
-        if self._ctx is None:
-            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
-        return self._ctx
-
-    def _sort_records(self, records, aliases):
+    def _compute(self, records, aliases):
+        c = self.config
         if self._sort is not None:
-            return self._sort(records, aliases, self.config.order_by, self.config.limit)
-        return record_utils.sort_records(records, aliases, self.config.order_by, limit=self.config.limit, ctx=self._context())
-
-    def async_main(self) -> None:
-        rec_handler = RecordHandler.initiate(self.operator_instance_config, self.inbound_exchanges, self.outbound_exchange)
-        try:
-            held = []
-            while True:
-                exchange_rec = rec_handler.next_record_to_hold()
-                if exchange_rec is None:
-                    break
-                held.append(exchange_rec)
-            if not held:
-                return
-            self.rows_in = sum(h.record.num_rows for h in held)
-            aliases = held[0].table_aliases
-            result = self._sort_records([h.record for h in held], aliases)
-            n, step = result.num_rows, self.config.max_rows_per_record
-            for record_id, start in enumerate(range(0, max(n, 1), step)):
-                rec_handler.send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), aliases)
-                self.records_sent += 1
-            self.rows_out = n
-            for h in held:
-                rec_handler.complete_record(h)
-        finally:
-            rec_handler.close()
+            return self._sort(records, aliases, c.order_by, c.limit), aliases
+        return record_utils.sort_records(records, aliases, c.order_by, limit=c.limit, ctx=self._context()), aliases
 
 
 class OrderByTaskBuilder(TaskBuilder):
@@ -396,18 +437,8 @@ class OrderByTaskBuilder(TaskBuilder):
         self._sort_fn = sort_fn
 
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
-        task = OrderByTask(op_in_config, OrderByConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
-                           sort_fn=self._sort_fn)
-
-        def run():
-            try:
-                task.async_main()
-                return None
-            except Exception as err:   # noqa: BLE001 -- any error ends the instance
-                return err
-
-        run.task = task
-        return run
+        return _runner(OrderByTask(op_in_config, OrderByConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
+                                   sort_fn=self._sort_fn))
 
 
 # ---- group by ---------------------------------------------------------------------------------------------------------
@@ -419,68 +450,34 @@ class AggregateConfig:
 
     @staticmethod
     def try_from(op_in_config: OperatorInstanceConfig) -> "AggregateConfig":
-        t = op_in_config.task
-        if not isinstance(t, AggregateOperatorTask):
-            raise ValueError("operator instance config is not an aggregate task")
+        t = _task_of(op_in_config, AggregateOperatorTask, "an aggregate")
         if not t.items:
             raise ValueError("an aggregate task needs at least one output item")
-        if t.max_rows_per_record < 1:
-            raise ValueError("max_rows_per_record must be at least 1")
-        return AggregateConfig(tuple(t.keys), tuple(t.items), t.max_rows_per_record)
+        return AggregateConfig(tuple(t.keys), tuple(t.items), _max_rows_per_record(t))
 
 
-class AggregateTask:
-    """A blocking, single-instance operator with the protocol of OrderByTask: pulls and holds every inbound record,
-    aggregates them all with ONE `aggregate_records` call, sends the groups (in key order) cut into records of at most
-    `max_rows_per_record` rows with record ids 0, 1, 2, ..., and only then acks its inputs.  When no record came in nothing
-    is sent, also without a GROUP BY key: there is no schema to aggregate over.
+def _no_aliases(record) -> List[list]:
+    """table aliases of a record whose columns are new: no table prefix reaches them"""
+    return [[] for _ in range(record.num_columns)]
+
+
+class AggregateTask(BlockingTask):
+    """Aggregates every inbound record with ONE `aggregate_records` call; the groups go out in key order, without table
+    aliases.  When no record came in nothing is sent also without a GROUP BY key: there is no schema to aggregate over.
     `aggregate_fn(records, table_aliases, keys, items)` replaces the library call (tests on the CPU)."""
 
     def __init__(self, op_in_config: OperatorInstanceConfig, config: AggregateConfig, inbound_exchanges, outbound_exchange,
                  aggregate_fn=None, ctx=None):
-        self.operator_instance_config = op_in_config
-        self.config = config
-        self.inbound_exchanges = inbound_exchanges
-        self.outbound_exchange = outbound_exchange
+        super().__init__(op_in_config, config, inbound_exchanges, outbound_exchange, ctx)
         self._aggregate = aggregate_fn
-        self._ctx = ctx
-        self.rows_in = 0
-        self.rows_out = 0
-        self.records_sent = 0
 
-    def _context(self):
-        if self._ctx is None:
-            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
-        return self._ctx
-
-    def _aggregate_records(self, records, aliases):
+    def _compute(self, records, aliases):
+        c = self.config
         if self._aggregate is not None:
-            return self._aggregate(records, aliases, self.config.keys, self.config.items)
-        return record_utils.aggregate_records(records, aliases, self.config.keys, self.config.items, ctx=self._context())
-
-    def async_main(self) -> None:
-        rec_handler = RecordHandler.initiate(self.operator_instance_config, self.inbound_exchanges, self.outbound_exchange)
-        try:
-            held = []
-            while True:
-                exchange_rec = rec_handler.next_record_to_hold()
-                if exchange_rec is None:
-                    break
-                held.append(exchange_rec)
-            if not held:
-                return
-            self.rows_in = sum(h.record.num_rows for h in held)
-            result = self._aggregate_records([h.record for h in held], held[0].table_aliases)
-            out_aliases = [[] for _ in range(result.num_columns)]   # the output columns are new: no table prefix reaches them
-            n, step = result.num_rows, self.config.max_rows_per_record
-            for record_id, start in enumerate(range(0, max(n, 1), step)):
-                rec_handler.send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), out_aliases)
-                self.records_sent += 1
-            self.rows_out = n
-            for h in held:
-                rec_handler.complete_record(h)
-        finally:
-            rec_handler.close()
+            result = self._aggregate(records, aliases, c.keys, c.items)
+        else:
+            result = record_utils.aggregate_records(records, aliases, c.keys, c.items, ctx=self._context())
+        return result, _no_aliases(result)
 
 
 class AggregateTaskBuilder(TaskBuilder):
@@ -488,18 +485,8 @@ class AggregateTaskBuilder(TaskBuilder):
         self._aggregate_fn = aggregate_fn
 
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
-        task = AggregateTask(op_in_config, AggregateConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
-                             aggregate_fn=self._aggregate_fn)
-
-        def run():
-            try:
-                task.async_main()
-                return None
-            except Exception as err:   # noqa: BLE001 -- any error ends the instance
-                return err
-
-        run.task = task
-        return run
+        return _runner(AggregateTask(op_in_config, AggregateConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
+                                     aggregate_fn=self._aggregate_fn))
 
 
 # ---- window functions -----------------------------------------------------------------------------------------------------
@@ -513,82 +500,39 @@ class WindowConfig:
 
     @staticmethod
     def try_from(op_in_config: OperatorInstanceConfig) -> "WindowConfig":
-        t = op_in_config.task
-        if not isinstance(t, WindowOperatorTask):
-            raise ValueError("operator instance config is not a window task")
+        t = _task_of(op_in_config, WindowOperatorTask, "a window")
         if not t.items:
             raise ValueError("a window task needs at least one item")
         if not t.projection:
             raise ValueError("a window task needs at least one projected field")
-        if t.max_rows_per_record < 1:
-            raise ValueError("max_rows_per_record must be at least 1")
-        return WindowConfig(tuple(t.partition_by), tuple(t.order_by), tuple(t.items), tuple(t.projection), t.max_rows_per_record)
+        return WindowConfig(tuple(t.partition_by), tuple(t.order_by), tuple(t.items), tuple(t.projection), _max_rows_per_record(t))
 
 
-class WindowTask:
-    """A blocking, single-instance operator with the protocol of AggregateTask: pulls and holds every inbound record,
-    evaluates every window item with ONE `window_records` call (the rows come back in input order: record order, then row
-    order), finishes the SELECT list with ONE `project_record` over that result, sends it cut into records of at most
-    `max_rows_per_record` rows with record ids 0, 1, 2, ..., and only then acks its inputs.  When no record came in nothing
-    is sent.  `window_fn(records, table_aliases, partition_by, order_by, items)` and `project_fn(fields, record,
-    table_aliases)` replace the library calls (tests on the CPU)."""
+class WindowTask(BlockingTask):
+    """Evaluates every window item with ONE `window_records` call over every inbound record (the rows come back in input
+    order: record order, then row order) and finishes the SELECT list with ONE `project_record` over that result, which
+    goes out without table aliases.  `window_fn(records, table_aliases, partition_by, order_by, items)` and
+    `project_fn(fields, record, table_aliases)` replace the library calls (tests on the CPU)."""
 
     def __init__(self, op_in_config: OperatorInstanceConfig, config: WindowConfig, inbound_exchanges, outbound_exchange,
                  window_fn=None, project_fn=None, ctx=None):
-        self.operator_instance_config = op_in_config
-        self.config = config
-        self.inbound_exchanges = inbound_exchanges
-        self.outbound_exchange = outbound_exchange
+        super().__init__(op_in_config, config, inbound_exchanges, outbound_exchange, ctx)
         self._window = window_fn
         self._project = project_fn
-        self._ctx = ctx
-        self.rows_in = 0
-        self.rows_out = 0
-        self.records_sent = 0
 
-    def _context(self):
-        if self._ctx is None:
-            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
-        return self._ctx
-
-    def _window_records(self, records, aliases):
+    def _compute(self, records, aliases):
         c = self.config
         if self._window is not None:
-            return self._window(records, aliases, c.partition_by, c.order_by, c.items)
-        return record_utils.window_records(records, aliases, c.partition_by, c.order_by, c.items, ctx=self._context())
-
-    def _project_record(self, rec, aliases):
+            windowed = self._window(records, aliases, c.partition_by, c.order_by, c.items)
+        else:
+            windowed = record_utils.window_records(records, aliases, c.partition_by, c.order_by, c.items, ctx=self._context())
+        # the item columns are new: no table prefix reaches them
+        win_aliases = None if aliases is None else list(aliases) + [[] for _ in range(windowed.num_columns - len(aliases))]
         if self._project is not None:
-            return self._project(self.config.projection, rec, aliases)
-        return record_utils.project_record(self.config.projection, rec, aliases, ctx=self._context())
-
-    def async_main(self) -> None:
-        rec_handler = RecordHandler.initiate(self.operator_instance_config, self.inbound_exchanges, self.outbound_exchange)
-        try:
-            held = []
-            while True:
-                exchange_rec = rec_handler.next_record_to_hold()
-                if exchange_rec is None:
-                    break
-                held.append(exchange_rec)
-            if not held:
-                return
-            self.rows_in = sum(h.record.num_rows for h in held)
-            aliases = held[0].table_aliases
-            windowed = self._window_records([h.record for h in held], aliases)
-            # the item columns are new: no table prefix reaches them
-            win_aliases = None if aliases is None else list(aliases) + [[] for _ in range(windowed.num_columns - len(aliases))]
-            result = self._project_record(windowed, win_aliases)
-            out_aliases = [[] for _ in range(result.num_columns)]
-            n, step = result.num_rows, self.config.max_rows_per_record
-            for record_id, start in enumerate(range(0, max(n, 1), step)):
-                rec_handler.send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), out_aliases)
-                self.records_sent += 1
-            self.rows_out = n
-            for h in held:
-                rec_handler.complete_record(h)
-        finally:
-            rec_handler.close()
+            result = self._project(c.projection, windowed, win_aliases)
+        else:
+            result = record_utils.project_record(c.projection, windowed, win_aliases, ctx=self._context())
+        return result, _no_aliases(result)
 
 
 class WindowTaskBuilder(TaskBuilder):
@@ -597,18 +541,8 @@ class WindowTaskBuilder(TaskBuilder):
         self._project_fn = project_fn
 
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
-        task = WindowTask(op_in_config, WindowConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
-                          window_fn=self._window_fn, project_fn=self._project_fn)
-
-        def run():
-            try:
-                task.async_main()
-                return None
-            except Exception as err:   # noqa: BLE001 -- any error ends the instance
-                return err
-
-        run.task = task
-        return run
+        return _runner(WindowTask(op_in_config, WindowConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
+                                  window_fn=self._window_fn, project_fn=self._project_fn))
 
 
 # ---- join ---------------------------------------------------------------------------------------------------------------
@@ -623,25 +557,21 @@ class JoinConfig:
 
     @staticmethod
     def try_from(op_in_config: OperatorInstanceConfig) -> "JoinConfig":
-        t = op_in_config.task
-        if not isinstance(t, JoinOperatorTask):
-            raise ValueError("operator instance config is not a join task")
+        t = _task_of(op_in_config, JoinOperatorTask, "a join")
         if not t.keys:
             raise ValueError("a join task needs at least one pair of key columns")
-        if t.max_rows_per_record < 1:
-            raise ValueError("max_rows_per_record must be at least 1")
+        max_rows_per_record = _max_rows_per_record(t)
         if t.kind not in JOIN_KINDS:
             raise ValueError(f"a join task's kind must be one of {', '.join(JOIN_KINDS)}, not {t.kind!r}")
-        return JoinConfig(tuple((l, r) for l, r in t.keys), t.max_rows_per_record, t.kind)
+        return JoinConfig(tuple((l, r) for l, r in t.keys), max_rows_per_record, t.kind)
 
 
-class JoinTask:
-    """A blocking, single-instance operator with the protocol of AggregateTask over TWO inbound exchanges (0: the left input,
-    1: the right): pulls and holds every record of both sides, joins them with ONE `join_records` call, sends the result
-    (in the row order of its kind; inner: ascending by left row, then by right row) cut into records of at most
-    `max_rows_per_record` rows with record ids 0, 1, 2, ... under the table aliases of the left columns followed by those of
-    the right columns (semi and anti: the left columns only), and only then acks both sides.  When either side delivered no
-    record nothing is sent, whatever the kind: there is no schema to join or to pad with.
+class JoinTask(BlockingTask):
+    """The blocking protocol over TWO sides (inbound exchange 0: the left input, 1: the right): joins every record of both
+    with ONE `join_records` call; the result goes out in the row order of its kind (inner: ascending by left row, then by
+    right row) under the table aliases of the left columns followed by those of the right columns (semi and anti: the left
+    columns only).  When either side delivered no record nothing is sent, whatever the kind: there is no schema to join or
+    to pad with.
     Each side has a RecordHandler of its own: a handler reads only its first exchange and tracks by record id, which the two
     exchanges may share.
     `join_fn(left_records, left_aliases, right_records, right_aliases, keys)` replaces the library call (tests on the CPU);
@@ -651,57 +581,24 @@ class JoinTask:
                  join_fn=None, ctx=None):
         if len(inbound_exchanges) != 2:
             raise ValueError(f"a join task takes two inbound exchanges (left, right), not {len(inbound_exchanges)}")
-        self.operator_instance_config = op_in_config
-        self.config = config
-        self.inbound_exchanges = inbound_exchanges
-        self.outbound_exchange = outbound_exchange
+        super().__init__(op_in_config, config, inbound_exchanges, outbound_exchange, ctx)
         self._join = join_fn
-        self._ctx = ctx
-        self.rows_in = 0
-        self.rows_out = 0
-        self.records_sent = 0
 
-    def _context(self):
-        if self._ctx is None:
-            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
-        return self._ctx
+    def _inbound_sides(self):
+        return [[ex] for ex in self.inbound_exchanges]
 
-    def _join_records(self, left, left_aliases, right, right_aliases):
-        kind = self.config.kind
-        if self._join is not None:
-            if kind == "inner":
-                return self._join(left, left_aliases, right, right_aliases, self.config.keys)
-            return self._join(left, left_aliases, right, right_aliases, self.config.keys, kind=kind)
-        return record_utils.join_records(left, left_aliases, right, right_aliases, self.config.keys, ctx=self._context(), how=kind)
-
-    def async_main(self) -> None:
-        handlers = [RecordHandler.initiate(self.operator_instance_config, [ex], self.outbound_exchange) for ex in self.inbound_exchanges]
-        try:
-            held = [[], []]
-            for side, handler in enumerate(handlers):
-                while True:
-                    exchange_rec = handler.next_record_to_hold()
-                    if exchange_rec is None:
-                        break
-                    held[side].append(exchange_rec)
-            self.rows_in = sum(h.record.num_rows for side in held for h in side)
-            if held[0] and held[1]:
-                left_aliases, right_aliases = held[0][0].table_aliases, held[1][0].table_aliases
-                result = self._join_records([h.record for h in held[0]], left_aliases, [h.record for h in held[1]], right_aliases)
-                out_aliases = [list(a) for a in left_aliases]
-                if self.config.kind not in ("semi", "anti"):
-                    out_aliases += [list(a) for a in right_aliases]
-                n, step = result.num_rows, self.config.max_rows_per_record
-                for record_id, start in enumerate(range(0, max(n, 1), step)):
-                    handlers[0].send_record_to_outbound_exchange(record_id, result.slice(start, min(step, n - start)), out_aliases)
-                    self.records_sent += 1
-                self.rows_out = n
-            for side, handler in enumerate(handlers):
-                for h in held[side]:
-                    handler.complete_record(h)
-        finally:
-            for handler in handlers:
-                handler.close()
+    def _compute(self, left, left_aliases, right, right_aliases):
+        c = self.config
+        if self._join is None:
+            result = record_utils.join_records(left, left_aliases, right, right_aliases, c.keys, ctx=self._context(), how=c.kind)
+        elif c.kind == "inner":
+            result = self._join(left, left_aliases, right, right_aliases, c.keys)
+        else:
+            result = self._join(left, left_aliases, right, right_aliases, c.keys, kind=c.kind)
+        out_aliases = [list(a) for a in left_aliases]
+        if c.kind not in ("semi", "anti"):
+            out_aliases += [list(a) for a in right_aliases]
+        return result, out_aliases
 
 
 class JoinTaskBuilder(TaskBuilder):
@@ -709,21 +606,12 @@ class JoinTaskBuilder(TaskBuilder):
         self._join_fn = join_fn
 
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
-        task = JoinTask(op_in_config, JoinConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange, join_fn=self._join_fn)
-
-        def run():
-            try:
-                task.async_main()
-                return None
-            except Exception as err:   # noqa: BLE001 -- any error ends the instance
-                return err
-
-        run.task = task
-        return run
+        return _runner(JoinTask(op_in_config, JoinConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
+                                join_fn=self._join_fn))
 
 
 # ---- read_files (the table function in front of the path) -----------------------------------------------------
-class ReadFilesTask:
+class ReadFilesTask(_LazyContext):
     """read_files_task.rs:129-291 with `read_records` (:233-282) on the GPU: every matching Parquet file is opened through a
     RANGE reader (the footer, then exactly the chunks that are decoded -- the reference reads through opendal ranges), its row
     groups are decoded in HBM (`chq_parquet_read_columns`) and forwarded as device-resident records cut into zero-copy slices
@@ -743,11 +631,6 @@ class ReadFilesTask:
         self.files_read: List[str] = []
         self.bytes_fetched = 0
         self.host_fallbacks = 0
-
-    def _context(self):
-        if self._ctx is None:
-            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
-        return self._ctx
 
     def _send(self, rec_handler, record) -> None:
         aliases = record_utils.get_record_table_aliases(self.config.alias, record)
@@ -810,20 +693,9 @@ class ReadFilesTaskBuilder(TaskBuilder):
         self._device_records = device_records
 
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
-        if not isinstance(op_in_config.task, ReadFilesOperatorTask):
-            raise ValueError("operator instance config is not a read_files task")
-        task = ReadFilesTask(op_in_config, op_in_config.task, self._root, outbound_exchange, columns=self._columns,
-                             device_records=self._device_records)
-
-        def run():
-            try:
-                task.async_main()
-                return None
-            except Exception as err:   # noqa: BLE001
-                return err
-
-        run.task = task
-        return run
+        task = _task_of(op_in_config, ReadFilesOperatorTask, "a read_files")
+        return _runner(ReadFilesTask(op_in_config, task, self._root, outbound_exchange, columns=self._columns,
+                                     device_records=self._device_records))
 
 
 # ---- materialize ----------------------------------------------------------------------------------------------
@@ -834,12 +706,11 @@ class MaterializeFilesConfig:
 
     @staticmethod
     def try_from(op_in_config: OperatorInstanceConfig) -> "MaterializeFilesConfig":
-        if not isinstance(op_in_config.task, MaterializeFilesOperatorTask):
-            raise ValueError("operator instance config is not a materialize files task")
-        return MaterializeFilesConfig(op_in_config.task.data_format, op_in_config.task.fields)
+        t = _task_of(op_in_config, MaterializeFilesOperatorTask, "a materialize files")
+        return MaterializeFilesConfig(t.data_format, t.fields)
 
 
-class MaterializeFilesTask:
+class MaterializeFilesTask(_LazyContext):
     def __init__(self, op_in_config, config: MaterializeFilesConfig, inbound_exchanges, outbound_exchange,
                  storage_root: str, project_fn=None, ctx=None):
         self.operator_instance_config = op_in_config
@@ -854,10 +725,8 @@ class MaterializeFilesTask:
     def _project_record(self, rec, aliases):
         if self._project is not None:
             return self._project(self.materialize_file_config.fields, rec, aliases)
-        if self._ctx is None:
-            self._ctx = record_utils.Context(self.operator_instance_config.device_id)
         # the projected batch stays in HBM: the Parquet pages are encoded there too
-        return record_utils.project_record(self.materialize_file_config.fields, rec, aliases, ctx=self._ctx, device_result=True)
+        return record_utils.project_record(self.materialize_file_config.fields, rec, aliases, ctx=self._context(), device_result=True)
 
     def _write_parquet(self, proj_rec, path: str) -> None:
         """materialize_files_task.rs:128-141 (AsyncArrowWriter ... write ... close).  A device-resident result is encoded on
@@ -907,18 +776,8 @@ class MaterializeFilesTaskBuilder(TaskBuilder):
         self._project_fn = project_fn
 
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
-        task = MaterializeFilesTask(op_in_config, MaterializeFilesConfig.try_from(op_in_config), inbound_exchanges,
-                                    outbound_exchange, self.storage_root, project_fn=self._project_fn)
-
-        def run():
-            try:
-                task.async_main()
-                return None
-            except Exception as err:   # noqa: BLE001
-                return err
-
-        run.task = task
-        return run
+        return _runner(MaterializeFilesTask(op_in_config, MaterializeFilesConfig.try_from(op_in_config), inbound_exchanges,
+                                            outbound_exchange, self.storage_root, project_fn=self._project_fn))
 
 
 def build_default_operator_task_registry(storage_root: str) -> OperatorTaskRegistry:
