@@ -376,6 +376,27 @@ chq_expr* chq_expr_nested(chq_expr* inner) {
   delete inner;
   return e;
 }
+chq_expr* chq_expr_like(chq_expr* operand, const char* pattern, int64_t pattern_len, int negated, int escape) {
+  chq_expr* e = new_expr(Expr::LIKE);
+  if (!e || !operand) { chq_expr_free(operand); delete e; return nullptr; }
+  if (pattern) {   // (null: the caller's pattern was not a string literal -- typing reports it)
+    e->e.r.reset(new Expr());
+    e->e.r->kind = Expr::STRING;
+    if (pattern_len > 0) e->e.r->text.assign(pattern, (size_t)pattern_len);
+  }
+  e->e.flag = negated != 0; e->e.op = escape < 0 ? -1 : escape;
+  e->e.l.reset(new Expr(std::move(operand->e)));
+  delete operand;
+  return e;
+}
+chq_expr* chq_expr_is_null(chq_expr* operand, int negated) {
+  chq_expr* e = new_expr(Expr::ISNULL);
+  if (!e || !operand) { chq_expr_free(operand); delete e; return nullptr; }
+  e->e.flag = negated != 0;
+  e->e.l.reset(new Expr(std::move(operand->e)));
+  delete operand;
+  return e;
+}
 chq_expr* chq_expr_unsupported(const char* debug) { chq_expr* e = new_expr(Expr::OTHER); if (e) e->e.text = debug ? debug : ""; return e; }
 void chq_expr_free(chq_expr* e) { delete e; }
 

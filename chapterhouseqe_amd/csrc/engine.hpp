@@ -14,6 +14,7 @@
 #include "../../include/chq.h"
 #include "device_program.h"
 #include "typed_ops.h"
+#include "like_device.h"
 #include "plan.hpp"
 
 namespace chq {
@@ -26,6 +27,8 @@ hipError_t launch_bit_compact(const BitCompactParams& p, int grid, hipStream_t s
 hipError_t launch_bit_compact_group(const BitCompactGroupParams& p, int grid, hipStream_t stream);
 hipError_t launch_cmp128(const Cmp128Params& p, hipStream_t stream);
 hipError_t launch_utf8_to_bool(const Utf8ToBoolParams& p, hipStream_t stream);
+hipError_t launch_is_null(const IsNullParams& p, hipStream_t stream);
+hipError_t launch_like(const LikeParams& p, hipStream_t stream);   // like.hip
 hipError_t launch_utf8_uniform(const Utf8UniformParams& p, hipStream_t stream);
 hipError_t launch_iota_offsets(const IotaOffsetsParams& p, hipStream_t stream);
 hipError_t launch_count_bits(const uint8_t* in, int64_t bit_offset, int64_t nbits, unsigned long long* out, hipStream_t stream);

@@ -154,14 +154,24 @@ void materialize_node(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols,
   te.nodes[node] = repl;
 }
 
-// Decimal128 comparisons and Utf8 -> Boolean casts are not device-program instructions (plan.hpp: Node): their own
-// kernels (typed_ops.hip) write a temporary Boolean column, which replaces the node like any other materialisation.
+// Decimal128 comparisons, Utf8 -> Boolean casts, LIKE and IS [NOT] NULL are not device-program instructions (plan.hpp:
+// Node): their own kernels (typed_ops.hip, like.hip) write a temporary Boolean column, which replaces the node like any
+// other materialisation.
 bool is_typed_op(const TypedExpr& te, int node) {
   const Node& n = te.nodes[node];
   return (n.kind == Node::CMP && n.from == T_FIXED_OPAQUE) || (n.kind == Node::TOBOOL && n.from == T_UTF8) ||
+         n.kind == Node::LIKE || n.kind == Node::ISNULL ||
          (n.kind == Node::CONST && n.cval.null);   // `'maybe' AND ..` folded to NULL, next to a column of a one-row batch
 }
-void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node) {
+void fit_subtree(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict, bool is_root);
+void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict) {
+  if (te.nodes[node].kind == Node::ISNULL || te.nodes[node].kind == Node::LIKE) {
+    // the operand as a column: a computed one (IS NULL only; a literal-only one was folded at typing) is evaluated first,
+    // with its data-dependent errors, in the order `strict` asks for
+    const int l = te.nodes[node].l;
+    fit_subtree(ctx, work, wcols, te, l, strict, false);
+    if (te.nodes[l].kind != Node::COL) materialize_node(ctx, work, wcols, te, l);
+  }
   const Node n = te.nodes[node];
   const int64_t nrows = work.nrows;
   const size_t words = (size_t)((nrows + 63) / 64) + 1;
@@ -173,6 +183,20 @@ void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wc
     check_hip(hipMemsetAsync(valid->ptr, 0, words * 8, ctx.stream), "memset");
     const u64 all = (u64)nrows;
     check_hip(hipMemcpyAsync(count->ptr, &all, 8, hipMemcpyHostToDevice, ctx.stream), "null count");
+  } else if (n.kind == Node::ISNULL) {
+    const Column& c = work.cols[(size_t)te.nodes[n.l].col];
+    IsNullParams p{};
+    p.validity = (c.validity && c.null_count != 0) ? c.validity : nullptr; p.validity_offset = c.offset;
+    p.nrows = nrows; p.negated = n.op; p.out_bits = (u64*)bits->ptr;
+    if (nrows > 0) check_hip(launch_is_null(p, ctx.stream), "launch is_null_kernel");
+  } else if (n.kind == Node::LIKE) {
+    const Column& c = work.cols[(size_t)te.nodes[n.l].col];
+    LikeParams p{};
+    p.offsets = (const int32_t*)c.values0(); p.data = c.data;
+    p.validity = (c.validity && c.null_count != 0) ? c.validity : nullptr; p.validity_offset = c.offset;
+    p.nrows = nrows; p.negated = n.op; p.pat = *n.like;
+    p.out_bits = (u64*)bits->ptr; p.out_validity = (u64*)valid->ptr; p.null_count = (u64*)count->ptr;
+    if (nrows > 0) check_hip(launch_like(p, ctx.stream), "launch like_kernel");
   } else if (n.kind == Node::CMP) {
     const Column& a = work.cols[(size_t)te.nodes[n.l].col];
     const Column& b = work.cols[(size_t)te.nodes[n.r].col];
@@ -211,7 +235,7 @@ void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wc
 }
 
 void fit_subtree(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict, bool is_root) {
-  if (is_typed_op(te, node)) { materialize_typed_op(ctx, work, wcols, te, node); return; }
+  if (is_typed_op(te, node)) { materialize_typed_op(ctx, work, wcols, te, node, strict); return; }
   if (is_leaf_node(te.nodes[node])) return;
   const int l = te.nodes[node].l, r = te.nodes[node].r;
   if (l >= 0) fit_subtree(ctx, work, wcols, te, l, strict, false);

@@ -243,6 +243,12 @@ Scalar fold_constant(const TypedExpr& t, int ni) {
       if (a.null || b.null) return null_scalar(T_BOOL);   // non-Kleene: validity = union
       return scalar_bits(T_BOOL, n.op == OP_AND ? (a.bits & b.bits & 1) : ((a.bits | b.bits) & 1));
     }
+    case Node::LIKE: {   // the matcher the device runs (like_device.h)
+      Scalar a = fold_constant(t, n.l);
+      if (a.null) return null_scalar(T_BOOL);
+      return scalar_bits(T_BOOL, like_match(*n.like, (const uint8_t*)a.str.data(), (int32_t)a.str.size()) != (n.op != 0));
+    }
+    case Node::ISNULL: return scalar_bits(T_BOOL, fold_constant(t, n.l).null == (n.op == 0));   // never null itself
     default: fail(CHQ_ERR_INVALID_HANDLE, "fold_constant on a column");
   }
 }
@@ -348,6 +354,30 @@ struct Typer {
         int l = build(*e.l);
         int r = build(*e.r);
         return binary(e, l, r);
+      }
+      case Expr::LIKE: {
+        const int l = build(*e.l);
+        const Expr* pe = e.r.get();
+        if (!pe || pe->kind != Expr::STRING) fail(CHQ_ERR_NOT_SUPPORTED, "the pattern of LIKE must be a single-quoted string literal");
+        if (t.nodes[l].type != T_UTF8)
+          fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, std::string("LIKE needs a Utf8 operand, found ") + dtype_name(t.nodes[l].type));
+        if (e.op < -1 || e.op > 127) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "the ESCAPE of LIKE must be one ASCII character");
+        auto pat = std::make_shared<LikePattern>();
+        switch (like_compile((const uint8_t*)pe->text.data(), (int64_t)pe->text.size(), e.op, pat.get())) {
+          case LIKE_TRAILING_ESCAPE: fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "LIKE pattern ends with its escape character: '" + pe->text + "'");
+          case LIKE_TOO_LONG:
+            fail(CHQ_ERR_NOT_SUPPORTED, "LIKE pattern has more than " + std::to_string(LIKE_MAX_ELEMS) + " elements (literal bytes and '_')");
+          default: break;
+        }
+        Node n{}; n.kind = Node::LIKE; n.type = T_BOOL; n.from = T_UTF8; n.l = l; n.op = e.flag ? 1 : 0; n.like = pat;
+        n.is_scalar = t.nodes[l].is_scalar; n.len1 = t.nodes[l].len1;
+        return maybe_fold(push(n));
+      }
+      case Expr::ISNULL: {
+        const int l = build(*e.l);
+        Node n{}; n.kind = Node::ISNULL; n.type = T_BOOL; n.from = t.nodes[l].type; n.l = l; n.op = e.flag ? 1 : 0;
+        n.is_scalar = t.nodes[l].is_scalar; n.len1 = t.nodes[l].len1;
+        return maybe_fold(push(n));
       }
       default: fail(CHQ_ERR_EXPRESSION_TYPE_NOT_IMPLEMENTED, "expression type not implemented: " + e.text);
     }
@@ -535,6 +565,8 @@ struct Gen {
         in.op = n.kind == Node::CAST ? OP_CAST : OP_TOBOOL; in.type = n.type; in.src_type = n.from; in.src_kind = SRC_NONE;
         emit(in);
         return;
+      case Node::LIKE: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "LIKE runs as its own kernel");
+      case Node::ISNULL: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "IS NULL runs as its own kernel");
       case Node::CMP:
         if (n.from == T_UTF8) { gen_strcmp(n); return; }
         if (n.from == T_FIXED_OPAQUE) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "Decimal128 comparison runs as its own kernel");

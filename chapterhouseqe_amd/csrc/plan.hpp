@@ -15,6 +15,7 @@
 
 #include "../../include/chq.h"
 #include "device_program.h"
+#include "like_device.h"
 
 namespace chq {
 
@@ -28,10 +29,12 @@ constexpr int CHQ_INTERNAL_PROGRAM_LIMIT = 1030;
 
 // ---- sqlparser::ast::Expr mirror -----------------------------------------------------------------
 struct Expr {
-  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER } kind;
+  // LIKE: l = the operand, r = the pattern (a STRING; null when the caller's pattern was not a string literal), flag = NOT
+  // LIKE, op = the ESCAPE byte or -1.  ISNULL: l = the operand, flag = IS NOT NULL.
+  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER, LIKE, ISNULL } kind;
   int op = 0;             // chq_binary_operator
   std::string text;       // number text / identifier / string bytes / debug text
-  bool flag = false;      // is_long / boolean value
+  bool flag = false;      // is_long / boolean value / negated
   std::vector<std::string> parts;
   std::unique_ptr<Expr> l, r;
 };
@@ -65,8 +68,10 @@ DType opaque_compare_class(const PlanColumn& c);
 
 struct Node {
   // (a CMP whose `from` is T_FIXED_OPAQUE compares two Decimal128 columns, a TOBOOL whose `from` is T_UTF8 parses a Utf8
-  // column: neither runs inside a device program -- the engine evaluates them into temporary Boolean columns first)
-  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL } kind;
+  // column: neither runs inside a device program -- the engine evaluates them into temporary Boolean columns first.  So do
+  // LIKE (l = the Utf8 operand, `like` = the compiled pattern, op = 1 for NOT LIKE) and ISNULL (l = the operand, op = 1 for
+  // IS NOT NULL): like.hip and typed_ops.hip.)
+  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL, LIKE, ISNULL } kind;
   DType type;
   bool is_scalar;   // ArrayDatum.is_scalar
   bool len1;        // array length is 1 regardless of the batch (built from literals only)
@@ -76,6 +81,7 @@ struct Node {
   int l = -1, r = -1;
   int ref_order = 0;
   DType from = T_BOOL;  // CAST / TOBOOL source type
+  std::shared_ptr<const LikePattern> like;   // LIKE
 };
 
 struct TypedExpr {

@@ -46,6 +46,7 @@ bool subtree_can_null(const TypedExpr& t, int ni, const std::vector<PlanColumn>&
   const Node& n = t.at(ni);
   if (n.kind == Node::COL) return cols[n.col].has_nulls;
   if (n.kind == Node::CONST) return n.cval.null;
+  if (n.kind == Node::ISNULL) return false;   // IS [NOT] NULL is never null
   bool r = n.kind == Node::TOBOOL && n.from == T_UTF8;   // a bad spelling is NULL
   if (n.l >= 0) r |= subtree_can_null(t, n.l, cols);
   if (n.r >= 0) r |= subtree_can_null(t, n.r, cols);

@@ -1,6 +1,7 @@
 // typed_ops.hip -- gfx950 kernels for the corners of the reference's type coverage that are not instructions of the
-// accumulator machine (device_program.h): Decimal128 comparisons and the Utf8 -> Boolean cast under AND / OR.  Both are
-// one pass over their input (32 B/row resp. the string bytes), one thread per row, one 64-bit ballot per wave as output.
+// accumulator machine (device_program.h): Decimal128 comparisons, the Utf8 -> Boolean cast under AND / OR and IS [NOT] NULL.
+// Each is one pass over its input (32 B/row, the string bytes, the validity bitmap), one thread per row, one 64-bit ballot
+// per wave as output.
 #include <hip/hip_runtime.h>
 
 #include "device_program.h"
@@ -114,6 +115,21 @@ __global__ __launch_bounds__(256) void utf8_to_bool_kernel(const Utf8ToBoolParam
     }
   }
 }
+
+// IS NULL / IS NOT NULL: the result is never null, so only the value words are written
+__global__ __launch_bounds__(256) void is_null_kernel(const IsNullParams p) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
+    const int64_t i = base + lane;
+    bool r = false;
+    if (i < p.nrows) {
+      const bool valid = !p.validity || bit_at(p.validity, p.validity_offset + i);
+      r = valid == (p.negated != 0);
+    }
+    const u64 rm = __ballot(r);
+    if (lane == 0) p.out_bits[base >> 6] = rm;
+  }
+}
 }  // namespace
 
 namespace {
@@ -149,6 +165,10 @@ static int grid_for(int64_t nrows) {
 }
 hipError_t launch_cmp128(const Cmp128Params& p, hipStream_t stream) {
   hipLaunchKernelGGL(cmp128_kernel, dim3(grid_for(p.nrows)), dim3(256), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_is_null(const IsNullParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(is_null_kernel, dim3(grid_for(p.nrows)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_utf8_uniform(const Utf8UniformParams& p, hipStream_t stream) {

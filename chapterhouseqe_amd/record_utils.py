@@ -318,6 +318,17 @@ def _expr_to_c(e: A.Expr):
     if isinstance(e, A.CompoundIdentifier):
         arr = (C.c_char_p * max(1, len(e.idents)))(*[i.value.encode() for i in e.idents])
         return lib.chq_expr_compound_identifier(arr, len(e.idents))
+    if isinstance(e, A.Like):
+        pat = e.pattern
+        while isinstance(pat, A.Nested):
+            pat = pat.expr
+        esc = -1 if e.escape_char is None else (ord(e.escape_char) if len(e.escape_char) == 1 and ord(e.escape_char) < 128 else 128)
+        if isinstance(pat, A.ValueExpr) and isinstance(pat.value, A.SingleQuotedString):
+            b = pat.value.value.encode()
+            return lib.chq_expr_like(_expr_to_c(e.expr), b, len(b), int(e.negated), esc)
+        return lib.chq_expr_like(_expr_to_c(e.expr), None, 0, int(e.negated), esc)   # the library reports NotSupported
+    if isinstance(e, A.IsNull):
+        return lib.chq_expr_is_null(_expr_to_c(e.expr), int(e.negated))
     if isinstance(e, A.UnsupportedExpr):
         return lib.chq_expr_unsupported(e.debug.encode())
     raise TypeError(f"not an Expr: {e!r}")

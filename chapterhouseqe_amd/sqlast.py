@@ -105,6 +105,23 @@ class Nested(Expr):
 
 
 @dataclass(frozen=True)
+class Like(Expr):
+    """Expr::Like { negated, expr, pattern, escape_char }: `expr [NOT] LIKE pattern [ESCAPE 'c']`.  The evaluator takes a
+    single-quoted string literal as `pattern` (Nested around it allowed); `escape_char` is None or one character."""
+    expr: Expr
+    pattern: Expr
+    negated: bool = False
+    escape_char: Optional[str] = None
+
+
+@dataclass(frozen=True)
+class IsNull(Expr):
+    """Expr::IsNull(expr) / Expr::IsNotNull(expr) (`negated`)"""
+    expr: Expr
+    negated: bool = False
+
+
+@dataclass(frozen=True)
 class UnsupportedExpr(Expr):
     """UnaryOp, Function, Case, ... -- compute_value.rs:338-342 rejects them."""
     debug: str

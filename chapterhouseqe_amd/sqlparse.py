@@ -3,9 +3,15 @@
 The reference gets its expressions from the third-party `sqlparser 0.52` crate (GenericDialect,
 reference: src/planner/logical_planner.rs:228-300; test use: record_utils/test_compute_value.rs:127-148).
 That crate is control-plane and out of scope; this module only restates enough of its *expression*
-grammar -- tokens, operator precedence (Or 5 < And 10 < comparison 20 < +,- 30 < *,/,% 40), left
+grammar -- tokens, operator precedence (Or 5 < And 10 < Is 17 < Like 19 < comparison 20 < +,- 30 < *,/,% 40), left
 associativity, `Nested` for parentheses, `Number` text kept verbatim -- for tests, the bench and the
 sample queries (reference: sample_queries/simple.sql) to be written as SQL text.
+
+    <expr> [not] like <expr> [escape '<one character>']      -> Like   (the evaluator wants a string literal as pattern)
+    <expr> is [not] null                                     -> IsNull
+  `like`, `not`, `is` and `escape` are operators only where these forms continue (`like` / `not like` in front of something
+  that can start an expression, `is` in front of `null` / `not null`, `escape` behind a pattern and in front of a string);
+  anywhere else they stay ordinary words, e.g. aliases.  Prefix `not <expr>` stays an UnsupportedExpr.
 
     select <items> from <func>('<path>') [[as] alias] {[inner] join <func>('<path>') [[as] alias] on <expr>}
         [where <expr>] [group by <column> {, ...}]
@@ -34,6 +40,7 @@ _TOKEN_RE = re.compile(
 )
 
 _PREC_OR, _PREC_AND, _PREC_NOT, _PREC_EQ = 5, 10, 15, 20
+_PREC_IS, _PREC_LIKE = 17, 19
 _PREC_PIPE, _PREC_CARET, _PREC_AMP, _PREC_XOR = 21, 22, 23, 24
 _PREC_PLUS, _PREC_MUL = 30, 40
 
@@ -138,8 +145,34 @@ class _Parser:
             raise SqlParseError(f"expected {op!r}, found {self.peek()[1]!r}")
 
     # ---- expressions: sqlparser Parser::parse_subexpr ------------------------------------------
+    def _word_at(self, j):
+        k, v = self.toks[self.i + j] if self.i + j < len(self.toks) else ("eof", "")
+        return v.upper() if k == "word" else None
+
+    def _starts_expr(self, j) -> bool:
+        k, v = self.toks[self.i + j] if self.i + j < len(self.toks) else ("eof", "")
+        if k == "word":
+            return v.upper() not in _STOP_WORDS
+        return k in ("number", "numberL", "string", "qident") or (k == "op" and v in ("(", "-", "+"))
+
+    def _infix_words(self):
+        """the word operator at the cursor: (node kind, negated, tokens it takes, precedence), or None"""
+        w = self._word_at(0)
+        if w == "LIKE" and self._starts_expr(1):
+            return ("like", False, 1, _PREC_LIKE)
+        if w == "NOT" and self._word_at(1) == "LIKE" and self._starts_expr(2):
+            return ("like", True, 2, _PREC_LIKE)
+        if w == "IS" and self._word_at(1) == "NULL":
+            return ("is", False, 2, _PREC_IS)
+        if w == "IS" and self._word_at(1) == "NOT" and self._word_at(2) == "NULL":
+            return ("is", True, 3, _PREC_IS)
+        return None
+
     def next_precedence(self):
         k, v = self.peek()
+        infix = self._infix_words()
+        if infix:
+            return infix[3]
         if k == "op" and v in _BINOPS:
             return _BINOPS[v][1]
         if k == "word" and v.upper() in _WORD_BINOPS:
@@ -152,6 +185,22 @@ class _Parser:
             nxt = self.next_precedence()
             if precedence >= nxt:
                 break
+            infix = self._infix_words()
+            if infix:   # sqlparser Parser::parse_infix: Keyword::LIKE / NOT / IS
+                kind, negated, ntok, _ = infix
+                self.i += ntok
+                if kind == "is":
+                    expr = A.IsNull(expr, negated)
+                    continue
+                pattern = self.parse_expr(_PREC_LIKE)
+                escape = None
+                if self._word_at(0) == "ESCAPE" and self.i + 1 < len(self.toks) and self.toks[self.i + 1][0] == "string":
+                    escape = self.toks[self.i + 1][1]
+                    self.i += 2
+                    if len(escape) != 1:
+                        raise SqlParseError(f"ESCAPE takes one character, found {escape!r}")
+                expr = A.Like(expr, pattern, negated, escape)
+                continue
             k, v = self.next()
             op = _BINOPS[v][0] if k == "op" else _WORD_BINOPS[v.upper()][0]
             right = self.parse_expr(nxt)

@@ -105,7 +105,8 @@ void* chq_ctx_stream(const chq_ctx* ctx);
  * Utf8 and Boolean comparisons, Float16 (widening, f16 arithmetic and comparisons), same-type comparisons of Date32 /
  * Date64 / Time32 / Time64 / Timestamp / Duration / Decimal128 columns, and casts to Boolean under AND / OR from numeric
  * and Utf8 operands (a spelling arrow-cast does not know is NULL).  CHQ_ERR_NOT_SUPPORTED remains for ARITHMETIC on
- * decimals, durations and date / timestamp differences, and for comparisons of FixedSizeBinary / interval columns. */
+ * decimals, durations and date / timestamp differences, and for comparisons of FixedSizeBinary / interval columns.
+ * Beyond the reference: [NOT] LIKE on Utf8 (chq_expr_like) and IS [NOT] NULL on every type (chq_expr_is_null). */
 chq_status chq_ctx_set_option(chq_ctx* ctx, const char* key, int64_t value);
 /* Counters of the last filter call: rows in, rows out, tiles, kernel launches. */
 typedef struct chq_call_stats {
@@ -141,6 +142,17 @@ chq_expr* chq_expr_unsupported_value(const char* debug);                      /*
  * Debug text, used in the BinaryOperatorNotImplemented message. */
 chq_expr* chq_expr_binary_op(chq_expr* left, chq_binary_operator op, const char* op_debug, chq_expr* right);
 chq_expr* chq_expr_nested(chq_expr* inner);                                   /* Expr::Nested; takes ownership */
+/* Expr::Like { negated, expr, pattern, escape_char }: `operand [NOT] LIKE 'pattern' [ESCAPE 'c']`; takes ownership of
+ * `operand`.  `pattern` / `pattern_len`: the bytes of the pattern when it is a single-quoted string literal (Nested around
+ * it removed), NULL otherwise -- typing then returns CHQ_ERR_NOT_SUPPORTED.  `escape`: -1 for none (there is NO default
+ * escape character), else one ASCII byte.  `%` = any run of bytes, `_` = one UTF-8 code point, anything else itself,
+ * bytewise and case-sensitive.  The operand must type to Utf8 (else CHQ_ERR_ARROW_INVALID_ARGUMENT, as for a pattern that
+ * ends in a lone escape); a compiled pattern holds at most 128 elements (literal bytes and `_`; more:
+ * CHQ_ERR_NOT_SUPPORTED).  Boolean, null exactly where the operand is null. */
+chq_expr* chq_expr_like(chq_expr* operand, const char* pattern, int64_t pattern_len, int negated, int escape);
+/* Expr::IsNull (negated = 0) / Expr::IsNotNull (negated = 1); takes ownership of `operand`, any expression that types
+ * (a bare column may have any type the library imports).  Boolean, never null. */
+chq_expr* chq_expr_is_null(chq_expr* operand, int negated);
 chq_expr* chq_expr_unsupported(const char* debug);                            /* any other Expr variant */
 void chq_expr_free(chq_expr* e);
 

@@ -165,6 +165,8 @@ extern "C" {
     pub fn chq_expr_unsupported_value(debug: *const c_char) -> *mut chq_expr;
     pub fn chq_expr_binary_op(left: *mut chq_expr, op: c_int, op_debug: *const c_char, right: *mut chq_expr) -> *mut chq_expr;
     pub fn chq_expr_nested(inner: *mut chq_expr) -> *mut chq_expr;
+    pub fn chq_expr_like(operand: *mut chq_expr, pattern: *const c_char, pattern_len: i64, negated: c_int, escape: c_int) -> *mut chq_expr;
+    pub fn chq_expr_is_null(operand: *mut chq_expr, negated: c_int) -> *mut chq_expr;
     pub fn chq_expr_unsupported(debug: *const c_char) -> *mut chq_expr;
     pub fn chq_expr_free(e: *mut chq_expr);
 

@@ -49,8 +49,9 @@ impl Drop for GpuContext {
     }
 }
 
-/// sqlparser::ast::Expr -> chq_expr (the variants compute_value.rs:62-343 matches on; everything else is
-/// passed as "unsupported" so the library reports the same ExpressionTypeNotImplemented error).
+/// sqlparser::ast::Expr -> chq_expr (the variants compute_value.rs:62-343 matches on, plus Like / IsNull / IsNotNull,
+/// which the library evaluates beyond the reference; everything else is passed as "unsupported" so the library reports
+/// the same ExpressionTypeNotImplemented error).
 fn lower_expr(e: &Expr) -> *mut chq_expr {
     let c = |s: &str| CString::new(s).unwrap();
     unsafe {
@@ -76,6 +77,25 @@ fn lower_expr(e: &Expr) -> *mut chq_expr {
                 let ptrs: Vec<*const c_char> = owned.iter().map(|s| s.as_ptr()).collect();
                 chq_expr_compound_identifier(ptrs.as_ptr(), ptrs.len() as i32)
             }
+            // `x [NOT] LIKE 'pattern' [ESCAPE 'c']`: the pattern goes over as bytes when it is a string literal (Nested
+            // removed), as NULL otherwise -- the library then answers NotSupported; a non-ASCII escape is not a byte
+            // (`any: true`, the `LIKE ANY (...)` form, is not a pattern literal: it takes the NULL route as well)
+            Expr::Like { negated, expr, pattern, escape_char, any } => {
+                let mut p: &Expr = pattern;
+                while let Expr::Nested(inner) = p { p = inner; }
+                let escape = match escape_char {   // sqlparser 0.52: Option<String>
+                    None => -1,
+                    Some(s) if s.len() == 1 && s.is_ascii() => s.as_bytes()[0] as i32,
+                    Some(_) => 128,
+                };
+                match p {
+                    Expr::Value(Value::SingleQuotedString(s)) if !*any =>
+                        chq_expr_like(lower_expr(expr), s.as_ptr() as *const c_char, s.len() as i64, *negated as i32, escape),
+                    _ => chq_expr_like(lower_expr(expr), std::ptr::null(), 0, *negated as i32, escape),
+                }
+            }
+            Expr::IsNull(inner) => chq_expr_is_null(lower_expr(inner), 0),
+            Expr::IsNotNull(inner) => chq_expr_is_null(lower_expr(inner), 1),
             other => chq_expr_unsupported(c(&format!("{:?}", other)).as_ptr()),
         }
     }
