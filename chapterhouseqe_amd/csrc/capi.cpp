@@ -397,6 +397,15 @@ chq_expr* chq_expr_is_null(chq_expr* operand, int negated) {
   delete operand;
   return e;
 }
+chq_expr* chq_expr_function(const char* name, chq_expr* const* args, int n_args) {
+  chq_expr* e = new_expr(Expr::FUNCTION);
+  bool ok = e && name && n_args >= 0 && (args || n_args == 0);
+  for (int i = 0; ok && i < n_args; ++i) ok = args[i] != nullptr;
+  if (!ok) { for (int i = 0; args && i < n_args; ++i) chq_expr_free(args[i]); delete e; return nullptr; }
+  e->e.text = name;
+  for (int i = 0; i < n_args; ++i) { e->e.args.emplace_back(new Expr(std::move(args[i]->e))); delete args[i]; }
+  return e;
+}
 chq_expr* chq_expr_unsupported(const char* debug) { chq_expr* e = new_expr(Expr::OTHER); if (e) e->e.text = debug ? debug : ""; return e; }
 void chq_expr_free(chq_expr* e) { delete e; }
 

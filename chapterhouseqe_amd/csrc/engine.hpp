@@ -15,6 +15,7 @@
 #include "device_program.h"
 #include "typed_ops.h"
 #include "like_device.h"
+#include "strfn_device.h"
 #include "plan.hpp"
 
 namespace chq {
@@ -29,6 +30,12 @@ hipError_t launch_cmp128(const Cmp128Params& p, hipStream_t stream);
 hipError_t launch_utf8_to_bool(const Utf8ToBoolParams& p, hipStream_t stream);
 hipError_t launch_is_null(const IsNullParams& p, hipStream_t stream);
 hipError_t launch_like(const LikeParams& p, hipStream_t stream);   // like.hip
+// strfn.hip
+hipError_t launch_strfn_bytemap(const StrByteMapParams& p, hipStream_t stream);
+hipError_t launch_strfn_rebase(const StrRebaseParams& p, hipStream_t stream);
+hipError_t launch_strfn_rows(const StrRowsParams& p, hipStream_t stream);
+hipError_t launch_strfn_scan(const StrScanParams& p, hipStream_t stream);   // sums: n_chunks + 1 words
+hipError_t launch_strfn_gather(const StrGatherParams& p, hipStream_t stream);
 hipError_t launch_utf8_uniform(const Utf8UniformParams& p, hipStream_t stream);
 hipError_t launch_iota_offsets(const IotaOffsetsParams& p, hipStream_t stream);
 hipError_t launch_count_bits(const uint8_t* in, int64_t bit_offset, int64_t nbits, unsigned long long* out, hipStream_t stream);

@@ -156,21 +156,161 @@ void materialize_node(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols,
 
 // Decimal128 comparisons, Utf8 -> Boolean casts, LIKE and IS [NOT] NULL are not device-program instructions (plan.hpp:
 // Node): their own kernels (typed_ops.hip, like.hip) write a temporary Boolean column, which replaces the node like any
-// other materialisation.
+// other materialisation.  The scalar string functions (strfn.hip) do the same with a temporary Utf8 or Int32 column.
 bool is_typed_op(const TypedExpr& te, int node) {
   const Node& n = te.nodes[node];
   return (n.kind == Node::CMP && n.from == T_FIXED_OPAQUE) || (n.kind == Node::TOBOOL && n.from == T_UTF8) ||
-         n.kind == Node::LIKE || n.kind == Node::ISNULL ||
+         n.kind == Node::LIKE || n.kind == Node::ISNULL || n.kind == Node::STRFN ||
          (n.kind == Node::CONST && n.cval.null);   // `'maybe' AND ..` folded to NULL, next to a column of a one-row batch
 }
 void fit_subtree(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict, bool is_root);
+// ---- the scalar string functions (strfn.hip) ------------------------------------------------------
+StrPart column_part(const Column& c) {
+  StrPart q{};
+  q.offsets = (const int32_t*)c.values0(); q.data = c.data;
+  q.validity = (c.validity && c.null_count != 0) ? c.validity : nullptr; q.validity_offset = c.offset;
+  return q;
+}
+// The temporary column of STRFN node `n`, whose operands are columns of `work` (or, for `||`, Utf8 literals).
+Column evaluate_strfn(Context& ctx, const Batch& work, const TypedExpr& te, const Node& n) {
+  const int64_t nrows = work.nrows;
+  Column c;
+  c.type = n.type; c.length = nrows;
+  if (n.type == T_UTF8) { c.format = "u"; c.width = 0; } else { c.format = "i"; c.width = 4; }
+  if (nrows == 0) {
+    auto vb = make_device_buffer(16, ctx.device);
+    check_hip(hipMemsetAsync(vb->ptr, 0, 16, ctx.stream), "memset");
+    c.values = (const uint8_t*)vb->ptr; c.owned.push_back(vb);
+    if (n.type == T_UTF8) { auto db = make_device_buffer(16, ctx.device); c.data = (const uint8_t*)db->ptr; c.data_bytes = 0; c.owned.push_back(db); }
+    check_hip(hipStreamSynchronize(ctx.stream), "sync");
+    return c;
+  }
+  const size_t words = (size_t)((nrows + 63) / 64) + 1;
+  auto valid = make_device_buffer(words * 8, ctx.device);
+  auto count = make_device_buffer(32, ctx.device);   // [0] null count (or valid count), [1] offsets[0], offsets[nrows] / the byte total
+  check_hip(hipMemsetAsync(count->ptr, 0, 32, ctx.stream), "memset");
+  u64 h_count[2] = {0, 0};
+  int64_t nulls = 0;
+  if (n.op == STRFN_UPPER || n.op == STRFN_LOWER) {
+    // the length is preserved: the input's offsets rebased to 0, a flat map over its byte range, its validity re-aligned
+    const Column& sc = work.cols[(size_t)te.nodes[n.l].col];
+    const int32_t* offs = (const int32_t*)sc.values0();
+    const bool may_null = sc.validity && sc.null_count != 0;
+    if (may_null) {
+      IsNullParams ip{};
+      ip.validity = sc.validity; ip.validity_offset = sc.offset; ip.nrows = nrows; ip.negated = 1; ip.out_bits = (u64*)valid->ptr;
+      check_hip(launch_is_null(ip, ctx.stream), "launch is_null_kernel");
+      check_hip(launch_count_bits(sc.validity, sc.offset, nrows, (u64*)count->ptr, ctx.stream), "launch count_bits_kernel");
+    }
+    int32_t ends[2] = {0, 0};
+    check_hip(hipMemcpyAsync(&ends[0], offs, 4, hipMemcpyDeviceToHost, ctx.stream), "read first offset");
+    check_hip(hipMemcpyAsync(&ends[1], offs + nrows, 4, hipMemcpyDeviceToHost, ctx.stream), "read last offset");
+    check_hip(hipMemcpyAsync(h_count, count->ptr, 8, hipMemcpyDeviceToHost, ctx.stream), "read valid count");
+    check_hip(hipStreamSynchronize(ctx.stream), "sync");
+    nulls = may_null ? nrows - (int64_t)h_count[0] : 0;
+    const int64_t bytes = (int64_t)ends[1] - ends[0];
+    auto offb = make_device_buffer((size_t)(nrows + 2) * 4, ctx.device), db = make_device_buffer((size_t)bytes + 16, ctx.device);
+    StrRebaseParams rp{offs, (int32_t*)offb->ptr, nrows + 1};
+    check_hip(launch_strfn_rebase(rp, ctx.stream), "launch strfn_rebase_kernel");
+    if (bytes > 0) {
+      StrByteMapParams bp{sc.data + ends[0], (uint8_t*)db->ptr, bytes, n.op == STRFN_UPPER ? 1 : 0, 0};
+      check_hip(launch_strfn_bytemap(bp, ctx.stream), "launch strfn_bytemap_kernel");
+    }
+    check_hip(hipStreamSynchronize(ctx.stream), "sync");
+    c.values = (const uint8_t*)offb->ptr; c.data = (const uint8_t*)db->ptr; c.data_bytes = bytes;
+    c.owned = {offb, db};
+  } else {
+    StrRowsParams rp{};
+    std::vector<BufferPtr> lits;
+    if (n.op == STRFN_CONCAT) {
+      for (int ci : n.parts) {
+        const Node& pn = te.nodes[(size_t)ci];
+        StrPart& q = rp.part[rp.n_parts++];
+        if (pn.kind == Node::COL) { q = column_part(work.cols[(size_t)pn.col]); continue; }
+        // a literal, the same for every row (the node's string outlives the copy: the stream is synchronised below)
+        auto lb = make_device_buffer(pn.cval.str.size() + 16, ctx.device);
+        if (!pn.cval.str.empty()) check_hip(hipMemcpyAsync(lb->ptr, pn.cval.str.data(), pn.cval.str.size(), hipMemcpyHostToDevice, ctx.stream), "upload string literal");
+        q.data = (const uint8_t*)lb->ptr; q.lit_len = (int32_t)pn.cval.str.size();
+        lits.push_back(lb);
+      }
+    } else {
+      rp.part[0] = column_part(work.cols[(size_t)te.nodes[n.l].col]);
+      rp.n_parts = 1;
+    }
+    rp.fn = n.op; rp.p = n.sub_p; rp.cnt = n.sub_cnt; rp.has_cnt = n.sub_has_cnt ? 1 : 0; rp.nrows = nrows;
+    auto i32 = make_device_buffer((size_t)nrows * 4 + 16, ctx.device);
+    rp.out_i32 = (int32_t*)i32->ptr; rp.out_validity = (u64*)valid->ptr; rp.null_count = (u64*)count->ptr;
+    const bool windowed = n.op != STRFN_CONCAT && n.type == T_UTF8;   // SUBSTRING / TRIM: one source range per row
+    BufferPtr start;
+    if (windowed) { start = make_device_buffer((size_t)nrows * 4 + 16, ctx.device); rp.out_start = (int32_t*)start->ptr; }
+    check_hip(launch_strfn_rows(rp, ctx.stream), "launch strfn_rows_kernel");
+    if (n.type == T_I32) {
+      check_hip(hipMemcpyAsync(h_count, count->ptr, 8, hipMemcpyDeviceToHost, ctx.stream), "read null count");
+      check_hip(hipStreamSynchronize(ctx.stream), "sync");
+      nulls = (int64_t)h_count[0];
+      c.values = (const uint8_t*)i32->ptr; c.owned = {i32};
+    } else {
+      StrScanParams sp{};
+      sp.len = (const uint32_t*)i32->ptr; sp.nrows = nrows; sp.n_chunks = (nrows + STRFN_SCAN_CHUNK - 1) / STRFN_SCAN_CHUNK;
+      auto sums = make_device_buffer((size_t)(sp.n_chunks + 1) * 8 + 16, ctx.device);
+      auto offb = make_device_buffer((size_t)(nrows + 2) * 4, ctx.device);
+      sp.sums = (u64*)sums->ptr; sp.out_offsets = (int32_t*)offb->ptr;
+      check_hip(launch_strfn_scan(sp, ctx.stream), "launch strfn_scan kernels");
+      check_hip(hipMemcpyAsync(&h_count[0], count->ptr, 8, hipMemcpyDeviceToHost, ctx.stream), "read null count");
+      check_hip(hipMemcpyAsync(&h_count[1], sp.sums + sp.n_chunks, 8, hipMemcpyDeviceToHost, ctx.stream), "read byte total");
+      check_hip(hipStreamSynchronize(ctx.stream), "sync");
+      nulls = (int64_t)h_count[0];
+      if (h_count[1] > (u64)INT32_MAX)
+        throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "the Utf8 result of a string function would hold " + std::to_string(h_count[1]) +
+                                                       " bytes, more than int32 offsets can address"};
+      const int64_t bytes = (int64_t)h_count[1];
+      auto db = make_device_buffer((size_t)bytes + 16, ctx.device);
+      if (bytes > 0) {
+        StrGatherParams gp{};
+        for (int k = 0; k < rp.n_parts; ++k) gp.part[k] = rp.part[k];
+        gp.n_parts = rp.n_parts; gp.nrows = nrows; gp.start = windowed ? (const int32_t*)start->ptr : nullptr;
+        gp.out_offsets = (const int32_t*)offb->ptr; gp.out_data = (uint8_t*)db->ptr;
+        check_hip(launch_strfn_gather(gp, ctx.stream), "launch strfn_gather_kernel");
+        check_hip(hipStreamSynchronize(ctx.stream), "sync");   // (the literals and the windows are let go on return)
+      }
+      c.values = (const uint8_t*)offb->ptr; c.data = (const uint8_t*)db->ptr; c.data_bytes = bytes;
+      c.owned = {offb, db};
+    }
+  }
+  c.null_count = nulls; c.nullable = nulls != 0;
+  if (nulls) { c.validity = (const uint8_t*)valid->ptr; c.owned.push_back(valid); }
+  return c;
+}
+
 void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict) {
-  if (te.nodes[node].kind == Node::ISNULL || te.nodes[node].kind == Node::LIKE) {
-    // the operand as a column: a computed one (IS NULL only; a literal-only one was folded at typing) is evaluated first,
-    // with its data-dependent errors, in the order `strict` asks for
-    const int l = te.nodes[node].l;
-    fit_subtree(ctx, work, wcols, te, l, strict, false);
-    if (te.nodes[l].kind != Node::COL) materialize_node(ctx, work, wcols, te, l);
+  {
+    // the operands as columns: a computed one (a literal-only one was folded at typing) is evaluated first, with its
+    // data-dependent errors, in the order `strict` asks for.  Until the string functions only IS NULL and LIKE had operands
+    // that were not columns; a Utf8 -> Boolean cast takes this route too now, for `upper(s) AND b` (its operand was always a
+    // column before, which this leaves alone).  A literal part of `||` -- and of `||` only -- stays a literal.
+    const Node::Kind kind = te.nodes[node].kind;
+    const bool is_concat = kind == Node::STRFN && te.nodes[node].op == STRFN_CONCAT;
+    std::vector<int> operands;
+    if (kind == Node::ISNULL || kind == Node::LIKE || kind == Node::TOBOOL || (kind == Node::STRFN && te.nodes[node].op != STRFN_CONCAT)) operands.push_back(te.nodes[node].l);
+    else if (kind == Node::STRFN) operands = te.nodes[node].parts;
+    for (int l : operands) {
+      fit_subtree(ctx, work, wcols, te, l, strict, false);
+      if (te.nodes[l].kind != Node::COL && !(is_concat && te.nodes[l].kind == Node::CONST)) materialize_node(ctx, work, wcols, te, l);
+    }
+  }
+  if (te.nodes[node].kind == Node::STRFN) {
+    const Node n = te.nodes[node];
+    Column c = evaluate_strfn(ctx, work, te, n);
+    c.name = "__chq_tmp_" + std::to_string(work.cols.size());
+    PlanColumn pc;
+    pc.name = c.name; pc.type = c.type; pc.has_nulls = c.null_count != 0; pc.alias_entry_present = true; pc.format = c.format; pc.width = c.width;
+    Node repl{};
+    repl.kind = Node::COL; repl.type = c.type; repl.is_scalar = false; repl.len1 = false;
+    repl.col = (int)work.cols.size(); repl.ref_order = n.ref_order;
+    work.cols.push_back(std::move(c));
+    wcols.push_back(std::move(pc));
+    te.nodes[node] = repl;
+    return;
   }
   const Node n = te.nodes[node];
   const int64_t nrows = work.nrows;

@@ -249,6 +249,30 @@ Scalar fold_constant(const TypedExpr& t, int ni) {
       return scalar_bits(T_BOOL, like_match(*n.like, (const uint8_t*)a.str.data(), (int32_t)a.str.size()) != (n.op != 0));
     }
     case Node::ISNULL: return scalar_bits(T_BOOL, fold_constant(t, n.l).null == (n.op == 0));   // never null itself
+    case Node::STRFN: {   // the per-row rules the device runs (strfn_device.h)
+      Scalar out; out.type = n.type;
+      if (n.op == STRFN_CONCAT) {
+        for (int c : n.parts) { Scalar a = fold_constant(t, c); if (a.null) return null_scalar(T_UTF8); out.str += a.str; }
+        return out;
+      }
+      const Scalar a = fold_constant(t, n.l);
+      if (a.null) return null_scalar(n.type);
+      const uint8_t* s = (const uint8_t*)a.str.data();
+      const int32_t len = (int32_t)a.str.size();
+      int32_t first = 0, count = len;
+      switch (n.op) {
+        case STRFN_UPPER: case STRFN_LOWER:
+          out.str = a.str;
+          for (char& c : out.str) c = (char)strfn_map_byte((uint8_t)c, n.op == STRFN_UPPER);
+          return out;
+        case STRFN_LENGTH: return scalar_bits(T_I32, (uint64_t)(int64_t)strfn_count_starts(s, len));
+        case STRFN_OCTET_LENGTH: return scalar_bits(T_I32, (uint64_t)(int64_t)len);
+        case STRFN_SUBSTRING: strfn_substr_window(s, len, n.sub_p, n.sub_has_cnt, n.sub_cnt, &first, &count); break;
+        default: strfn_trim_window(s, len, n.op != STRFN_RTRIM, n.op != STRFN_LTRIM, &first, &count); break;
+      }
+      out.str = a.str.substr((size_t)first, (size_t)count);
+      return out;
+    }
     default: fail(CHQ_ERR_INVALID_HANDLE, "fold_constant on a column");
   }
 }
@@ -379,8 +403,57 @@ struct Typer {
         n.is_scalar = t.nodes[l].is_scalar; n.len1 = t.nodes[l].len1;
         return maybe_fold(push(n));
       }
+      case Expr::FUNCTION: return function(e);
       default: fail(CHQ_ERR_EXPRESSION_TYPE_NOT_IMPLEMENTED, "expression type not implemented: " + e.text);
     }
+  }
+
+  // a scalar string function (strfn_device.h); names are case-insensitive
+  int function(const Expr& e) {
+    static const struct { const char* name; int fn; size_t min_args, max_args; } kFns[] = {
+        {"upper", STRFN_UPPER, 1, 1}, {"lower", STRFN_LOWER, 1, 1}, {"length", STRFN_LENGTH, 1, 1}, {"char_length", STRFN_LENGTH, 1, 1},
+        {"character_length", STRFN_LENGTH, 1, 1}, {"octet_length", STRFN_OCTET_LENGTH, 1, 1}, {"substring", STRFN_SUBSTRING, 2, 3},
+        {"substr", STRFN_SUBSTRING, 2, 3}, {"trim", STRFN_TRIM, 1, 1}, {"ltrim", STRFN_LTRIM, 1, 1}, {"rtrim", STRFN_RTRIM, 1, 1}};
+    int fn = -1; size_t lo = 0, hi = 0;
+    for (const auto& f : kFns) if (!strcasecmp(e.text.c_str(), f.name)) { fn = f.fn; lo = f.min_args; hi = f.max_args; }
+    // (an unknown name: what every call answered before there were functions)
+    if (fn < 0) fail(CHQ_ERR_EXPRESSION_TYPE_NOT_IMPLEMENTED, "expression type not implemented: Function(" + e.text + ")");
+    if (e.args.size() < lo || e.args.size() > hi)
+      fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, e.text + " takes " + (lo == hi ? std::to_string(lo) : std::to_string(lo) + " or " + std::to_string(hi)) +
+                                               " argument" + (hi == 1 ? "" : "s") + ", found " + std::to_string(e.args.size()));
+    const int l = build(*e.args[0]);
+    if (t.nodes[l].type != T_UTF8)
+      fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, e.text + " needs a Utf8 operand, found " + dtype_name(t.nodes[l].type));
+    Node n{}; n.kind = Node::STRFN; n.op = fn; n.from = T_UTF8; n.l = l;
+    n.type = (fn == STRFN_LENGTH || fn == STRFN_OCTET_LENGTH) ? T_I32 : T_UTF8;
+    n.is_scalar = t.nodes[l].is_scalar; n.len1 = t.nodes[l].len1;
+    if (fn == STRFN_SUBSTRING) {
+      int64_t v[2] = {0, 0};
+      for (size_t k = 1; k < e.args.size(); ++k) {
+        const Expr* a = e.args[k].get();
+        while (a->kind == Expr::NESTED) a = a->l.get();
+        if (a->kind != Expr::NUMBER || a->flag || !rust_parse_int(a->text, INT32_MIN, INT32_MAX, &v[k - 1]))
+          fail(CHQ_ERR_NOT_SUPPORTED, "the position and the length of " + e.text + " must be integer literals that fit Int32");
+      }
+      n.sub_p = (int32_t)v[0]; n.sub_cnt = (int32_t)v[1]; n.sub_has_cnt = e.args.size() == 3;
+      if (n.sub_has_cnt && n.sub_cnt < 0) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative substring length not allowed: " + std::to_string(n.sub_cnt));
+    }
+    return maybe_fold(push(n));
+  }
+
+  // `a || b`: both Utf8, no implicit cast.  A chain is left-associative: while the left side is itself an unfolded `||` with
+  // room, the right side joins its parts (one operation, one pass over the output) instead of nesting.
+  int concat(int l, int r) {
+    const Node &ln = t.nodes[l], &rn = t.nodes[r];
+    if (ln.type != T_UTF8 || rn.type != T_UTF8)
+      fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, std::string("|| needs Utf8 operands, found ") + dtype_name(ln.type) + " and " + dtype_name(rn.type));
+    Node n{}; n.kind = Node::STRFN; n.op = STRFN_CONCAT; n.type = T_UTF8; n.from = T_UTF8;
+    if (ln.kind == Node::STRFN && ln.op == STRFN_CONCAT && (int)ln.parts.size() < STRFN_MAX_PARTS) n.parts = ln.parts;
+    else n.parts.push_back(l);
+    n.parts.push_back(r);
+    n.is_scalar = true; n.len1 = true;
+    for (int c : n.parts) { n.is_scalar = n.is_scalar && t.nodes[c].is_scalar; n.len1 = n.len1 && t.nodes[c].len1; }
+    return maybe_fold(push(n));
   }
 
   // length of a datum: 1 for literal-built arrays, nrows for everything else
@@ -398,6 +471,7 @@ struct Typer {
       n.is_scalar = false; n.len1 = ln.len1 && rn.len1; n.l = l; n.r = r;
       return maybe_fold(push(n));
     }
+    if (e.op == CHQ_BINOP_STRING_CONCAT) return concat(l, r);
     int aop = -1, cop = -1;
     switch (e.op) {
       case CHQ_BINOP_PLUS: aop = OP_ADD; break;
@@ -470,7 +544,9 @@ struct Typer {
 static bool has_checked_arith(const TypedExpr& t, int ni) {
   const Node& n = t.at(ni);
   if (n.kind == Node::ARITH && is_int(n.type) && !n.len1) return true;
-  return (n.l >= 0 && has_checked_arith(t, n.l)) || (n.r >= 0 && has_checked_arith(t, n.r));
+  bool any = false;
+  n.each_child([&](int c) { any = any || has_checked_arith(t, c); });
+  return any;
 }
 
 TypedExpr type_expr(const Expr& e, const std::vector<PlanColumn>& cols, int64_t nrows, bool enable_minus) {
@@ -481,7 +557,7 @@ TypedExpr type_expr(const Expr& e, const std::vector<PlanColumn>& cols, int64_t 
   } catch (const ChqError& err) {
     // completed subtrees = nodes nobody points at; keep those that can fail on data, in evaluation order
     std::vector<char> is_child(ty.t.nodes.size(), 0);
-    for (const Node& n : ty.t.nodes) { if (n.l >= 0) is_child[n.l] = 1; if (n.r >= 0) is_child[n.r] = 1; }
+    for (const Node& n : ty.t.nodes) n.each_child([&](int c) { is_child[c] = 1; });
     std::vector<int> roots;
     for (size_t i = 0; i < ty.t.nodes.size(); ++i)
       if (!is_child[i] && has_checked_arith(ty.t, (int)i)) roots.push_back((int)i);
@@ -567,6 +643,7 @@ struct Gen {
         return;
       case Node::LIKE: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "LIKE runs as its own kernel");
       case Node::ISNULL: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "IS NULL runs as its own kernel");
+      case Node::STRFN: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "a string function runs as its own kernel");
       case Node::CMP:
         if (n.from == T_UTF8) { gen_strcmp(n); return; }
         if (n.from == T_FIXED_OPAQUE) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "Decimal128 comparison runs as its own kernel");
@@ -604,6 +681,7 @@ struct Gen {
     if (l.kind == Node::COL && r.kind == Node::CONST) { in.src_idx = (uint16_t)ref_of(l.col); in.imm = ((uint64_t)n.op << 56) | str_idx(r); }
     else if (l.kind == Node::CONST && r.kind == Node::COL) { in.src_idx = (uint16_t)ref_of(r.col); in.imm = ((uint64_t)n.op << 56) | str_idx(l); in.flags |= IF_REV; }
     else if (l.kind == Node::COL && r.kind == Node::COL) { in.src_idx = (uint16_t)ref_of(l.col); in.imm = ((uint64_t)n.op << 56) | (uint64_t)ref_of(r.col); in.flags |= IF_STR_RHS_COL; }
+    else if (l.kind == Node::STRFN || r.kind == Node::STRFN) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "a string function runs as its own kernel");
     else fail(CHQ_ERR_NOT_SUPPORTED, "Utf8 comparison operands must be columns or literals");
     emit(in);
   }

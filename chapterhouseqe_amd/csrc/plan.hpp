@@ -16,6 +16,7 @@
 #include "../../include/chq.h"
 #include "device_program.h"
 #include "like_device.h"
+#include "strfn_device.h"
 
 namespace chq {
 
@@ -30,13 +31,15 @@ constexpr int CHQ_INTERNAL_PROGRAM_LIMIT = 1030;
 // ---- sqlparser::ast::Expr mirror -----------------------------------------------------------------
 struct Expr {
   // LIKE: l = the operand, r = the pattern (a STRING; null when the caller's pattern was not a string literal), flag = NOT
-  // LIKE, op = the ESCAPE byte or -1.  ISNULL: l = the operand, flag = IS NOT NULL.
-  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER, LIKE, ISNULL } kind;
+  // LIKE, op = the ESCAPE byte or -1.  ISNULL: l = the operand, flag = IS NOT NULL.  FUNCTION: text = the name as written,
+  // args = the arguments (a scalar string function, strfn_device.h; any other name answers like OTHER "Function(name)").
+  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER, LIKE, ISNULL, FUNCTION } kind;
   int op = 0;             // chq_binary_operator
   std::string text;       // number text / identifier / string bytes / debug text
   bool flag = false;      // is_long / boolean value / negated
   std::vector<std::string> parts;
   std::unique_ptr<Expr> l, r;
+  std::vector<std::unique_ptr<Expr>> args;
 };
 
 const char* dtype_name(DType t);
@@ -70,8 +73,10 @@ struct Node {
   // (a CMP whose `from` is T_FIXED_OPAQUE compares two Decimal128 columns, a TOBOOL whose `from` is T_UTF8 parses a Utf8
   // column: neither runs inside a device program -- the engine evaluates them into temporary Boolean columns first.  So do
   // LIKE (l = the Utf8 operand, `like` = the compiled pattern, op = 1 for NOT LIKE) and ISNULL (l = the operand, op = 1 for
-  // IS NOT NULL): like.hip and typed_ops.hip.)
-  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL, LIKE, ISNULL } kind;
+  // IS NOT NULL): like.hip and typed_ops.hip.  STRFN is a scalar string function (op = its StrFn, l = the Utf8 operand; for
+  // STRFN_CONCAT `parts` = the 2..STRFN_MAX_PARTS operands of a flattened `a || b || ..` chain and l = r = -1; for
+  // STRFN_SUBSTRING sub_*): strfn.hip writes a temporary Utf8 or Int32 column.)
+  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL, LIKE, ISNULL, STRFN } kind;
   DType type;
   bool is_scalar;   // ArrayDatum.is_scalar
   bool len1;        // array length is 1 regardless of the batch (built from literals only)
@@ -82,6 +87,11 @@ struct Node {
   int ref_order = 0;
   DType from = T_BOOL;  // CAST / TOBOOL source type
   std::shared_ptr<const LikePattern> like;   // LIKE
+  std::vector<int> parts;                    // STRFN_CONCAT
+  int32_t sub_p = 0, sub_cnt = 0;            // STRFN_SUBSTRING: FROM sub_p [FOR sub_cnt]
+  bool sub_has_cnt = false;
+  // every operand: l, r and the parts
+  template <class F> void each_child(F f) const { if (l >= 0) f(l); if (r >= 0) f(r); for (int c : parts) f(c); }
 };
 
 struct TypedExpr {

@@ -5,6 +5,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <functional>
 
 namespace chq {
 
@@ -48,8 +49,7 @@ bool subtree_can_null(const TypedExpr& t, int ni, const std::vector<PlanColumn>&
   if (n.kind == Node::CONST) return n.cval.null;
   if (n.kind == Node::ISNULL) return false;   // IS [NOT] NULL is never null
   bool r = n.kind == Node::TOBOOL && n.from == T_UTF8;   // a bad spelling is NULL
-  if (n.l >= 0) r |= subtree_can_null(t, n.l, cols);
-  if (n.r >= 0) r |= subtree_can_null(t, n.r, cols);
+  n.each_child([&](int c) { r = r || subtree_can_null(t, c, cols); });   // (a string function: null where an operand is)
   return r;
 }
 
@@ -99,11 +99,20 @@ std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::ve
     const Node& root = exprs[k]->at(exprs[k]->root);
     Column& o = results[k];
     o.type = root.type; o.format = format_of(root.type); o.width = dtype_width(root.type); o.length = nrows;
-    if (root.type == T_UTF8 || root.type == T_FIXED_OPAQUE)
+    // (a Utf8 result is a string function's: fitting below turns it into a temporary column, which IS the result)
+    if ((root.type == T_UTF8 && root.kind != Node::STRFN) || root.type == T_FIXED_OPAQUE)
       throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("expression result of type ") + dtype_name(root.type) + " is outside this build's scope"};
   }
   if (nrows == 0) {
-    for (Column& o : results) { auto vb = make_device_buffer(16, ctx.device); o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb); }
+    for (Column& o : results) {
+      auto vb = make_device_buffer(16, ctx.device);
+      o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
+      if (o.type != T_UTF8) continue;
+      auto db = make_device_buffer(16, ctx.device);   // offsets = {0}, no bytes
+      check_hip(hipMemsetAsync(vb->ptr, 0, 16, ctx.stream), "memset");
+      o.data = (const uint8_t*)db->ptr; o.data_bytes = 0; o.owned.push_back(db);
+    }
+    check_hip(hipStreamSynchronize(ctx.stream), "sync");
     return results;
   }
   ensure_scratch(ctx, 1);
@@ -114,6 +123,12 @@ std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::ve
       // rest is evaluated like any other expression
       Batch work; std::vector<PlanColumn> wcols; TypedExpr fitted;
       fit_to_device(ctx, rec, pcols, *exprs[k], work, wcols, fitted);
+      if (fitted.at(fitted.root).kind == Node::COL) {   // a typed operation at the root: its temporary column is the result
+        results[k] = work.cols[(size_t)fitted.at(fitted.root).col];
+        results[k].name.clear();
+        ++k;
+        continue;
+      }
       std::vector<const TypedExpr*> one{&fitted};
       Column c = std::move(evaluate_dense(ctx, work, wcols, one)[0]);
       results[k] = std::move(c);
@@ -563,6 +578,18 @@ std::string describe_plan(const ArrowSchema* schema, const chq_table_aliases* al
     if (e.code != CHQ_INTERNAL_PROGRAM_LIMIT) throw;
     // valid, but more than one device program: the engine evaluates sub-trees into temporary columns first (fit_to_device)
     out += "split " + e.msg + "\n";
+    // the string functions of the tree, operands first: one line each, with the parts of a flattened `||` chain
+    static const char* kStrFn[] = {"upper", "lower", "length", "octet_length", "substring", "trim", "ltrim", "rtrim", "concat"};
+    std::function<void(int)> walk = [&](int ni) {
+      const Node& n = te.at(ni);
+      n.each_child(walk);
+      if (n.kind != Node::STRFN) return;
+      out += std::string("strfn ") + kStrFn[n.op];
+      if (n.op == STRFN_CONCAT) out += " parts=" + std::to_string(n.parts.size());
+      if (n.op == STRFN_SUBSTRING) out += " from=" + std::to_string(n.sub_p) + (n.sub_has_cnt ? " for=" + std::to_string(n.sub_cnt) : "");
+      out += "\n";
+    };
+    walk(te.root);
     return out;
   }
   out += "program wide=" + std::to_string((int)lw.wide) + " num_temps=" + std::to_string(lw.num_temps) + " refs=";

@@ -24,8 +24,11 @@ from . import sqlast as A
 _OPS = {A.BinaryOperator.And: 0, A.BinaryOperator.Or: 1, A.BinaryOperator.Plus: 2, A.BinaryOperator.Minus: 3,
         A.BinaryOperator.Multiply: 4, A.BinaryOperator.Divide: 5, A.BinaryOperator.Modulo: 6,
         A.BinaryOperator.Eq: 7, A.BinaryOperator.NotEq: 8, A.BinaryOperator.Gt: 9, A.BinaryOperator.GtEq: 10,
-        A.BinaryOperator.Lt: 11, A.BinaryOperator.LtEq: 12}
+        A.BinaryOperator.Lt: 11, A.BinaryOperator.LtEq: 12, A.BinaryOperator.StringConcat: 14}
 _OP_OTHER = 13
+# the scalar string functions the library evaluates (include/chq.h: chq_expr_function); every other call stays unsupported
+_SCALAR_FUNCTIONS = {"upper", "lower", "length", "char_length", "character_length", "octet_length", "substring", "substr",
+                     "trim", "ltrim", "rtrim"}
 
 
 class ChqError(Exception):
@@ -329,6 +332,17 @@ def _expr_to_c(e: A.Expr):
         return lib.chq_expr_like(_expr_to_c(e.expr), None, 0, int(e.negated), esc)   # the library reports NotSupported
     if isinstance(e, A.IsNull):
         return lib.chq_expr_is_null(_expr_to_c(e.expr), int(e.negated))
+    if isinstance(e, A.Function) and e.over is None and not e.star and e.args is not None and e.name.lower() in _SCALAR_FUNCTIONS:
+        built = []
+        try:
+            for a in e.args:
+                built.append(_expr_to_c(a))
+        except BaseException:
+            for h in built:   # (only chq_expr_function takes ownership of them)
+                lib.chq_expr_free(h)
+            raise
+        arr = (C.c_void_p * max(1, len(built)))(*built)
+        return lib.chq_expr_function(e.name.encode(), arr, len(built))
     if isinstance(e, A.UnsupportedExpr):
         return lib.chq_expr_unsupported(e.debug.encode())
     raise TypeError(f"not an Expr: {e!r}")

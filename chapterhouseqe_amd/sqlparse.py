@@ -242,7 +242,9 @@ class _Parser:
 
     def _function_call(self, name: str) -> A.Expr:
         """`name ( [* | expr {, expr}] )`; anything else between the parentheses is skipped (args None).  compute_value
-        rejects every call, so the evaluator sees `Function(name)` whatever the arguments are."""
+        rejects every call, so the reference's evaluator sees `Function(name)` whatever the arguments are.  `substring(s from p
+        [for n])` is the comma form spelled differently: the same `Function` with args (s, p[, n]).  The position and length
+        of substring / substr may carry a sign (`-3`): they are integer literals, kept as one Number."""
         start = self.i
         args, star = None, False
         try:
@@ -251,6 +253,15 @@ class _Parser:
                 star, parsed = True, []
             elif self.peek() == ("op", ")"):
                 parsed = []
+            elif name.lower() in ("substring", "substr"):
+                parsed = [self.parse_expr(0)]
+                if name.lower() == "substring" and self.accept_word("FROM"):
+                    parsed.append(self._signed_number_or_expr())
+                    if self.accept_word("FOR"):
+                        parsed.append(self._signed_number_or_expr())
+                else:
+                    while self.accept_op(","):
+                        parsed.append(self._signed_number_or_expr())
             else:
                 parsed = [self.parse_expr(0)]
                 while self.accept_op(","):
@@ -271,6 +282,16 @@ class _Parser:
                         break
         over = self._window_spec() if self.accept_word("OVER") else None
         return A.Function(f"Function({name})", name, args, star, over)
+
+    def _signed_number_or_expr(self) -> A.Expr:
+        """an argument that is `[-|+] number` alone becomes that signed Number; anything else parses as any expression"""
+        k, v = self.peek()
+        if k == "op" and v in ("-", "+") and self.i + 2 < len(self.toks) and self.toks[self.i + 1][0] == "number" and \
+                (self.toks[self.i + 2] in (("op", ","), ("op", ")")) or
+                 (self.toks[self.i + 2][0] == "word" and self.toks[self.i + 2][1].upper() == "FOR")):
+            self.i += 2
+            return A.ValueExpr(A.Number(("-" if v == "-" else "") + self.toks[self.i - 1][1], False))
+        return self.parse_expr(0)
 
     def _window_spec(self) -> A.WindowSpec:
         """`( [PARTITION BY e {, e}] [ORDER BY o {, o}] [ROWS | RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW |

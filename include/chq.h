@@ -106,7 +106,8 @@ void* chq_ctx_stream(const chq_ctx* ctx);
  * Date64 / Time32 / Time64 / Timestamp / Duration / Decimal128 columns, and casts to Boolean under AND / OR from numeric
  * and Utf8 operands (a spelling arrow-cast does not know is NULL).  CHQ_ERR_NOT_SUPPORTED remains for ARITHMETIC on
  * decimals, durations and date / timestamp differences, and for comparisons of FixedSizeBinary / interval columns.
- * Beyond the reference: [NOT] LIKE on Utf8 (chq_expr_like) and IS [NOT] NULL on every type (chq_expr_is_null). */
+ * Beyond the reference: [NOT] LIKE on Utf8 (chq_expr_like), IS [NOT] NULL on every type (chq_expr_is_null) and the scalar
+ * string functions (CHQ_BINOP_STRING_CONCAT, chq_expr_function), whose results are Utf8 or Int32 columns. */
 chq_status chq_ctx_set_option(chq_ctx* ctx, const char* key, int64_t value);
 /* Counters of the last filter call: rows in, rows out, tiles, kernel launches. */
 typedef struct chq_call_stats {
@@ -125,11 +126,14 @@ typedef struct chq_expr chq_expr;
 
 /* sqlparser::ast::BinaryOperator; arms implemented by RU/compute_value.rs:70-209 plus Minus, which the
  * reference rejects (compute_value.rs:210-216) and so does this library unless the context option
- * "enable_minus" is set. Any other operator: CHQ_BINOP_OTHER. */
+ * "enable_minus" is set. Any other operator: CHQ_BINOP_OTHER.
+ * CHQ_BINOP_STRING_CONCAT (`a || b`, beyond the reference; appended behind CHQ_BINOP_OTHER so that every earlier value keeps
+ * its number): the bytes of `a` followed by the bytes of `b`, null if either is null; both operands must type to Utf8 (no
+ * implicit cast, else CHQ_ERR_ARROW_INVALID_ARGUMENT). */
 typedef enum chq_binary_operator {
   CHQ_BINOP_AND = 0, CHQ_BINOP_OR, CHQ_BINOP_PLUS, CHQ_BINOP_MINUS, CHQ_BINOP_MULTIPLY, CHQ_BINOP_DIVIDE,
   CHQ_BINOP_MODULO, CHQ_BINOP_EQ, CHQ_BINOP_NOTEQ, CHQ_BINOP_GT, CHQ_BINOP_GTEQ, CHQ_BINOP_LT, CHQ_BINOP_LTEQ,
-  CHQ_BINOP_OTHER
+  CHQ_BINOP_OTHER, CHQ_BINOP_STRING_CONCAT
 } chq_binary_operator;
 
 chq_expr* chq_expr_identifier(const char* name);                              /* Expr::Identifier */
@@ -153,6 +157,28 @@ chq_expr* chq_expr_like(chq_expr* operand, const char* pattern, int64_t pattern_
 /* Expr::IsNull (negated = 0) / Expr::IsNotNull (negated = 1); takes ownership of `operand`, any expression that types
  * (a bare column may have any type the library imports).  Boolean, never null. */
 chq_expr* chq_expr_is_null(chq_expr* operand, int negated);
+/* Expr::Function: a scalar string function `name(args)`; takes ownership of the `n_args` arguments (also when it fails and
+ * returns NULL).  Names are case-insensitive.  This library's own semantics, bytewise and ASCII-only where case or
+ * whitespace is involved; a CODE POINT START is a byte that is not 0x80..0xBF (what `_` takes in LIKE); invalid UTF-8 is
+ * never an error and never makes a row read outside its own bytes.
+ *   upper(s), lower(s)                          Utf8   bytes a..z / A..Z mapped, every other byte unchanged
+ *   length(s), char_length(s),
+ *   character_length(s)                         Int32  code point starts in the row
+ *   octet_length(s)                             Int32  bytes in the row
+ *   substring(s, p[, n]), substr(s, p[, n])     Utf8   the SQL / PostgreSQL window over 1-based code point positions: position q
+ *                                                      is kept iff p <= q, q < p + n (with n) and 1 <= q <= length(s); p <= 0
+ *                                                      is legal.  As bytes: from byte 0 when p <= 1, else from the p-th start
+ *                                                      (or the row's end), to the max(p + n, 1)-th start (or the row's end).
+ *                                                      p and n: Number literals that fit Int32 (text may carry a sign, Nested
+ *                                                      allowed), else CHQ_ERR_NOT_SUPPORTED; n < 0: CHQ_ERR_ARROW_INVALID_ARGUMENT
+ *   trim(s), ltrim(s), rtrim(s)                 Utf8   byte 0x20 stripped from both ends / the left / the right
+ * Every result is null exactly where `s` is.  `s` must type to Utf8 (CHQ_ERR_ARROW_INVALID_ARGUMENT naming the function and
+ * the type found; the same status for a wrong argument count).  A call over literals only is folded on the host with the code
+ * the device runs.  A result column of more than 2^31 - 1 bytes: CHQ_ERR_ARROW_INVALID_ARGUMENT.  Any other name answers
+ * exactly like chq_expr_unsupported("Function(name)").  Out of scope: trim(both 'x' from s), position / strpos, replace,
+ * concat() as a function, initcap, reverse, lpad / rpad, ILIKE, implicit casts of numbers to strings, non-literal p / n,
+ * LargeUtf8, and these functions as ORDER BY / GROUP BY / JOIN / PARTITION keys. */
+chq_expr* chq_expr_function(const char* name, chq_expr* const* args, int n_args);
 chq_expr* chq_expr_unsupported(const char* debug);                            /* any other Expr variant */
 void chq_expr_free(chq_expr* e);
 

@@ -63,7 +63,9 @@ fn lower_expr(e: &Expr) -> *mut chq_expr {
                     BinaryOperator::Minus => 3, BinaryOperator::Multiply => 4, BinaryOperator::Divide => 5,
                     BinaryOperator::Modulo => 6, BinaryOperator::Eq => 7, BinaryOperator::NotEq => 8,
                     BinaryOperator::Gt => 9, BinaryOperator::GtEq => 10, BinaryOperator::Lt => 11,
-                    BinaryOperator::LtEq => 12, _ => 13,
+                    BinaryOperator::LtEq => 12,
+                    BinaryOperator::StringConcat => 14,   // CHQ_BINOP_STRING_CONCAT (beyond the reference; 13 = any other operator)
+                    _ => 13,
                 };
                 chq_expr_binary_op(lower_expr(left), code, c(&format!("{:?}", op)).as_ptr(), lower_expr(right))
             }
