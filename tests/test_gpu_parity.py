@@ -305,6 +305,10 @@ def test_fuzz_compute_value_vs_oracle(ctx, n):
 
 
 # ---- the reference's remaining type coverage: temporal / decimal same-type comparisons, Float16, Utf8 under AND / OR -------
+# spellings of the Utf8 -> Boolean cast: accepted ones, white space around them (Unicode too), near misses and the empty string
+BOOL_WORDS = ["true", "false", " yes", "NO ", "t", "0", "1", "off", "maybe", "", "on", "\u2003Y\u00a0", "fals", "truee"]
+
+
 def make_typed_batch(n, seed, nulls=True):
     import decimal
     rng = np.random.default_rng(seed)
@@ -322,7 +326,7 @@ def make_typed_batch(n, seed, nulls=True):
 
     halves = np.concatenate([np.array([0.0, -0.0, 1.0, 0.5, 65504.0, 6e-8, np.inf, -np.inf], dtype=np.float16),
                              (rng.standard_normal(64) * 8).astype(np.float16)])
-    words = np.array(["true", "false", " yes", "NO ", "t", "0", "1", "off", "maybe", "", "on", "\u2003Y\u00a0", "fals", "truee"])
+    words = np.array(BOOL_WORDS)
     cols = {
         "h": pa.array(halves[rng.integers(0, len(halves), n)], pa.float16(), mask=m(0.1)),
         "k": pa.array(halves[rng.integers(0, len(halves), n)], pa.float16()),
