@@ -19,43 +19,8 @@
 namespace chq {
 namespace {
 
-constexpr int kWaves = kAggBlock / 64;
-
-// sum of every thread's v over the workgroup (256 threads)
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* wave_sums) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (lane_id() == 0) wave_sums[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t tot = 0;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) tot += wave_sums[k];
-  __syncthreads();   // wave_sums may be reused
-  return tot;
-}
-
-// exclusive prefix of `v` over the workgroup (thread order); *total = sum of every thread's v
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wave_sums, uint32_t* total) {
-  const int lane = lane_id(), w = (int)(threadIdx.x >> 6);
-  uint32_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, (unsigned)o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wave_sums[w] = x;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) {
-    const uint32_t s = wave_sums[k];
-    if (k < w) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + x - v;
-}
+constexpr int kWaves = kScanWaves;
+static_assert(kAggBlock == kScanBlock && kAggItems == kScanItems && kAggTile == kScanTile, "the aggregate's tiles (the join's and the window's too) are the shared scan geometry");
 
 // ---- group heads ----------------------------------------------------------------------------------------------------------
 // do rows a and b fall into different groups by this key?  (both null: the same group; else equal bit patterns)
@@ -107,22 +72,14 @@ __global__ __launch_bounds__(kAggBlock) void agg_heads_kernel(const AggHeadsPara
   uint64_t* slot = (uint64_t*)(p.heads + p0);
   if (p.accumulate) word |= *slot;
   *slot = word;
-  const uint32_t tot = block_sum((uint32_t)__popcll(word), sums);
+  const uint32_t tot = block_sum<uint32_t>((uint32_t)__popcll(word), sums);
   if (threadIdx.x == 0) p.tile_counts[blockIdx.x] = tot;
 }
 
 // one workgroup: exclusive scan of the tile counts in place, the number of groups behind them
 __global__ __launch_bounds__(kAggBlock) void agg_head_scan_kernel(const AggGroupsParams p) {
   __shared__ uint32_t sums[kWaves];
-  uint32_t carry = 0, tot;
-  for (int64_t c0 = 0; c0 < p.ntiles; c0 += kAggBlock) {
-    const int64_t t = c0 + threadIdx.x;
-    const uint32_t v = t < p.ntiles ? p.tile_counts[t] : 0;
-    const uint32_t pre = block_exclusive_scan(v, sums, &tot) + carry;
-    if (t < p.ntiles) p.tile_counts[t] = pre;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) p.tile_counts[p.ntiles] = carry;
+  scan_totals_in_place<uint32_t>(p.tile_counts, p.ntiles, sums);
 }
 
 __global__ __launch_bounds__(kAggBlock) void agg_head_write_kernel(const AggGroupsParams p) {
@@ -130,7 +87,7 @@ __global__ __launch_bounds__(kAggBlock) void agg_head_write_kernel(const AggGrou
   const int64_t p0 = (int64_t)blockIdx.x * kAggTile + (int64_t)threadIdx.x * kAggItems;
   const uint64_t word = *(const uint64_t*)(p.heads + p0);
   uint32_t tot;
-  uint32_t g = block_exclusive_scan((uint32_t)__popcll(word), sums, &tot) + p.tile_counts[blockIdx.x];   // heads before p0
+  uint32_t g = block_exclusive_scan<uint32_t>((uint32_t)__popcll(word), sums, &tot) + p.tile_counts[blockIdx.x];   // heads before p0
 #pragma unroll
   for (int k = 0; k < kAggItems; ++k) {
     const int64_t pos = p0 + k;

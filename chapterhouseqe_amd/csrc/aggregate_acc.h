@@ -1,33 +1,14 @@
 // aggregate_acc.h -- device side only: the one accumulator of every aggregate (AggAcc, aggregate_device.h) -- identity,
-// combine, load through the permutation, conversion to the output value -- and the small loads around it.  Shared by the
+// combine, load through the permutation, conversion to the output value (the small loads around it: scan_device.h).  Shared by the
 // GROUP BY kernels (aggregate.hip: segmented reduce) and the window-function kernels (window.hip: segmented scan); the
 // parameter block P is AggReduceParams or WinAggParams, which name these fields alike.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "aggregate_device.h"
+#include "scan_device.h"   // lane_id, bit_at, load_uint, load_int
 
 namespace chq {
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
-__device__ __forceinline__ bool bit_at(const uint8_t* bits, int64_t pos) { return (bits[pos >> 3] >> (pos & 7)) & 1; }
-
-__device__ __forceinline__ uint64_t load_uint(const uint8_t* values, uint32_t r, int width) {
-  switch (width) {
-    case 1: return values[r];
-    case 2: return ((const uint16_t*)values)[r];
-    case 4: return ((const uint32_t*)values)[r];
-    default: return ((const uint64_t*)values)[r];
-  }
-}
-__device__ __forceinline__ int64_t load_int(const uint8_t* values, uint32_t r, int width) {
-  switch (width) {
-    case 1: return ((const int8_t*)values)[r];
-    case 2: return ((const int16_t*)values)[r];
-    case 4: return ((const int32_t*)values)[r];
-    default: return ((const int64_t*)values)[r];
-  }
-}
 
 __device__ __forceinline__ double as_double(uint64_t u) { return __longlong_as_double((long long)u); }
 __device__ __forceinline__ uint64_t as_bits(double d) { return (uint64_t)__double_as_longlong(d); }

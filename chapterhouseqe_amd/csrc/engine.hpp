@@ -34,7 +34,7 @@ hipError_t launch_like(const LikeParams& p, hipStream_t stream);   // like.hip
 hipError_t launch_strfn_bytemap(const StrByteMapParams& p, hipStream_t stream);
 hipError_t launch_strfn_rebase(const StrRebaseParams& p, hipStream_t stream);
 hipError_t launch_strfn_rows(const StrRowsParams& p, hipStream_t stream);
-hipError_t launch_strfn_scan(const StrScanParams& p, hipStream_t stream);   // sums: n_chunks + 1 words
+hipError_t launch_offsets_scan(const OffsetsScanParams& p, hipStream_t stream);   // scan.hip: 3 launches; tile_sums: ntiles + 1 words
 hipError_t launch_strfn_gather(const StrGatherParams& p, hipStream_t stream);
 hipError_t launch_utf8_uniform(const Utf8UniformParams& p, hipStream_t stream);
 hipError_t launch_iota_offsets(const IotaOffsetsParams& p, hipStream_t stream);

@@ -250,14 +250,14 @@ Column evaluate_strfn(Context& ctx, const Batch& work, const TypedExpr& te, cons
       nulls = (int64_t)h_count[0];
       c.values = (const uint8_t*)i32->ptr; c.owned = {i32};
     } else {
-      StrScanParams sp{};
-      sp.len = (const uint32_t*)i32->ptr; sp.nrows = nrows; sp.n_chunks = (nrows + STRFN_SCAN_CHUNK - 1) / STRFN_SCAN_CHUNK;
-      auto sums = make_device_buffer((size_t)(sp.n_chunks + 1) * 8 + 16, ctx.device);
+      OffsetsScanParams sp{};
+      sp.len = (const uint32_t*)i32->ptr; sp.n = nrows; sp.ntiles = (nrows + STRFN_SCAN_CHUNK - 1) / STRFN_SCAN_CHUNK;
+      auto sums = make_device_buffer((size_t)(sp.ntiles + 1) * 8 + 16, ctx.device);
       auto offb = make_device_buffer((size_t)(nrows + 2) * 4, ctx.device);
-      sp.sums = (u64*)sums->ptr; sp.out_offsets = (int32_t*)offb->ptr;
-      check_hip(launch_strfn_scan(sp, ctx.stream), "launch strfn_scan kernels");
+      sp.tile_sums = (uint64_t*)sums->ptr; sp.out = (uint32_t*)offb->ptr; sp.write_total = 1;
+      check_hip(launch_offsets_scan(sp, ctx.stream), "launch the offsets scan of the row lengths");
       check_hip(hipMemcpyAsync(&h_count[0], count->ptr, 8, hipMemcpyDeviceToHost, ctx.stream), "read null count");
-      check_hip(hipMemcpyAsync(&h_count[1], sp.sums + sp.n_chunks, 8, hipMemcpyDeviceToHost, ctx.stream), "read byte total");
+      check_hip(hipMemcpyAsync(&h_count[1], sp.tile_sums + sp.ntiles, 8, hipMemcpyDeviceToHost, ctx.stream), "read byte total");
       check_hip(hipStreamSynchronize(ctx.stream), "sync");
       nulls = (int64_t)h_count[0];
       if (h_count[1] > (u64)INT32_MAX)

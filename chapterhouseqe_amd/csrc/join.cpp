@@ -144,9 +144,9 @@ Batch join_resolved(Context& ctx, std::vector<Batch>& left, std::vector<Batch>& 
     }
     ++ctx.stats.launches;
     t.read += n * 8 + nL * 8; t.written += left_only ? nL * 4 : nL * 8;
-    JoinScanParams scp{};
-    scp.cnt = cp.cnt; scp.n_left = nL; scp.ntiles = ltiles; scp.tile_sums = (uint64_t*)sums->ptr; scp.off = (uint32_t*)off->ptr;
-    check_hip(launch_join_scan(scp, ctx.stream), "launch join_tile_sums/scan_sums/offsets_kernel");
+    OffsetsScanParams scp{};
+    scp.len = cp.cnt; scp.n = nL; scp.ntiles = ltiles; scp.tile_sums = (uint64_t*)sums->ptr; scp.out = (uint32_t*)off->ptr;
+    check_hip(launch_offsets_scan(scp, ctx.stream), "launch the offsets scan of the left rows");
     ctx.stats.launches += 3;
     t.read += nL * 8 + ltiles * 24; t.written += nL * 4 + ltiles * 16;
     // FULL: the right rows nobody matched, flagged in right input order and scanned like the counts
@@ -162,9 +162,9 @@ Batch join_resolved(Context& ctx, std::vector<Batch>& left, std::vector<Batch>& 
       check_hip(launch_join_tail_flag(tp, ctx.stream), "launch join_tail_flag_kernel");
       ++ctx.stats.launches;
       t.read += n * 8 + nR * 12; t.written += nR * 4;
-      JoinScanParams rsp{};
-      rsp.cnt = tp.flag; rsp.n_left = nR; rsp.ntiles = rtiles; rsp.tile_sums = (uint64_t*)rsums->ptr; rsp.off = (uint32_t*)roff->ptr;
-      check_hip(launch_join_scan(rsp, ctx.stream), "launch join_tile_sums/scan_sums/offsets_kernel");
+      OffsetsScanParams rsp{};
+      rsp.len = tp.flag; rsp.n = nR; rsp.ntiles = rtiles; rsp.tile_sums = (uint64_t*)rsums->ptr; rsp.out = (uint32_t*)roff->ptr;
+      check_hip(launch_offsets_scan(rsp, ctx.stream), "launch the offsets scan of the right rows");
       ctx.stats.launches += 3;
       t.read += nR * 8 + rtiles * 24; t.written += nR * 4 + rtiles * 16;
     }
@@ -182,7 +182,7 @@ Batch join_resolved(Context& ctx, std::vector<Batch>& left, std::vector<Batch>& 
       lidx = make_device_buffer((size_t)M * 4 + 16, ctx.device);
       if (!left_only) ridx = make_device_buffer((size_t)M * 4 + 16, ctx.device);
       JoinExpandParams ep{};
-      ep.perm = perm; ep.off = scp.off; ep.first = cp.first; ep.n_left = nL; ep.m = m_left;
+      ep.perm = perm; ep.off = scp.out; ep.first = cp.first; ep.n_left = nL; ep.m = m_left;
       ep.lidx = (uint32_t*)lidx->ptr; ep.ridx = ridx ? (uint32_t*)ridx->ptr : nullptr;
       if (m_left > 0) {
         if (kind == CHQ_JOIN_INNER) check_hip(launch_join_expand(ep, ctx.stream), "launch join_expand_kernel");

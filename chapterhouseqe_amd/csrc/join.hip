@@ -4,8 +4,7 @@
 // A run of equal keys lies in the sorted positions as [right rows in input order][left rows in input order]:
 //   split       split[g] = the position where the left rows of group g begin (a group with a null key: no right rows)
 //   count       for every left row l: cnt[l] = right rows of its group, first[l] = their first position
-//   scan        exclusive scan of cnt over the left rows in input order: tile sums, one workgroup over the sums IN 64 BITS
-//               (65 536 x 65 536 equal keys are 2^32 output rows: the total must not wrap), then the offsets per tile
+//   scan        exclusive scan of cnt over the left rows in input order, the total in 64 bits: launch_offsets_scan (scan.hip)
 //   expand      output j -> left row l = the largest l with off[l] <= j, right row perm[first[l] + (j - off[l])]: a binary
 //               search per output, narrowed to the left rows the tile covers -- O(log nL) at worst whatever the skew, and
 //               no thread walks a run or a gap
@@ -22,38 +21,10 @@
 #include <hip/hip_runtime.h>
 
 #include "join_device.h"
+#include "scan_device.h"
 
 namespace chq {
 namespace {
-
-constexpr int kWaves = kJoinBlock / 64;
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
-__device__ __forceinline__ bool bit_at(const uint8_t* bits, int64_t pos) { return (bits[pos >> 3] >> (pos & 7)) & 1; }
-
-// exclusive prefix of `v` over the workgroup (thread order); *total = sum of every thread's v
-template <typename T>
-__device__ __forceinline__ T block_exclusive_scan(T v, T* wave_sums, T* total) {
-  const int lane = lane_id(), w = (int)(threadIdx.x >> 6);
-  T x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T y = __shfl_up(x, (unsigned)o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wave_sums[w] = x;
-  __syncthreads();
-  T base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) {
-    const T s = wave_sums[k];
-    if (k < w) base += s;
-    tot += s;
-  }
-  __syncthreads();   // wave_sums may be reused
-  *total = tot;
-  return base + x - v;
-}
 
 // ---- split ------------------------------------------------------------------------------------------------------------------
 // Exactly one position per group writes: the last right row of the group, or -- a group without right rows -- its head.
@@ -116,60 +87,6 @@ __global__ __launch_bounds__(kJoinBlock) void join_count_kind_kernel(const JoinC
     } else {
       p.cnt[l] = q.rule == JOIN_COUNT_SEMI ? (c != 0) : (c == 0);
     }
-  }
-}
-
-// ---- scan -------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kJoinBlock) void join_tile_sums_kernel(const JoinScanParams p) {
-  __shared__ unsigned long long sums[kWaves];
-  const int64_t l0 = (int64_t)blockIdx.x * kJoinTile + (int64_t)threadIdx.x * kJoinItems;
-  unsigned long long v = 0;
-#pragma unroll
-  for (int k = 0; k < kJoinItems; ++k)
-    if (l0 + k < p.n_left) v += p.cnt[l0 + k];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (lane_id() == 0) sums[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long tot = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) tot += sums[k];
-    p.tile_sums[blockIdx.x] = tot;
-  }
-}
-
-// one workgroup: exclusive scan of the tile sums in place, in 64 bits; the total behind them
-__global__ __launch_bounds__(kJoinBlock) void join_scan_sums_kernel(const JoinScanParams p) {
-  __shared__ unsigned long long sums[kWaves];
-  unsigned long long carry = 0, tot;
-  for (int64_t c0 = 0; c0 < p.ntiles; c0 += kJoinBlock) {
-    const int64_t t = c0 + threadIdx.x;
-    const unsigned long long v = t < p.ntiles ? p.tile_sums[t] : 0;
-    const unsigned long long pre = block_exclusive_scan<unsigned long long>(v, sums, &tot) + carry;
-    if (t < p.ntiles) p.tile_sums[t] = pre;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) p.tile_sums[p.ntiles] = carry;
-}
-
-// off[l] = tile prefix + prefix inside the tile (u32: the caller refuses a total of 2^32 or more before it reads them)
-__global__ __launch_bounds__(kJoinBlock) void join_offsets_kernel(const JoinScanParams p) {
-  __shared__ uint32_t sums[kWaves];
-  const int64_t l0 = (int64_t)blockIdx.x * kJoinTile + (int64_t)threadIdx.x * kJoinItems;
-  uint32_t c[kJoinItems];
-  uint32_t v = 0;
-#pragma unroll
-  for (int k = 0; k < kJoinItems; ++k) {
-    c[k] = l0 + k < p.n_left ? p.cnt[l0 + k] : 0u;
-    v += c[k];
-  }
-  uint32_t tot;
-  uint32_t at = block_exclusive_scan<uint32_t>(v, sums, &tot) + (uint32_t)p.tile_sums[blockIdx.x];
-#pragma unroll
-  for (int k = 0; k < kJoinItems; ++k) {
-    if (l0 + k < p.n_left) p.off[l0 + k] = at;
-    at += c[k];
   }
 }
 
@@ -272,12 +189,6 @@ hipError_t launch_join_count(const JoinCountParams& p, hipStream_t stream) {
 }
 hipError_t launch_join_count_kind(const JoinCountKindParams& p, hipStream_t stream) {
   hipLaunchKernelGGL(join_count_kind_kernel, dim3(tiles_of(p.base.n)), dim3(kJoinBlock), 0, stream, p);
-  return hipGetLastError();
-}
-hipError_t launch_join_scan(const JoinScanParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(join_tile_sums_kernel, dim3((unsigned)p.ntiles), dim3(kJoinBlock), 0, stream, p);
-  hipLaunchKernelGGL(join_scan_sums_kernel, dim3(1), dim3(kJoinBlock), 0, stream, p);
-  hipLaunchKernelGGL(join_offsets_kernel, dim3((unsigned)p.ntiles), dim3(kJoinBlock), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_join_expand(const JoinExpandParams& p, hipStream_t stream) {

@@ -12,7 +12,6 @@ namespace chq {
 // join.hip
 hipError_t launch_join_split(const JoinSplitParams& p, hipStream_t stream);
 hipError_t launch_join_count(const JoinCountParams& p, hipStream_t stream);
-hipError_t launch_join_scan(const JoinScanParams& p, hipStream_t stream);   // tile sums, scan of the sums, offsets: 3 launches
 hipError_t launch_join_expand(const JoinExpandParams& p, hipStream_t stream);
 // the kinds other than INNER: count with a rule, expand with "no row" (right: LEFT / FULL; else lidx only), FULL's tail
 hipError_t launch_join_count_kind(const JoinCountKindParams& p, hipStream_t stream);

@@ -56,14 +56,6 @@ struct JoinCountKindParams {   // join_count_kind_kernel: join_count_kernel with
   int32_t pad;
 };
 
-struct JoinScanParams {   // join_tile_sums_kernel, join_scan_sums_kernel (one workgroup), join_offsets_kernel
-  const uint32_t* cnt;       // [nL]
-  int64_t n_left;
-  int64_t ntiles;            // tiles of kJoinTile left rows
-  uint64_t* tile_sums;       // [ntiles + 1]: matches per tile; after the scan their exclusive prefix, then the total M
-  uint32_t* off;             // [nL]: output rows before left row l (exact once M < 2^32 is known)
-};
-
 struct JoinExpandParams {   // join_expand_kernel: output j -> (left row, right row)
   const uint32_t* perm;      // [n] (null: identity)
   const uint32_t* off;       // [nL]
@@ -84,7 +76,7 @@ struct JoinTailParams {   // FULL's tail: the right rows no left row matches, as
   const uint32_t* starts;    // [G + 1] (starts[G] = n)
   const uint32_t* split;     // [G]
   uint32_t* flag;            // [nR] join_tail_flag_kernel: 1 iff right row r is in a run with a null key or without left rows
-  const uint32_t* off;       // [nR] join_tail_write_kernel: exclusive scan of flag (launch_join_scan)
+  const uint32_t* off;       // [nR] join_tail_write_kernel: exclusive scan of flag (launch_offsets_scan)
   int64_t m_left;            // rows of the LEFT part
   int64_t m;                 // m_left + the tail's length
   uint32_t* lidx;            // [m] lidx[m_left + off[r]] = kJoinNoRow

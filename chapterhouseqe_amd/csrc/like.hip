@@ -14,14 +14,11 @@
 #include <hip/hip_runtime.h>
 
 #include "like_device.h"
+#include "scan_device.h"   // bit_at
 
 namespace chq {
 namespace {
 typedef unsigned long long u64;
-
-__device__ __forceinline__ bool bit_at(const void* bits, int64_t i) {
-  return (((const uint8_t*)bits)[i >> 3] >> (i & 7)) & 1;
-}
 
 // the pieces between the anchored ones, found by the whole wave in s[pos, lim): every argument is wave-uniform
 __device__ bool wave_search(const LikePattern& pat, const uint8_t* s, int32_t pos, int32_t lim, int lane) {

@@ -7,51 +7,14 @@
 #include <hip/hip_runtime.h>
 
 #include "partition_device.h"
+#include "scan_device.h"
 
 namespace chq {
 namespace {
 
-constexpr int kWaves = kPartBlock / 64;
+constexpr int kWaves = kScanWaves;
+static_assert(kPartBlock == kScanBlock && kPartItems == kScanItems && kPartTile == kScanTile, "the partitioning's tiles are the shared scan geometry");
 static_assert(kPartBlock == kPartMaxPartitions, "one thread per partition id in the count, scan and scatter kernels");
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
-__device__ __forceinline__ uint64_t lanes_below() { return (1ull << lane_id()) - 1; }
-
-// exclusive prefix of `v` over the workgroup (256 threads, thread order); *total = sum of every thread's v
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wave_sums, uint32_t* total) {
-  const int lane = lane_id(), w = (int)(threadIdx.x >> 6);
-  uint32_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, (unsigned)o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wave_sums[w] = x;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) {
-    const uint32_t s = wave_sums[k];
-    if (k < w) base += s;
-    tot += s;
-  }
-  __syncthreads();   // wave_sums may be reused
-  *total = tot;
-  return base + x - v;
-}
-
-// lanes of this wave whose `d` (8 bits) equals this lane's, among the lanes in `active`
-__device__ __forceinline__ uint64_t id_peers(uint32_t d, uint64_t active) {
-  uint64_t peers = active;
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    const uint64_t m = __ballot((d >> b) & 1);
-    peers &= ((d >> b) & 1) ? m : ~m;
-  }
-  return peers;
-}
-
-__device__ __forceinline__ bool bit_at(const uint8_t* bits, int64_t pos) { return (bits[pos >> 3] >> (pos & 7)) & 1; }
 
 // ---- the pinned hash (include/chq.h: chq_partition_records) ------------------------------------------------------------
 constexpr uint64_t kGold = 0x9E3779B97F4A7C15ull;
@@ -121,7 +84,7 @@ __global__ __launch_bounds__(kPartBlock) void part_hash_kernel(const PartHashPar
     }
     const uint32_t d = valid ? (uint32_t)(((h >> 32) * (uint64_t)p.n_partitions) >> 32) : 0u;
     if (valid) p.ids[i] = (uint8_t)d;
-    const uint64_t peers = id_peers(d, __ballot(valid));
+    const uint64_t peers = byte_peers(d, __ballot(valid));
     if (valid && (peers & lanes_below()) == 0) atomicAdd(&cnt[d], (uint32_t)__popcll(peers));
   }
   __syncthreads();
@@ -136,23 +99,8 @@ __global__ __launch_bounds__(kPartBlock) void part_hash_kernel(const PartHashPar
 __global__ __launch_bounds__(kPartBlock) void part_scan_kernel(const PartScatterParams p) {
   __shared__ uint32_t sums[kWaves];
   const unsigned d = blockIdx.x;
-  uint32_t before = 0, tot = 0;
-  (void)block_exclusive_scan(threadIdx.x < d ? p.totals[threadIdx.x] : 0u, sums, &before);
-  uint32_t carry = before;
-  uint32_t* row = p.tile_counts + (int64_t)d * p.ntiles;
-  for (int64_t c0 = 0; c0 < p.ntiles; c0 += kPartTile) {
-    const int64_t at = c0 + (int64_t)threadIdx.x * kPartItems;
-    uint32_t v[kPartItems], s = 0;
-#pragma unroll
-    for (int k = 0; k < kPartItems; ++k) { v[k] = at + k < p.ntiles ? row[at + k] : 0; s += v[k]; }
-    uint32_t pre = block_exclusive_scan(s, sums, &tot) + carry;
-#pragma unroll
-    for (int k = 0; k < kPartItems; ++k) {
-      if (at + k < p.ntiles) row[at + k] = pre;
-      pre += v[k];
-    }
-    carry += tot;
-  }
+  const uint32_t before = block_sum<uint32_t>(threadIdx.x < d ? p.totals[threadIdx.x] : 0u, sums);
+  scan_count_rows<kPartItems>(p.tile_counts + (int64_t)d * p.ntiles, p.ntiles, before, sums);
 }
 
 // ranks every row of the tile, stages the row ids in LDS in partition order, then writes each partition's run contiguously
@@ -175,40 +123,16 @@ __global__ __launch_bounds__(kPartBlock) void part_scatter_kernel(const PartScat
     id[j] = i < p.n ? p.ids[i] : 0u;
   }
   __syncthreads();
-  uint32_t rank[kPartItems];
+  uint32_t pos[kPartItems];
+  const uint32_t out0 = threadIdx.x < p.n_partitions ? p.tile_counts[(int64_t)threadIdx.x * p.ntiles + tile] : 0u;
+  tile_positions<kPartItems>([&](int j) { return id[j]; }, wbase, p.n, wcnt, dstart, sums, pos);
+  gbase[threadIdx.x] = out0 - dstart[threadIdx.x];   // (mod 2^32: gbase + position < 2^32)
 #pragma unroll
   for (int j = 0; j < kPartItems; ++j) {
     const int64_t i = wbase + j * 64 + lane_id();
-    const bool valid = i < p.n;
-    const uint32_t d = id[j];
-    const uint64_t peers = id_peers(d, __ballot(valid));
-    const uint32_t before = wcnt[w][d];
-    rank[j] = before + (uint32_t)__popcll(peers & lanes_below());
-    // one lane per id moves the wave's counter on; every lane of the wave has read it above (LDS is in order per wave)
-    if (valid && (peers & lanes_below()) == 0) wcnt[w][d] = before + (uint32_t)__popcll(peers);
-  }
-  __syncthreads();
-  {   // per partition: offsets of the waves inside its run, and where the run starts in the tile and in the output
-    const unsigned d = threadIdx.x;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) { const uint32_t c = wcnt[k][d]; wcnt[k][d] = s; s += c; }
-    uint32_t total;
-    const uint32_t start = block_exclusive_scan(s, sums, &total);
-    dstart[d] = start;
-    gbase[d] = (d < p.n_partitions ? p.tile_counts[(int64_t)d * p.ntiles + tile] : 0u) - start;   // (mod 2^32: gbase + position < 2^32)
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kPartItems; ++j) {
-    const int64_t i = wbase + j * 64 + lane_id();
-    if (i < p.n) {
-      const uint32_t d = id[j];
-      const uint32_t pos = dstart[d] + wcnt[w][d] + rank[j];
-      if (pos < (uint32_t)kPartTile) {
-        sv[pos] = (uint32_t)i;
-        sd[pos] = (uint8_t)d;
-      }
+    if (i < p.n && pos[j] < (uint32_t)kPartTile) {
+      sv[pos[j]] = (uint32_t)i;
+      sd[pos[j]] = (uint8_t)id[j];
     }
   }
   __syncthreads();

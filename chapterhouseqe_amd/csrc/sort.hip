@@ -7,69 +7,14 @@
 
 #include <type_traits>
 
+#include "scan_device.h"
 #include "sort_device.h"
 
 namespace chq {
 namespace {
 
-constexpr int kWaves = kSortBlock / 64;
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
-__device__ __forceinline__ uint64_t lanes_below() { return (1ull << lane_id()) - 1; }
-
-// exclusive prefix of `v` over the workgroup (256 threads, thread order); *total = sum of every thread's v
-template <typename T>
-__device__ __forceinline__ T block_exclusive_scan(T v, T* wave_sums, T* total) {
-  const int lane = lane_id(), w = (int)(threadIdx.x >> 6);
-  T x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T y = __shfl_up(x, (unsigned)o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wave_sums[w] = x;
-  __syncthreads();
-  T base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) {
-    const T s = wave_sums[k];
-    if (k < w) base += s;
-    tot += s;
-  }
-  __syncthreads();   // wave_sums may be reused
-  *total = tot;
-  return base + x - v;
-}
-
-// lanes of this wave whose `d` (8 bits) equals this lane's, among the lanes in `active`
-__device__ __forceinline__ uint64_t digit_peers(uint32_t d, uint64_t active) {
-  uint64_t peers = active;
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    const uint64_t m = __ballot((d >> b) & 1);
-    peers &= ((d >> b) & 1) ? m : ~m;
-  }
-  return peers;
-}
-
-__device__ __forceinline__ bool bit_at(const uint8_t* bits, int64_t pos) { return (bits[pos >> 3] >> (pos & 7)) & 1; }
-
-__device__ __forceinline__ uint64_t load_uint(const uint8_t* values, uint32_t r, int width) {
-  switch (width) {
-    case 1: return values[r];
-    case 2: return ((const uint16_t*)values)[r];
-    case 4: return ((const uint32_t*)values)[r];
-    default: return ((const uint64_t*)values)[r];
-  }
-}
-__device__ __forceinline__ int64_t load_int(const uint8_t* values, uint32_t r, int width) {
-  switch (width) {
-    case 1: return ((const int8_t*)values)[r];
-    case 2: return ((const int16_t*)values)[r];
-    case 4: return ((const int32_t*)values)[r];
-    default: return ((const int64_t*)values)[r];
-  }
-}
+constexpr int kWaves = kScanWaves;
+static_assert(kSortBlock == kScanBlock && kSortItems == kScanItems && kSortTile == kScanTile, "the sort's tiles are the shared scan geometry");
 
 // ---- key words ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSortBlock) void sort_norm_kernel(const SortNormParams p) {
@@ -160,7 +105,7 @@ __global__ __launch_bounds__(kSortBlock) void sort_count_kernel(const SortPassPa
     const int64_t i = wbase + j * 64 + lane_id();
     const bool valid = i < p.n;
     const uint32_t d = valid ? (uint32_t)(p.keys_in[i] >> p.shift) & 255 : 0;
-    const uint64_t peers = digit_peers(d, __ballot(valid));
+    const uint64_t peers = byte_peers(d, __ballot(valid));
     if (valid && (peers & lanes_below()) == 0) atomicAdd(&cnt[d], (uint32_t)__popcll(peers));
   }
   __syncthreads();
@@ -171,23 +116,8 @@ __global__ __launch_bounds__(kSortBlock) void sort_count_kernel(const SortPassPa
 __global__ __launch_bounds__(kSortBlock) void sort_scan_kernel(const SortPassParams p) {
   __shared__ uint32_t sums[kWaves];
   const int d = blockIdx.x;
-  uint32_t before = 0, tot = 0;
-  (void)block_exclusive_scan<uint32_t>(threadIdx.x < (unsigned)d ? p.digit_hist[threadIdx.x] : 0u, sums, &before);
-  uint32_t carry = before;
-  uint32_t* row = p.tile_counts + (int64_t)d * p.ntiles;
-  for (int64_t c0 = 0; c0 < p.ntiles; c0 += kSortTile) {
-    const int64_t at = c0 + (int64_t)threadIdx.x * kSortItems;
-    uint32_t v[kSortItems], s = 0;
-#pragma unroll
-    for (int k = 0; k < kSortItems; ++k) { v[k] = at + k < p.ntiles ? row[at + k] : 0; s += v[k]; }
-    uint32_t pre = block_exclusive_scan<uint32_t>(s, sums, &tot) + carry;
-#pragma unroll
-    for (int k = 0; k < kSortItems; ++k) {
-      if (at + k < p.ntiles) row[at + k] = pre;
-      pre += v[k];
-    }
-    carry += tot;
-  }
+  const uint32_t before = block_sum<uint32_t>(threadIdx.x < (unsigned)d ? p.digit_hist[threadIdx.x] : 0u, sums);
+  scan_count_rows<kSortItems>(p.tile_counts + (int64_t)d * p.ntiles, p.ntiles, before, sums);
 }
 
 // ranks every pair of the tile, stages the tile in LDS in digit order, then writes each digit's run contiguously
@@ -212,40 +142,15 @@ __global__ __launch_bounds__(kSortBlock) void sort_scatter_kernel(const SortPass
     val[j] = i < p.n ? p.vals_in[i] : 0;
   }
   __syncthreads();
-  uint32_t rank[kSortItems];
+  uint32_t pos[kSortItems];
+  const uint32_t out0 = p.tile_counts[(int64_t)threadIdx.x * p.ntiles + tile];
+  tile_positions<kSortItems>([&](int j) { return (uint32_t)(key[j] >> p.shift) & 255; }, wbase, p.n, wcnt, dstart, sums, pos);
+  gbase[threadIdx.x] = out0 - dstart[threadIdx.x];   // (mod 2^32: gbase + position < 2^32)
 #pragma unroll
   for (int j = 0; j < kSortItems; ++j) {
-    const int64_t i = wbase + j * 64 + lane_id();
-    const bool valid = i < p.n;
-    const uint32_t d = (uint32_t)(key[j] >> p.shift) & 255;
-    const uint64_t peers = digit_peers(d, __ballot(valid));
-    const uint32_t before = wcnt[w][d];
-    rank[j] = before + (uint32_t)__popcll(peers & lanes_below());
-    // one lane per digit moves the wave's counter on; every lane of the wave has read it above (LDS is in order per wave)
-    if (valid && (peers & lanes_below()) == 0) wcnt[w][d] = before + (uint32_t)__popcll(peers);
-  }
-  __syncthreads();
-  {   // per digit: offsets of the waves inside the digit's run, and where the run starts in the tile and in the output
-    const int d = threadIdx.x;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) { const uint32_t c = wcnt[k][d]; wcnt[k][d] = s; s += c; }
-    uint32_t total;
-    const uint32_t start = block_exclusive_scan<uint32_t>(s, sums, &total);
-    dstart[d] = start;
-    gbase[d] = p.tile_counts[(int64_t)d * p.ntiles + tile] - start;   // (mod 2^32: gbase + position < 2^32)
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kSortItems; ++j) {
-    const int64_t i = wbase + j * 64 + lane_id();
-    if (i < p.n) {
-      const uint32_t d = (uint32_t)(key[j] >> p.shift) & 255;
-      const uint32_t pos = dstart[d] + wcnt[w][d] + rank[j];
-      if (pos < (uint32_t)kSortTile) {
-        sk[pos] = key[j];
-        sv[pos] = val[j];
-      }
+    if (wbase + j * 64 + lane_id() < p.n && pos[j] < (uint32_t)kSortTile) {
+      sk[pos[j]] = key[j];
+      sv[pos[j]] = val[j];
     }
   }
   __syncthreads();
@@ -343,23 +248,14 @@ __global__ __launch_bounds__(kSortBlock) void sort_utf8_tile_sums_kernel(const S
   uint64_t s = 0;
 #pragma unroll
   for (int k = 0; k < kSortItems; ++k) s += gathered_len<kPad>(p, at + k);
-  uint64_t tot;
-  (void)block_exclusive_scan<uint64_t>(s, sums, &tot);
+  const uint64_t tot = block_sum<uint64_t>(s, sums);
   if (threadIdx.x == 0) p.tile_sums[blockIdx.x] = tot;
 }
 
 // Utf8 step 2 (one workgroup): exclusive scan of the tile totals in place, the grand total behind them
 __global__ __launch_bounds__(kSortBlock) void sort_utf8_scan_sums_kernel(const SortGatherParams p) {
   __shared__ uint64_t sums[kWaves];
-  uint64_t carry = 0, tot;
-  for (int64_t c0 = 0; c0 < p.ntiles; c0 += kSortBlock) {
-    const int64_t t = c0 + threadIdx.x;
-    const uint64_t v = t < p.ntiles ? p.tile_sums[t] : 0;
-    const uint64_t pre = block_exclusive_scan<uint64_t>(v, sums, &tot) + carry;
-    if (t < p.ntiles) p.tile_sums[t] = pre;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) p.tile_sums[p.ntiles] = carry;
+  scan_totals_in_place<uint64_t>(p.tile_sums, p.ntiles, sums);
 }
 
 // Utf8 step 3: output offsets (the host has checked that the grand total fits int32)

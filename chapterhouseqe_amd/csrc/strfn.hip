@@ -8,12 +8,13 @@
 //                          row lengths of `||`; validity word and null count like typed_ops.hip.  Two modes like like.hip:
 //                          lane per row, or -- more than STRFN_WAVE_MODE_BYTES in the wave's 64 rows -- wave per row with a
 //                          ballot + popcount per 64-byte step.
-//   strfn_scan_*           exclusive scan of the row lengths -> Int32 offsets and the 64-bit byte total.
+//   (scan.hip)             exclusive scan of the row lengths -> Int32 offsets and the 64-bit byte total: launch_offsets_scan.
 //   strfn_gather_kernel    the bytes of every output row from 1 source range or up to STRFN_MAX_PARTS parts; same two modes.
 // Every load of string data is a byte load inside [offsets[i], offsets[i + 1]) of a VALID row i < nrows (the byte map: inside
 // [offsets[0], offsets[nrows])): no padding is assumed, and data may be null when there are no bytes.
 #include <hip/hip_runtime.h>
 
+#include "scan_device.h"
 #include "strfn_device.h"
 
 namespace chq {
@@ -21,10 +22,6 @@ namespace {
 typedef unsigned long long u64;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 u32x4_unaligned __attribute__((aligned(1)));
-
-__device__ __forceinline__ bool bit_at(const void* bits, int64_t i) {
-  return (((const uint8_t*)bits)[i >> 3] >> (i & 7)) & 1;
-}
 
 // ---- UPPER / LOWER -------------------------------------------------------------------------------------------------------
 // four bytes at once: bit 7 of each byte of `m` marks an ASCII letter of the case that changes; its bit 5 is flipped
@@ -164,64 +161,6 @@ __global__ __launch_bounds__(256) void strfn_rows_kernel(const StrRowsParams p) 
   }
 }
 
-// ---- scan ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 wave_inclusive_scan(u64 v, int lane) {
-  for (int d = 1; d < 64; d <<= 1) {
-    const u64 o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// block c: the sum of the lengths of rows [c CHUNK, (c + 1) CHUNK)
-__global__ __launch_bounds__(256) void strfn_scan_sums_kernel(const StrScanParams p) {
-  __shared__ u64 wave_sum[4];
-  const int64_t row0 = (int64_t)blockIdx.x * STRFN_SCAN_CHUNK;
-  u64 s = 0;
-  for (int j = 0; j < STRFN_SCAN_CHUNK / 256; ++j) {
-    const int64_t i = row0 + j * 256 + threadIdx.x;
-    if (i < p.nrows) s += p.len[i];
-  }
-  const int lane = threadIdx.x & 63;
-  s = wave_inclusive_scan(s, lane);
-  if (lane == 63) wave_sum[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) p.sums[blockIdx.x] = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-}
-// one wave: sums[c] becomes the bytes before chunk c, sums[n_chunks] the total
-__global__ __launch_bounds__(64) void strfn_scan_chunks_kernel(const StrScanParams p) {
-  const int lane = threadIdx.x;
-  u64 carry = 0;
-  for (int64_t c0 = 0; c0 < p.n_chunks; c0 += 64) {
-    const int64_t c = c0 + lane;
-    const u64 v = c < p.n_chunks ? p.sums[c] : 0;
-    const u64 inc = wave_inclusive_scan(v, lane);
-    if (c < p.n_chunks) p.sums[c] = carry + inc - v;
-    carry += __shfl(inc, 63);
-  }
-  if (lane == 0) p.sums[p.n_chunks] = carry;
-}
-// block c: the offsets of its rows; thread t takes 8 consecutive rows
-__global__ __launch_bounds__(256) void strfn_scan_offsets_kernel(const StrScanParams p) {
-  __shared__ u64 wave_sum[4];
-  constexpr int PER = STRFN_SCAN_CHUNK / 256;
-  const int64_t row0 = (int64_t)blockIdx.x * STRFN_SCAN_CHUNK + (int64_t)threadIdx.x * PER;
-  uint32_t len[PER];
-  u64 s = 0;
-  for (int j = 0; j < PER; ++j) { len[j] = row0 + j < p.nrows ? p.len[row0 + j] : 0; s += len[j]; }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const u64 inc = wave_inclusive_scan(s, lane);
-  if (lane == 63) wave_sum[wave] = inc;
-  __syncthreads();
-  u64 at = p.sums[blockIdx.x] + inc - s;
-  for (int w = 0; w < wave; ++w) at += wave_sum[w];
-  for (int j = 0; j < PER; ++j) {
-    if (row0 + j < p.nrows) p.out_offsets[row0 + j] = (int32_t)(uint32_t)at;
-    at += len[j];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) p.out_offsets[p.nrows] = (int32_t)(uint32_t)p.sums[p.n_chunks];
-}
-
 // ---- gather ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void strfn_gather_kernel(const StrGatherParams p) {
   const int lane = threadIdx.x & 63;
@@ -284,13 +223,6 @@ hipError_t launch_strfn_rebase(const StrRebaseParams& p, hipStream_t stream) {
 }
 hipError_t launch_strfn_rows(const StrRowsParams& p, hipStream_t stream) {
   hipLaunchKernelGGL(strfn_rows_kernel, dim3(capped_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
-  return hipGetLastError();
-}
-// sums: n_chunks + 1 words
-hipError_t launch_strfn_scan(const StrScanParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(strfn_scan_sums_kernel, dim3((unsigned)p.n_chunks), dim3(256), 0, stream, p);
-  hipLaunchKernelGGL(strfn_scan_chunks_kernel, dim3(1), dim3(64), 0, stream, p);
-  hipLaunchKernelGGL(strfn_scan_offsets_kernel, dim3((unsigned)p.n_chunks), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_strfn_gather(const StrGatherParams& p, hipStream_t stream) {

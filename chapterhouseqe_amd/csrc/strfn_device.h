@@ -105,12 +105,11 @@ struct StrRowsParams {
   unsigned long long* out_validity; unsigned long long* null_count;
 };
 
-// The exclusive scan of the row lengths in three launches: sums of STRFN_SCAN_CHUNK rows, their scan by one block (which
-// also leaves the 64-bit total in sums[n_chunks]), the Int32 offsets [nrows + 1].  The host checks the total against the
-// Int32 range before anything reads offsets that wrapped.  The lengths are read as UNSIGNED: a `||` row whose parts sum past
-// 2^32 - 1 is stored as that, which alone puts the total out of range.
+// The exclusive scan of the row lengths is launch_offsets_scan (scan.hip, typed_ops.h) over tiles of STRFN_SCAN_CHUNK rows,
+// the total written behind the offsets.  The host checks the 64-bit total against the Int32 range before anything reads
+// offsets that wrapped.  The lengths are read as UNSIGNED: a `||` row whose parts sum past 2^32 - 1 is stored as that, which
+// alone puts the total out of range.
 constexpr int STRFN_SCAN_CHUNK = 2048;
-struct StrScanParams { const uint32_t* len; int64_t nrows; int64_t n_chunks; unsigned long long* sums; int32_t* out_offsets; };
 
 // strfn_gather_kernel: row i of the output = for each part, its bytes ([start[i], start[i] + length) of part[0].data when
 // `start` is given: SUBSTRING / TRIM).  Rows whose output is empty (null rows among them) are not read.

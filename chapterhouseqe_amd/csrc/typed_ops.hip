@@ -5,13 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include "device_program.h"
+#include "scan_device.h"   // bit_at
 #include "typed_ops.h"
 
 namespace chq {
 namespace {
-__device__ __forceinline__ bool bit_at(const void* bits, int64_t i) {
-  return (((const uint8_t*)bits)[i >> 3] >> (i & 7)) & 1;
-}
 
 // arrow-ord cmp::{eq,neq,lt,lt_eq,gt,gt_eq} on i128 natives (RU/compute_value.rs:118-209 after the `left == right` arm of
 // get_common_type, :355).  Validity = both valid.

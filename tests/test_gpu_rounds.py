@@ -1,5 +1,6 @@
 """GPU: the SECOND round of every loop that walks its input in rounds -- the single-workgroup scans that carry a running total
-from one round of tile totals into the next (join.hip, partition.hip, sort.hip, strfn.hip), and the launches whose grid is
+from one round of tile totals into the next (scan_device.h: one loop for the join, the sort, the group heads and the string
+functions, one for the count rows of partition.hip and sort.hip), and the launches whose grid is
 capped so that a thread strides on to further rows (strfn.hip, like.hip, typed_ops.hip).  Each test feeds the smallest input
 that puts more than one full tile (or one full wave) into the second round, compares the whole result with the host reference
 its sibling tests use, and asserts that a non-trivial part of the output is produced by the second round.
@@ -10,13 +11,16 @@ Python reference is evaluated once per pool entry and expanded with the same ind
 side is the cost.
 
   loop                                          one round covers          its second round is reached by
-  join_scan_sums_kernel, left rows              256 tiles x 2048          test_{inner,left,semi_and_anti}_join_left_rows_past_one_scan_round
-  join_scan_sums_kernel, FULL's right rows      256 tiles x 2048          test_full_join_tail_of_right_rows_past_one_scan_round
-  part_scan_kernel                              2048 tiles x 2048 rows    test_partition_more_tiles_than_one_scan_round (3 and 256 partitions)
-  sort_utf8_scan_sums_kernel, plain             256 tiles x 2048          test_sorted_utf8_payload_past_one_scan_round
-  sort_utf8_scan_sums_kernel, "no row" padding  256 tiles x 2048          test_left_joined_utf8_payload_past_one_scan_round
-  strfn_scan_chunks_kernel                      64 chunks x 2048 rows     test_string_functions_more_chunks_than_one_scan_round (two chunks in round
-                                                                          two), and at 1 025 chunks test_gpu_strfn.py::test_more_rows_than_one_grid_pass
+  scan_totals_in_place (scan_device.h), the shared loop over tile totals, one total per thread of one workgroup, as
+    scan_totals_kernel, the join's left rows    256 tiles x 2048          test_{inner,left,semi_and_anti}_join_left_rows_past_one_scan_round
+    scan_totals_kernel, FULL's right rows       256 tiles x 2048          test_full_join_tail_of_right_rows_past_one_scan_round
+    scan_totals_kernel, string functions        256 tiles x 2048          test_string_functions_more_chunks_than_one_scan_round (two tiles in round
+                                                                          two), and at 1 025 tiles test_gpu_strfn.py::test_more_rows_than_one_grid_pass
+    sort_utf8_scan_sums_kernel, plain           256 tiles x 2048          test_sorted_utf8_payload_past_one_scan_round
+    sort_utf8_scan_sums_kernel, "no row"        256 tiles x 2048          test_left_joined_utf8_payload_past_one_scan_round
+    agg_head_scan_kernel                        256 tiles x 2048          every join above (the runs of the concatenated keys)
+  scan_count_rows (scan_device.h), as
+    part_scan_kernel                            2048 tiles x 2048 rows    test_partition_more_tiles_than_one_scan_round (3 and 256 partitions)
   strfn_rows_kernel, strfn_gather_kernel        8192 workgroups x 256     test_string_functions_more_rows_than_one_grid_pass (wave per row in the strided
                                                                           iteration, a sliced view), ..._short_rows_in_the_strided_iteration (lane per
                                                                           row), test_gpu_strfn.py::test_more_rows_than_one_grid_pass (rows of 0..3 bytes)
@@ -55,10 +59,10 @@ from .test_gpu_strfn import WAVE_MODE_BYTES as STRFN_WAVE_MODE_BYTES
 
 pytestmark = pytest.mark.gpu
 
-T = 2048                              # rows (or tile totals) per workgroup tile: kAggTile = kJoinTile, kPartTile, kSortTile, STRFN_SCAN_CHUNK
-SCAN_ROUND = 256 * T                  # join_scan_sums_kernel, sort_utf8_scan_sums_kernel: one tile total per thread and round
-PART_ROUND = T * T                    # part_scan_kernel: kPartItems tile counts per thread and round
-STRFN_ROUND = 64 * T                  # strfn_scan_chunks_kernel: one wave, one chunk total per lane and round
+T = 2048                              # rows (or tile totals) per workgroup tile: kScanTile = kAggTile = kJoinTile, kPartTile, kSortTile, STRFN_SCAN_CHUNK
+SCAN_ROUND = 256 * T                  # scan_totals_in_place (the join's scans, sort_utf8_scan_sums_kernel): one tile total per thread and round
+PART_ROUND = T * T                    # part_scan_kernel (scan_count_rows): kPartItems tile counts per thread and round
+STRFN_ROUND = 256 * T                 # scan_totals_in_place under the string functions: the same loop, the same round
 STRIDE_ROWS = 8192 * 256              # rows one pass of a grid capped at 256 * 32 workgroups covers (strfn rows / gather, like, typed_ops)
 BYTEMAP_BYTES = 4096 * 256 * 16       # bytes one pass of strfn_bytemap_kernel's grid covers (capped at 256 * 16 workgroups)
 REBASE_ROWS = 4096 * 256              # offsets one pass of strfn_rebase_kernel's grid covers
@@ -126,7 +130,7 @@ def same_array(got, exp, what):
             raise AssertionError(f"{what}: values differ first at rows {bad.tolist()}: got {g[bad].tolist()} expected {e[bad].tolist()}")
 
 
-# ---- joins: join_scan_sums_kernel over more than 256 tiles of left rows -----------------------------------------------------
+# ---- joins: scan_totals_kernel over more than 256 tiles of left rows --------------------------------------------------------
 def payload_strings(rng, count):
     """Utf8 payload pool: lengths 0..40 (both branches of the gather's copy: up to 32 bytes a lane, beyond that the wave), a few
     long strings, and a null"""
@@ -336,7 +340,8 @@ def check_strfn(ctx, dev, idx, pool, sqls, what):
 
 
 def test_string_functions_more_chunks_than_one_scan_round(ctx):
-    """strfn_scan_chunks_kernel: 66 chunk totals, two of them (one full chunk and five rows) behind the first round of 64"""
+    """scan_totals_kernel under the string functions: 258 tile totals, two of them (one full tile and five rows) behind the first
+    round of 256"""
     rng = np.random.default_rng(20261024)
     n = STRFN_ROWS
     pool = list(STRFN_POOL) + [b"  two  words  ", b"\xc3\xa9\xc3\xa9\xc3\xa9\xc3\xa9", None]

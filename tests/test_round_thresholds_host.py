@@ -43,37 +43,48 @@ def only(pattern, text):
 
 
 def test_tiles_of_the_scans():
-    agg, part, sort, strfn, join = (source(h) for h in ("aggregate_device.h", "partition_device.h", "sort_device.h", "strfn_device.h", "join_device.h"))
-    agg_block, agg_items = constant(agg, "kAggBlock"), constant(agg, "kAggItems")
-    part_block, part_items = constant(part, "kPartBlock"), constant(part, "kPartItems")
-    sort_block, sort_items = constant(sort, "kSortBlock"), constant(sort, "kSortItems")
-    for name, of in (("Agg", agg), ("Part", part), ("Sort", sort)):           # a tile is a workgroup's threads times their items
-        assert re.search(rf"constexpr\s+int\s+k{name}Tile\s*=\s*k{name}Block\s*\*\s*k{name}Items\s*;", of), name
-    for name in ("Block", "Items", "Tile"):                                    # the join kernels take the aggregate's geometry
+    # the one geometry (scan_device.h): a tile is a workgroup's threads times their items
+    shared = source("scan_device.h")
+    block, items = constant(shared, "kScanBlock"), constant(shared, "kScanItems")
+    assert re.search(r"constexpr\s+int\s+kScanTile\s*=\s*kScanBlock\s*\*\s*kScanItems\s*;", shared)
+    assert G.T == block * items
+
+    # every operator's constants are tied to it: a static_assert in its kernels, an alias of the aggregate's for join and window
+    agg, part, sort, strfn, join, win = (source(h) for h in ("aggregate_device.h", "partition_device.h", "sort_device.h", "strfn_device.h",
+                                                             "join_device.h", "window_device.h"))
+    for name, header, kernels in (("Agg", agg, "aggregate.hip"), ("Part", part, "partition.hip"), ("Sort", sort, "sort.hip")):
+        assert constant(header, f"k{name}Block") == block and constant(header, f"k{name}Items") == items, name
+        assert re.search(rf"constexpr\s+int\s+k{name}Tile\s*=\s*k{name}Block\s*\*\s*k{name}Items\s*;", header), name
+        assert f"static_assert(k{name}Block == kScanBlock && k{name}Items == kScanItems && k{name}Tile == kScanTile," in source(kernels), name
+    for name in ("Block", "Items", "Tile"):
         assert re.search(rf"constexpr\s+int\s+kJoin{name}\s*=\s*kAgg{name}\s*;", join), name
-    assert G.T == agg_block * agg_items == part_block * part_items == sort_block * sort_items == constant(strfn, "STRFN_SCAN_CHUNK")
+        assert re.search(rf"constexpr\s+int\s+kWin{name}\s*=\s*kAgg{name}\s*;", win), name
+    scan = source("scan.hip")
+    assert "static_assert(kJoinTile == kScanTile && STRFN_SCAN_CHUNK == kScanTile," in scan
+    assert G.T == constant(strfn, "STRFN_SCAN_CHUNK")
 
-    # join_scan_sums_kernel, sort_utf8_scan_sums_kernel: one tile total per thread of ONE workgroup and round
-    scan = body_of(source("join.hip"), "void join_scan_sums_kernel(")
-    assert only(r"c0 \+= (\w+)\)", scan) == "kJoinBlock" and "dim3(1), dim3(kJoinBlock)" in body_of(source("join.hip"), "hipError_t launch_join_scan(")
-    assert G.SCAN_ROUND == agg_block * G.T
-    scan = body_of(source("sort.hip"), "void sort_utf8_scan_sums_kernel(")
-    assert only(r"c0 \+= (\w+)\)", scan) == "kSortBlock"
-    assert "sort_utf8_scan_sums_kernel, dim3(1), dim3(kSortBlock)" in source("sort.hip")
-    assert G.SCAN_ROUND == sort_block * G.T
+    # scan_totals_in_place, the one loop over tile totals: one total per thread of ONE workgroup and round.  Its three users --
+    # the offsets scan of the join and the string functions, the Utf8 gather of the sort, the group heads -- launch it alike.
+    loop = body_of(shared, "void scan_totals_in_place(")
+    assert only(r"c0 \+= (\w+)\)", loop) == "kScanBlock" and "t = c0 + threadIdx.x;" in loop
+    assert len(re.findall(r"c0 \+= ", shared)) == 2                            # (the other one: scan_count_rows, below)
+    for text, kernel, name in ((scan, "scan_totals_kernel", "Scan"), (source("sort.hip"), "sort_utf8_scan_sums_kernel", "Sort"),
+                               (source("aggregate.hip"), "agg_head_scan_kernel", "Agg")):
+        assert "scan_totals_in_place<" in body_of(text, f"void {kernel}("), kernel
+        assert f"{kernel}, dim3(1), dim3(k{name}Block)" in text, kernel
+    for caller in ("join.cpp", "filter.cpp"):
+        assert "launch_offsets_scan(" in source(caller), caller
+    assert G.SCAN_ROUND == G.STRFN_ROUND == block * G.T
 
-    # part_scan_kernel: kPartItems tile counts per thread and round
-    scan = body_of(source("partition.hip"), "void part_scan_kernel(")
-    assert only(r"c0 \+= (\w+)\)", scan) == "kPartTile" and "threadIdx.x * kPartItems" in scan
-    assert "part_scan_kernel, dim3(p.n_partitions), dim3(kPartBlock)" in source("partition.hip")
-    assert G.PART_ROUND == (part_block * part_items) * G.T
-
-    # strfn_scan_chunks_kernel: one wave, one chunk total per lane and round
-    text = source("strfn.hip")
-    scan = body_of(text, "void strfn_scan_chunks_kernel(")
-    lanes = int(only(r"c0 \+= (\d+)\)", scan))
-    assert lanes == 64 and f"strfn_scan_chunks_kernel, dim3(1), dim3({lanes})" in text
-    assert G.STRFN_ROUND == lanes * constant(source("strfn_device.h"), "STRFN_SCAN_CHUNK")
+    # part_scan_kernel (and sort_scan_kernel): scan_count_rows with kPartItems tile counts per thread and round, a round of
+    # kPartTile counts
+    loop = body_of(shared, "void scan_count_rows(")
+    assert only(r"c0 \+= ([\w *]+)\)", loop) == "kScanBlock * ITEMS" and "threadIdx.x * ITEMS" in loop
+    text = source("partition.hip")
+    assert "scan_count_rows<kPartItems>(" in body_of(text, "void part_scan_kernel(")
+    assert "part_scan_kernel, dim3(p.n_partitions), dim3(kPartBlock)" in text
+    assert "scan_count_rows<kSortItems>(" in body_of(source("sort.hip"), "void sort_scan_kernel(")
+    assert G.PART_ROUND == (block * items) * G.T
     assert G.SCAN_ROWS == G.SCAN_ROUND + G.T + 5 and G.PART_ROWS == G.PART_ROUND + G.T + 5 and G.STRFN_ROWS == G.STRFN_ROUND + G.T + 5
 
 
