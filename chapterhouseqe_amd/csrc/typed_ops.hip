@@ -66,10 +66,12 @@ __device__ int parse_bool(const uint8_t* p, int n) {
       if (ws_at(p + n - w, w) == w) { n -= w; again = true; break; }
   }
   if (n < 1 || n > 5) return -1;
-  // the trimmed spelling as one little-endian integer of lower-cased bytes
+  // the trimmed spelling as one little-endian integer of lower-cased bytes.  The integer does not hold the length: a NUL
+  // byte is refused here, or `true\0` would have the key of `true`
   u64 key = 0;
   for (int i = 0; i < n; ++i) {
     const uint8_t c = p[i];
+    if (c == 0) return -1;
     key |= (u64)((c >= 'A' && c <= 'Z') ? c + 32 : c) << (8 * i);
   }
 #define K1(a) ((u64)(a))

@@ -79,7 +79,11 @@ def arrays_identical(a: pa.Array, b: pa.Array, nan_payload: bool = True) -> bool
     if pa.types.is_temporal(a.type):   # raw values (a timestamp may lie outside datetime's range)
         raw = pa.int32() if a.type.bit_width == 32 else pa.int64()
         return a.view(raw).to_pylist() == b.view(raw).to_pylist()
-    if pa.types.is_string(a.type) or pa.types.is_boolean(a.type) or pa.types.is_decimal(a.type) or pa.types.is_fixed_size_binary(a.type):
+    if pa.types.is_decimal(a.type):   # raw patterns (a value may lie outside the declared precision)
+        w = a.type.bit_width // 8
+        ra, rb = (np.frombuffer(x.buffers()[1], dtype=np.uint8, count=w * (x.offset + len(x)))[w * x.offset:].reshape(len(x), w) for x in (a, b))
+        return bool(np.array_equal(ra[va], rb[vb]))
+    if pa.types.is_string(a.type) or pa.types.is_boolean(a.type) or pa.types.is_fixed_size_binary(a.type):
         return a.to_pylist() == b.to_pylist()
     xa = a.fill_null(0).to_numpy(zero_copy_only=False)
     xb = b.fill_null(0).to_numpy(zero_copy_only=False)

@@ -32,8 +32,7 @@ def key_bits(arr: pa.Array) -> List[Optional[object]]:
         offs = np.frombuffer(arr.buffers()[1], dtype=np.int32, count=arr.offset + n + 1)[arr.offset:].tolist()
         data = arr.buffers()[2].to_pybytes() if arr.buffers()[2] is not None else b""
         bits = [data[offs[i]:offs[i + 1]] for i in range(n)]
-    elif pa.types.is_decimal(t):
-        assert t.bit_width == 128
+    elif pa.types.is_decimal(t) and t.bit_width == 128:
         w = np.frombuffer(arr.buffers()[1], dtype=np.uint64, count=2 * (arr.offset + n))[2 * arr.offset:].reshape(n, 2)
         bits = [tuple(x) for x in w.tolist()]
     elif pa.types.is_fixed_size_binary(t) or t.bit_width not in (8, 16, 32, 64):

@@ -68,7 +68,7 @@ def value_hashes(arr: pa.Array) -> np.ndarray:
             lens = np.array([len(bits[i]) for i in rows], dtype=np.uint64)
             out[rows] = _hash_chunks(lens, [padded[:, c] for c in range(nch)])
         return out
-    if pa.types.is_decimal(t):
+    if pa.types.is_decimal(t) and t.bit_width == 128:
         w = np.array([b if b is not None else (0, 0) for b in bits], dtype=np.uint64).reshape(n, 2)
         v = _hash_chunks(np.full(n, 16), [w[:, 0], w[:, 1]])
     elif pa.types.is_boolean(t):

@@ -46,7 +46,8 @@ def value_words(arr: pa.Array) -> List[np.ndarray]:
         rank = {v: i for i, v in enumerate(sorted(set(vals)))}
         return [np.array([rank[v] for v in vals], dtype=np.uint64)]
     if pa.types.is_decimal(t):
-        assert t.bit_width == 128
+        if t.bit_width <= 64:   # ordered as its signed integer
+            return [_signed(_fixed_raw(arr, t.bit_width // 8), t.bit_width // 8)]
         w = np.frombuffer(arr.buffers()[1], dtype=np.uint64, count=2 * (arr.offset + n))[2 * arr.offset:].reshape(n, 2)
         return [w[:, 1] ^ SIGN64, w[:, 0].copy()]
     if pa.types.is_floating(t):

@@ -198,6 +198,19 @@ def test_every_payload_type_through_the_padded_side(ctx, kind):
         check(ctx, left, right, KK, "right", device_in=True)
 
 
+@pytest.mark.parametrize("kind", ["decimal", "decimal32", "decimal64", "decimal128_edges"])
+def test_every_key_type_of_the_decimals(ctx, kind):
+    """decimal keys of 4, 8 and 16 bytes through every join kind: both sides draw from one pool (nulls among them), so matched
+    rows, unmatched rows and null keys all occur"""
+    rng = np.random.default_rng(400 + KINDS.index(kind))
+    pool = key_array(rng, 300, kind, True)
+    sides = [pa.RecordBatch.from_arrays([pool.take(pa.array(rng.integers(0, 300, n))), pa.array(np.arange(n, dtype=np.int32))], names=["k", row])
+             for n, row in ((1500, "lrow"), (1000, "rrow"))]
+    assert min(OJ.census(*sides, KK)) > 0
+    got = check_all(ctx, *sides, KK, device_in=kind == "decimal64")
+    assert got["full"].num_rows > got["left"].num_rows > got["inner"].num_rows > 0 and got["anti"].num_rows >= sides[0].column(0).null_count > 0
+
+
 def test_payload_of_every_importable_type_on_both_sides(ctx):
     rng = np.random.default_rng(33)
     left, right = payload_batch(rng, 700), payload_batch(rng, 600)

@@ -16,6 +16,7 @@ from chapterhouseqe_amd import sqlast as A
 from chapterhouseqe_amd.sqlparse import parse_select
 
 from . import sort_reference as R
+from . import typed_reference as TR
 from .helpers import batches_identical, explain_diff
 
 pytestmark = pytest.mark.gpu
@@ -106,6 +107,15 @@ def key_array(rng, n, kind, nulls):
     if kind == "decimal":
         vals = [decimal.Decimal(int(x) * 10 ** int(e)).scaleb(-4) for x, e in zip(rng.integers(-10**9, 10**9, n), rng.integers(0, 20, n))]
         return pa.array(vals, type=pa.decimal128(38, 4), mask=mask)
+    if kind in ("decimal32", "decimal64"):   # keys of up to 8 bytes: ordered as their signed integers
+        t, it = (pa.decimal32(9, 2), np.int32) if kind == "decimal32" else (pa.decimal64(18, 4), np.int64)
+        info = np.iinfo(it)
+        v = np.where(rng.random(n) < 0.5, small, rng.integers(info.min, info.max, n, dtype=it, endpoint=True)).astype(it)
+        v[: min(n, 3)] = [info.min, info.max, -1][: min(n, 3)]
+        return TR.decimal_array(v.tolist(), None if mask is None else ~mask, t)
+    if kind == "decimal128_edges":           # raw patterns: every byte of the key takes values other than 0x00 / 0xFF
+        edges = TR.I128_EDGES
+        return TR.decimal128_array([edges[i] for i in rng.integers(0, len(edges), n)], None if mask is None else ~mask)
     if kind == "utf8":
         pool = ["", "a", "ab", "ab\x00", "abc", "b", "é", "zz", "a" * 7, "a" * 8, "a" * 9, "a" * 8 + "b"]
         return pa.array([pool[i] for i in rng.integers(0, len(pool), n)], mask=mask)
@@ -130,7 +140,8 @@ def key_array(rng, n, kind, nulls):
 
 
 KINDS = ["int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "float16", "float32", "float64", "bool",
-         "date32", "date64", "time32s", "time32ms", "time64us", "time64ns", "ts_us_utc", "ts_ns", "duration_ms", "decimal", "utf8"]
+         "date32", "date64", "time32s", "time32ms", "time64us", "time64ns", "ts_us_utc", "ts_ns", "duration_ms", "decimal", "utf8",
+         "decimal32", "decimal64", "decimal128_edges"]
 
 
 def keyed_batch(rng, n, kind, nulls=True):
