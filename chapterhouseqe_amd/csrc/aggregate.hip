@@ -79,7 +79,7 @@ __global__ __launch_bounds__(kAggBlock) void agg_heads_kernel(const AggHeadsPara
 // one workgroup: exclusive scan of the tile counts in place, the number of groups behind them
 __global__ __launch_bounds__(kAggBlock) void agg_head_scan_kernel(const AggGroupsParams p) {
   __shared__ uint32_t sums[kWaves];
-  scan_totals_in_place<uint32_t>(p.tile_counts, p.ntiles, sums);
+  scan_totals_in_place<uint32_t>(p.tile_counts, p.ntiles, p.tile_counts + p.ntiles, sums);
 }
 
 __global__ __launch_bounds__(kAggBlock) void agg_head_write_kernel(const AggGroupsParams p) {

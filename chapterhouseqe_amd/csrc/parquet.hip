@@ -16,24 +16,18 @@
 //               pq_ba_walk_kernel       PLAIN BYTE_ARRAY pages / dictionary page -> (position, length) per value
 //               pq_dict_ba_kernel       RLE_DICTIONARY BYTE_ARRAY pages  -> (position, length) per value
 //   rows        pq_gather_fixed_kernel, pq_pack_bits_kernel, pq_rowlen_* (offset scan), pq_utf8_copy_kernel
+// The workgroup sum and scans (page scan, pq_rowlen_*), the bitmap words and the row copy are the shared pieces of scan_device.h.
 // Memory-bound integer/byte work: no MFMA.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "parquet_device.h"
+#include "scan_device.h"
 
 namespace chq {
 
 namespace {
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned lane_rank64(unsigned long long m) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-}
 __device__ __forceinline__ void flag_error(uint32_t* err, uint32_t code) { atomicMax(err, code); }
 
 // The RLE / bit-packed hybrid of Parquet (definition levels, dictionary indices, RLE booleans): a sequence of runs, each
@@ -106,51 +100,31 @@ __device__ __forceinline__ uint32_t hybrid_decode_block(const uint8_t* g, uint32
   return k;
 }
 constexpr int PQ_HYB_BLOCK = 256;
+static_assert(PQ_HYB_BLOCK == kScanBlock, "the workgroup sum and scans of scan_device.h are for workgroups of kScanBlock threads");
 
 }  // namespace
 
 // ---- definition levels: one byte per row, non-null count per page -----------------------------------------------------
 __global__ __launch_bounds__(PQ_HYB_BLOCK) void pq_levels_kernel(const PqDecodeParams p) {
   __shared__ uint32_t s_win[PQ_HYB_WINDOW / 4 + 4];
-  __shared__ uint32_t s_ones;
+  __shared__ uint32_t s_ones[kScanWaves];
   const int page = blockIdx.x;
   const PqPageDesc d = p.pages[page];
   uint8_t* valid = p.valid8 + d.first_row;
-  if (threadIdx.x == 0) s_ones = 0;
   uint32_t ones = 0;
   const uint32_t got = hybrid_decode_block<PQ_HYB_BLOCK>(p.chunk + d.levels_at, d.levels_len, 1, d.num_rows, s_win,
                                                          [&](uint32_t k, uint32_t v) { valid[k] = (uint8_t)v; ones += v; });
   if (got != d.num_rows && threadIdx.x == 0) flag_error(p.err, PQ_ERR_LEVELS);
-  ones = wave_sum_u32(ones);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&s_ones, ones);
-  __syncthreads();
-  if (threadIdx.x == 0) p.nonnull[page] = s_ones;
+  ones = block_sum<uint32_t>(ones, s_ones);
+  if (threadIdx.x == 0) p.nonnull[page] = ones;
 }
 
 // ---- first value index of every page (exclusive scan of the non-null counts; one block) -------------------------------
-__global__ __launch_bounds__(256) void pq_page_scan_kernel(const PqDecodeParams p) {
-  __shared__ uint32_t s_part[256];
-  __shared__ uint32_t s_carry;
-  const int tid = threadIdx.x;
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
-  for (int base = 0; base < p.n_pages; base += 256) {
-    const int i = base + tid;
-    const uint32_t v = i < p.n_pages ? p.nonnull[i] : 0u;
-    s_part[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-      const uint32_t t = tid >= o ? s_part[tid - o] : 0u;
-      __syncthreads();
-      s_part[tid] += t;
-      __syncthreads();
-    }
-    if (i < p.n_pages) p.value_base[i] = s_carry + s_part[tid] - v;
-    __syncthreads();
-    if (tid == 255) s_carry += s_part[255];
-    __syncthreads();
-  }
-  if (tid == 0) *p.total_values = s_carry;
+__global__ __launch_bounds__(kScanBlock) void pq_page_scan_kernel(const PqDecodeParams p) {
+  __shared__ uint32_t sums[kScanWaves];
+  // (the scan is in place: every thread copies the counts it scans, the levels kernel's output stays as it is)
+  for (int i = threadIdx.x; i < p.n_pages; i += kScanBlock) p.value_base[i] = p.nonnull[i];
+  scan_totals_in_place<uint32_t>(p.value_base, p.n_pages, p.total_values, sums);
 }
 
 // ---- value index of every row (-1 = null): one wave per page, 64 rows per step -----------------------------------------
@@ -213,7 +187,7 @@ __global__ __launch_bounds__(256) void pq_bool_kernel(const PqDecodeParams p) {
   if ((uint64_t)d.values_len * 8 < n) { if (threadIdx.x == 0) flag_error(p.err, PQ_ERR_VALUES); return; }
   const uint8_t* src = p.chunk + d.values_at;
   uint8_t* out = p.dense + p.value_base[page];
-  for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) out[k] = (src[k >> 3] >> (k & 7)) & 1;
+  for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) out[k] = bit_at(src, k);
 }
 
 // ---- RLE BOOLEAN pages (what V2 writers use): [4-byte length][hybrid runs, bit width 1] -> one byte per value ----------
@@ -363,108 +337,60 @@ __global__ __launch_bounds__(256) void pq_gather_fixed_kernel(const PqRowParams 
 
 // Arrow bitmap (LSB first) from one byte per row: src8[row], or src8[row_val[row]] with nulls reading as 0
 __global__ __launch_bounds__(256) void pq_pack_bits_kernel(const PqRowParams p) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nwords = (p.n_rows + 63) >> 6;
-  for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nwords; w += ((int64_t)gridDim.x * blockDim.x) >> 6) {
-    const int64_t r = (w << 6) + lane;
-    bool bit = false;
-    if (r < p.n_rows) {
-      if (p.row_val) { const int32_t v = p.row_val[r]; bit = v >= 0 && p.dense[v] != 0; }
-      else bit = p.dense[r] != 0;
-    }
-    const unsigned long long m = __ballot(bit);
-    if (lane == 0) ((unsigned long long*)p.out)[w] = m;
-  }
+  pack_ballot_words(p.out, p.n_rows, [&](int64_t r) {
+    if (!p.row_val) return p.dense[r] != 0;
+    const int32_t v = p.row_val[r];
+    return v >= 0 && p.dense[v] != 0;
+  });
 }
 
 // Utf8 offsets = exclusive scan of the row lengths (vlen[row_val[row]], 0 for a null), three small kernels:
-// block sums (PQ_SCAN_ROWS rows per block) -> scan of the block sums (one block) -> offsets
-constexpr int PQ_SCAN_ROWS = 4096;
+// block sums (PQ_SCAN_ROWS rows per block, parquet_device.h) -> scan of the block sums (one block) -> offsets
 __device__ __forceinline__ uint32_t row_length(const PqRowParams& p, int64_t r) {
   if (r >= p.n_rows) return 0;
   if (!p.row_val) return p.vlen[r];
   const int32_t v = p.row_val[r];
   return v >= 0 ? p.vlen[v] : 0u;
 }
-__global__ __launch_bounds__(256) void pq_rowlen_sums_kernel(const PqRowParams p) {
-  __shared__ unsigned long long s_w[4];
+__global__ __launch_bounds__(kScanBlock) void pq_rowlen_sums_kernel(const PqRowParams p) {
+  __shared__ unsigned long long sums[kScanWaves];
   const int64_t r0 = (int64_t)blockIdx.x * PQ_SCAN_ROWS;
   unsigned long long s = 0;
-  for (int i = threadIdx.x; i < PQ_SCAN_ROWS; i += 256) s += row_length(p, r0 + i);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) p.block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  for (int i = threadIdx.x; i < PQ_SCAN_ROWS; i += kScanBlock) s += row_length(p, r0 + i);
+  s = block_sum<unsigned long long>(s, sums);
+  if (threadIdx.x == 0) p.block_sums[blockIdx.x] = s;
 }
-__global__ __launch_bounds__(256) void pq_rowlen_scan_kernel(const PqRowParams p) {
-  __shared__ unsigned long long s_part[256];
-  __shared__ unsigned long long s_carry;
-  const int tid = threadIdx.x;
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < p.n_blocks; base += 256) {
-    const int64_t i = base + tid;
-    const unsigned long long v = i < p.n_blocks ? p.block_sums[i] : 0ull;
-    s_part[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-      const unsigned long long t = tid >= o ? s_part[tid - o] : 0ull;
-      __syncthreads();
-      s_part[tid] += t;
-      __syncthreads();
-    }
-    if (i < p.n_blocks) p.block_sums[i] = s_carry + s_part[tid] - v;
-    __syncthreads();
-    if (tid == 255) s_carry += s_part[255];
-    __syncthreads();
-  }
-  if (tid == 0) *p.total_bytes = s_carry;
+__global__ __launch_bounds__(kScanBlock) void pq_rowlen_scan_kernel(const PqRowParams p) {
+  __shared__ unsigned long long sums[kScanWaves];
+  scan_totals_in_place<unsigned long long>(p.block_sums, p.n_blocks, p.total_bytes, sums);
 }
-__global__ __launch_bounds__(256) void pq_rowlen_offsets_kernel(const PqRowParams p) {
-  __shared__ uint32_t s_wave[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+__global__ __launch_bounds__(kScanBlock) void pq_rowlen_offsets_kernel(const PqRowParams p) {
+  __shared__ uint32_t sums[kScanWaves];
   const int64_t r0 = (int64_t)blockIdx.x * PQ_SCAN_ROWS;
   unsigned long long run = p.block_sums[blockIdx.x];
   int32_t* offs = (int32_t*)p.out;
-  for (int step = 0; step < PQ_SCAN_ROWS; step += 256) {
-    const int64_t r = r0 + step + tid;
-    const uint32_t len = row_length(p, r);
-    uint32_t inc = len;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int w = 0; w < wv; ++w) before += s_wave[w];
-    const uint32_t all = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    if (r < p.n_rows) offs[r] = (int32_t)(run + before + inc - len);   // (the host checks the total against 2^31 before trusting these)
+  for (int step = 0; step < PQ_SCAN_ROWS; step += kScanBlock) {
+    const int64_t r = r0 + step + threadIdx.x;
+    uint32_t all;
+    const uint32_t before = block_exclusive_scan<uint32_t>(row_length(p, r), sums, &all);
+    if (r < p.n_rows) offs[r] = (int32_t)(run + before);   // (the host checks the total against 2^31 before trusting these)
     run += all;
-    __syncthreads();
   }
-  if (blockIdx.x == gridDim.x - 1 && tid == 0) offs[p.n_rows] = (int32_t)*p.total_bytes;
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) offs[p.n_rows] = (int32_t)*p.total_bytes;
 }
 
-// bytes of every row: eight lanes per row, 16-byte chunks, then the tail byte by byte
+// bytes of every row: eight lanes per row
 __global__ __launch_bounds__(256) void pq_utf8_copy_kernel(const PqRowParams p) {
-  const int sl = threadIdx.x & 7;
   const int32_t* offs = (const int32_t*)p.offsets;
   for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; r < p.n_rows; r += ((int64_t)gridDim.x * blockDim.x) >> 3) {
-    int32_t v = p.row_val ? p.row_val[r] : (int32_t)r;
-    if (v < 0) continue;
-    const uint32_t len = p.vlen[v];
-    const uint8_t* src = p.chunk + p.vsrc[v];
-    uint8_t* dst = p.data_out + offs[r];
-    uint32_t b = (uint32_t)sl * 16;
-    for (; b + 16 <= len; b += 128) { uint4 w; __builtin_memcpy(&w, src + b, 16); __builtin_memcpy(dst + b, &w, 16); }
-    const uint32_t tail = len & ~15u;
-    for (uint32_t k = tail + sl; k < len; k += 8) dst[k] = src[k];
+    const int32_t v = p.row_val ? p.row_val[r] : (int32_t)r;
+    if (v >= 0) copy_row_by_8_lanes(p.data_out + offs[r], p.chunk + p.vsrc[v], p.vlen[v], threadIdx.x & 7);
   }
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 hipError_t pq_launch_levels(const PqDecodeParams& p, hipStream_t s) { hipLaunchKernelGGL(pq_levels_kernel, dim3(p.n_pages), dim3(PQ_HYB_BLOCK), 0, s, p); return hipGetLastError(); }
-hipError_t pq_launch_page_scan(const PqDecodeParams& p, hipStream_t s) { hipLaunchKernelGGL(pq_page_scan_kernel, dim3(1), dim3(256), 0, s, p); return hipGetLastError(); }
+hipError_t pq_launch_page_scan(const PqDecodeParams& p, hipStream_t s) { hipLaunchKernelGGL(pq_page_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, p); return hipGetLastError(); }
 hipError_t pq_launch_rowval(const PqDecodeParams& p, hipStream_t s) { hipLaunchKernelGGL(pq_rowval_kernel, dim3(p.n_pages), dim3(64), 0, s, p); return hipGetLastError(); }
 hipError_t pq_launch_plain_copy(const PqDecodeParams& p, int n_list, hipStream_t s) { hipLaunchKernelGGL(pq_plain_copy_kernel, dim3(n_list, 16), dim3(256), 0, s, p); return hipGetLastError(); }
 hipError_t pq_launch_dict_fixed(const PqDecodeParams& p, int n_list, hipStream_t s) {
@@ -489,9 +415,9 @@ hipError_t pq_launch_gather_fixed(const PqRowParams& p, int width, int grid, hip
 }
 hipError_t pq_launch_pack_bits(const PqRowParams& p, int grid, hipStream_t s) { hipLaunchKernelGGL(pq_pack_bits_kernel, dim3(grid), dim3(256), 0, s, p); return hipGetLastError(); }
 hipError_t pq_launch_rowlen(const PqRowParams& p, hipStream_t s) {
-  hipLaunchKernelGGL(pq_rowlen_sums_kernel, dim3((unsigned)p.n_blocks), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(pq_rowlen_scan_kernel, dim3(1), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(pq_rowlen_offsets_kernel, dim3((unsigned)p.n_blocks), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(pq_rowlen_sums_kernel, dim3((unsigned)p.n_blocks), dim3(kScanBlock), 0, s, p);
+  hipLaunchKernelGGL(pq_rowlen_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, p);
+  hipLaunchKernelGGL(pq_rowlen_offsets_kernel, dim3((unsigned)p.n_blocks), dim3(kScanBlock), 0, s, p);
   return hipGetLastError();
 }
 hipError_t pq_launch_utf8_copy(const PqRowParams& p, int grid, hipStream_t s) { hipLaunchKernelGGL(pq_utf8_copy_kernel, dim3(grid), dim3(256), 0, s, p); return hipGetLastError(); }

@@ -110,7 +110,7 @@ hipError_t pq_launch_gather_fixed(const PqRowParams& p, int width, int grid, hip
 hipError_t pq_launch_pack_bits(const PqRowParams& p, int grid, hipStream_t s);
 hipError_t pq_launch_rowlen(const PqRowParams& p, hipStream_t s);
 hipError_t pq_launch_utf8_copy(const PqRowParams& p, int grid, hipStream_t s);
-constexpr int PQ_SCAN_ROWS_HOST = 4096;   // = PQ_SCAN_ROWS of parquet.hip
+constexpr int PQ_SCAN_ROWS = 4096;   // rows per block of pq_launch_rowlen: n_blocks = ceil(n_rows / PQ_SCAN_ROWS)
 
 // ---- Parquet write (parquet_write.hip) -------------------------------------------------------------------------------
 struct PwParams {
@@ -125,7 +125,7 @@ struct PwParams {
   int32_t pad;
   uint8_t* out;
   unsigned long long* block_sums;   // [n_blocks]
-  int64_t n_blocks;                 // ceil(n_rows / PW_BLOCK_ROWS_HOST)
+  int64_t n_blocks;                 // ceil(n_rows / PW_BLOCK_ROWS)
   unsigned long long* total_bytes;
 };
 // pw_stats_kernel: min / max of the non-null (and, for floats, non-NaN) values of a column, for the chunk's Statistics.
@@ -148,7 +148,7 @@ hipError_t pw_launch_stats(const PwStatsParams& p, int grid, hipStream_t s);
 struct PwPiece { unsigned long long dst; const uint8_t* src; unsigned long long len; };
 struct PwAssembleParams { const PwPiece* pieces; uint8_t* image; unsigned long long seg; };   // seg: bytes per block (multiple of 16)
 hipError_t pw_launch_assemble(const PwAssembleParams& p, int n_pieces, int n_segs, hipStream_t s);
-constexpr int PW_BLOCK_ROWS_HOST = 4096;   // = PW_BLOCK_ROWS of parquet_write.hip
+constexpr int PW_BLOCK_ROWS = 4096;   // rows per block of pw_launch_scan / pw_launch_encode; pages are multiples of it
 hipError_t pw_launch_scan(const PwParams& p, hipStream_t s);
 hipError_t pw_launch_encode(const PwParams& p, hipStream_t s);
 hipError_t pw_launch_bits_to_bytes(const PwParams& p, int grid, hipStream_t s);

@@ -347,7 +347,7 @@ void phase_a(Context& ctx, const PqFile& f, int row_group, RowGroupJob& job, siz
       }
       // offsets = exclusive scan of the row lengths
       w.offsets = make_device_buffer((size_t)(rows + 2) * 4, ctx.device);
-      const int64_t n_blocks = (rows + PQ_SCAN_ROWS_HOST - 1) / PQ_SCAN_ROWS_HOST;
+      const int64_t n_blocks = (rows + PQ_SCAN_ROWS - 1) / PQ_SCAN_ROWS;
       w.block_sums = make_device_buffer((size_t)n_blocks * 8 + 16, ctx.device);
       PqRowParams r{};
       r.n_rows = rows; r.row_val = w.has_levels ? (const int32_t*)w.row_val->ptr : nullptr;

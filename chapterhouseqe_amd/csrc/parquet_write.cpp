@@ -98,13 +98,13 @@ RowGroupPlan plan_row_group(Context& ctx, const Batch& in, int64_t& at) {
   rg.plan.resize(nc);
   std::vector<ColumnPlan>& plan = rg.plan;
   const int grid = ctx.num_cus * 8;
-  const int64_t n_blocks = std::max<int64_t>(1, (rows + PW_BLOCK_ROWS_HOST - 1) / PW_BLOCK_ROWS_HOST);
+  const int64_t n_blocks = std::max<int64_t>(1, (rows + PW_BLOCK_ROWS - 1) / PW_BLOCK_ROWS);
   // Several pages per chunk (round 3): pages are what a reader decodes in parallel (this library's scan: one workgroup per
   // page), the parquet crate cuts them at ~1 MiB.  Page boundaries sit on multiples of 4096 rows (the block size of the
   // stream scan, and a whole number of level bytes); at most 64 pages per chunk, so that a file image needs a bounded
   // number of device-to-host copies.
-  int64_t page_rows = std::max<int64_t>(PW_BLOCK_ROWS_HOST, ctx.opt_parquet_page_rows / PW_BLOCK_ROWS_HOST * PW_BLOCK_ROWS_HOST);
-  if (rows > 64 * page_rows) page_rows = ((rows + 63) / 64 + PW_BLOCK_ROWS_HOST - 1) / PW_BLOCK_ROWS_HOST * PW_BLOCK_ROWS_HOST;
+  int64_t page_rows = std::max<int64_t>(PW_BLOCK_ROWS, ctx.opt_parquet_page_rows / PW_BLOCK_ROWS * PW_BLOCK_ROWS);
+  if (rows > 64 * page_rows) page_rows = ((rows + 63) / 64 + PW_BLOCK_ROWS - 1) / PW_BLOCK_ROWS * PW_BLOCK_ROWS;
   const int64_t n_pages = std::max<int64_t>(1, (rows + page_rows - 1) / page_rows);
   auto totals = make_device_buffer(8 * (nc + 1), ctx.device);
   check_hip(hipMemsetAsync(totals->ptr, 0, 8 * (nc + 1), ctx.stream), "memset");
@@ -286,8 +286,8 @@ RowGroupPlan plan_row_group(Context& ctx, const Batch& in, int64_t& at) {
         else if (pl.boolean) { b0 = r0 / 8; b1 = (r0 + pg.rows + 7) / 8; }
         else if (!pl.needs_scan) { b0 = r0 * (int64_t)c.width; b1 = (r0 + pg.rows) * (int64_t)c.width; }
         else {
-          b0 = (int64_t)pl.prefix[(size_t)(r0 / PW_BLOCK_ROWS_HOST)];
-          b1 = k + 1 < np ? (int64_t)pl.prefix[(size_t)((r0 + pg.rows) / PW_BLOCK_ROWS_HOST)] : pl.stream_bytes;
+          b0 = (int64_t)pl.prefix[(size_t)(r0 / PW_BLOCK_ROWS)];
+          b1 = k + 1 < np ? (int64_t)pl.prefix[(size_t)((r0 + pg.rows) / PW_BLOCK_ROWS)] : pl.stream_bytes;
         }
         pg.stream = (const uint8_t*)pl.stream + b0; pg.stream_bytes = b1 - b0;
       }

@@ -4,26 +4,26 @@
 // copies the streams into the file image.
 //   non-null fixed-width columns need no kernel at all: the Arrow values buffer IS the PLAIN stream;
 //   definition levels are the Arrow validity bitmap behind a one-run header (bit width 1, LSB first: the same bit order);
-//   pw_counts_kernel / pw_scan_kernel   per-block totals of "bytes this row contributes" and their exclusive scan
-//   pw_compact_fixed_kernel             values of the non-null rows, densely packed
-//   pw_utf8_encode_kernel               [4-byte length][bytes] per non-null row
+//   pw_counts_kernel / pw_scan_kernel   totals of "bytes this row contributes" per block of PW_BLOCK_ROWS rows (parquet_device.h)
+//                                       and their exclusive scan (scan_totals_in_place of scan_device.h)
+//   pw_encode_kernel<W>                 W > 0: values of the non-null rows, densely packed; W = 0: [4-byte length][bytes] per
+//                                       non-null row
 //   pw_bits_to_bytes_kernel             Boolean bitmap (any bit offset) -> one byte per row (then compacted and re-packed)
+//   pw_bytes_to_bits_kernel, pw_shift_bits_kernel   bitmap words from a predicate per row (pack_ballot_words of scan_device.h)
+// The workgroup sum and scans, the bitmap words and the row copy are the shared pieces of scan_device.h.
 // Memory-bound byte work: no MFMA.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "parquet_device.h"
+#include "scan_device.h"
 
 namespace chq {
 
 namespace {
-constexpr int PW_BLOCK_ROWS = 4096;
-
-__device__ __forceinline__ bool row_valid(const PwParams& p, int64_t r) {
-  if (!p.validity) return true;
-  const int64_t b = p.bit_offset + r;
-  return (p.validity[b >> 3] >> (b & 7)) & 1;
-}
+// PwParams and PwStatsParams: is row r valid?
+template <typename Params>
+__device__ __forceinline__ bool row_valid(const Params& p, int64_t r) { return !p.validity || bit_at(p.validity, p.bit_offset + r); }
 // bytes row r contributes to the value stream
 __device__ __forceinline__ uint32_t row_bytes(const PwParams& p, int64_t r) {
   if (r >= p.n_rows || !row_valid(p, r)) return 0;
@@ -32,130 +32,78 @@ __device__ __forceinline__ uint32_t row_bytes(const PwParams& p, int64_t r) {
 }
 }  // namespace
 
-__global__ __launch_bounds__(256) void pw_counts_kernel(const PwParams p) {
-  __shared__ unsigned long long s_w[4];
+__global__ __launch_bounds__(kScanBlock) void pw_counts_kernel(const PwParams p) {
+  __shared__ unsigned long long sums[kScanWaves];
   const int64_t r0 = (int64_t)blockIdx.x * PW_BLOCK_ROWS;
   unsigned long long s = 0;
-  for (int i = threadIdx.x; i < PW_BLOCK_ROWS; i += 256) s += row_bytes(p, r0 + i);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) p.block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  for (int i = threadIdx.x; i < PW_BLOCK_ROWS; i += kScanBlock) s += row_bytes(p, r0 + i);
+  s = block_sum<unsigned long long>(s, sums);
+  if (threadIdx.x == 0) p.block_sums[blockIdx.x] = s;
 }
 
-__global__ __launch_bounds__(256) void pw_scan_kernel(const PwParams p) {
-  __shared__ unsigned long long s_part[256];
-  __shared__ unsigned long long s_carry;
-  const int tid = threadIdx.x;
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < p.n_blocks; base += 256) {
-    const int64_t i = base + tid;
-    const unsigned long long v = i < p.n_blocks ? p.block_sums[i] : 0ull;
-    s_part[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-      const unsigned long long t = tid >= o ? s_part[tid - o] : 0ull;
-      __syncthreads();
-      s_part[tid] += t;
-      __syncthreads();
-    }
-    if (i < p.n_blocks) p.block_sums[i] = s_carry + s_part[tid] - v;
-    __syncthreads();
-    if (tid == 255) s_carry += s_part[255];
-    __syncthreads();
-  }
-  if (tid == 0) *p.total_bytes = s_carry;
+__global__ __launch_bounds__(kScanBlock) void pw_scan_kernel(const PwParams p) {
+  __shared__ unsigned long long sums[kScanWaves];
+  scan_totals_in_place<unsigned long long>(p.block_sums, p.n_blocks, p.total_bytes, sums);
 }
 
-// One block per PW_BLOCK_ROWS rows; 256 rows per step, positions from a block-local scan on top of the block's base.
+// One block per PW_BLOCK_ROWS rows; kScanBlock rows per step, positions from a block-local scan on top of the block's base.
 // Fixed-width: out[pos] = value; Utf8: out[pos] = length, bytes behind it.
 template <int W>
-__global__ __launch_bounds__(256) void pw_encode_kernel(const PwParams p) {
-  __shared__ uint32_t s_wave[4];
-  __shared__ uint32_t s_dst[256], s_len[256];   // Utf8: where each row of the step goes, how long it is (~0: nothing to write)
-  __shared__ int32_t s_src[256];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+__global__ __launch_bounds__(kScanBlock) void pw_encode_kernel(const PwParams p) {
+  __shared__ uint32_t sums[kScanWaves];
+  __shared__ uint32_t s_dst[kScanBlock], s_len[kScanBlock];   // Utf8: where each row of the step goes, how long it is (~0: nothing to write)
+  __shared__ int32_t s_src[kScanBlock];
+  const int tid = threadIdx.x;
   const int64_t r0 = (int64_t)blockIdx.x * PW_BLOCK_ROWS;
   unsigned long long run = p.block_sums[blockIdx.x];
-  for (int step = 0; step < PW_BLOCK_ROWS; step += 256) {
+  for (int step = 0; step < PW_BLOCK_ROWS; step += kScanBlock) {
     const int64_t r = r0 + step + tid;
     const uint32_t nb = row_bytes(p, r);
-    uint32_t inc = nb;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int w = 0; w < wv; ++w) before += s_wave[w];
-    const uint32_t all = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    uint32_t all;
+    const uint32_t before = block_exclusive_scan<uint32_t>(nb, sums, &all);   // relative to this step's first byte
     if (W > 0) {
       if (nb) {
-        uint8_t* dst = p.out + run + before + inc - nb;
+        uint8_t* dst = p.out + run + before;
         const uint8_t* src = p.values + r * W;
 #pragma unroll
         for (int b = 0; b < W; ++b) dst[b] = src[b];          // (the stream is only byte aligned)
       }
     } else {
-      // [4-byte length][bytes]: positions by one thread per row, the bytes by eight lanes per row in 16-byte chunks
-      s_dst[tid] = before + inc - nb;                          // relative to this step's first byte
+      // [4-byte length][bytes]: positions by one thread per row, the bytes by eight lanes per row
+      s_dst[tid] = before;
       s_len[tid] = nb ? nb - 4 : ~0u;
       s_src[tid] = nb ? p.offsets[r] : 0;
       __syncthreads();
       uint8_t* base = p.out + run;
-      const int sl = tid & 7;
-      for (int row = tid >> 3; row < 256; row += 32) {
+      for (int row = tid >> 3; row < kScanBlock; row += kScanBlock / 8) {
         const uint32_t len = s_len[row];
         if (len == ~0u) continue;
         uint8_t* dst = base + s_dst[row];
-        const uint8_t* src = p.data + s_src[row];
-        if (sl == 0) __builtin_memcpy(dst, &len, 4);
-        uint32_t b = (uint32_t)sl * 16;
-        for (; b + 16 <= len; b += 128) { uint4 w; __builtin_memcpy(&w, src + b, 16); __builtin_memcpy(dst + 4 + b, &w, 16); }
-        for (uint32_t k = (len & ~15u) + sl; k < len; k += 8) dst[4 + k] = src[k];
+        if ((tid & 7) == 0) __builtin_memcpy(dst, &len, 4);
+        copy_row_by_8_lanes(dst + 4, p.data + s_src[row], len, tid & 7);
       }
+      __syncthreads();   // s_dst, s_len, s_src are rewritten in the next step
     }
     run += all;
-    __syncthreads();
   }
 }
 
 // Boolean values (bitmap at bit offset `value_bit_offset`) -> one byte per row
 __global__ __launch_bounds__(256) void pw_bits_to_bytes_kernel(const PwParams p) {
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < p.n_rows; r += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = p.value_bit_offset + r;
-    p.out[r] = (p.values[b >> 3] >> (b & 7)) & 1;
-  }
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < p.n_rows; r += (int64_t)gridDim.x * blockDim.x)
+    p.out[r] = bit_at(p.values, p.value_bit_offset + r);
 }
 // one byte per value -> bit-packed, LSB first (PLAIN BOOLEAN); n_rows = number of values
 __global__ __launch_bounds__(256) void pw_bytes_to_bits_kernel(const PwParams p) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nwords = (p.n_rows + 63) >> 6;
-  for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nwords; w += ((int64_t)gridDim.x * blockDim.x) >> 6) {
-    const int64_t r = (w << 6) + lane;
-    const unsigned long long m = __ballot(r < p.n_rows && p.values[r] != 0);
-    if (lane == 0) ((unsigned long long*)p.out)[w] = m;
-  }
+  pack_ballot_words(p.out, p.n_rows, [&](int64_t r) { return p.values[r] != 0; });
 }
 // validity bitmap at a bit offset -> the same bits from bit 0 (definition levels of a sliced column); n_rows bits
 __global__ __launch_bounds__(256) void pw_shift_bits_kernel(const PwParams p) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nwords = (p.n_rows + 63) >> 6;
-  for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nwords; w += ((int64_t)gridDim.x * blockDim.x) >> 6) {
-    const int64_t r = (w << 6) + lane;
-    const unsigned long long m = __ballot(r < p.n_rows && row_valid(p, r));
-    if (lane == 0) ((unsigned long long*)p.out)[w] = m;
-  }
+  pack_ballot_words(p.out, p.n_rows, [&](int64_t r) { return row_valid(p, r); });
 }
 
 // ---- chunk statistics: min / max ------------------------------------------------------------------------------------
 namespace {
-__device__ __forceinline__ bool stats_valid(const PwStatsParams& p, int64_t r) {
-  if (!p.validity) return true;
-  const int64_t b = p.bit_offset + r;
-  return (p.validity[b >> 3] >> (b & 7)) & 1;
-}
 // unsigned byte-lexicographic a < b (Parquet's order for BYTE_ARRAY / UTF8)
 __device__ bool utf8_less(const PwStatsParams& p, int64_t a, int64_t b) {
   const int32_t ao = p.offsets[a], bo = p.offsets[b];
@@ -181,7 +129,7 @@ __global__ __launch_bounds__(256) void pw_stats_kernel(const PwStatsParams p) {
       if (rmax < 0 || utf8_less(p, rmax, r)) rmax = r;
     };
     if (p.n_cand > 0) { for (int i = threadIdx.x; i < 2 * p.n_cand; i += blockDim.x) take(p.cand[i]); }
-    else for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < p.n_rows; r += stride) if (stats_valid(p, r)) { take(r); ++cnt; }
+    else for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < p.n_rows; r += stride) if (row_valid(p, r)) { take(r); ++cnt; }
     for (int o = 32; o > 0; o >>= 1) {
       const long long omin = __shfl_xor(rmin, o, 64), omax = __shfl_xor(rmax, o, 64);
       if (omin >= 0 && (rmin < 0 || utf8_less(p, omin, rmin))) rmin = omin;
@@ -202,7 +150,7 @@ __global__ __launch_bounds__(256) void pw_stats_kernel(const PwStatsParams p) {
     return;
   }
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < p.n_rows; r += stride) {
-    if (!stats_valid(p, r)) continue;
+    if (!row_valid(p, r)) continue;
     long long k;
     switch (p.kind) {
       case PW_STATS_I32: k = ((const int32_t*)p.values)[r]; break;
@@ -251,12 +199,12 @@ hipError_t pw_launch_assemble(const PwAssembleParams& p, int n_pieces, int n_seg
 }
 
 hipError_t pw_launch_scan(const PwParams& p, hipStream_t s) {
-  hipLaunchKernelGGL(pw_counts_kernel, dim3((unsigned)p.n_blocks), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(pw_scan_kernel, dim3(1), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(pw_counts_kernel, dim3((unsigned)p.n_blocks), dim3(kScanBlock), 0, s, p);
+  hipLaunchKernelGGL(pw_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, p);
   return hipGetLastError();
 }
 hipError_t pw_launch_encode(const PwParams& p, hipStream_t s) {
-  const dim3 g((unsigned)p.n_blocks), b(256);
+  const dim3 g((unsigned)p.n_blocks), b(kScanBlock);
   if (p.offsets) hipLaunchKernelGGL(pw_encode_kernel<0>, g, b, 0, s, p);
   else switch (p.width) {
     case 1: hipLaunchKernelGGL(pw_encode_kernel<1>, g, b, 0, s, p); break;

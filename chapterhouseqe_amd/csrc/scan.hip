@@ -28,7 +28,7 @@ __global__ __launch_bounds__(kScanBlock) void scan_tile_sums_kernel(const Offset
 // one workgroup, in 64 bits: 65 536 x 65 536 equal join keys are 2^32 output rows, and the total must not wrap
 __global__ __launch_bounds__(kScanBlock) void scan_totals_kernel(const OffsetsScanParams p) {
   __shared__ uint64_t sums[kScanWaves];
-  scan_totals_in_place<uint64_t>(p.tile_sums, p.ntiles, sums);
+  scan_totals_in_place<uint64_t>(p.tile_sums, p.ntiles, p.tile_sums + p.ntiles, sums);
 }
 
 // out[i] = tile prefix + prefix inside the tile, mod 2^32; a thread takes kScanItems consecutive items

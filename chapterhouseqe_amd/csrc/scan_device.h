@@ -1,6 +1,7 @@
 // scan_device.h -- device side only (.hip files include it): the one workgroup geometry of every tiled operator and the scan
 // pieces they share -- the small loads, the workgroup sum and exclusive scan, the one-workgroup scan of tile totals in rounds,
-// the scan of a row of per-tile counts, and the ranking of a tile's items by an 8-bit id (radix pass, hash partitioning).
+// the scan of a row of per-tile counts, the bitmap words and row copies of the Parquet kernels, and the ranking of a tile's
+// items by an 8-bit id (radix pass, hash partitioning).
 // Everything here is integer arithmetic: the result does not depend on the order of the additions.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,6 +16,11 @@ constexpr int kScanTile = kScanBlock * kScanItems;   // items per workgroup tile
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 __device__ __forceinline__ uint64_t lanes_below() { return (1ull << lane_id()) - 1; }
+// the lanes below this one whose bit is set in m: two v_mbcnt, no mask to build (popcount(m & lanes_below()) costs a 64-bit
+// shift, two ands, two counts and two more VGPRs)
+__device__ __forceinline__ uint32_t lane_rank64(uint64_t m) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
 __device__ __forceinline__ bool bit_at(const void* bits, int64_t pos) { return (((const uint8_t*)bits)[pos >> 3] >> (pos & 7)) & 1; }
 
 __device__ __forceinline__ uint64_t load_uint(const uint8_t* values, uint32_t r, int width) {
@@ -72,10 +78,10 @@ __device__ __forceinline__ T block_exclusive_scan(T v, T* wave_sums, T* total) {
   return base + x - v;
 }
 
-// One workgroup: exclusive scan of sums[0, n) in place, sums[n] = the grand total.  A round takes one total per thread and
-// carries the running total into the next.
+// One workgroup: exclusive scan of sums[0, n) in place, *total = the grand total (sums + n where it follows the totals).  A round
+// takes one total per thread and carries the running total into the next.
 template <typename T>
-__device__ __forceinline__ void scan_totals_in_place(T* sums, int64_t n, T* lds) {
+__device__ __forceinline__ void scan_totals_in_place(T* sums, int64_t n, T* total, T* lds) {
   T carry = 0, tot;
   for (int64_t c0 = 0; c0 < n; c0 += kScanBlock) {
     const int64_t t = c0 + threadIdx.x;
@@ -84,7 +90,7 @@ __device__ __forceinline__ void scan_totals_in_place(T* sums, int64_t n, T* lds)
     if (t < n) sums[t] = pre;
     carry += tot;
   }
-  if (threadIdx.x == 0) sums[n] = carry;
+  if (threadIdx.x == 0) *total = carry;
 }
 
 // One workgroup: exclusive scan of row[0, ntiles) in place (the per-tile counts of one digit or partition), offset by
@@ -105,6 +111,25 @@ __device__ __forceinline__ void scan_count_rows(uint32_t* row, int64_t ntiles, u
     }
     carry += tot;
   }
+}
+
+// Arrow bitmap words (LSB first) of one predicate per row: words[w] = the ballot of pred(64 w + lane) over the rows below n.
+// A wave per word, grid-stride.
+template <class Pred>
+__device__ __forceinline__ void pack_ballot_words(void* words, int64_t n, Pred pred) {
+  const int64_t nwords = (n + 63) >> 6;
+  for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nwords; w += ((int64_t)gridDim.x * blockDim.x) >> 6) {
+    const int64_t r = (w << 6) + lane_id();
+    const uint64_t m = __ballot(r < n && pred(r));
+    if (lane_id() == 0) ((uint64_t*)words)[w] = m;
+  }
+}
+
+// Eight lanes (sl = 0 .. 7) copy the len bytes of one row: 16-byte chunks, then the tail byte by byte.  (Source and destination
+// are only byte aligned: the chunks go through memcpy, global memory takes unaligned accesses.)
+__device__ __forceinline__ void copy_row_by_8_lanes(uint8_t* dst, const uint8_t* src, uint32_t len, int sl) {
+  for (uint32_t b = (uint32_t)sl * 16; b + 16 <= len; b += 128) { uint4 w; __builtin_memcpy(&w, src + b, 16); __builtin_memcpy(dst + b, &w, 16); }
+  for (uint32_t k = (len & ~15u) + sl; k < len; k += 8) dst[k] = src[k];
 }
 
 // lanes of this wave whose `d` (8 bits) equals this lane's, among the lanes in `active`

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(kSortBlock) void sort_utf8_tile_sums_kernel(const S
 // Utf8 step 2 (one workgroup): exclusive scan of the tile totals in place, the grand total behind them
 __global__ __launch_bounds__(kSortBlock) void sort_utf8_scan_sums_kernel(const SortGatherParams p) {
   __shared__ uint64_t sums[kWaves];
-  scan_totals_in_place<uint64_t>(p.tile_sums, p.ntiles, sums);
+  scan_totals_in_place<uint64_t>(p.tile_sums, p.ntiles, p.tile_sums + p.ntiles, sums);
 }
 
 // Utf8 step 3: output offsets (the host has checked that the grand total fits int32)

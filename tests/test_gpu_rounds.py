@@ -1,9 +1,10 @@
 """GPU: the SECOND round of every loop that walks its input in rounds -- the single-workgroup scans that carry a running total
-from one round of tile totals into the next (scan_device.h: one loop for the join, the sort, the group heads and the string
-functions, one for the count rows of partition.hip and sort.hip), and the launches whose grid is
-capped so that a thread strides on to further rows (strfn.hip, like.hip, typed_ops.hip).  Each test feeds the smallest input
-that puts more than one full tile (or one full wave) into the second round, compares the whole result with the host reference
-its sibling tests use, and asserts that a non-trivial part of the output is produced by the second round.
+from one round of tile totals into the next (scan_device.h: one loop for the join, the sort, the group heads, the string
+functions and the block totals of the Parquet scan and writer, one for the count rows of partition.hip and sort.hip), and the
+launches whose grid is capped so that a thread strides on to further rows (strfn.hip, like.hip, typed_ops.hip).  Each test
+feeds the smallest input that puts more than one full tile (or one full wave; for Parquet, one block) into the second round,
+compares the whole result with the host reference its sibling tests use, and asserts that a non-trivial part of the output is
+produced by the second round.
 
 The round sizes below restate the tiles and grid caps of the sources; tests/test_round_thresholds_host.py reads the sources
 and fails when they drift apart.  Inputs are drawn from small pools of distinct values (`pool.take(indices)`), and a per-row
@@ -19,6 +20,11 @@ side is the cost.
     sort_utf8_scan_sums_kernel, plain           256 tiles x 2048          test_sorted_utf8_payload_past_one_scan_round
     sort_utf8_scan_sums_kernel, "no row"        256 tiles x 2048          test_left_joined_utf8_payload_past_one_scan_round
     agg_head_scan_kernel                        256 tiles x 2048          every join above (the runs of the concatenated keys)
+    pq_page_scan_kernel                         256 pages                 tests/parquet_forged_cases.py::more_than_256_pages
+    pq_rowlen_scan_kernel (Parquet scan)        256 blocks x 4096 rows    test_parquet_scan_utf8_offsets_past_one_scan_round (PLAIN with and without
+                                                                          nulls, dictionary: one block, of one row, in round two)
+    pw_scan_kernel (Parquet write)              256 blocks x 4096 rows    test_parquet_write_past_one_scan_round (a batch, and a view nine rows into its
+                                                                          parent: the 17th page starts at block 256)
   scan_count_rows (scan_device.h), as
     part_scan_kernel                            2048 tiles x 2048 rows    test_partition_more_tiles_than_one_scan_round (3 and 256 partitions)
   strfn_rows_kernel, strfn_gather_kernel        8192 workgroups x 256     test_string_functions_more_rows_than_one_grid_pass (wave per row in the strided
@@ -34,8 +40,11 @@ side is the cost.
   iota_offsets_kernel                           8192 workgroups x 256     the same, and test_gpu_scale.py::test_reference_schema_group_full_size (a
                                                                           joined output of some 3 x 10^7 rows, offsets compared with 8 i)
 """
+import io
+
 import numpy as np
 import pyarrow as pa
+import pyarrow.parquet as pq
 import pytest
 
 import chapterhouseqe_amd as chq
@@ -49,9 +58,11 @@ from . import partition_reference as P
 from . import sort_reference as R
 from . import strfn_reference as SR
 from .cases import empty_aliases
+from .helpers import batches_identical, explain_diff
 from .test_gpu_join import aliases, int_side, same, to_host
 from .test_gpu_like import POOL as LIKE_POOL
 from .test_gpu_like import WAVE_MODE_BYTES as LIKE_WAVE_MODE_BYTES
+from .test_gpu_parquet import check as check_scan
 from .test_gpu_parity import BOOL_WORDS
 from .test_gpu_sort import explain, identical, ob
 from .test_gpu_strfn import POOL as STRFN_POOL
@@ -66,11 +77,14 @@ STRFN_ROUND = 256 * T                 # scan_totals_in_place under the string fu
 STRIDE_ROWS = 8192 * 256              # rows one pass of a grid capped at 256 * 32 workgroups covers (strfn rows / gather, like, typed_ops)
 BYTEMAP_BYTES = 4096 * 256 * 16       # bytes one pass of strfn_bytemap_kernel's grid covers (capped at 256 * 16 workgroups)
 REBASE_ROWS = 4096 * 256              # offsets one pass of strfn_rebase_kernel's grid covers
+PQ_BLOCK = 4096                       # rows per block total of the Parquet offset scan (PQ_SCAN_ROWS) and of the writer (PW_BLOCK_ROWS)
+PQ_ROUND = 256 * PQ_BLOCK             # pq_rowlen_scan_kernel, pw_scan_kernel: one block total per thread and round
 
 SCAN_ROWS = SCAN_ROUND + T + 5        # the smallest sizes that put more than one full tile into the second round
 PART_ROWS = PART_ROUND + T + 5
 STRFN_ROWS = STRFN_ROUND + T + 5
 STRIDE_N = STRIDE_ROWS + 64 + 1       # ... more than one full wave into the strided iteration
+PQ_ROWS = PQ_ROUND + 1                # ... one block total, of one row, into the second round
 LONG_TAIL = 4096                      # the last rows of a strided column are long: wave-per-row mode in the strided iteration too
 KK = [("k", "k")]
 
@@ -550,3 +564,76 @@ def test_uniform_length_check_more_rows_than_one_grid_pass(ragged_row):
         assert launches - bare_launches == 2, (launches, bare_launches)
     else:                    # refused: no launch more than with the rewrite switched off
         assert launches == plain_launches, (launches, plain_launches)
+
+
+# ---- Parquet: the block totals of the Utf8 offset scan and of the page encoder past 256 blocks of 4096 rows ------------------
+PQ_POOL = [b"", b"a", b"\xc3\xa9", b"bcd", b"a string of more than sixteen bytes", b"xy", None]
+
+
+def parquet_pool_indices(rng, n):
+    """pool entries for n rows: the last two rows are valid and not empty, and so are the rows on either side of every multiple
+    of PQ_ROUND"""
+    idx = rng.integers(0, len(PQ_POOL), n)
+    idx[n - 2], idx[n - 1] = 4, 2
+    for seam in range(PQ_ROUND, n, PQ_ROUND):
+        idx[seam - 1] = 3
+    return idx
+
+
+def test_parquet_scan_utf8_offsets_past_one_scan_round(ctx):
+    """pq_rowlen_sums / _scan / _offsets over 257 blocks: (a) PLAIN with nulls, (b) the same rows without nulls (no row -> value
+    map), (c) a dictionary with nulls, in ONE row group (pyarrow's default would cut the table at row 2^20, one row short of
+    the second round).  offsets[PQ_ROUND] and offsets[PQ_ROWS] are the two values that only the second round produces"""
+    rng = np.random.default_rng(20261030)
+    n = PQ_ROWS
+    idx = parquet_pool_indices(rng, n)
+    a = utf8_pool(PQ_POOL).take(pa.array(idx))
+    b = utf8_pool([c or b"" for c in PQ_POOL]).take(pa.array(idx))
+    c = utf8_pool(PQ_POOL).take(pa.array(np.concatenate([rng.permutation(idx[:n - 2]), [1, 4]])))
+    assert a.null_count > 0 and b.null_count == 0 and c.null_count > 0
+    table = pa.Table.from_arrays([a, b, c], schema=pa.schema([pa.field("a", pa.utf8()), pa.field("b", pa.utf8(), nullable=False), pa.field("c", pa.utf8())]))
+    sink = io.BytesIO()
+    pq.write_table(table, sink, compression="none", row_group_size=1 << 21, use_dictionary=["c"])
+    raw = sink.getvalue()
+    md = pq.ParquetFile(io.BytesIO(raw)).metadata
+    assert md.num_row_groups == 1 and md.num_rows == n
+    encodings = [set(md.row_group(0).column(i).encodings) for i in range(3)]
+    assert "RLE_DICTIONARY" not in encodings[0] | encodings[1] and "PLAIN_DICTIONARY" not in encodings[0] | encodings[1]
+    assert {"RLE_DICTIONARY", "PLAIN_DICTIONARY"} & encodings[2]
+    check_scan(raw, ctx)                                                     # every column, whole, against pyarrow's reading
+    f = chq.ParquetFile(raw)
+    got = f.read_row_group(0, ctx=ctx).to_host()
+    f.close()
+    for name, col in zip("abc", (a, b, c)):
+        go, eo = offsets_of(got.column(name)), offsets_of(col)
+        assert len(go) == n + 1 and eo[0] == 0
+        assert int(go[PQ_ROUND]) == int(eo[PQ_ROUND]) > 0, name            # the base of block 256: the carry of the first round
+        assert int(go[n]) == byte_total(col) > int(go[PQ_ROUND]), name     # the grand total behind the second round
+
+
+@pytest.mark.parametrize("lead", [0, 9])
+def test_parquet_write_past_one_scan_round(ctx, lead):
+    """pw_counts / pw_scan / pw_encode over 257 blocks: nullable Int32 (30 % nulls), Utf8 and Boolean columns of a device batch
+    through record_to_parquet with the default 65 536 rows per page.  Page 16 starts at block 256: its base in the value stream
+    is the first total of the scan's second round.  lead = 9: a view nine rows into its parent, validity at bit offset 9 % 8"""
+    rng = np.random.default_rng(20261031 + lead)
+    n = PQ_ROWS
+    rows = n + lead
+    valid = rng.random(rows) >= 0.3
+    valid[rows - 2:] = True
+    parent = pa.RecordBatch.from_arrays(
+        [pa.array(rng.integers(-2**31, 2**31, rows).astype(np.int32), mask=~valid),
+         utf8_pool(PQ_POOL).take(pa.array(parquet_pool_indices(rng, rows))),
+         pa.array(rng.random(rows) < 0.5, mask=rng.random(rows) < 0.2)], names=["i", "s", "flag"])
+    want = parent.slice(lead, n)
+    assert all(want.column(k).null_count > 0 for k in range(3))
+    assert all(want.column(k).slice(n - 2).null_count == 0 for k in (0, 1))
+    dev = chq.DeviceRecordBatch.from_host(parent, ctx)
+    raw = chq.record_to_parquet(dev.slice(lead, n) if lead else dev, ctx=ctx)
+    back = pq.ParquetFile(io.BytesIO(raw))
+    md = back.metadata
+    assert md.num_row_groups == 1 and md.num_rows == n
+    got = back.read_row_group(0).combine_chunks().to_batches()
+    assert len(got) == 1 and batches_identical(got[0], want), explain_diff(got[0], want)
+    for name in ("i", "s"):                                                  # page 16 is the last row alone: valid, not empty
+        assert got[0].column(name)[n - 1].as_py() == want.column(name)[n - 1].as_py() not in (None, ""), name

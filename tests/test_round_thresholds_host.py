@@ -76,6 +76,22 @@ def test_tiles_of_the_scans():
         assert "launch_offsets_scan(" in source(caller), caller
     assert G.SCAN_ROUND == G.STRFN_ROUND == block * G.T
 
+    # ... and the three scans of the Parquet kernels: the same loop over page counts and over the totals of blocks of
+    # PQ_SCAN_ROWS / PW_BLOCK_ROWS rows, which parquet_device.h defines once for the host (n_blocks) and the kernels
+    shared_pq = source("parquet_device.h")
+    assert G.PQ_BLOCK == constant(shared_pq, "PQ_SCAN_ROWS") == constant(shared_pq, "PW_BLOCK_ROWS")
+    for name, kernels in (("PQ_SCAN_ROWS", ("parquet.hip", "parquet_scan.cpp")), ("PW_BLOCK_ROWS", ("parquet_write.hip", "parquet_write.cpp"))):
+        for text in map(source, kernels):
+            assert name in text and not re.search(r"constexpr\s+int\s+" + name, text), name
+    pq, pw = source("parquet.hip"), source("parquet_write.hip")
+    for text, kernel, total in ((pq, "pq_page_scan_kernel", "p.total_values"), (pq, "pq_rowlen_scan_kernel", "p.total_bytes"),
+                                (pw, "pw_scan_kernel", "p.total_bytes")):
+        assert "scan_totals_in_place<" in body_of(text, f"void {kernel}(") and f", {total}, sums);" in body_of(text, f"void {kernel}("), kernel
+        assert f"{kernel}, dim3(1), dim3(kScanBlock)" in text, kernel
+    assert "(int64_t)blockIdx.x * PQ_SCAN_ROWS" in body_of(pq, "void pq_rowlen_sums_kernel(")
+    assert "(int64_t)blockIdx.x * PW_BLOCK_ROWS" in body_of(pw, "void pw_counts_kernel(")
+    assert G.PQ_ROUND == block * G.PQ_BLOCK and G.PQ_ROWS == G.PQ_ROUND + 1
+
     # part_scan_kernel (and sort_scan_kernel): scan_count_rows with kPartItems tile counts per thread and round, a round of
     # kPartTile counts
     loop = body_of(shared, "void scan_count_rows(")
