@@ -406,6 +406,42 @@ chq_expr* chq_expr_function(const char* name, chq_expr* const* args, int n_args)
   for (int i = 0; i < n_args; ++i) { e->e.args.emplace_back(new Expr(std::move(args[i]->e))); delete args[i]; }
   return e;
 }
+// (shared by the three below) moves `n` handles into e->args; false -- and every handle freed -- when one is missing
+static bool take_children(chq_expr* e, chq_expr* const* list, int n) {
+  bool ok = e && n >= 0 && (list || n == 0);
+  for (int i = 0; ok && i < n; ++i) ok = list[i] != nullptr;
+  if (!ok) { for (int i = 0; list && i < n; ++i) chq_expr_free(list[i]); return false; }
+  for (int i = 0; i < n; ++i) { e->e.args.emplace_back(new Expr(std::move(list[i]->e))); delete list[i]; }
+  return true;
+}
+chq_expr* chq_expr_case(chq_expr* operand, chq_expr* const* conditions, chq_expr* const* results, int n_when, chq_expr* else_result) {
+  chq_expr* e = new_expr(Expr::CASE);
+  const bool ok_c = take_children(e, conditions, n_when);
+  const bool ok_r = take_children(ok_c ? e : nullptr, results, n_when);
+  if (!ok_c || !ok_r || n_when < 1) { chq_expr_free(operand); chq_expr_free(else_result); delete e; return nullptr; }
+  if (operand) { e->e.l.reset(new Expr(std::move(operand->e))); delete operand; }
+  if (else_result) { e->e.r.reset(new Expr(std::move(else_result->e))); delete else_result; }
+  return e;
+}
+chq_expr* chq_expr_in_list(chq_expr* expr, chq_expr* const* list, int n, int negated) {
+  chq_expr* e = new_expr(Expr::IN_LIST);
+  const bool ok = take_children(e, list, n);
+  if (!ok || !expr) { chq_expr_free(expr); delete e; return nullptr; }
+  e->e.flag = negated != 0;
+  e->e.l.reset(new Expr(std::move(expr->e)));
+  delete expr;
+  return e;
+}
+chq_expr* chq_expr_between(chq_expr* expr, int negated, chq_expr* low, chq_expr* high) {
+  chq_expr* e = new_expr(Expr::BETWEEN);
+  if (!e || !expr || !low || !high) { chq_expr_free(expr); chq_expr_free(low); chq_expr_free(high); delete e; return nullptr; }
+  e->e.flag = negated != 0;
+  e->e.l.reset(new Expr(std::move(expr->e)));
+  e->e.args.emplace_back(new Expr(std::move(low->e)));
+  e->e.args.emplace_back(new Expr(std::move(high->e)));
+  delete expr; delete low; delete high;
+  return e;
+}
 chq_expr* chq_expr_unsupported(const char* debug) { chq_expr* e = new_expr(Expr::OTHER); if (e) e->e.text = debug ? debug : ""; return e; }
 void chq_expr_free(chq_expr* e) { delete e; }
 

@@ -36,6 +36,13 @@ hipError_t launch_strfn_rebase(const StrRebaseParams& p, hipStream_t stream);
 hipError_t launch_strfn_rows(const StrRowsParams& p, hipStream_t stream);
 hipError_t launch_offsets_scan(const OffsetsScanParams& p, hipStream_t stream);   // scan.hip: 3 launches; tile_sums: ntiles + 1 words
 hipError_t launch_strfn_gather(const StrGatherParams& p, hipStream_t stream);
+// case.hip
+hipError_t launch_case_masks(const CaseMasksParams& p, hipStream_t stream);
+hipError_t launch_case_and(const CaseAndParams& p, hipStream_t stream);
+hipError_t launch_case_select_bool(const CaseSelectParams& p, hipStream_t stream);
+hipError_t launch_case_select_fixed(const CaseSelectParams& p, hipStream_t stream);
+hipError_t launch_case_rows(const CaseSelectParams& p, hipStream_t stream);
+hipError_t launch_case_gather(const CaseSelectParams& p, hipStream_t stream);
 hipError_t launch_utf8_uniform(const Utf8UniformParams& p, hipStream_t stream);
 hipError_t launch_iota_offsets(const IotaOffsetsParams& p, hipStream_t stream);
 hipError_t launch_count_bits(const uint8_t* in, int64_t bit_offset, int64_t nbits, unsigned long long* out, hipStream_t stream);

@@ -156,11 +156,12 @@ void materialize_node(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols,
 
 // Decimal128 comparisons, Utf8 -> Boolean casts, LIKE and IS [NOT] NULL are not device-program instructions (plan.hpp:
 // Node): their own kernels (typed_ops.hip, like.hip) write a temporary Boolean column, which replaces the node like any
-// other materialisation.  The scalar string functions (strfn.hip) do the same with a temporary Utf8 or Int32 column.
+// other materialisation.  The scalar string functions (strfn.hip) do the same with a temporary Utf8 or Int32 column, CASE
+// (case.hip) with a temporary column of its result type.
 bool is_typed_op(const TypedExpr& te, int node) {
   const Node& n = te.nodes[node];
   return (n.kind == Node::CMP && n.from == T_FIXED_OPAQUE) || (n.kind == Node::TOBOOL && n.from == T_UTF8) ||
-         n.kind == Node::LIKE || n.kind == Node::ISNULL || n.kind == Node::STRFN ||
+         n.kind == Node::LIKE || n.kind == Node::ISNULL || n.kind == Node::STRFN || n.kind == Node::CASE ||
          (n.kind == Node::CONST && n.cval.null);   // `'maybe' AND ..` folded to NULL, next to a column of a one-row batch
 }
 void fit_subtree(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict, bool is_root);
@@ -282,7 +283,194 @@ Column evaluate_strfn(Context& ctx, const Batch& work, const TypedExpr& te, cons
   return c;
 }
 
+// ---- CASE, COALESCE, NULLIF (case.hip) ------------------------------------------------------------
+const char* fixed_format(DType t) {
+  static const char* fmts[T_NTYPES] = {"b", "c", "s", "i", "l", "C", "S", "I", "L", "e", "f", "g", "u", ""};
+  return fmts[t];
+}
+// A copy of the sub-tree at `node`, appended to te.nodes, that reads VIEWS of its columns: the same values, a validity that is
+// the column's AND `guard` (words aligned to bit 0).  kernels.hip raises data-dependent errors on valid slots only, so the
+// copy reports nothing on rows outside the guard and is null there.  The views are appended to `work` / `wcols`.
+int guarded_copy(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, const u64* guard,
+                 std::vector<std::pair<int, int>>& views) {
+  Node n = te.nodes[(size_t)node];
+  if (n.kind == Node::COL) {
+    int vi = -1;
+    for (const auto& v : views) if (v.first == n.col) vi = v.second;
+    if (vi < 0) {
+      const int64_t nrows = work.nrows;
+      const size_t words = (size_t)((nrows + 63) / 64) + 1;
+      Column v = work.cols[(size_t)n.col];
+      PlanColumn pc = wcols[(size_t)n.col];
+      auto vb = make_device_buffer(words * 8, ctx.device);
+      CaseAndParams ap{(v.validity && v.null_count != 0) ? v.validity : nullptr, v.offset, guard, nrows, (u64*)vb->ptr};
+      check_hip(launch_case_and(ap, ctx.stream), "launch case_and_kernel");
+      if (v.type == T_BOOL) {   // the values of a Boolean column are read from the same bit offset: re-aligned too
+        auto bb = make_device_buffer(words * 8, ctx.device);
+        CaseAndParams bp{v.values, v.offset, nullptr, nrows, (u64*)bb->ptr};
+        check_hip(launch_case_and(bp, ctx.stream), "launch case_and_kernel");
+        v.values = (const uint8_t*)bb->ptr; v.owned.push_back(bb);
+      } else {
+        v.values = (const uint8_t*)v.values0();
+      }
+      v.offset = 0; v.validity = (const uint8_t*)vb->ptr; v.null_count = -1; v.owned.push_back(vb);
+      v.name = "__chq_view_" + std::to_string(work.cols.size());
+      pc.name = v.name; pc.has_nulls = true;
+      vi = (int)work.cols.size();
+      work.cols.push_back(std::move(v));
+      wcols.push_back(std::move(pc));
+      views.emplace_back(n.col, vi);
+    }
+    n.col = vi;
+  } else {
+    if (n.l >= 0) n.l = guarded_copy(ctx, work, wcols, te, n.l, guard, views);
+    if (n.r >= 0) n.r = guarded_copy(ctx, work, wcols, te, n.r, guard, views);
+    for (int& c : n.parts) c = guarded_copy(ctx, work, wcols, te, c, guard, views);
+  }
+  te.nodes.push_back(std::move(n));
+  return (int)te.nodes.size() - 1;
+}
+
+// The temporary column of CASE node `node`.  Operands are evaluated in the order c1..cn, r1..rn, else; one that can fail on
+// data (case_guarded_parts) is evaluated under its guard -- a result under its take mask, a condition under what remained
+// after the WHENs before it, so the masks are then built WHEN by WHEN -- and everything else unguarded, all masks in one launch.
+Column evaluate_case(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict) {
+  const int64_t nrows = work.nrows;
+  const Node head = te.nodes[(size_t)node];
+  const int nw = head.op;
+  Column c;
+  c.type = head.type; c.length = nrows;
+  if (head.type == T_FIXED_OPAQUE) { c.format = wcols[(size_t)head.fmt_col].format; c.width = wcols[(size_t)head.fmt_col].width; }
+  else { c.format = fixed_format(head.type); c.width = dtype_width(head.type); }
+  if (nrows == 0) {
+    auto vb = make_device_buffer(16, ctx.device);
+    check_hip(hipMemsetAsync(vb->ptr, 0, 16, ctx.stream), "memset");
+    c.values = (const uint8_t*)vb->ptr; c.owned.push_back(vb);
+    if (head.type == T_UTF8) { auto db = make_device_buffer(16, ctx.device); c.data = (const uint8_t*)db->ptr; c.data_bytes = 0; c.owned.push_back(db); }
+    check_hip(hipStreamSynchronize(ctx.stream), "sync");
+    return c;
+  }
+  const int64_t words = (nrows + 63) / 64;
+  auto masks = make_device_buffer((size_t)(nw + 1) * (size_t)words * 8 + 16, ctx.device);
+  u64* const d_masks = (u64*)masks->ptr;
+  std::vector<char> guard;
+  case_guarded_parts(te, node, &guard);
+  // an operand as a column or a literal: fitted, evaluated (under `g` when it is guarded) and replaced
+  auto operand = [&](size_t j, const u64* g) {
+    int q = te.nodes[(size_t)node].parts[j];
+    if (te.nodes[(size_t)q].kind == Node::CONST) return;
+    if (guard[j]) {
+      std::vector<std::pair<int, int>> views;
+      q = guarded_copy(ctx, work, wcols, te, q, g, views);
+      te.nodes[(size_t)node].parts[j] = q;
+    }
+    fit_subtree(ctx, work, wcols, te, q, strict, false);
+    if (te.nodes[(size_t)q].kind != Node::COL) materialize_node(ctx, work, wcols, te, q);
+  };
+  int done = 0;   // WHENs whose take masks are written
+  auto masks_through = [&](int k1) {
+    if (k1 <= done) return;
+    CaseMasksParams mp{};
+    mp.first = done; mp.n = k1 - done; mp.n_total = nw; mp.nrows = nrows; mp.words = words; mp.masks = d_masks;
+    for (int k = done; k < k1; ++k) {
+      const Node& cn = te.nodes[(size_t)te.nodes[(size_t)node].parts[(size_t)k]];
+      CaseCond& cc = mp.cond[k - done];
+      if (cn.kind == Node::CONST) { cc.kind = cn.cval.null ? CASE_NULL : CASE_CONST; cc.const_val = (int32_t)(cn.cval.bits & 1); continue; }
+      const Column& col = work.cols[(size_t)cn.col];
+      cc.kind = CASE_COLUMN; cc.values = col.values; cc.validity = (col.validity && col.null_count != 0) ? col.validity : nullptr; cc.offset = col.offset;
+    }
+    check_hip(launch_case_masks(mp, ctx.stream), "launch case_masks_kernel");
+    done = k1;
+  };
+  for (int k = 0; k < nw; ++k) {
+    if (guard[(size_t)k]) masks_through(k);   // (its guard: what remained after the WHENs before it)
+    operand((size_t)k, d_masks + (size_t)nw * (size_t)words);
+  }
+  masks_through(nw);
+  for (size_t j = (size_t)nw; j < head.parts.size(); ++j) operand(j, d_masks + (j - (size_t)nw) * (size_t)words);
+
+  CaseSelectParams sp{};
+  std::vector<BufferPtr> lits;
+  sp.n_when = nw; sp.width = c.width; sp.nrows = nrows; sp.words = words; sp.masks = d_masks;
+  for (int k = 0; k <= nw; ++k) {
+    CaseBranch& b = sp.br[k];
+    if (k == nw && !head.case_else) { b.kind = CASE_NULL; continue; }
+    const Node& rn = te.nodes[(size_t)te.nodes[(size_t)node].parts[(size_t)(nw + k)]];
+    if (rn.kind == Node::CONST) {
+      if (rn.cval.null) { b.kind = CASE_NULL; continue; }
+      b.kind = CASE_CONST; b.const_lo = rn.cval.bits;
+      if (head.type == T_UTF8) {   // (the node's string outlives the copy: the stream is synchronised below)
+        auto lb = make_device_buffer(rn.cval.str.size() + 16, ctx.device);
+        if (!rn.cval.str.empty()) check_hip(hipMemcpyAsync(lb->ptr, rn.cval.str.data(), rn.cval.str.size(), hipMemcpyHostToDevice, ctx.stream), "upload string literal");
+        b.data = (const uint8_t*)lb->ptr; b.lit_len = (int32_t)rn.cval.str.size();
+        lits.push_back(lb);
+      }
+      continue;
+    }
+    const Column& col = work.cols[(size_t)rn.col];
+    b.kind = CASE_COLUMN;
+    b.values = head.type == T_BOOL ? col.values : (const uint8_t*)col.values0();
+    b.data = col.data; b.validity = (col.validity && col.null_count != 0) ? col.validity : nullptr; b.offset = col.offset;
+  }
+  auto valid = make_device_buffer((size_t)(words + 1) * 8, ctx.device);
+  auto count = make_device_buffer(32, ctx.device);
+  check_hip(hipMemsetAsync(count->ptr, 0, 32, ctx.stream), "memset");
+  sp.out_validity = (u64*)valid->ptr; sp.null_count = (u64*)count->ptr;
+  u64 h_count[2] = {0, 0};
+  if (head.type == T_UTF8) {
+    auto len = make_device_buffer((size_t)nrows * 4 + 16, ctx.device);
+    sp.out_len = (int32_t*)len->ptr;
+    check_hip(launch_case_rows(sp, ctx.stream), "launch case_rows_kernel");
+    OffsetsScanParams op{};
+    op.len = (const uint32_t*)len->ptr; op.n = nrows; op.ntiles = (nrows + STRFN_SCAN_CHUNK - 1) / STRFN_SCAN_CHUNK;
+    auto sums = make_device_buffer((size_t)(op.ntiles + 1) * 8 + 16, ctx.device);
+    auto offb = make_device_buffer((size_t)(nrows + 2) * 4, ctx.device);
+    op.tile_sums = (uint64_t*)sums->ptr; op.out = (uint32_t*)offb->ptr; op.write_total = 1;
+    check_hip(launch_offsets_scan(op, ctx.stream), "launch the offsets scan of the row lengths");
+    check_hip(hipMemcpyAsync(&h_count[0], count->ptr, 8, hipMemcpyDeviceToHost, ctx.stream), "read null count");
+    check_hip(hipMemcpyAsync(&h_count[1], op.tile_sums + op.ntiles, 8, hipMemcpyDeviceToHost, ctx.stream), "read byte total");
+    check_hip(hipStreamSynchronize(ctx.stream), "sync");
+    if (h_count[1] > (u64)INT32_MAX)
+      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "the Utf8 result of CASE would hold " + std::to_string(h_count[1]) +
+                                                     " bytes, more than int32 offsets can address"};
+    const int64_t bytes = (int64_t)h_count[1];
+    auto db = make_device_buffer((size_t)bytes + 16, ctx.device);
+    if (bytes > 0) {
+      sp.out_offsets = (const int32_t*)offb->ptr; sp.out_data = (uint8_t*)db->ptr;
+      check_hip(launch_case_gather(sp, ctx.stream), "launch case_gather_kernel");
+      check_hip(hipStreamSynchronize(ctx.stream), "sync");   // (the literals and the masks are let go on return)
+    }
+    c.values = (const uint8_t*)offb->ptr; c.data = (const uint8_t*)db->ptr; c.data_bytes = bytes;
+    c.owned = {offb, db};
+  } else {
+    const size_t vbytes = head.type == T_BOOL ? (size_t)(words + 1) * 8 : (size_t)nrows * (size_t)c.width + 16;
+    auto vb = make_device_buffer(vbytes, ctx.device);
+    sp.out_values = vb->ptr;
+    if (head.type == T_BOOL) check_hip(launch_case_select_bool(sp, ctx.stream), "launch case_select_bool_kernel");
+    else check_hip(launch_case_select_fixed(sp, ctx.stream), "launch case_select_fixed_kernel");
+    check_hip(hipMemcpyAsync(&h_count[0], count->ptr, 8, hipMemcpyDeviceToHost, ctx.stream), "read null count");
+    check_hip(hipStreamSynchronize(ctx.stream), "sync");
+    c.values = (const uint8_t*)vb->ptr; c.owned = {vb};
+  }
+  c.null_count = (int64_t)h_count[0]; c.nullable = c.null_count != 0;
+  if (c.null_count) { c.validity = (const uint8_t*)valid->ptr; c.owned.push_back(valid); }
+  return c;
+}
+
 void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict) {
+  if (te.nodes[node].kind == Node::CASE) {
+    Column c = evaluate_case(ctx, work, wcols, te, node, strict);
+    c.name = "__chq_tmp_" + std::to_string(work.cols.size());
+    PlanColumn pc;
+    pc.name = c.name; pc.type = c.type; pc.has_nulls = c.null_count != 0; pc.alias_entry_present = true; pc.format = c.format; pc.width = c.width;
+    Node repl{};
+    repl.kind = Node::COL; repl.type = c.type; repl.is_scalar = false; repl.len1 = false;
+    repl.col = (int)work.cols.size(); repl.ref_order = te.nodes[node].ref_order;
+    work.cols.push_back(std::move(c));
+    wcols.push_back(std::move(pc));
+    te.nodes[node] = repl;
+    return;
+  }
   {
     // the operands as columns: a computed one (a literal-only one was folded at typing) is evaluated first, with its
     // data-dependent errors, in the order `strict` asks for.  Until the string functions only IS NULL and LIKE had operands
@@ -319,6 +507,8 @@ void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wc
   auto count = make_device_buffer(16, ctx.device);
   check_hip(hipMemsetAsync(count->ptr, 0, 16, ctx.stream), "memset");
   if (n.kind == Node::CONST) {
+    if (n.type != T_BOOL)   // (nullif / CASE over literals can fold to one; only a Boolean one was ever met before)
+      throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("a NULL literal-built ") + dtype_name(n.type) + " value next to a column is outside this build's scope"};
     check_hip(hipMemsetAsync(bits->ptr, 0, words * 8, ctx.stream), "memset");
     check_hip(hipMemsetAsync(valid->ptr, 0, words * 8, ctx.stream), "memset");
     const u64 all = (u64)nrows;

@@ -1,6 +1,7 @@
 // plan.cpp -- typing and lowering of sqlparser expressions (see plan.hpp for the reference map).
 #include "plan.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -273,6 +274,14 @@ Scalar fold_constant(const TypedExpr& t, int ni) {
       out.str = a.str.substr((size_t)first, (size_t)count);
       return out;
     }
+    case Node::CASE: {   // the word rule the device runs (case_device.h), on one-row words
+      uint64_t remaining = 1;
+      for (int k = 0; k < n.op; ++k) {
+        const Scalar c = fold_constant(t, n.parts[(size_t)k]);
+        if (case_take(&remaining, c.bits & 1, c.null ? 0 : 1)) return fold_constant(t, n.parts[(size_t)(n.op + k)]);
+      }
+      return n.case_else ? fold_constant(t, n.parts.back()) : null_scalar(n.type);
+    }
     default: fail(CHQ_ERR_INVALID_HANDLE, "fold_constant on a column");
   }
 }
@@ -404,6 +413,49 @@ struct Typer {
         return maybe_fold(push(n));
       }
       case Expr::FUNCTION: return function(e);
+      case Expr::CASE: {
+        const size_t nw = e.args.size() / 2;
+        if (nw == 0 || e.args.size() != 2 * nw) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "CASE needs at least one WHEN, each with a THEN");
+        // a simple CASE: the operand is typed once; WHEN k is `operand = value k` by the ordinary rules of `=`
+        const int x = e.l ? build(*e.l) : -1;
+        std::vector<int> conds, results;
+        Expr eq; eq.kind = Expr::BINARY; eq.op = CHQ_BINOP_EQ; eq.text = "Eq";
+        for (size_t k = 0; k < nw; ++k) { const int c = build(*e.args[k]); conds.push_back(x >= 0 ? binary(eq, x, c) : c); }
+        for (size_t k = 0; k < nw; ++k) results.push_back(build(*e.args[nw + k]));
+        const int els = e.r ? build(*e.r) : -1;
+        return case_node(conds, results, els, "CASE");
+      }
+      case Expr::BETWEEN: {   // x >= lo AND x <= hi / x < lo OR x > hi, x typed once
+        if (e.args.size() != 2 || !e.l) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "BETWEEN needs an operand, a low and a high bound");
+        const int x = build(*e.l), lo = build(*e.args[0]), hi = build(*e.args[1]);
+        Expr a; a.kind = Expr::BINARY; a.op = e.flag ? CHQ_BINOP_LT : CHQ_BINOP_GTEQ; a.text = e.flag ? "Lt" : "GtEq";
+        Expr b; b.kind = Expr::BINARY; b.op = e.flag ? CHQ_BINOP_GT : CHQ_BINOP_LTEQ; b.text = e.flag ? "Gt" : "LtEq";
+        Expr j; j.kind = Expr::BINARY; j.op = e.flag ? CHQ_BINOP_OR : CHQ_BINOP_AND; j.text = e.flag ? "Or" : "And";
+        const int l = binary(a, x, lo);
+        const int r = binary(b, x, hi);
+        return binary(j, l, r);
+      }
+      case Expr::IN_LIST: {   // x = l1 OR x = l2 .. / x <> l1 AND x <> l2 .., x typed once
+        if (!e.l) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "IN needs an operand");
+        if (e.args.empty() || (int)e.args.size() > CASE_MAX_IN_LIST)
+          fail(CHQ_ERR_NOT_SUPPORTED, "an IN list holds 1 to " + std::to_string(CASE_MAX_IN_LIST) + " literals, found " + std::to_string(e.args.size()));
+        for (const auto& a : e.args) {
+          const Expr* q = a.get();
+          while (q->kind == Expr::NESTED) q = q->l.get();
+          if (q->kind != Expr::NUMBER && q->kind != Expr::BOOLEAN && q->kind != Expr::STRING && q->kind != Expr::VALUE_OTHER)
+            fail(CHQ_ERR_NOT_SUPPORTED, "every item of an IN list must be a literal");
+        }
+        const int x = build(*e.l);
+        Expr c; c.kind = Expr::BINARY; c.op = e.flag ? CHQ_BINOP_NOTEQ : CHQ_BINOP_EQ; c.text = e.flag ? "NotEq" : "Eq";
+        Expr j; j.kind = Expr::BINARY; j.op = e.flag ? CHQ_BINOP_AND : CHQ_BINOP_OR; j.text = e.flag ? "And" : "Or";
+        int acc = -1;
+        for (const auto& a : e.args) {
+          const int item = build(*a);
+          const int one = binary(c, x, item);
+          acc = acc < 0 ? one : binary(j, acc, one);
+        }
+        return acc;
+      }
       default: fail(CHQ_ERR_EXPRESSION_TYPE_NOT_IMPLEMENTED, "expression type not implemented: " + e.text);
     }
   }
@@ -414,6 +466,30 @@ struct Typer {
         {"upper", STRFN_UPPER, 1, 1}, {"lower", STRFN_LOWER, 1, 1}, {"length", STRFN_LENGTH, 1, 1}, {"char_length", STRFN_LENGTH, 1, 1},
         {"character_length", STRFN_LENGTH, 1, 1}, {"octet_length", STRFN_OCTET_LENGTH, 1, 1}, {"substring", STRFN_SUBSTRING, 2, 3},
         {"substr", STRFN_SUBSTRING, 2, 3}, {"trim", STRFN_TRIM, 1, 1}, {"ltrim", STRFN_LTRIM, 1, 1}, {"rtrim", STRFN_RTRIM, 1, 1}};
+    if (!strcasecmp(e.text.c_str(), "coalesce")) {   // CASE WHEN a1 IS NOT NULL THEN a1 .. ELSE an END, every a_k typed once
+      if (e.args.empty()) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, e.text + " takes at least 1 argument, found 0");
+      std::vector<int> conds, results;
+      int els = -1;
+      for (size_t k = 0; k < e.args.size(); ++k) {
+        const int a = build(*e.args[k]);
+        if (k + 1 == e.args.size()) { els = a; break; }
+        Node n{}; n.kind = Node::ISNULL; n.type = T_BOOL; n.from = t.nodes[a].type; n.l = a; n.op = 1;
+        n.is_scalar = t.nodes[a].is_scalar; n.len1 = t.nodes[a].len1;
+        conds.push_back(maybe_fold(push(n)));
+        results.push_back(a);
+      }
+      return case_node(conds, results, els, e.text.c_str());
+    }
+    if (!strcasecmp(e.text.c_str(), "nullif")) {   // CASE WHEN a = b THEN <null> ELSE a END, of a's own type
+      if (e.args.size() != 2) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, e.text + " takes 2 arguments, found " + std::to_string(e.args.size()));
+      const int a = build(*e.args[0]), b = build(*e.args[1]);
+      Expr eq; eq.kind = Expr::BINARY; eq.op = CHQ_BINOP_EQ; eq.text = "Eq";
+      const int c = binary(eq, a, b);
+      Node z{}; z.kind = Node::CONST; z.type = t.nodes[a].type; z.is_scalar = true; z.len1 = true; z.cval = null_scalar(z.type);
+      z.fmt_col = opaque_col(t.nodes[a]);
+      const int nul = push(z);
+      return case_node({c}, {nul}, a, e.text.c_str());
+    }
     int fn = -1; size_t lo = 0, hi = 0;
     for (const auto& f : kFns) if (!strcasecmp(e.text.c_str(), f.name)) { fn = f.fn; lo = f.min_args; hi = f.max_args; }
     // (an unknown name: what every call answered before there were functions)
@@ -439,6 +515,51 @@ struct Typer {
       if (n.sub_has_cnt && n.sub_cnt < 0) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative substring length not allowed: " + std::to_string(n.sub_cnt));
     }
     return maybe_fold(push(n));
+  }
+
+  // the batch column whose format a T_FIXED_OPAQUE value has: a column's own, a CASE's fmt_col
+  static int opaque_col(const Node& n) { return n.kind == Node::COL ? n.col : n.fmt_col; }
+
+  // Searched CASE over typed conditions and results (`els` < 0: no ELSE).  No implicit cast to Boolean in WHEN; the result
+  // type is common_type folded left to right over the results and the ELSE, each wrapped by cast_to (widening casts: none
+  // can fail).  More than CASE_MAX_WHENS nest: WHEN 9 onward is a CASE in the ELSE slot.
+  int case_node(std::vector<int> conds, std::vector<int> results, int els, const char* what) {
+    for (size_t k = 0; k < conds.size(); ++k)
+      if (t.nodes[conds[k]].type != T_BOOL)
+        fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, std::string("WHEN ") + std::to_string(k + 1) + " of " + what + " must be Boolean, found " + dtype_name(t.nodes[conds[k]].type));
+    std::vector<int> all = results;
+    if (els >= 0) all.push_back(els);
+    if (conds.empty()) return els;   // coalesce(a)
+    DType ct = t.nodes[all[0]].type;
+    int fmt = opaque_col(t.nodes[all[0]]);
+    for (size_t k = 1; k < all.size(); ++k) {
+      const Node& b = t.nodes[all[k]];
+      DType next;
+      const bool ok = common_type(ct, b.type, &next) &&
+                      (ct != T_FIXED_OPAQUE || (fmt >= 0 && opaque_col(b) >= 0 && canonical_format(cols[fmt].format) == canonical_format(cols[opaque_col(b)].format)));
+      if (!ok) fail(CHQ_ERR_UNSUPPORTED_TYPE_COERSION, std::string("unsupported type coersion for operation between types ") +
+                                                          dtype_name(ct) + " and " + dtype_name(b.type));
+      ct = next;
+    }
+    for (int& r : all) r = cast_to(r, ct);
+    int tail = els >= 0 ? all.back() : -1;
+    bool has_tail = els >= 0;
+    const size_t nw = conds.size();
+    // innermost group first: WHENs [first, first + n) with everything behind them as their ELSE
+    size_t first = nw > 0 ? (nw - 1) / CASE_MAX_WHENS * CASE_MAX_WHENS : 0;
+    while (true) {
+      const size_t n = std::min<size_t>(CASE_MAX_WHENS, nw - first);
+      Node c{}; c.kind = Node::CASE; c.type = ct; c.op = (int)n; c.case_else = has_tail; c.fmt_col = ct == T_FIXED_OPAQUE ? fmt : -1;
+      for (size_t k = 0; k < n; ++k) c.parts.push_back(conds[first + k]);
+      for (size_t k = 0; k < n; ++k) c.parts.push_back(all[first + k]);
+      if (has_tail) c.parts.push_back(tail);
+      c.is_scalar = true; c.len1 = true;
+      for (int q : c.parts) { c.is_scalar = c.is_scalar && t.nodes[q].is_scalar; c.len1 = c.len1 && t.nodes[q].len1; }
+      tail = maybe_fold(push(c));
+      has_tail = true;
+      if (first == 0) return tail;
+      first -= CASE_MAX_WHENS;
+    }
   }
 
   // `a || b`: both Utf8, no implicit cast.  A chain is left-associative: while the left side is itself an unfolded `||` with
@@ -492,6 +613,9 @@ struct Typer {
     // cast_to_common_type, RU/compute_value.rs:433-461
     DType lt = t.nodes[l].type, rt = t.nodes[r].type, ct;
     // (a temporal / decimal value is always a plain column: no literal and no operator produces one)
+    // (.. or, since CASE, a CASE over such columns, whose temporary column no operator reads yet)
+    if ((lt == T_FIXED_OPAQUE && t.nodes[l].kind != Node::COL) || (rt == T_FIXED_OPAQUE && t.nodes[r].kind != Node::COL))
+      fail(CHQ_ERR_NOT_SUPPORTED, "an operator on the temporal / decimal result of CASE, coalesce or nullif is outside this build's scope");
     const bool both_opaque = lt == T_FIXED_OPAQUE && rt == T_FIXED_OPAQUE;
     const bool same_opaque = both_opaque && canonical_format(cols[t.nodes[l].col].format) == canonical_format(cols[t.nodes[r].col].format);
     if (!common_type(lt, rt, &ct) || (both_opaque && !same_opaque))
@@ -541,7 +665,16 @@ struct Typer {
 };
 }  // namespace
 
-static bool has_checked_arith(const TypedExpr& t, int ni) {
+int case_guarded_parts(const TypedExpr& t, int ni, std::vector<char>* guard) {
+  const Node& n = t.at(ni);
+  int count = 0;
+  if (guard) guard->assign(n.parts.size(), 0);
+  for (size_t j = 1; j < n.parts.size(); ++j)   // (parts[0] is the first condition: every row evaluates it)
+    if (has_checked_arith(t, n.parts[j])) { ++count; if (guard) (*guard)[j] = 1; }
+  return count;
+}
+
+bool has_checked_arith(const TypedExpr& t, int ni) {
   const Node& n = t.at(ni);
   if (n.kind == Node::ARITH && is_int(n.type) && !n.len1) return true;
   bool any = false;
@@ -644,6 +777,7 @@ struct Gen {
       case Node::LIKE: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "LIKE runs as its own kernel");
       case Node::ISNULL: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "IS NULL runs as its own kernel");
       case Node::STRFN: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "a string function runs as its own kernel");
+      case Node::CASE: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "CASE runs as its own kernel");
       case Node::CMP:
         if (n.from == T_UTF8) { gen_strcmp(n); return; }
         if (n.from == T_FIXED_OPAQUE) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "Decimal128 comparison runs as its own kernel");
@@ -682,6 +816,7 @@ struct Gen {
     else if (l.kind == Node::CONST && r.kind == Node::COL) { in.src_idx = (uint16_t)ref_of(r.col); in.imm = ((uint64_t)n.op << 56) | str_idx(l); in.flags |= IF_REV; }
     else if (l.kind == Node::COL && r.kind == Node::COL) { in.src_idx = (uint16_t)ref_of(l.col); in.imm = ((uint64_t)n.op << 56) | (uint64_t)ref_of(r.col); in.flags |= IF_STR_RHS_COL; }
     else if (l.kind == Node::STRFN || r.kind == Node::STRFN) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "a string function runs as its own kernel");
+    else if (l.kind == Node::CASE || r.kind == Node::CASE) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "CASE runs as its own kernel");
     else fail(CHQ_ERR_NOT_SUPPORTED, "Utf8 comparison operands must be columns or literals");
     emit(in);
   }

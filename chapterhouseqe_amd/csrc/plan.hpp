@@ -17,6 +17,7 @@
 #include "device_program.h"
 #include "like_device.h"
 #include "strfn_device.h"
+#include "case_device.h"
 
 namespace chq {
 
@@ -32,8 +33,11 @@ constexpr int CHQ_INTERNAL_PROGRAM_LIMIT = 1030;
 struct Expr {
   // LIKE: l = the operand, r = the pattern (a STRING; null when the caller's pattern was not a string literal), flag = NOT
   // LIKE, op = the ESCAPE byte or -1.  ISNULL: l = the operand, flag = IS NOT NULL.  FUNCTION: text = the name as written,
-  // args = the arguments (a scalar string function, strfn_device.h; any other name answers like OTHER "Function(name)").
-  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER, LIKE, ISNULL, FUNCTION } kind;
+  // args = the arguments (a scalar string function, strfn_device.h, or coalesce / nullif; any other name answers like OTHER
+  // "Function(name)").  CASE: l = the operand of a simple CASE or null, args = the n conditions (simple CASE: the values)
+  // followed by the n results, r = the ELSE or null.  IN_LIST: l = the operand, args = the list, flag = NOT IN.  BETWEEN:
+  // l = the operand, args = {low, high}, flag = NOT BETWEEN.
+  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER, LIKE, ISNULL, FUNCTION, CASE, IN_LIST, BETWEEN } kind;
   int op = 0;             // chq_binary_operator
   std::string text;       // number text / identifier / string bytes / debug text
   bool flag = false;      // is_long / boolean value / negated
@@ -75,8 +79,12 @@ struct Node {
   // LIKE (l = the Utf8 operand, `like` = the compiled pattern, op = 1 for NOT LIKE) and ISNULL (l = the operand, op = 1 for
   // IS NOT NULL): like.hip and typed_ops.hip.  STRFN is a scalar string function (op = its StrFn, l = the Utf8 operand; for
   // STRFN_CONCAT `parts` = the 2..STRFN_MAX_PARTS operands of a flattened `a || b || ..` chain and l = r = -1; for
-  // STRFN_SUBSTRING sub_*): strfn.hip writes a temporary Utf8 or Int32 column.)
-  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL, LIKE, ISNULL, STRFN } kind;
+  // STRFN_SUBSTRING sub_*): strfn.hip writes a temporary Utf8 or Int32 column.  CASE (searched CASE, and what types to it:
+  // simple CASE, coalesce, nullif) has op = n WHENs, 1..CASE_MAX_WHENS, `parts` = the n Boolean conditions, the n results and
+  // -- case_else -- the ELSE, every result of the node's type, l = r = -1: case.hip writes a temporary column of that type.
+  // A result may be a CONST whose cval is null, of any type (nullif).  fmt_col: the batch column whose Arrow format a
+  // T_FIXED_OPAQUE result has (a COL's is its own).)
+  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL, LIKE, ISNULL, STRFN, CASE } kind;
   DType type;
   bool is_scalar;   // ArrayDatum.is_scalar
   bool len1;        // array length is 1 regardless of the batch (built from literals only)
@@ -87,7 +95,9 @@ struct Node {
   int ref_order = 0;
   DType from = T_BOOL;  // CAST / TOBOOL source type
   std::shared_ptr<const LikePattern> like;   // LIKE
-  std::vector<int> parts;                    // STRFN_CONCAT
+  std::vector<int> parts;                    // STRFN_CONCAT, CASE
+  bool case_else = false;                    // CASE
+  int fmt_col = -1;                          // CASE of T_FIXED_OPAQUE
   int32_t sub_p = 0, sub_cnt = 0;            // STRFN_SUBSTRING: FROM sub_p [FOR sub_cnt]
   bool sub_has_cnt = false;
   // every operand: l, r and the parts
@@ -114,6 +124,12 @@ TypedExpr type_expr(const Expr& e, const std::vector<PlanColumn>& cols, int64_t 
 // Evaluate a len-1 (literal-only) subtree on the host with the device kernels' semantics.
 // Throws ChqError for arithmetic errors.  `valid` is always true (literals are never null).
 Scalar fold_constant(const TypedExpr& t, int node);
+
+// true: the sub-tree at `node` holds checked integer arithmetic on columns, i.e. it can fail on data
+bool has_checked_arith(const TypedExpr& t, int node);
+// CASE node `node`: guard[j] = operand parts[j] is evaluated under a guard (the lazy-error rule): it
+// can fail on data and is not the first condition, which every row evaluates.  Returns how many are.
+int case_guarded_parts(const TypedExpr& t, int node, std::vector<char>* guard);
 
 // Lowered program (host form; engine patches column pointers in)
 struct Lowered {

@@ -100,7 +100,9 @@ std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::ve
     Column& o = results[k];
     o.type = root.type; o.format = format_of(root.type); o.width = dtype_width(root.type); o.length = nrows;
     // (a Utf8 result is a string function's: fitting below turns it into a temporary column, which IS the result)
-    if ((root.type == T_UTF8 && root.kind != Node::STRFN) || root.type == T_FIXED_OPAQUE)
+    // (.. or a CASE's, of any type)
+    if (root.kind == Node::CASE && root.type == T_FIXED_OPAQUE) { o.format = pcols[(size_t)root.fmt_col].format; o.width = pcols[(size_t)root.fmt_col].width; }
+    if (root.kind != Node::CASE && ((root.type == T_UTF8 && root.kind != Node::STRFN) || root.type == T_FIXED_OPAQUE))
       throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("expression result of type ") + dtype_name(root.type) + " is outside this build's scope"};
   }
   if (nrows == 0) {
@@ -590,6 +592,15 @@ std::string describe_plan(const ArrowSchema* schema, const chq_table_aliases* al
       out += "\n";
     };
     walk(te.root);
+    // the CASEs of the tree, operands first: WHENs, ELSE, result type, operands evaluated under a guard
+    std::function<void(int)> cases = [&](int ni) {
+      const Node& n = te.at(ni);
+      n.each_child(cases);
+      if (n.kind != Node::CASE) return;
+      out += "case whens=" + std::to_string(n.op) + " else=" + (n.case_else ? "1" : "0") + " type=" + dtype_name(n.type) +
+             " guarded=" + std::to_string(case_guarded_parts(te, ni, nullptr)) + "\n";
+    };
+    cases(te.root);
     return out;
   }
   out += "program wide=" + std::to_string((int)lw.wide) + " num_temps=" + std::to_string(lw.num_temps) + " refs=";

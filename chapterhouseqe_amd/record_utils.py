@@ -28,7 +28,7 @@ _OPS = {A.BinaryOperator.And: 0, A.BinaryOperator.Or: 1, A.BinaryOperator.Plus: 
 _OP_OTHER = 13
 # the scalar string functions the library evaluates (include/chq.h: chq_expr_function); every other call stays unsupported
 _SCALAR_FUNCTIONS = {"upper", "lower", "length", "char_length", "character_length", "octet_length", "substring", "substr",
-                     "trim", "ltrim", "rtrim"}
+                     "trim", "ltrim", "rtrim", "coalesce", "nullif"}
 
 
 class ChqError(Exception):
@@ -343,6 +343,34 @@ def _expr_to_c(e: A.Expr):
             raise
         arr = (C.c_void_p * max(1, len(built)))(*built)
         return lib.chq_expr_function(e.name.encode(), arr, len(built))
+    if isinstance(e, (A.Case, A.InList, A.Between)):
+        # every child first; the constructors take ownership of all of them, also when they fail
+        if isinstance(e, A.Case):
+            if len(e.conditions) != len(e.results) or not e.conditions:
+                raise ValueError("Case needs as many results as conditions, at least one")
+            kids = [e.operand, *e.conditions, *e.results, e.else_result]
+        elif isinstance(e, A.InList):
+            kids = [e.expr, *e.list]
+        else:
+            kids = [e.expr, e.low, e.high]
+        built = []
+        try:
+            for a in kids:
+                built.append(None if a is None else _expr_to_c(a))
+        except BaseException:
+            for h in built:
+                if h:
+                    lib.chq_expr_free(h)
+            raise
+        if isinstance(e, A.Case):
+            n = len(e.conditions)
+            conds = (C.c_void_p * n)(*built[1:1 + n])
+            ress = (C.c_void_p * n)(*built[1 + n:1 + 2 * n])
+            return lib.chq_expr_case(built[0], conds, ress, n, built[-1])
+        if isinstance(e, A.InList):
+            arr = (C.c_void_p * max(1, len(e.list)))(*built[1:])
+            return lib.chq_expr_in_list(built[0], arr, len(e.list), int(e.negated))
+        return lib.chq_expr_between(built[0], int(e.negated), built[1], built[2])
     if isinstance(e, A.UnsupportedExpr):
         return lib.chq_expr_unsupported(e.debug.encode())
     raise TypeError(f"not an Expr: {e!r}")

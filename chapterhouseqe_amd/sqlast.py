@@ -122,8 +122,35 @@ class IsNull(Expr):
 
 
 @dataclass(frozen=True)
+class Case(Expr):
+    """Expr::Case { operand, conditions, results, else_result }: `CASE [operand] WHEN c THEN r ... [ELSE e] END`.  With an
+    operand (simple CASE) the conditions are the values it is compared with."""
+    operand: Optional[Expr]
+    conditions: Tuple[Expr, ...]
+    results: Tuple[Expr, ...]
+    else_result: Optional[Expr] = None
+
+
+@dataclass(frozen=True)
+class InList(Expr):
+    """Expr::InList { expr, list, negated }: `expr [NOT] IN (l1, ..)`"""
+    expr: Expr
+    list: Tuple[Expr, ...]
+    negated: bool = False
+
+
+@dataclass(frozen=True)
+class Between(Expr):
+    """Expr::Between { expr, negated, low, high }: `expr [NOT] BETWEEN low AND high`"""
+    expr: Expr
+    negated: bool
+    low: Expr
+    high: Expr
+
+
+@dataclass(frozen=True)
 class UnsupportedExpr(Expr):
-    """UnaryOp, Function, Case, ... -- compute_value.rs:338-342 rejects them."""
+    """UnaryOp, Function, Subquery, ... -- compute_value.rs:338-342 rejects them."""
     debug: str
 
 

@@ -9,6 +9,12 @@ sample queries (reference: sample_queries/simple.sql) to be written as SQL text.
 
     <expr> [not] like <expr> [escape '<one character>']      -> Like   (the evaluator wants a string literal as pattern)
     <expr> is [not] null                                     -> IsNull
+    <expr> [not] in ( <expr> {, <expr>} )                    -> InList   (comparison precedence)
+    <expr> [not] between <low> and <high>                    -> Between  (comparison precedence; <low> and <high> are parsed
+                                                                at that precedence, so the `and` belongs to BETWEEN)
+    case [<expr>] when <expr> then <expr> {when ..} [else <expr>] end   -> Case
+  `case` opens a CASE where `when` or something that can start an expression follows; `when`, `then`, `else` and `end` are
+  never implicit aliases (quoted identifiers still are).
   `like`, `not`, `is` and `escape` are operators only where these forms continue (`like` / `not like` in front of something
   that can start an expression, `is` in front of `null` / `not null`, `escape` behind a pattern and in front of a string);
   anywhere else they stay ordinary words, e.g. aliases.  Prefix `not <expr>` stays an UnsupportedExpr.
@@ -58,6 +64,7 @@ _BINOPS = {
 _WORD_BINOPS = {"OR": (A.BinaryOperator.Or, _PREC_OR), "AND": (A.BinaryOperator.And, _PREC_AND),
                 "XOR": (A.BinaryOperator.Xor, _PREC_XOR)}
 _STOP_WORDS = {"FROM", "WHERE", "AS", "GROUP", "ORDER", "LIMIT", "JOIN", "INNER", "ON"}
+_CASE_WORDS = {"WHEN", "THEN", "ELSE", "END"}
 _OTHER_JOINS = {"LEFT", "RIGHT", "FULL", "OUTER", "CROSS"}
 
 
@@ -152,7 +159,7 @@ class _Parser:
     def _starts_expr(self, j) -> bool:
         k, v = self.toks[self.i + j] if self.i + j < len(self.toks) else ("eof", "")
         if k == "word":
-            return v.upper() not in _STOP_WORDS
+            return v.upper() not in _STOP_WORDS and v.upper() not in _CASE_WORDS
         return k in ("number", "numberL", "string", "qident") or (k == "op" and v in ("(", "-", "+"))
 
     def _infix_words(self):
@@ -166,6 +173,11 @@ class _Parser:
             return ("is", False, 2, _PREC_IS)
         if w == "IS" and self._word_at(1) == "NOT" and self._word_at(2) == "NULL":
             return ("is", True, 3, _PREC_IS)
+        neg = 1 if w == "NOT" else 0
+        if self._word_at(neg) == "IN" and self.i + neg + 1 < len(self.toks) and self.toks[self.i + neg + 1] == ("op", "("):
+            return ("in", bool(neg), neg + 1, _PREC_EQ)
+        if self._word_at(neg) == "BETWEEN" and self._starts_expr(neg + 1):
+            return ("between", bool(neg), neg + 1, _PREC_EQ)
         return None
 
     def next_precedence(self):
@@ -191,6 +203,21 @@ class _Parser:
                 self.i += ntok
                 if kind == "is":
                     expr = A.IsNull(expr, negated)
+                    continue
+                if kind == "in":   # Keyword::IN: a parenthesised expression list (a subquery is not part of this grammar)
+                    self.expect_op("(")
+                    items = [self.parse_expr(0)]
+                    while self.accept_op(","):
+                        items.append(self.parse_expr(0))
+                    self.expect_op(")")
+                    expr = A.InList(expr, tuple(items), negated)
+                    continue
+                if kind == "between":   # Keyword::BETWEEN: parse_between
+                    low = self.parse_expr(_PREC_EQ)
+                    if not self.accept_word("AND"):
+                        raise SqlParseError(f"expected AND after the low bound of BETWEEN, found {self.peek()[1]!r}")
+                    high = self.parse_expr(_PREC_EQ)
+                    expr = A.Between(expr, negated, low, high)
                     continue
                 pattern = self.parse_expr(_PREC_LIKE)
                 escape = None
@@ -233,12 +260,31 @@ class _Parser:
             if up == "NOT":
                 inner = self.parse_expr(_PREC_NOT)
                 return A.UnsupportedExpr(f"UnaryOp {{ op: Not, expr: {inner!r} }}")
+            # (`case + 1` and `case - 1` stay arithmetic on a column of that name)
+            if up == "CASE" and (self._word_at(0) == "WHEN" or (self._starts_expr(0) and self.peek() not in (("op", "-"), ("op", "+")))):
+                return self._case()
             if self.peek() == ("op", "("):
                 return self._function_call(v)
             return self._identifier_tail(A.Ident(v))
         if k == "qident":
             return self._identifier_tail(A.Ident(v, '"'))
         raise SqlParseError(f"unexpected token {v!r}")
+
+    def _case(self) -> A.Expr:
+        """sqlparser Parser::parse_case_expr, behind the CASE keyword"""
+        operand = None if self._word_at(0) == "WHEN" else self.parse_expr(0)
+        conditions, results = [], []
+        while self.accept_word("WHEN"):
+            conditions.append(self.parse_expr(0))
+            if not self.accept_word("THEN"):
+                raise SqlParseError(f"expected THEN after the condition of WHEN, found {self.peek()[1]!r}")
+            results.append(self.parse_expr(0))
+        if not conditions:
+            raise SqlParseError(f"expected WHEN after CASE, found {self.peek()[1]!r}")
+        else_result = self.parse_expr(0) if self.accept_word("ELSE") else None
+        if not self.accept_word("END"):
+            raise SqlParseError(f"expected END to close CASE, found {self.peek()[1]!r}")
+        return A.Case(operand, tuple(conditions), tuple(results), else_result)
 
     def _function_call(self, name: str) -> A.Expr:
         """`name ( [* | expr {, expr}] )`; anything else between the parentheses is skipped (args None).  compute_value
@@ -363,7 +409,7 @@ class _Parser:
                 raise SqlParseError("expected alias after AS")
             return A.ExprWithAlias(expr, A.Ident(v, '"' if k == "qident" else None))
         k, v = self.peek()
-        if k == "word" and v.upper() not in _STOP_WORDS:
+        if k == "word" and v.upper() not in _STOP_WORDS and v.upper() not in _CASE_WORDS:
             self.next()
             return A.ExprWithAlias(expr, A.Ident(v))
         return A.UnnamedExpr(expr)

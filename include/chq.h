@@ -107,7 +107,9 @@ void* chq_ctx_stream(const chq_ctx* ctx);
  * and Utf8 operands (a spelling arrow-cast does not know is NULL).  CHQ_ERR_NOT_SUPPORTED remains for ARITHMETIC on
  * decimals, durations and date / timestamp differences, and for comparisons of FixedSizeBinary / interval columns.
  * Beyond the reference: [NOT] LIKE on Utf8 (chq_expr_like), IS [NOT] NULL on every type (chq_expr_is_null) and the scalar
- * string functions (CHQ_BINOP_STRING_CONCAT, chq_expr_function), whose results are Utf8 or Int32 columns. */
+ * string functions (CHQ_BINOP_STRING_CONCAT, chq_expr_function), whose results are Utf8 or Int32 columns; CASE, coalesce and
+ * nullif (chq_expr_case, chq_expr_function), whose result has any of these types; BETWEEN and IN lists (chq_expr_between,
+ * chq_expr_in_list). */
 chq_status chq_ctx_set_option(chq_ctx* ctx, const char* key, int64_t value);
 /* Counters of the last filter call: rows in, rows out, tiles, kernel launches. */
 typedef struct chq_call_stats {
@@ -179,6 +181,40 @@ chq_expr* chq_expr_is_null(chq_expr* operand, int negated);
  * concat() as a function, initcap, reverse, lpad / rpad, ILIKE, implicit casts of numbers to strings, non-literal p / n,
  * LargeUtf8, and these functions as ORDER BY / GROUP BY / JOIN / PARTITION keys. */
 chq_expr* chq_expr_function(const char* name, chq_expr* const* args, int n_args);
+/* Expr::Case { operand, conditions, results, else_result }; takes ownership of every child, also on failure.  `operand` and
+ * `else_result` may be NULL; `conditions` and `results` hold n_when >= 1 handles each.  These semantics are this library's
+ * own (the reference rejects the form).
+ *   Searched CASE (operand NULL): row i takes results[k] for the first k whose conditions[k] is TRUE AND VALID on that row,
+ *   else else_result, else NULL.  Every condition must type to Boolean -- no implicit cast; CHQ_ERR_ARROW_INVALID_ARGUMENT
+ *   names the WHEN's position and the type found.  The result type is the coercion table of the binary operators folded left
+ *   to right over results[0..n), else_result: Utf8 goes only with Utf8, Boolean only with Boolean, temporal and Decimal128
+ *   only with columns of the same type (the output keeps it); a pair without an entry is
+ *   CHQ_ERR_UNSUPPORTED_TYPE_COERSION.  The result is null exactly where the chosen branch is, or where none is chosen and
+ *   there is no ELSE; an output column is nullable iff it holds a null.  A literal branch next to columns is broadcast; a CASE
+ *   over literals only is folded on the host with the rule the device runs.
+ *   Simple CASE (operand given): conditions[k] is the VALUE, and WHEN k is `operand = value` by the ordinary rules and
+ *   statuses of `=`; the operand is typed once.
+ *   Lazy errors: a data-dependent error (integer overflow, division by zero) in results[k] counts only on rows that take
+ *   it, in conditions[k] only on rows where no earlier condition was true (a NULL earlier condition is not true), in
+ *   else_result only on rows where no condition was true; the first error in the order conditions, results, else_result is
+ *   reported.  A literal-only sub-expression is folded at typing: `1 / 0` fails wherever it stands.
+ *   More than 8 WHENs nest (WHEN 9 onward becomes a CASE in the ELSE slot).  A Utf8 result of more than 2^31 - 1 bytes:
+ *   CHQ_ERR_ARROW_INVALID_ARGUMENT.
+ * chq_expr_function also takes, names case-insensitive, a wrong argument count CHQ_ERR_ARROW_INVALID_ARGUMENT:
+ *   coalesce(a1, .., an), n >= 1   = CASE WHEN a1 IS NOT NULL THEN a1 .. ELSE an END
+ *   nullif(a, b)                   = CASE WHEN a = b THEN <null> ELSE a END, of a's own type
+ * Out of scope: prefix NOT, the NULL literal, unary minus, implicit casts to Boolean in WHEN, an operator on a temporal /
+ * decimal result (CHQ_ERR_NOT_SUPPORTED), LargeUtf8, and these forms as ORDER BY / GROUP BY / JOIN / PARTITION keys or
+ * aggregate arguments (project first). */
+chq_expr* chq_expr_case(chq_expr* operand, chq_expr* const* conditions, chq_expr* const* results, int n_when, chq_expr* else_result);
+/* Expr::InList { expr, list, negated }; takes ownership of every child, also on failure.  Typing-time sugar: `expr = l1 OR
+ * expr = l2 ..`, negated `expr <> l1 AND expr <> l2 ..`, with the values, nulls and statuses of that spelled-out chain; `expr`
+ * is typed once.  Every item must be a literal (Nested allowed) and n must lie in 1..32, else CHQ_ERR_NOT_SUPPORTED. */
+chq_expr* chq_expr_in_list(chq_expr* expr, chq_expr* const* list, int n, int negated);
+/* Expr::Between { expr, negated, low, high }; takes ownership of every child, also on failure.  Typing-time sugar:
+ * `expr >= low AND expr <= high`, negated `expr < low OR expr > high`, with the values, nulls and statuses of that
+ * spelled-out form; `expr` is typed once. */
+chq_expr* chq_expr_between(chq_expr* expr, int negated, chq_expr* low, chq_expr* high);
 chq_expr* chq_expr_unsupported(const char* debug);                            /* any other Expr variant */
 void chq_expr_free(chq_expr* e);
 

@@ -168,6 +168,9 @@ extern "C" {
     pub fn chq_expr_like(operand: *mut chq_expr, pattern: *const c_char, pattern_len: i64, negated: c_int, escape: c_int) -> *mut chq_expr;
     pub fn chq_expr_is_null(operand: *mut chq_expr, negated: c_int) -> *mut chq_expr;
     pub fn chq_expr_function(name: *const c_char, args: *const *mut chq_expr, n_args: c_int) -> *mut chq_expr;
+    pub fn chq_expr_case(operand: *mut chq_expr, conditions: *const *mut chq_expr, results: *const *mut chq_expr, n_when: c_int, else_result: *mut chq_expr) -> *mut chq_expr;
+    pub fn chq_expr_in_list(expr: *mut chq_expr, list: *const *mut chq_expr, n: c_int, negated: c_int) -> *mut chq_expr;
+    pub fn chq_expr_between(expr: *mut chq_expr, negated: c_int, low: *mut chq_expr, high: *mut chq_expr) -> *mut chq_expr;
     pub fn chq_expr_unsupported(debug: *const c_char) -> *mut chq_expr;
     pub fn chq_expr_free(e: *mut chq_expr);
 

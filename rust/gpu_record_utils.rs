@@ -98,6 +98,20 @@ fn lower_expr(e: &Expr) -> *mut chq_expr {
             }
             Expr::IsNull(inner) => chq_expr_is_null(lower_expr(inner), 0),
             Expr::IsNotNull(inner) => chq_expr_is_null(lower_expr(inner), 1),
+            // CASE, IN (list) and BETWEEN: every child goes over as a handle the library takes ownership of
+            Expr::Case { operand, conditions, results, else_result } => {
+                let cs: Vec<*mut chq_expr> = conditions.iter().map(lower_expr).collect();
+                let rs: Vec<*mut chq_expr> = results.iter().map(lower_expr).collect();
+                let op = operand.as_ref().map_or(std::ptr::null_mut(), |o| lower_expr(o));
+                let el = else_result.as_ref().map_or(std::ptr::null_mut(), |o| lower_expr(o));
+                chq_expr_case(op, cs.as_ptr(), rs.as_ptr(), cs.len() as i32, el)
+            }
+            Expr::InList { expr, list, negated } => {
+                let ls: Vec<*mut chq_expr> = list.iter().map(lower_expr).collect();
+                chq_expr_in_list(lower_expr(expr), ls.as_ptr(), ls.len() as i32, *negated as i32)
+            }
+            Expr::Between { expr, negated, low, high } =>
+                chq_expr_between(lower_expr(expr), *negated as i32, lower_expr(low), lower_expr(high)),
             other => chq_expr_unsupported(c(&format!("{:?}", other)).as_ptr()),
         }
     }
