@@ -4,12 +4,15 @@
 // consecutive sorted positions, and the groups come out in key order.  The kernels of aggregate.hip mark where a run begins,
 // number the runs and reduce every aggregate over them, reading the values through the permutation -- no column is gathered
 // but the key columns, and those only at one representative row per group.  Two read-backs besides the sort's: the number
-// of groups (it sizes the outputs), and one block of null counts and overflow flags at the end.  DESIGN.md section 3.7.
+// of groups (it sizes the outputs), and one block of null counts and overflow flags at the end.  COUNT(DISTINCT c) sorts a
+// second time, by (keys, c), finds the runs of that order and counts them per group; a call without it does none of that.
+// DESIGN.md section 3.7.
 //
 // The run finder (find_runs) and the typing of the aggregates (plan_aggregate) are defined here for JOIN (join.cpp) and the
 // window functions (window.cpp) as well: aggregate.hpp declares them.
 #include <algorithm>
 #include <cstring>
+#include <map>
 #include <string>
 
 #include "aggregate.hpp"
@@ -25,12 +28,15 @@ const char* kind_name(int kind) {
     case CHQ_AGG_SUM: return "SUM";
     case CHQ_AGG_MIN: return "MIN";
     case CHQ_AGG_MAX: return "MAX";
+    case CHQ_AGG_AVG: return "AVG";
+    case CHQ_AGG_COUNT_DISTINCT: return "COUNT_DISTINCT";
     default: return "aggregate";
   }
 }
 
-static_assert(CHQ_AGG_SUM - CHQ_AGG_COUNT == AGG_FN_SUM && CHQ_AGG_MIN - CHQ_AGG_COUNT == AGG_FN_MIN && CHQ_AGG_MAX - CHQ_AGG_COUNT == AGG_FN_MAX,
-              "chq_agg_kind numbers COUNT, SUM, MIN, MAX like AggFn");
+static_assert(CHQ_AGG_SUM - CHQ_AGG_COUNT == AGG_FN_SUM && CHQ_AGG_MIN - CHQ_AGG_COUNT == AGG_FN_MIN && CHQ_AGG_MAX - CHQ_AGG_COUNT == AGG_FN_MAX &&
+              CHQ_AGG_AVG - CHQ_AGG_COUNT == AGG_FN_AVG,
+              "chq_agg_kind numbers COUNT, SUM, MIN, MAX, AVG like AggFn");
 
 AggKey key_of(const Column& c) {
   AggKey k{};
@@ -68,6 +74,12 @@ AggPlan plan_aggregate(AggFn fn, const char* name, const Column& c) {
       if (!(is_signed || is_unsigned || is_float || orders_as_signed(c))) throw unsupported();
       pl.op = fn == AGG_FN_MIN ? AO_MIN : AO_MAX;
       pl.format = c.format; pl.type = c.type; pl.width = c.width;
+      break;
+    case AGG_FN_AVG:   // the types SUM takes; Float64 whatever the input
+      if (is_signed || is_unsigned) pl.op = AO_AVG_INT;
+      else if (c.type == T_F32 || c.type == T_F64) pl.op = AO_AVG_FLOAT;
+      else throw unsupported();
+      pl.format = "g"; pl.type = T_F64;
       break;
   }
   return pl;
@@ -159,11 +171,18 @@ Batch aggregate_records(Context& ctx, std::vector<Batch>& in, const chq_table_al
                                                        std::to_string(keys.size())};
       plans[i].col = key_cols[(size_t)it.key_index];
     } else if (it.kind != CHQ_AGG_COUNT_STAR) {
-      if (it.kind < CHQ_AGG_COUNT || it.kind > CHQ_AGG_MAX)
+      if (it.kind < CHQ_AGG_COUNT || it.kind > CHQ_AGG_COUNT_DISTINCT)
         throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "unknown aggregate kind " + std::to_string(it.kind)};
       if (!it.column) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null column of ") + kind_name(it.kind)};
       const int col = resolve_key(*it.column, pcols, rows, std::string("the argument of ") + kind_name(it.kind));
-      plans[i] = plan_aggregate((AggFn)(it.kind - CHQ_AGG_COUNT), kind_name(it.kind), in[0].cols[(size_t)col]);
+      const Column& c = in[0].cols[(size_t)col];
+      if (it.kind == CHQ_AGG_COUNT_DISTINCT) {   // the argument is sorted behind the keys: the types of a key (Int64 out, the default plan)
+        if (!sortable(c))
+          throw ChqError{CHQ_ERR_NOT_SUPPORTED, "COUNT_DISTINCT over column '" + c.name + "' of Arrow type '" + c.format +
+                                                "' is not supported in this build: the type has no order"};
+      } else {
+        plans[i] = plan_aggregate((AggFn)(it.kind - CHQ_AGG_COUNT), kind_name(it.kind), c);
+      }
       plans[i].col = col;
     }
   }
@@ -196,6 +215,7 @@ Batch aggregate_records(Context& ctx, std::vector<Batch>& in, const chq_table_al
   BufferPtr words = make_device_buffer(ni * 16 + 16, ctx.device);
   check_hip(hipMemsetAsync(words->ptr, 0, ni * 16, ctx.stream), "hipMemsetAsync");
   BufferPtr part_first, part_last;
+  std::map<int, Runs> fine_runs;   // COUNT_DISTINCT: the runs of (keys, argument column), by argument column
   Batch out;
   out.nrows = G; out.on_device = true; out.device_id = ctx.device;
   for (size_t i = 0; i < ni; ++i) {
@@ -211,6 +231,37 @@ Batch aggregate_records(Context& ctx, std::vector<Batch>& in, const chq_table_al
     const Column* c = pl.col >= 0 ? &rec.cols[(size_t)pl.col] : nullptr;
     const bool nulls = c && c->validity && c->null_count != 0;
     BufferPtr values = make_device_buffer((size_t)(G * pl.width) + 16, ctx.device);
+    if (it.kind == CHQ_AGG_COUNT_DISTINCT) {
+      if (n == 0) {   // (G is 0 or 1: a group without rows has no value)
+        check_hip(hipMemsetAsync(values->ptr, 0, (size_t)(G * pl.width) + 16, ctx.stream), "hipMemsetAsync");
+      } else {
+        // The rows sorted by (keys, c): the sort is stable and the keys come first, so group g keeps its sorted positions
+        // [starts[g], starts[g + 1]) and the runs of (keys, c) -- the fine runs -- cut it into its distinct values, nulls
+        // last.  One more sort and one more run finding per argument column, shared by the items that name it.
+        auto found = fine_runs.find(pl.col);
+        if (found == fine_runs.end()) {
+          std::vector<int> cols2 = key_cols;
+          std::vector<SortKeyArg> keys2 = sort_keys;
+          cols2.push_back(pl.col);
+          keys2.push_back(SortKeyArg{it.column, false, false});
+          const BufferPtr perm2 = sort_permutation(ctx, rec, cols2, keys2, t);
+          Runs fine = find_runs(ctx, rec, perm2 ? (const uint32_t*)perm2->ptr : nullptr, cols2, t);
+          fine.gids = nullptr;   // 4n bytes that the distinct kernel never reads: only starts and rep stay until the call ends
+          found = fine_runs.emplace(pl.col, std::move(fine)).first;
+        }
+        const Runs& fine = found->second;
+        AggDistinctParams dp{};
+        dp.starts = (const uint32_t*)starts->ptr; dp.G = G;
+        dp.starts2 = (const uint32_t*)fine.starts->ptr; dp.rep2 = (const uint32_t*)fine.rep->ptr; dp.G2 = fine.G;
+        dp.validity = nulls ? c->validity : nullptr; dp.bit_offset = c->offset;
+        dp.out = (int64_t*)values->ptr;
+        check_hip(launch_agg_distinct(dp, ctx.stream), "launch agg_distinct_kernel");
+        ++ctx.stats.launches;
+        t.read += G * 8 + fine.G * 4 + (nulls ? G * 5 : 0); t.written += G * 8;
+      }
+      out.cols.push_back(fixed_column(it.name, pl, false, G, values));
+      continue;
+    }
     if (it.kind == CHQ_AGG_COUNT_STAR || (it.kind == CHQ_AGG_COUNT && !nulls)) {   // the group's rows
       AggCountStarParams cp{(const uint32_t*)starts->ptr, G, (int64_t*)values->ptr};
       if (G > 0) { check_hip(launch_agg_count_star(cp, ctx.stream), "launch agg_count_star_kernel"); ++ctx.stats.launches; }

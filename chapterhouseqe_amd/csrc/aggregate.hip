@@ -9,6 +9,8 @@
 //                    into a neighbour tile to part_first / part_last
 //   fold             one workgroup per tile boundary; the one that sits behind the FIRST tile of a group spanning several
 //                    tiles combines that group's partials in tile order, by a tree whose shape depends on the tile count only
+//   distinct         COUNT(DISTINCT c): the rows are sorted a second time, by (keys, c), and their runs found again (the FINE
+//                    runs); a thread per group counts the fine runs between the group's two ends by binary search
 // Every hand-off happens at a launch boundary: no workgroup waits for another, nothing spins, nothing depends on dispatch
 // order.  No float atomics: a float sum is combined in an order fixed by the sorted positions, bit-identical from run to run.
 #include <hip/hip_runtime.h>
@@ -219,6 +221,26 @@ __global__ __launch_bounds__(kAggBlock) void agg_count_star_kernel(const AggCoun
   if (g < p.G) p.out[g] = (int64_t)p.starts[g + 1] - (int64_t)p.starts[g];
 }
 
+// COUNT(DISTINCT c): one group per thread.  Both ends of a group are starts of fine runs, so the two binary searches over
+// starts2 find them exactly; the group's last fine run holds the nulls of c, if it has any (nulls sort last).
+__device__ __forceinline__ int64_t fine_run_at(const AggDistinctParams& p, uint32_t pos) {
+  int64_t lo = 0, hi = p.G2;   // the first index in [0, G2] whose start is >= pos (starts2[G2] = n >= pos)
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (p.starts2[mid] < pos) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(kAggBlock) void agg_distinct_kernel(const AggDistinctParams p) {
+  const int64_t g = (int64_t)blockIdx.x * kAggBlock + threadIdx.x;
+  if (g >= p.G) return;
+  const int64_t lo = fine_run_at(p, p.starts[g]), hi = fine_run_at(p, p.starts[g + 1]);
+  int64_t runs = hi - lo;
+  if (runs > 0 && p.validity && !bit_at(p.validity, p.bit_offset + p.rep2[hi - 1])) --runs;
+  p.out[g] = runs;
+}
+
 // one validity word of 32 groups per thread
 __global__ __launch_bounds__(kAggBlock) void agg_validity_kernel(const AggValidityParams p) {
   const int64_t wi = (int64_t)blockIdx.x * kAggBlock + threadIdx.x;
@@ -264,8 +286,14 @@ hipError_t launch_agg_reduce(const AggReduceParams& p, hipStream_t stream) {
     case AO_SUM_FLOAT: launch_reduce<AO_SUM_FLOAT>(p, stream); break;
     case AO_MIN: launch_reduce<AO_MIN>(p, stream); break;
     case AO_MAX: launch_reduce<AO_MAX>(p, stream); break;
+    case AO_AVG_INT: launch_reduce<AO_AVG_INT>(p, stream); break;
+    case AO_AVG_FLOAT: launch_reduce<AO_AVG_FLOAT>(p, stream); break;
     default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+hipError_t launch_agg_distinct(const AggDistinctParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(agg_distinct_kernel, dim3(blocks_for(p.G, kAggBlock)), dim3(kAggBlock), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_agg_count_star(const AggCountStarParams& p, hipStream_t stream) {

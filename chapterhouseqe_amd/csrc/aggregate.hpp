@@ -1,4 +1,4 @@
-// aggregate.hpp -- GROUP BY: grouped COUNT / SUM / MIN / MAX of a record batch, or of a group of them joined into one
+// aggregate.hpp -- GROUP BY: grouped COUNT / SUM / MIN / MAX / AVG / COUNT(DISTINCT) of a record batch, or of a group of them joined into one
 // (aggregate.cpp), on top of the stable sort (sort.hpp).
 #pragma once
 #include <cstdint>
@@ -16,6 +16,7 @@ hipError_t launch_agg_head_scan(const AggGroupsParams& p, hipStream_t stream);
 hipError_t launch_agg_head_write(const AggGroupsParams& p, hipStream_t stream);
 hipError_t launch_agg_reduce(const AggReduceParams& p, hipStream_t stream);   // reduce, then (two tiles or more) fold
 hipError_t launch_agg_count_star(const AggCountStarParams& p, hipStream_t stream);
+hipError_t launch_agg_distinct(const AggDistinctParams& p, hipStream_t stream);
 hipError_t launch_agg_validity(const AggValidityParams& p, hipStream_t stream);
 
 // The pieces of GROUP BY that JOIN (join.cpp) and the window functions (window.cpp) stand on.
@@ -28,8 +29,9 @@ struct Runs {
 // column: one heads launch that marks position 0, so all rows are one run.
 Runs find_runs(Context& ctx, const Batch& rec, const uint32_t* perm, const std::vector<int>& cols, Traffic& t);
 
-// the four aggregates with an argument, whatever the caller's enum numbers them (chq_agg_kind, chq_window_kind)
-enum AggFn { AGG_FN_COUNT, AGG_FN_SUM, AGG_FN_MIN, AGG_FN_MAX };
+// the aggregates with an argument that reduce through the one accumulator, whatever the caller's enum numbers them
+// (chq_agg_kind, chq_window_kind; AVG is GROUP BY's alone: the window functions do not take it)
+enum AggFn { AGG_FN_COUNT, AGG_FN_SUM, AGG_FN_MIN, AGG_FN_MAX, AGG_FN_AVG };
 // what one output item does, decided against the schema before any data moves
 struct AggPlan {
   int col = -1;                 // argument column (key column for CHQ_AGG_KEY)

@@ -6,17 +6,21 @@
 #include <hip/hip_runtime.h>
 
 #include "aggregate_device.h"
+#include "avg_rn.h"        // avg_rn128
 #include "scan_device.h"   // lane_id, bit_at, load_uint, load_int
 
 namespace chq {
 
 __device__ __forceinline__ double as_double(uint64_t u) { return __longlong_as_double((long long)u); }
 __device__ __forceinline__ uint64_t as_bits(double d) { return (uint64_t)__double_as_longlong(d); }
+// the averages accumulate as the sums of their kind
+constexpr bool acc_int_total(int op) { return op == AO_SUM_INT || op == AO_AVG_INT; }
+constexpr bool acc_float_total(int op) { return op == AO_SUM_FLOAT || op == AO_AVG_FLOAT; }
 
 template <int OP>
 __device__ __forceinline__ AggAcc acc_identity() {
   AggAcc x{0, 0, 0};
-  if (OP == AO_SUM_FLOAT) x.a = 1ull << 63;   // -0.0: v + -0.0 == v for every v, -0.0 and +0.0 included
+  if (acc_float_total(OP)) x.a = 1ull << 63;   // -0.0: v + -0.0 == v for every v, -0.0 and +0.0 included
   if (OP == AO_MIN) x.a = ~0ull;
   return x;
 }
@@ -27,10 +31,10 @@ __device__ __forceinline__ AggAcc acc_combine(const AggAcc& x, const AggAcc& y) 
   AggAcc r;
   r.cnt = x.cnt + y.cnt;
   r.b = 0;
-  if (OP == AO_SUM_INT) {
+  if (acc_int_total(OP)) {
     r.a = x.a + y.a;
     r.b = x.b + y.b + (r.a < x.a ? 1 : 0);
-  } else if (OP == AO_SUM_FLOAT) {
+  } else if (acc_float_total(OP)) {
     r.a = as_bits(as_double(x.a) + as_double(y.a));
   } else if (OP == AO_MIN) {
     r.a = x.a < y.a ? x.a : y.a;
@@ -47,7 +51,7 @@ __device__ __forceinline__ AggAcc acc_load(const P& p, int64_t pos) {
   const uint32_t r = p.perm ? p.perm[pos] : (uint32_t)pos;
   if (p.validity && !bit_at(p.validity, p.bit_offset + r)) return acc_identity<OP>();
   AggAcc x{0, 0, 1};
-  if (OP == AO_SUM_INT) {
+  if (acc_int_total(OP)) {
     if (p.value_kind == AV_SIGNED) {
       const int64_t v = load_int(p.values, r, p.width);
       x.a = (uint64_t)v;
@@ -55,7 +59,7 @@ __device__ __forceinline__ AggAcc acc_load(const P& p, int64_t pos) {
     } else {
       x.a = load_uint(p.values, r, p.width);
     }
-  } else if (OP == AO_SUM_FLOAT) {
+  } else if (acc_float_total(OP)) {
     x.a = as_bits(p.width == 4 ? (double)((const float*)p.values)[r] : ((const double*)p.values)[r]);   // Float32 widens exactly
   } else if (OP == AO_MIN || OP == AO_MAX) {
     if (p.value_kind == AV_SIGNED) {
@@ -86,6 +90,10 @@ __device__ __forceinline__ void acc_finalize(const P& p, uint32_t g, const AggAc
     ((uint64_t*)p.out)[g] = acc.a;
   } else if (OP == AO_SUM_FLOAT) {
     ((uint64_t*)p.out)[g] = acc.cnt ? acc.a : 0;
+  } else if (OP == AO_AVG_INT) {   // RN(exact total) / count: one rounding of the total, one IEEE division; no overflow
+    ((uint64_t*)p.out)[g] = acc.cnt ? as_bits(avg_rn128(acc.a, acc.b, p.value_kind == AV_SIGNED) / (double)acc.cnt) : 0;
+  } else if (OP == AO_AVG_FLOAT) {   // the SUM's bits over the count, in one IEEE division
+    ((uint64_t*)p.out)[g] = acc.cnt ? as_bits(as_double(acc.a) / (double)acc.cnt) : 0;
   } else {
     uint64_t u = 0;
     if (acc.cnt) {

@@ -53,13 +53,15 @@ struct AggGroupsParams {   // agg_head_scan_kernel (one workgroup), then agg_hea
   int64_t G;                 // write kernel only (read back after the scan)
 };
 
-enum AggOp : int32_t { AO_COUNT = 0, AO_SUM_INT, AO_SUM_FLOAT, AO_MIN, AO_MAX };
+// AO_AVG_INT / AO_AVG_FLOAT accumulate exactly like AO_SUM_INT / AO_SUM_FLOAT -- the same identity, load, combine and tree --
+// and differ only in the value written for a finished group: the total over the count (aggregate_acc.h: acc_finalize)
+enum AggOp : int32_t { AO_COUNT = 0, AO_SUM_INT, AO_SUM_FLOAT, AO_MIN, AO_MAX, AO_AVG_INT, AO_AVG_FLOAT };
 // how a value is read (AO_SUM_INT: widened to 128 bits; AO_MIN / AO_MAX: mapped to an order-preserving u64 and back)
 enum AggValueKind : int32_t { AV_SIGNED = 0, AV_UNSIGNED, AV_FLOAT };
 
 // One accumulator shape for every aggregate: cnt = non-null values; a (, b) by AggOp:
-//   AO_SUM_INT    a = low, b = high word of the exact 128-bit total
-//   AO_SUM_FLOAT  a = bits of the binary64 partial sum
+//   AO_SUM_INT    a = low, b = high word of the exact 128-bit total (AO_AVG_INT too)
+//   AO_SUM_FLOAT  a = bits of the binary64 partial sum (AO_AVG_FLOAT too)
 //   AO_MIN/AO_MAX a = order-preserving u64 of the value (sort.hip: sort_norm_kernel)
 struct AggAcc {
   uint64_t a, b, cnt;
@@ -77,9 +79,9 @@ struct AggReduceParams {   // agg_reduce_kernel (one workgroup per tile), then a
   int64_t bit_offset;
   AggAcc* part_first;        // [ntiles]: the tile's share of a group that began in an earlier tile
   AggAcc* part_last;         // [ntiles]: the tile's share of a group that begins in it and goes on behind it
-  uint8_t* out;              // [G] values: i64 (AO_COUNT), 8 bytes (sums), `width` bytes (AO_MIN / AO_MAX)
+  uint8_t* out;              // [G] values: i64 (AO_COUNT), 8 bytes (sums, averages), `width` bytes (AO_MIN / AO_MAX)
   uint64_t* cnt_out;         // [G] non-null values per group (null: AO_COUNT)
-  uint32_t* overflow;        // AO_SUM_INT: set when a group's exact total does not fit 64 bits
+  uint32_t* overflow;        // AO_SUM_INT: set when a group's exact total does not fit 64 bits (AO_AVG_INT never touches it)
   int32_t op;                // AggOp
   int32_t value_kind;        // AggValueKind
   int32_t width;             // bytes per input value
@@ -90,6 +92,20 @@ struct AggCountStarParams {   // agg_count_star_kernel: out[g] = starts[g + 1] -
   const uint32_t* starts;
   int64_t G;
   int64_t* out;
+};
+
+// agg_distinct_kernel: COUNT(DISTINCT c).  The rows sorted by (keys, c) have the FINE runs starts2 / rep2 (runs of equal keys
+// and equal c); group g covers the same sorted positions [starts[g], starts[g + 1]) under that order as under the keys' own,
+// and the null values of c are the last fine run inside it.  out[g] = fine runs inside the group, less the null run.
+struct AggDistinctParams {
+  const uint32_t* starts;    // [G + 1]
+  int64_t G;
+  const uint32_t* starts2;   // [G2 + 1], ascending, starts2[G2] = n; every starts[g] is among them
+  const uint32_t* rep2;      // [G2]: one row of every fine run
+  int64_t G2;
+  const uint8_t* validity;   // of c (null: no nulls)
+  int64_t bit_offset;
+  int64_t* out;              // [G]
 };
 
 struct AggValidityParams {   // agg_validity_kernel: bit g = cnt[g] != 0; *ones += set bits

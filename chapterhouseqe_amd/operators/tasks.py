@@ -83,10 +83,14 @@ class OrderByOperatorTask:
 
 @dataclasses.dataclass(frozen=True)
 class AggregateOperatorTask:
-    """GROUP BY keys with the output items of the SELECT list (`sqlparse.aggregate_plan`); shaped like OrderByOperatorTask"""
+    """GROUP BY keys with the output items of the SELECT list (`sqlparse.aggregate_plan`); shaped like OrderByOperatorTask.
+    With HAVING (`sqlparse.having_plan`): `having` is the predicate over the output columns of `items`, of which the first
+    `n_visible` are the SELECT list's (None: all of them)."""
     keys: Sequence[A.Expr]
     items: Sequence[A.AggItem]
     max_rows_per_record: int = 10_000
+    having: Optional[A.Expr] = None
+    n_visible: Optional[int] = None
 
     def task_name(self) -> str:
         return "aggregate"
@@ -447,13 +451,17 @@ class AggregateConfig:
     keys: Sequence[A.Expr]
     items: Sequence[A.AggItem]
     max_rows_per_record: int = 10_000
+    having: Optional[A.Expr] = None
+    n_visible: Optional[int] = None
 
     @staticmethod
     def try_from(op_in_config: OperatorInstanceConfig) -> "AggregateConfig":
         t = _task_of(op_in_config, AggregateOperatorTask, "an aggregate")
         if not t.items:
             raise ValueError("an aggregate task needs at least one output item")
-        return AggregateConfig(tuple(t.keys), tuple(t.items), _max_rows_per_record(t))
+        if t.n_visible is not None and not 1 <= t.n_visible <= len(t.items):
+            raise ValueError(f"an aggregate task shows 1 to {len(t.items)} of its items, not {t.n_visible}")
+        return AggregateConfig(tuple(t.keys), tuple(t.items), _max_rows_per_record(t), t.having, t.n_visible)
 
 
 def _no_aliases(record) -> List[list]:
@@ -464,29 +472,65 @@ def _no_aliases(record) -> List[list]:
 class AggregateTask(BlockingTask):
     """Aggregates every inbound record with ONE `aggregate_records` call; the groups go out in key order, without table
     aliases.  When no record came in nothing is sent also without a GROUP BY key: there is no schema to aggregate over.
-    `aggregate_fn(records, table_aliases, keys, items)` replaces the library call (tests on the CPU)."""
+    HAVING is composition on that call's result: ONE `filter_record` with the predicate (a null drops the group), then,
+    when hidden items stand behind the visible ones, ONE `project_record` to the first `n_visible` columns -- by position:
+    visible items that share an output name aggregate under names of their own and get theirs back in the projection.
+    `aggregate_fn(records, table_aliases, keys, items)`, `filter_fn(record, table_aliases, predicate)` and
+    `project_fn(fields, record, table_aliases)` replace the library calls (tests on the CPU)."""
 
     def __init__(self, op_in_config: OperatorInstanceConfig, config: AggregateConfig, inbound_exchanges, outbound_exchange,
-                 aggregate_fn=None, ctx=None):
+                 aggregate_fn=None, ctx=None, filter_fn=None, project_fn=None):
         super().__init__(op_in_config, config, inbound_exchanges, outbound_exchange, ctx)
         self._aggregate = aggregate_fn
+        self._filter = filter_fn
+        self._project = project_fn
 
     def _compute(self, records, aliases):
         c = self.config
+        hidden = c.n_visible is not None and c.n_visible < len(c.items)
+        items = list(c.items)
+        if hidden:
+            # The projection below names its columns, and a name resolves to the FIRST column that has it.  Visible items
+            # that share an output name (`having_plan` never points the predicate at one of them) therefore aggregate
+            # under names of their own, and the projection gives them their names back: the cut is positional.
+            names = [it.name for it in items]
+            taken = set(names)
+            for i in range(c.n_visible):
+                if names.count(names[i]) > 1:
+                    k = i
+                    while f"__visible_{k}" in taken:
+                        k += 1
+                    taken.add(f"__visible_{k}")
+                    items[i] = dataclasses.replace(items[i], name=f"__visible_{k}")
         if self._aggregate is not None:
-            result = self._aggregate(records, aliases, c.keys, c.items)
+            result = self._aggregate(records, aliases, c.keys, tuple(items))
         else:
-            result = record_utils.aggregate_records(records, aliases, c.keys, c.items, ctx=self._context())
+            result = record_utils.aggregate_records(records, aliases, c.keys, items, ctx=self._context())
+        if c.having is not None:
+            if self._filter is not None:
+                result = self._filter(result, _no_aliases(result), c.having)
+            else:
+                result = record_utils.filter_record(result, _no_aliases(result), c.having, ctx=self._context())
+        if hidden:
+            fields = [A.UnnamedExpr(A.Identifier(A.Ident(it.name))) if it.name == orig.name else
+                      A.ExprWithAlias(A.Identifier(A.Ident(it.name)), A.Ident(orig.name))
+                      for it, orig in zip(items[:c.n_visible], c.items)]
+            if self._project is not None:
+                result = self._project(fields, result, _no_aliases(result))
+            else:
+                result = record_utils.project_record(fields, result, _no_aliases(result), ctx=self._context())
         return result, _no_aliases(result)
 
 
 class AggregateTaskBuilder(TaskBuilder):
-    def __init__(self, aggregate_fn=None):
+    def __init__(self, aggregate_fn=None, filter_fn=None, project_fn=None):
         self._aggregate_fn = aggregate_fn
+        self._filter_fn = filter_fn
+        self._project_fn = project_fn
 
     def build(self, op_in_config, inbound_exchanges, outbound_exchange):
         return _runner(AggregateTask(op_in_config, AggregateConfig.try_from(op_in_config), inbound_exchanges, outbound_exchange,
-                                     aggregate_fn=self._aggregate_fn))
+                                     aggregate_fn=self._aggregate_fn, filter_fn=self._filter_fn, project_fn=self._project_fn))
 
 
 # ---- window functions -----------------------------------------------------------------------------------------------------

@@ -976,6 +976,9 @@ def aggregate_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]
                      items: Sequence[A.AggItem], *, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
     """GROUP BY (`chq_aggregate_record`): one row per group of `rec` by the key columns `keys` (none: one group), in key
     order (ascending, nulls last), one column per `items` entry (`sqlparse.aggregate_plan` builds both from a SELECT).
+    The kinds are `sqlast.AggKind`'s: KEY, COUNT_STAR, COUNT, SUM, MIN, MAX, AVG (Float64; never an overflow) and
+    COUNT_DISTINCT (distinct non-null bit patterns; one more sort per distinct argument column).  HAVING is composition:
+    `sqlparse.having_plan` names the items and the predicate, `filter_record` over this call's result applies it.
     Result residency follows the input unless `device_result` says otherwise."""
     return _call_record(rec, ctx, device_result, _aggregate_call(L.lib().chq_aggregate_record, table_aliases, keys, items))
 
@@ -983,7 +986,7 @@ def aggregate_record(rec: Record, table_aliases: Optional[Sequence[Sequence[str]
 def aggregate_records(recs, table_aliases: Optional[Sequence[Sequence[str]]], keys: Sequence[A.Expr],
                       items: Sequence[A.AggItem], *, ctx: Optional[Context] = None, device_result: Optional[bool] = None):
     """GROUP BY over a group (`chq_aggregate_records`): the batches of `recs` (a sequence of same-schema batches or a
-    `RecordGroup`) aggregated as if they were one batch."""
+    `RecordGroup`) aggregated as if they were one batch; the item kinds are those of `aggregate_record`."""
     return _call_group(recs, ctx, device_result, "aggregate_records",
                        _aggregate_call(L.lib().chq_aggregate_records, table_aliases, keys, items))
 

@@ -227,11 +227,15 @@ class AggKind(enum.IntEnum):
     SUM = 3
     MIN = 4
     MAX = 5
+    AVG = 6
+    COUNT_DISTINCT = 7
 
 
 @dataclass(frozen=True)
 class AggItem:
-    """`KEY`: `key_index` into the GROUP BY keys; `COUNT_STAR`: nothing else; the others: their argument `column`."""
+    """`KEY`: `key_index` into the GROUP BY keys; `COUNT_STAR`: nothing else; the others: their argument `column`.
+    `AVG` is Float64 (integers: the exact total rounded once, over the count; it never overflows); `COUNT_DISTINCT` counts
+    the distinct non-null bit patterns of `column`, which may have any type ORDER BY takes as a key."""
     kind: AggKind
     name: str
     key_index: int = -1

@@ -19,8 +19,12 @@ sample queries (reference: sample_queries/simple.sql) to be written as SQL text.
   that can start an expression, `is` in front of `null` / `not null`, `escape` behind a pattern and in front of a string);
   anywhere else they stay ordinary words, e.g. aliases.  Prefix `not <expr>` stays an UnsupportedExpr.
 
-    select <items> from <func>('<path>') [[as] alias] {[inner] join <func>('<path>') [[as] alias] on <expr>}
-        [where <expr>] [group by <column> {, ...}]
+    select [distinct] <items> from <func>('<path>') [[as] alias] {[inner] join <func>('<path>') [[as] alias] on <expr>}
+        [where <expr>] [group by <column> {, ...}] [having <expr>]
+  `distinct` is the keyword right behind `select` where something that can start an expression, or `*`, follows (`select
+  distinct from t` selects a column called `distinct`); `having` is never an implicit alias.  The aggregates of a SELECT
+  list and of HAVING are count(*), count(c), sum(c), min(c), max(c) and avg(c); `count(distinct c)` is not spelled here
+  (AggKind.COUNT_DISTINCT is reached through AggItem).
     a select item may be a window call: <name>(<args>) over ([partition by <column> {, ...}] [order by ...]
         [rows|range between unbounded preceding and current row|unbounded following])
         [order by <expr> [asc|desc] [nulls first|last] {, ...}] [limit <n>]
@@ -63,7 +67,7 @@ _BINOPS = {
 }
 _WORD_BINOPS = {"OR": (A.BinaryOperator.Or, _PREC_OR), "AND": (A.BinaryOperator.And, _PREC_AND),
                 "XOR": (A.BinaryOperator.Xor, _PREC_XOR)}
-_STOP_WORDS = {"FROM", "WHERE", "AS", "GROUP", "ORDER", "LIMIT", "JOIN", "INNER", "ON"}
+_STOP_WORDS = {"FROM", "WHERE", "AS", "GROUP", "HAVING", "ORDER", "LIMIT", "JOIN", "INNER", "ON"}
 _CASE_WORDS = {"WHEN", "THEN", "ELSE", "END"}
 _OTHER_JOINS = {"LEFT", "RIGHT", "FULL", "OUTER", "CROSS"}
 
@@ -96,6 +100,8 @@ class Select:
     limit: Optional[int] = None
     group_by: Tuple[A.Expr, ...] = ()
     joins: Tuple[Join, ...] = ()
+    having: Optional[A.Expr] = None
+    distinct: bool = False
 
 
 def _tokenize(text: str) -> List[Tuple[str, str]]:
@@ -448,6 +454,10 @@ class _Parser:
     def parse_select(self) -> Select:
         if not self.accept_word("SELECT"):
             raise SqlParseError("expected SELECT")
+        distinct = False
+        if self._word_at(0) == "DISTINCT" and (self._starts_expr(1) or (self.i + 1 < len(self.toks) and self.toks[self.i + 1] == ("op", "*"))):
+            self.i += 1
+            distinct = True
         items = [self.parse_select_item()]
         while self.accept_op(","):
             items.append(self.parse_select_item())
@@ -476,6 +486,7 @@ class _Parser:
             group_by.append(self.parse_expr(0))
             while self.accept_op(","):
                 group_by.append(self.parse_expr(0))
+        having = self.parse_expr(0) if self.accept_word("HAVING") else None
         order_by: List[A.OrderByExpr] = []
         if self.accept_word("ORDER"):
             if not self.accept_word("BY"):
@@ -490,7 +501,7 @@ class _Parser:
                 raise SqlParseError(f"expected a non-negative integer after LIMIT, found {v!r}")
             limit = int(v)
         self.accept_op(";")
-        return Select(tuple(items), from_, selection, tuple(order_by), limit, tuple(group_by), tuple(joins))
+        return Select(tuple(items), from_, selection, tuple(order_by), limit, tuple(group_by), tuple(joins), having, distinct)
 
     def parse_order_by_expr(self) -> A.OrderByExpr:
         """sqlparser Parser::parse_order_by_expr"""
@@ -508,7 +519,7 @@ class _Parser:
 
 
 # ---- GROUP BY: the SELECT list as keys and output items -----------------------------------------------
-_AGGREGATES = {"count": A.AggKind.COUNT, "sum": A.AggKind.SUM, "min": A.AggKind.MIN, "max": A.AggKind.MAX}
+_AGGREGATES = {"count": A.AggKind.COUNT, "sum": A.AggKind.SUM, "min": A.AggKind.MIN, "max": A.AggKind.MAX, "avg": A.AggKind.AVG}
 
 
 def _expr_text(e: A.Expr) -> str:
@@ -531,9 +542,13 @@ def is_aggregate_call(e: A.Expr) -> bool:
 def aggregate_plan(select: Select):
     """A `Select` with GROUP BY or aggregate calls -> `(keys, items)` as `record_utils.aggregate_record(s)` takes them
     (None: the statement has neither).  Every SELECT item must be a GROUP BY key or one of count(*), count(c), sum(c),
-    min(c), max(c) (names case-insensitive); an item is named by its alias, else a key by its column name and an
-    aggregate by its lower-cased call text."""
+    min(c), max(c), avg(c) (names case-insensitive); an item is named by its alias, else a key by its column name and an
+    aggregate by its lower-cased call text.  A HAVING clause is ignored here: `having_plan` builds on this result.
+    `select distinct a, b` is GROUP BY a, b with one KEY item each -- the rows come out in key order, which is a property
+    of this operator, not something SQL promises -- and takes plain columns only."""
     exprs = [(f.expr if isinstance(f, (A.UnnamedExpr, A.ExprWithAlias)) else None) for f in select.projection]
+    if select.distinct:
+        return _distinct_plan(select, exprs)
     if not select.group_by and not any(e is not None and is_aggregate_call(e) for e in exprs):
         return None
     keys = tuple(select.group_by)
@@ -560,6 +575,97 @@ def aggregate_plan(select: Select):
         else:
             raise SqlParseError(f"SELECT item {_expr_text(e)} is neither a GROUP BY key nor an aggregate")
     return keys, tuple(items)
+
+
+def _column_tail(e: A.Expr) -> str:
+    return e.ident.value if isinstance(e, A.Identifier) else e.idents[-1].value
+
+
+def _distinct_plan(select: Select, exprs):
+    if select.group_by or select.having is not None:
+        raise SqlParseError("SELECT DISTINCT cannot be combined with GROUP BY or HAVING")
+    items = []
+    for f, e in zip(select.projection, exprs):
+        if e is None:
+            raise SqlParseError("SELECT DISTINCT takes plain columns, not a wildcard")
+        if is_aggregate_call(e) or _has_window_call(e):
+            raise SqlParseError(f"SELECT DISTINCT cannot be combined with aggregates or window calls: {_expr_text(e)}")
+        if not isinstance(e, (A.Identifier, A.CompoundIdentifier)):
+            raise SqlParseError(f"SELECT DISTINCT takes plain columns, not {_term_text(e)}")
+        items.append(A.AggItem(A.AggKind.KEY, f.alias.value if isinstance(f, A.ExprWithAlias) else _column_tail(e), len(items)))
+    return tuple(exprs), tuple(items)
+
+
+def having_plan(select: Select):
+    """A `Select` with HAVING -> `(keys, items, predicate, n_visible)` (None: the statement has no HAVING).  `keys` and
+    `items[:n_visible]` are `aggregate_plan`'s.  `predicate` is the HAVING expression with every aggregate call (count(*),
+    count / sum / min / max / avg of one column) and every GROUP BY key column replaced by an identifier of an output column
+    of the aggregate: a visible item of the same kind and argument when its output name is unique among the items, else a
+    hidden item `__having_<k>` appended behind the visible ones.  The statement runs as aggregate(all items), then
+    `filter_record(predicate)` over that result (null drops the row), then, with hidden items, a projection to the first
+    `n_visible` columns.  The statement must be an aggregate statement by its SELECT list and GROUP BY (`aggregate_plan` is
+    not None): aggregates that stand in HAVING alone do not make it one -- without GROUP BY there is no key, so no SELECT
+    item other than an aggregate could be selected next to them."""
+    if select.having is None:
+        return None
+    plan = aggregate_plan(select)
+    if plan is None:
+        exprs = [(f.expr if isinstance(f, (A.UnnamedExpr, A.ExprWithAlias)) else None) for f in select.projection]
+        if any(e is not None and _has_window_call(e) for e in exprs):
+            raise SqlParseError("HAVING cannot be combined with window calls")
+        raise SqlParseError("HAVING needs GROUP BY or an aggregate in the SELECT list (an aggregate in HAVING alone does not "
+                            "group the statement: its SELECT items are neither keys nor aggregates)")
+    keys, visible = plan
+    items = list(visible)
+
+    def column_for(kind, key_index=-1, column=None) -> A.Expr:
+        for it in items:
+            if (it.kind, it.key_index, it.column) == (kind, key_index, column) and sum(o.name == it.name for o in items) == 1:
+                return A.Identifier(A.Ident(it.name))
+        k = len(items) - len(visible)
+        while any(o.name == f"__having_{k}" for o in items):
+            k += 1
+        items.append(A.AggItem(kind, f"__having_{k}", key_index, column))
+        return A.Identifier(A.Ident(items[-1].name))
+
+    def rewrite(e: A.Expr) -> A.Expr:
+        if isinstance(e, A.Function):
+            if e.over is not None:
+                raise SqlParseError(f"a window call cannot stand in HAVING: {_expr_text(e)}")
+            if not is_aggregate_call(e):   # a scalar function: the evaluator's business, over rewritten arguments
+                return e if e.args is None else A.Function(e.debug, e.name, tuple(rewrite(x) for x in e.args), e.star, None)
+            kind = _AGGREGATES[e.name.lower()]
+            if e.star:
+                if kind != A.AggKind.COUNT:
+                    raise SqlParseError(f"{e.name}(*) is not an aggregate; only count(*) takes '*'")
+                return column_for(A.AggKind.COUNT_STAR)
+            if e.args is None or len(e.args) != 1 or not isinstance(e.args[0], (A.Identifier, A.CompoundIdentifier)):
+                raise SqlParseError(f"{e.name} in HAVING takes exactly one plain column: "
+                                    f"{_expr_text(e) if e.args is not None else e.name + '(...)'}")
+            return column_for(kind, -1, e.args[0])
+        if isinstance(e, (A.Identifier, A.CompoundIdentifier)):
+            if e not in keys:
+                raise SqlParseError(f"column {_expr_text(e)} in HAVING is neither a GROUP BY key nor inside an aggregate")
+            return column_for(A.AggKind.KEY, keys.index(e))
+        if isinstance(e, A.BinaryOp):
+            return A.BinaryOp(rewrite(e.left), e.op, rewrite(e.right))
+        if isinstance(e, A.Nested):
+            return A.Nested(rewrite(e.expr))
+        if isinstance(e, A.IsNull):
+            return A.IsNull(rewrite(e.expr), e.negated)
+        if isinstance(e, A.Like):
+            return A.Like(rewrite(e.expr), rewrite(e.pattern), e.negated, e.escape_char)
+        if isinstance(e, A.InList):
+            return A.InList(rewrite(e.expr), tuple(rewrite(x) for x in e.list), e.negated)
+        if isinstance(e, A.Between):
+            return A.Between(rewrite(e.expr), e.negated, rewrite(e.low), rewrite(e.high))
+        if isinstance(e, A.Case):
+            return A.Case(None if e.operand is None else rewrite(e.operand), tuple(rewrite(x) for x in e.conditions),
+                          tuple(rewrite(x) for x in e.results), None if e.else_result is None else rewrite(e.else_result))
+        return e   # literals, and what the evaluator rejects by itself
+
+    predicate = rewrite(select.having)
+    return keys, tuple(items), predicate, len(visible)
 
 
 # ---- window functions: the SELECT list as one window call's items ------------------------------------------------------

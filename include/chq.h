@@ -459,7 +459,7 @@ chq_status chq_sort_records(chq_ctx* ctx, int n_records, const struct ArrowDevic
                             const chq_sort_key* keys, int n_keys, int64_t limit, int out_device,
                             struct ArrowDeviceArray* out, struct ArrowSchema* out_schema);
 
-/* ---- GROUP BY: grouped COUNT / SUM / MIN / MAX on top of the stable sort ---------------------------
+/* ---- GROUP BY: grouped COUNT / SUM / MIN / MAX / AVG / COUNT(DISTINCT) on top of the stable sort -----
  * The reference has no GROUP BY; these semantics are this library's own (unpinned), chosen so that none of them depends on
  * the order in which rows are combined:
  *   - zero or more keys, each a column (Identifier / CompoundIdentifier) resolved exactly like a sort key (a missing
@@ -482,11 +482,24 @@ chq_status chq_sort_records(chq_ctx* ctx, int n_records, const struct ArrowDevic
  *       CHQ_AGG_MIN / MAX   nulls skipped; the input type, nullable; Int8..64, UInt8..64, Float16/32/64 in totalOrder, and
  *                           Date, Time, Timestamp, Duration and decimals of up to 8 bytes as signed integers.  The result
  *                           is the bits of an actual input value.
- *     CHQ_ERR_NOT_SUPPORTED, naming the column and its type: SUM over Float16, Boolean, temporal types, decimals, Utf8;
- *     MIN / MAX over Utf8, Boolean, Decimal128.  An empty item list, or a key_index outside the keys:
+ *       CHQ_AGG_AVG         nulls skipped; the input types of SUM; Float64, nullable, null for a group without a non-null
+ *                           value.  Floats: the group's SUM -- the very bits a CHQ_AGG_SUM item over the same column in the
+ *                           same call gives -- divided by binary64(count) in one IEEE division (NaN and +-inf propagate).
+ *                           Integers: RN(T) / binary64(count), T the EXACT 128-bit total of the group and RN its rounding to
+ *                           the nearest binary64, ties to even (Python: float(T) / float(count)).  AVG never fails with
+ *                           CHQ_ERR_ARROW_ARITHMETIC_OVERFLOW: the average of {INT64_MAX, INT64_MAX} is 9.223372036854775807e18.
+ *       CHQ_AGG_COUNT_DISTINCT  distinct non-null values of `column` in the group, equal by BIT PATTERN as the keys are (-0
+ *                           and +0 are two values, so are NaNs with different payloads; Utf8: length and bytes).  Int64, not
+ *                           nullable; 0 for a group whose values are all null and for the group over zero rows.  `column` may
+ *                           have any type ORDER BY takes as a key.  Cost: one more sort (by the keys, then `column`) and one
+ *                           more run finding per distinct argument column of the call, shared by the items that name it.
+ *     CHQ_ERR_NOT_SUPPORTED, naming the column and its type: SUM and AVG over Float16, Boolean, temporal types, decimals,
+ *     Utf8; MIN / MAX over Utf8, Boolean, Decimal128; COUNT_DISTINCT over a type without an order.  A kind outside 0..7:
+ *     CHQ_ERR_ARROW_INVALID_ARGUMENT.  An empty item list, or a key_index outside the keys:
  *     CHQ_ERR_ARROW_INVALID_ARGUMENT.
  *   - fewer than 2^32 rows per call (else CHQ_ERR_NOT_SUPPORTED).
- * AVG, DISTINCT aggregates, HAVING, expressions as keys or arguments, and partial / merge aggregation across instances are
+ * HAVING (the Python front-end composes it from this call and chq_filter_record), VAR / STDDEV, SUM(DISTINCT), expressions
+ * as keys or arguments, and partial / merge aggregation across instances are
  * out of scope (the route to several instances is chq_partition_records by the keys: a group lies wholly inside one partition).  Inputs may be host or device resident and sliced; `out_device` is ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM.
  * On failure nothing is returned (release == NULL). */
 typedef enum chq_agg_kind {
@@ -495,12 +508,14 @@ typedef enum chq_agg_kind {
   CHQ_AGG_COUNT = 2,
   CHQ_AGG_SUM = 3,
   CHQ_AGG_MIN = 4,
-  CHQ_AGG_MAX = 5
+  CHQ_AGG_MAX = 5,
+  CHQ_AGG_AVG = 6,
+  CHQ_AGG_COUNT_DISTINCT = 7
 } chq_agg_kind;
 typedef struct chq_agg_item {
   int kind;                /* chq_agg_kind */
   int key_index;           /* CHQ_AGG_KEY: index into `keys` */
-  const chq_expr* column;  /* COUNT, SUM, MIN, MAX: the argument column; NULL otherwise */
+  const chq_expr* column;  /* COUNT, SUM, MIN, MAX, AVG, COUNT_DISTINCT: the argument column; NULL otherwise */
   const char* name;        /* output column name */
 } chq_agg_item;
 chq_status chq_aggregate_record(chq_ctx* ctx, const struct ArrowDeviceArray* rec, const struct ArrowSchema* schema,

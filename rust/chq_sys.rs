@@ -52,7 +52,7 @@ pub struct chq_sort_key {
     pub nulls_first: c_int,
 }
 
-/// struct chq_agg_item: one output column of GROUP BY (kind: 0 key, 1 COUNT(*), 2 COUNT, 3 SUM, 4 MIN, 5 MAX)
+/// struct chq_agg_item: one output column of GROUP BY (kind: 0 key, 1 COUNT(*), 2 COUNT, 3 SUM, 4 MIN, 5 MAX, 6 AVG, 7 COUNT(DISTINCT))
 #[repr(C)]
 pub struct chq_agg_item {
     pub kind: c_int,
