@@ -442,6 +442,14 @@ chq_expr* chq_expr_between(chq_expr* expr, int negated, chq_expr* low, chq_expr*
   delete expr; delete low; delete high;
   return e;
 }
+chq_expr* chq_expr_cast(chq_expr* operand, chq_cast_type to, int try_cast) {
+  chq_expr* e = new_expr(Expr::CAST);
+  if (!e || !operand) { chq_expr_free(operand); delete e; return nullptr; }
+  e->e.op = (int)to; e->e.flag = try_cast != 0;
+  e->e.l.reset(new Expr(std::move(operand->e)));
+  delete operand;
+  return e;
+}
 chq_expr* chq_expr_unsupported(const char* debug) { chq_expr* e = new_expr(Expr::OTHER); if (e) e->e.text = debug ? debug : ""; return e; }
 void chq_expr_free(chq_expr* e) { delete e; }
 

@@ -16,6 +16,7 @@
 #include "typed_ops.h"
 #include "like_device.h"
 #include "strfn_device.h"
+#include "cast_device.h"
 #include "plan.hpp"
 
 namespace chq {
@@ -43,6 +44,11 @@ hipError_t launch_case_select_bool(const CaseSelectParams& p, hipStream_t stream
 hipError_t launch_case_select_fixed(const CaseSelectParams& p, hipStream_t stream);
 hipError_t launch_case_rows(const CaseSelectParams& p, hipStream_t stream);
 hipError_t launch_case_gather(const CaseSelectParams& p, hipStream_t stream);
+// cast.hip
+hipError_t launch_cast_fixed(const CastFixedParams& p, hipStream_t stream);
+hipError_t launch_cast_parse(const CastParseParams& p, hipStream_t stream);
+hipError_t launch_cast_len(const CastPrintParams& p, hipStream_t stream);
+hipError_t launch_cast_write(const CastPrintParams& p, hipStream_t stream);
 hipError_t launch_utf8_uniform(const Utf8UniformParams& p, hipStream_t stream);
 hipError_t launch_iota_offsets(const IotaOffsetsParams& p, hipStream_t stream);
 hipError_t launch_count_bits(const uint8_t* in, int64_t bit_offset, int64_t nbits, unsigned long long* out, hipStream_t stream);

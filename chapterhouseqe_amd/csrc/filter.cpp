@@ -157,11 +157,11 @@ void materialize_node(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols,
 // Decimal128 comparisons, Utf8 -> Boolean casts, LIKE and IS [NOT] NULL are not device-program instructions (plan.hpp:
 // Node): their own kernels (typed_ops.hip, like.hip) write a temporary Boolean column, which replaces the node like any
 // other materialisation.  The scalar string functions (strfn.hip) do the same with a temporary Utf8 or Int32 column, CASE
-// (case.hip) with a temporary column of its result type.
+// (case.hip) with a temporary column of its result type, CAST / TRY_CAST (cast.hip) with one of the target type.
 bool is_typed_op(const TypedExpr& te, int node) {
   const Node& n = te.nodes[node];
   return (n.kind == Node::CMP && n.from == T_FIXED_OPAQUE) || (n.kind == Node::TOBOOL && n.from == T_UTF8) ||
-         n.kind == Node::LIKE || n.kind == Node::ISNULL || n.kind == Node::STRFN || n.kind == Node::CASE ||
+         n.kind == Node::LIKE || n.kind == Node::ISNULL || n.kind == Node::STRFN || n.kind == Node::CASE || n.kind == Node::XCAST ||
          (n.kind == Node::CONST && n.cval.null);   // `'maybe' AND ..` folded to NULL, next to a column of a one-row batch
 }
 void fit_subtree(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict, bool is_root);
@@ -457,6 +457,110 @@ Column evaluate_case(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, 
   return c;
 }
 
+// ---- CAST, TRY_CAST (cast.hip) ---------------------------------------------------------------------
+// the Utf8 result of a cast may hold at most INT32_MAX bytes (int32 offsets); `total` is the 64-bit sum the scan read back
+void check_cast_utf8_total(u64 total) {
+  if (total > (u64)INT32_MAX)
+    throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "the Utf8 result of a cast would hold " + std::to_string(total) +
+                                                   " bytes, more than int32 offsets can address"};
+}
+// The temporary column of XCAST node `n`, whose operand is a column of `work`.  A CAST fails with CHQ_ERR_ARROW_CAST when a
+// VALID row cannot be converted; under TRY_CAST such rows are null.
+Column evaluate_cast(Context& ctx, const Batch& work, const TypedExpr& te, const Node& n) {
+  const int64_t nrows = work.nrows;
+  const Column& sc = work.cols[(size_t)te.nodes[n.l].col];
+  const DType from = n.from, to = n.type;
+  const bool try_cast = n.op != 0;
+  Column c;
+  c.type = to; c.length = nrows; c.format = fixed_format(to); c.width = dtype_width(to);
+  if (nrows == 0) {
+    auto vb = make_device_buffer(16, ctx.device);
+    check_hip(hipMemsetAsync(vb->ptr, 0, 16, ctx.stream), "memset");
+    c.values = (const uint8_t*)vb->ptr; c.owned.push_back(vb);
+    if (to == T_UTF8) { auto db = make_device_buffer(16, ctx.device); c.data = (const uint8_t*)db->ptr; c.data_bytes = 0; c.owned.push_back(db); }
+    check_hip(hipStreamSynchronize(ctx.stream), "sync");
+    return c;
+  }
+  const size_t words = (size_t)((nrows + 63) / 64) + 1;
+  const void* in_validity = (sc.validity && sc.null_count != 0) ? sc.validity : nullptr;
+  auto valid = make_device_buffer(words * 8, ctx.device);
+  // [0] rows valid in the output, [1] the failure flag (low 32 bits), [2] rows valid in the input (Utf8 -> Boolean)
+  auto count = make_device_buffer(32, ctx.device);
+  check_hip(hipMemsetAsync(count->ptr, 0, 32, ctx.stream), "memset");
+  u64* const d_count = (u64*)count->ptr;
+  u64 h_count[4] = {0, 0, 0, 0};
+  auto read_counts = [&](const uint64_t* total) {
+    check_hip(launch_count_bits((const uint8_t*)valid->ptr, 0, nrows, d_count, ctx.stream), "launch count_bits_kernel");
+    check_hip(hipMemcpyAsync(h_count, d_count, 24, hipMemcpyDeviceToHost, ctx.stream), "read valid count and failure flag");
+    if (total) check_hip(hipMemcpyAsync(&h_count[3], total, 8, hipMemcpyDeviceToHost, ctx.stream), "read byte total");
+    check_hip(hipStreamSynchronize(ctx.stream), "sync");
+  };
+  bool failed = false;
+  if (to == T_UTF8) {   // integer / Boolean -> Utf8: lengths, offsets, bytes
+    CastPrintParams p{};
+    p.values = from == T_BOOL ? (const void*)sc.values : sc.values0(); p.values_offset = from == T_BOOL ? sc.offset : 0;
+    p.validity = in_validity; p.validity_offset = sc.offset; p.nrows = nrows; p.from = from;
+    auto len = make_device_buffer((size_t)nrows * 4 + 16, ctx.device);
+    p.out_len = (uint32_t*)len->ptr; p.out_validity = (u64*)valid->ptr;
+    check_hip(launch_cast_len(p, ctx.stream), "launch cast_len_kernel");
+    OffsetsScanParams sp{};
+    sp.len = (const uint32_t*)len->ptr; sp.n = nrows; sp.ntiles = (nrows + STRFN_SCAN_CHUNK - 1) / STRFN_SCAN_CHUNK;
+    auto sums = make_device_buffer((size_t)(sp.ntiles + 1) * 8 + 16, ctx.device);
+    auto offb = make_device_buffer((size_t)(nrows + 2) * 4, ctx.device);
+    sp.tile_sums = (uint64_t*)sums->ptr; sp.out = (uint32_t*)offb->ptr; sp.write_total = 1;
+    check_hip(launch_offsets_scan(sp, ctx.stream), "launch the offsets scan of the row lengths");
+    read_counts(sp.tile_sums + sp.ntiles);
+    check_cast_utf8_total(h_count[3]);
+    const int64_t bytes = (int64_t)h_count[3];
+    auto db = make_device_buffer((size_t)bytes + 16, ctx.device);
+    if (bytes > 0) {
+      p.out_offsets = (const int32_t*)offb->ptr; p.out_data = (uint8_t*)db->ptr;
+      check_hip(launch_cast_write(p, ctx.stream), "launch cast_write_kernel");
+      check_hip(hipStreamSynchronize(ctx.stream), "sync");   // (the lengths are let go on return)
+    }
+    c.values = (const uint8_t*)offb->ptr; c.data = (const uint8_t*)db->ptr; c.data_bytes = bytes;
+    c.owned = {offb, db};
+  } else if (from == T_UTF8 && to == T_BOOL) {
+    // the kernel of the cast under AND / OR: a spelling it does not know comes out null.  CAST: such a row on a valid input
+    // row is the failure, i.e. the output holds fewer valid rows than the input
+    auto bits = make_device_buffer(words * 8, ctx.device);
+    Utf8ToBoolParams p{};
+    p.offsets = (const int32_t*)sc.values0(); p.data = sc.data;
+    p.validity = in_validity; p.validity_offset = sc.offset; p.nrows = nrows;
+    p.out_bits = (u64*)bits->ptr; p.out_validity = (u64*)valid->ptr; p.null_count = d_count + 3;   // (not read)
+    check_hip(launch_utf8_to_bool(p, ctx.stream), "launch utf8_to_bool_kernel");
+    if (in_validity) check_hip(launch_count_bits(sc.validity, sc.offset, nrows, d_count + 2, ctx.stream), "launch count_bits_kernel");
+    read_counts(nullptr);
+    failed = !try_cast && h_count[0] != (in_validity ? h_count[2] : (u64)nrows);
+    c.values = (const uint8_t*)bits->ptr; c.owned = {bits};
+  } else {
+    const size_t vbytes = to == T_BOOL ? words * 8 : (size_t)nrows * (size_t)c.width + 16;
+    auto vb = make_device_buffer(vbytes, ctx.device);
+    if (from == T_UTF8) {
+      CastParseParams p{};
+      p.offsets = (const int32_t*)sc.values0(); p.data = sc.data;
+      p.validity = in_validity; p.validity_offset = sc.offset; p.nrows = nrows; p.to = to; p.try_cast = try_cast ? 1 : 0;
+      p.out_values = vb->ptr; p.out_validity = (u64*)valid->ptr; p.fail = (uint32_t*)(d_count + 1);
+      check_hip(launch_cast_parse(p, ctx.stream), "launch cast_parse_kernel");
+    } else {
+      CastFixedParams p{};
+      p.values = from == T_BOOL ? (const void*)sc.values : sc.values0(); p.values_offset = from == T_BOOL ? sc.offset : 0;
+      p.validity = in_validity; p.validity_offset = sc.offset; p.nrows = nrows;
+      p.from = from; p.to = to; p.try_cast = try_cast ? 1 : 0;
+      p.out_values = vb->ptr; p.out_validity = (u64*)valid->ptr; p.fail = (uint32_t*)(d_count + 1);
+      check_hip(launch_cast_fixed(p, ctx.stream), "launch cast_fixed_kernel");
+    }
+    read_counts(nullptr);
+    failed = (uint32_t)h_count[1] != 0;
+    c.values = (const uint8_t*)vb->ptr; c.owned = {vb};
+  }
+  if (failed)
+    throw ChqError{CHQ_ERR_ARROW_CAST, std::string("Cast error: a ") + dtype_name(from) + " value cannot be cast to " + dtype_name(to)};
+  c.null_count = nrows - (int64_t)h_count[0]; c.nullable = c.null_count != 0;
+  if (c.null_count) { c.validity = (const uint8_t*)valid->ptr; c.owned.push_back(valid); }
+  return c;
+}
+
 void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict) {
   if (te.nodes[node].kind == Node::CASE) {
     Column c = evaluate_case(ctx, work, wcols, te, node, strict);
@@ -479,16 +583,16 @@ void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wc
     const Node::Kind kind = te.nodes[node].kind;
     const bool is_concat = kind == Node::STRFN && te.nodes[node].op == STRFN_CONCAT;
     std::vector<int> operands;
-    if (kind == Node::ISNULL || kind == Node::LIKE || kind == Node::TOBOOL || (kind == Node::STRFN && te.nodes[node].op != STRFN_CONCAT)) operands.push_back(te.nodes[node].l);
+    if (kind == Node::ISNULL || kind == Node::LIKE || kind == Node::TOBOOL || kind == Node::XCAST || (kind == Node::STRFN && te.nodes[node].op != STRFN_CONCAT)) operands.push_back(te.nodes[node].l);
     else if (kind == Node::STRFN) operands = te.nodes[node].parts;
     for (int l : operands) {
       fit_subtree(ctx, work, wcols, te, l, strict, false);
       if (te.nodes[l].kind != Node::COL && !(is_concat && te.nodes[l].kind == Node::CONST)) materialize_node(ctx, work, wcols, te, l);
     }
   }
-  if (te.nodes[node].kind == Node::STRFN) {
+  if (te.nodes[node].kind == Node::STRFN || te.nodes[node].kind == Node::XCAST) {
     const Node n = te.nodes[node];
-    Column c = evaluate_strfn(ctx, work, te, n);
+    Column c = n.kind == Node::STRFN ? evaluate_strfn(ctx, work, te, n) : evaluate_cast(ctx, work, te, n);
     c.name = "__chq_tmp_" + std::to_string(work.cols.size());
     PlanColumn pc;
     pc.name = c.name; pc.type = c.type; pc.has_nulls = c.null_count != 0; pc.alias_entry_present = true; pc.format = c.format; pc.width = c.width;
@@ -1068,7 +1172,7 @@ void fit_to_device(Context& ctx, const Batch& rec, const std::vector<PlanColumn>
       fit_subtree(ctx, work, wcols, te, te.root, /*strict=*/pass == 1, true);
       return;
     } catch (const ChqError& e) {
-      const bool data_error = e.code == CHQ_ERR_ARROW_ARITHMETIC_OVERFLOW || e.code == CHQ_ERR_ARROW_DIVIDE_BY_ZERO;
+      const bool data_error = e.code == CHQ_ERR_ARROW_ARITHMETIC_OVERFLOW || e.code == CHQ_ERR_ARROW_DIVIDE_BY_ZERO || e.code == CHQ_ERR_ARROW_CAST;
       if (pass == 1 || !data_error) throw;   // strict order reports the reference's first error
     }
   }

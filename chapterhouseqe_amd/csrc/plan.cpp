@@ -178,6 +178,33 @@ static Scalar cast_scalar(const Scalar& s, DType to) {
   fail(CHQ_ERR_ARROW_CAST, std::string("Casting from ") + dtype_name(s.type) + " to " + dtype_name(to) + " not supported");
 }
 
+// An explicit CAST / TRY_CAST of one literal-built value, with the per-row rules the device runs (cast_device.h).  A failing
+// CAST is the typing-time error of the call, a failing TRY_CAST a typed null.
+static std::string cast_error(DType from, DType to) {
+  return std::string("Cast error: a ") + dtype_name(from) + " value cannot be cast to " + dtype_name(to);
+}
+static Scalar explicit_cast_scalar(const Scalar& s, DType to, bool try_cast) {
+  if (s.null) return null_scalar(to);
+  Scalar out; out.type = to;
+  bool ok = true;
+  if (s.type == T_UTF8 && to == T_BOOL) {
+    const int v = utf8_to_bool((const uint8_t*)s.str.data(), (int64_t)s.str.size());
+    ok = v >= 0; out.bits = v > 0;
+  } else if (s.type == T_UTF8) {
+    ok = s.str.size() <= (size_t)INT32_MAX && cast_parse_int((const uint8_t*)s.str.data(), (int32_t)s.str.size(), to, &out.bits);
+  } else if (to == T_UTF8) {
+    if (s.type == T_BOOL) { out.str.resize((size_t)cast_bool_len(s.bits & 1)); cast_write_bool(s.bits & 1, (uint8_t*)&out.str[0]); }
+    else { const int32_t n = cast_decimal_len(s.bits, is_signed(s.type)); out.str.resize((size_t)n); cast_write_decimal(s.bits, is_signed(s.type), (uint8_t*)&out.str[0], n); }
+  } else {
+    ok = cast_fixed_value(s.bits, s.type, to, &out.bits);
+    // (the Scalar convention: an integer's bits are extended to 64 by its signedness)
+    if (ok && is_int(to)) { const int sh = 64 - cast_int_bits(to); out.bits = is_signed(to) ? (uint64_t)((int64_t)(out.bits << sh) >> sh) : (out.bits << sh) >> sh; }
+  }
+  if (ok) return out;
+  if (try_cast) return null_scalar(to);
+  fail(CHQ_ERR_ARROW_CAST, cast_error(s.type, to));
+}
+
 static int32_t f32_key(uint32_t b) { int32_t s = (int32_t)b; return s ^ (int32_t)(((uint32_t)(s >> 31)) >> 1); }
 static int64_t f64_key(uint64_t b) { int64_t s = (int64_t)b; return s ^ (int64_t)(((uint64_t)(s >> 63)) >> 1); }
 
@@ -236,6 +263,7 @@ Scalar fold_constant(const TypedExpr& t, int ni) {
     case Node::CONST: return n.cval;
     case Node::CAST: return cast_scalar(fold_constant(t, n.l), n.type);
     case Node::TOBOOL: return cast_scalar(fold_constant(t, n.l), T_BOOL);
+    case Node::XCAST: return explicit_cast_scalar(fold_constant(t, n.l), n.type, n.op != 0);
     // (a NULL operand gives a NULL result; the operation -- and so its errors -- is evaluated on valid slots only)
     case Node::ARITH: { Scalar a = fold_constant(t, n.l), b = fold_constant(t, n.r); return a.null || b.null ? null_scalar(n.type) : eval_arith(n.op, a, b); }
     case Node::CMP: { Scalar a = fold_constant(t, n.l), b = fold_constant(t, n.r); return a.null || b.null ? null_scalar(T_BOOL) : eval_cmp(n.op, a, b); }
@@ -413,6 +441,24 @@ struct Typer {
         return maybe_fold(push(n));
       }
       case Expr::FUNCTION: return function(e);
+      case Expr::CAST: {
+        if (!e.l) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "CAST needs an operand");
+        const int l = build(*e.l);
+        static const DType kTo[] = {T_BOOL, T_I8, T_I16, T_I32, T_I64, T_U8, T_U16, T_U32, T_U64, T_F16, T_F32, T_F64, T_UTF8};
+        const char* what = e.flag ? "TRY_CAST" : "CAST";
+        if (e.op < 0 || e.op >= (int)(sizeof kTo / sizeof kTo[0]))
+          fail(CHQ_ERR_NOT_SUPPORTED, std::string(what) + " to this type is outside this build's scope");
+        const DType from = t.nodes[l].type, to = kTo[e.op];
+        if (from == T_FIXED_OPAQUE)
+          fail(CHQ_ERR_NOT_SUPPORTED, std::string(what) + " of a temporal, decimal or other opaque fixed-width value is outside this build's scope");
+        if (from == to) return l;   // the operand itself: no node, no kernel
+        const auto is_fp = [](DType x) { return x == T_F16 || x == T_F32 || x == T_F64; };
+        if ((is_fp(from) && to == T_UTF8) || (from == T_UTF8 && is_fp(to)))
+          fail(CHQ_ERR_NOT_SUPPORTED, std::string(what) + " between " + dtype_name(from) + " and " + dtype_name(to) + " is outside this build's scope");
+        Node n{}; n.kind = Node::XCAST; n.type = to; n.from = from; n.l = l; n.op = e.flag ? 1 : 0;
+        n.is_scalar = t.nodes[l].is_scalar; n.len1 = t.nodes[l].len1;
+        return maybe_fold(push(n));
+      }
       case Expr::CASE: {
         const size_t nw = e.args.size() / 2;
         if (nw == 0 || e.args.size() != 2 * nw) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "CASE needs at least one WHEN, each with a THEN");
@@ -677,6 +723,7 @@ int case_guarded_parts(const TypedExpr& t, int ni, std::vector<char>* guard) {
 bool has_checked_arith(const TypedExpr& t, int ni) {
   const Node& n = t.at(ni);
   if (n.kind == Node::ARITH && is_int(n.type) && !n.len1) return true;
+  if (n.kind == Node::XCAST && n.op == 0 && !n.len1 && cast_can_fail(n.from, n.type)) return true;
   bool any = false;
   n.each_child([&](int c) { any = any || has_checked_arith(t, c); });
   return any;
@@ -778,6 +825,7 @@ struct Gen {
       case Node::ISNULL: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "IS NULL runs as its own kernel");
       case Node::STRFN: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "a string function runs as its own kernel");
       case Node::CASE: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "CASE runs as its own kernel");
+      case Node::XCAST: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "an explicit cast runs as its own kernel");
       case Node::CMP:
         if (n.from == T_UTF8) { gen_strcmp(n); return; }
         if (n.from == T_FIXED_OPAQUE) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "Decimal128 comparison runs as its own kernel");
@@ -817,6 +865,7 @@ struct Gen {
     else if (l.kind == Node::COL && r.kind == Node::COL) { in.src_idx = (uint16_t)ref_of(l.col); in.imm = ((uint64_t)n.op << 56) | (uint64_t)ref_of(r.col); in.flags |= IF_STR_RHS_COL; }
     else if (l.kind == Node::STRFN || r.kind == Node::STRFN) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "a string function runs as its own kernel");
     else if (l.kind == Node::CASE || r.kind == Node::CASE) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "CASE runs as its own kernel");
+    else if (l.kind == Node::XCAST || r.kind == Node::XCAST) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "an explicit cast runs as its own kernel");
     else fail(CHQ_ERR_NOT_SUPPORTED, "Utf8 comparison operands must be columns or literals");
     emit(in);
   }

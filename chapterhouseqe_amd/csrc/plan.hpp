@@ -18,6 +18,7 @@
 #include "like_device.h"
 #include "strfn_device.h"
 #include "case_device.h"
+#include "cast_device.h"
 
 namespace chq {
 
@@ -36,8 +37,8 @@ struct Expr {
   // args = the arguments (a scalar string function, strfn_device.h, or coalesce / nullif; any other name answers like OTHER
   // "Function(name)").  CASE: l = the operand of a simple CASE or null, args = the n conditions (simple CASE: the values)
   // followed by the n results, r = the ELSE or null.  IN_LIST: l = the operand, args = the list, flag = NOT IN.  BETWEEN:
-  // l = the operand, args = {low, high}, flag = NOT BETWEEN.
-  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER, LIKE, ISNULL, FUNCTION, CASE, IN_LIST, BETWEEN } kind;
+  // l = the operand, args = {low, high}, flag = NOT BETWEEN.  CAST: l = the operand, op = the chq_cast_type, flag = TRY_CAST.
+  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER, LIKE, ISNULL, FUNCTION, CASE, IN_LIST, BETWEEN, CAST } kind;
   int op = 0;             // chq_binary_operator
   std::string text;       // number text / identifier / string bytes / debug text
   bool flag = false;      // is_long / boolean value / negated
@@ -64,7 +65,7 @@ struct Scalar {
   DType type = T_BOOL;
   uint64_t bits = 0;          // value bits (sign-extended ints, IEEE bits for floats, 0/1 for bool)
   std::string str;            // utf8
-  bool null = false;          // only a Utf8 -> Boolean cast of a literal can make one (arrow-cast: bad spelling = NULL)
+  bool null = false;          // a Utf8 -> Boolean cast of a literal can make one (arrow-cast: bad spelling = NULL), a failing TRY_CAST, nullif
 };
 
 // arrow-cast 53 cast_utf8_to_boolean on one value: 1 / 0, or -1 when the spelling is not a boolean (= NULL, safe cast)
@@ -83,8 +84,10 @@ struct Node {
   // simple CASE, coalesce, nullif) has op = n WHENs, 1..CASE_MAX_WHENS, `parts` = the n Boolean conditions, the n results and
   // -- case_else -- the ELSE, every result of the node's type, l = r = -1: case.hip writes a temporary column of that type.
   // A result may be a CONST whose cval is null, of any type (nullif).  fmt_col: the batch column whose Arrow format a
-  // T_FIXED_OPAQUE result has (a COL's is its own).)
-  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL, LIKE, ISNULL, STRFN, CASE } kind;
+  // T_FIXED_OPAQUE result has (a COL's is its own).  XCAST is an explicit CAST / TRY_CAST (l = the operand, `from` its type,
+  // `type` the target, op = 1 for TRY_CAST): cast.hip writes a temporary column of the target type.  CAST stays the implicit
+  // widening of the coercion table, an instruction of the device program.)
+  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL, LIKE, ISNULL, STRFN, CASE, XCAST } kind;
   DType type;
   bool is_scalar;   // ArrayDatum.is_scalar
   bool len1;        // array length is 1 regardless of the batch (built from literals only)
@@ -125,7 +128,8 @@ TypedExpr type_expr(const Expr& e, const std::vector<PlanColumn>& cols, int64_t 
 // Throws ChqError for arithmetic errors.  `valid` is always true (literals are never null).
 Scalar fold_constant(const TypedExpr& t, int node);
 
-// true: the sub-tree at `node` holds checked integer arithmetic on columns, i.e. it can fail on data
+// true: the sub-tree at `node` holds checked integer arithmetic on columns, or a CAST (not TRY_CAST) of a column whose
+// conversion can fail (cast_can_fail), i.e. it can fail on data
 bool has_checked_arith(const TypedExpr& t, int node);
 // CASE node `node`: guard[j] = operand parts[j] is evaluated under a guard (the lazy-error rule): it
 // can fail on data and is not the first condition, which every row evaluates.  Returns how many are.

@@ -48,7 +48,8 @@ bool subtree_can_null(const TypedExpr& t, int ni, const std::vector<PlanColumn>&
   if (n.kind == Node::COL) return cols[n.col].has_nulls;
   if (n.kind == Node::CONST) return n.cval.null;
   if (n.kind == Node::ISNULL) return false;   // IS [NOT] NULL is never null
-  bool r = n.kind == Node::TOBOOL && n.from == T_UTF8;   // a bad spelling is NULL
+  bool r = (n.kind == Node::TOBOOL && n.from == T_UTF8) ||   // a bad spelling is NULL
+           (n.kind == Node::XCAST && n.op != 0 && cast_can_fail(n.from, n.type));   // a failing TRY_CAST row too
   n.each_child([&](int c) { r = r || subtree_can_null(t, c, cols); });   // (a string function: null where an operand is)
   return r;
 }
@@ -102,7 +103,8 @@ std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::ve
     // (a Utf8 result is a string function's: fitting below turns it into a temporary column, which IS the result)
     // (.. or a CASE's, of any type)
     if (root.kind == Node::CASE && root.type == T_FIXED_OPAQUE) { o.format = pcols[(size_t)root.fmt_col].format; o.width = pcols[(size_t)root.fmt_col].width; }
-    if (root.kind != Node::CASE && ((root.type == T_UTF8 && root.kind != Node::STRFN) || root.type == T_FIXED_OPAQUE))
+    // (.. or an explicit cast's to Utf8)
+    if (root.kind != Node::CASE && ((root.type == T_UTF8 && root.kind != Node::STRFN && root.kind != Node::XCAST) || root.type == T_FIXED_OPAQUE))
       throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("expression result of type ") + dtype_name(root.type) + " is outside this build's scope"};
   }
   if (nrows == 0) {
@@ -601,6 +603,14 @@ std::string describe_plan(const ArrowSchema* schema, const chq_table_aliases* al
              " guarded=" + std::to_string(case_guarded_parts(te, ni, nullptr)) + "\n";
     };
     cases(te.root);
+    // the explicit casts of the tree, operands first
+    std::function<void(int)> casts = [&](int ni) {
+      const Node& n = te.at(ni);
+      n.each_child(casts);
+      if (n.kind != Node::XCAST) return;
+      out += std::string("cast ") + dtype_name(n.from) + " -> " + dtype_name(n.type) + (n.op ? " try" : "") + "\n";
+    };
+    casts(te.root);
     return out;
   }
   out += "program wide=" + std::to_string((int)lw.wide) + " num_temps=" + std::to_string(lw.num_temps) + " refs=";

@@ -343,6 +343,8 @@ def _expr_to_c(e: A.Expr):
             raise
         arr = (C.c_void_p * max(1, len(built)))(*built)
         return lib.chq_expr_function(e.name.encode(), arr, len(built))
+    if isinstance(e, A.Cast):
+        return lib.chq_expr_cast(_expr_to_c(e.expr), int(e.data_type), int(e.try_cast))
     if isinstance(e, (A.Case, A.InList, A.Between)):
         # every child first; the constructors take ownership of all of them, also when they fail
         if isinstance(e, A.Case):

@@ -148,6 +148,39 @@ class Between(Expr):
     high: Expr
 
 
+class CastType(enum.IntEnum):
+    """the target of a Cast (include/chq.h: chq_cast_type)"""
+    Boolean = 0
+    Int8 = 1
+    Int16 = 2
+    Int32 = 3
+    Int64 = 4
+    UInt8 = 5
+    UInt16 = 6
+    UInt32 = 7
+    UInt64 = 8
+    Float16 = 9
+    Float32 = 10
+    Float64 = 11
+    Utf8 = 12
+    Other = 13
+
+
+@dataclass(frozen=True)
+class Cast(Expr):
+    """Expr::Cast { kind, expr, data_type }: `CAST(expr AS T)`, `expr::T` and -- `try_cast` -- `TRY_CAST(expr AS T)`"""
+    expr: Expr
+    data_type: CastType
+    try_cast: bool = False
+
+    @property
+    def args(self):
+        """None, as for every call whose parentheses hold no plain expression list (`Function.args`): before the grammar
+        knew the form, `cast(a as int)` parsed as such a call, and code that asks an expression for its call arguments
+        (the GROUP BY and window front-ends) keeps getting that answer."""
+        return None
+
+
 @dataclass(frozen=True)
 class UnsupportedExpr(Expr):
     """UnaryOp, Function, Subquery, ... -- compute_value.rs:338-342 rejects them."""

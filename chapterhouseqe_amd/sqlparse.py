@@ -18,6 +18,10 @@ sample queries (reference: sample_queries/simple.sql) to be written as SQL text.
   `like`, `not`, `is` and `escape` are operators only where these forms continue (`like` / `not like` in front of something
   that can start an expression, `is` in front of `null` / `not null`, `escape` behind a pattern and in front of a string);
   anywhere else they stay ordinary words, e.g. aliases.  Prefix `not <expr>` stays an UnsupportedExpr.
+    cast ( <expr> as <type> ) | try_cast ( <expr> as <type> ) | <expr> :: <type>   -> Cast
+  `cast` / `try_cast` open the form only in front of `(`; `::` binds tighter than any binary operator.  <type> is one of
+  boolean | bool | tinyint | smallint | int | integer | bigint (each integer name optionally followed by `unsigned`) | real |
+  float | double [precision] | varchar | text | string; a length or precision argument and any other name are errors.
 
     select [distinct] <items> from <func>('<path>') [[as] alias] {[inner] join <func>('<path>') [[as] alias] on <expr>}
         [where <expr>] [group by <column> {, ...}] [having <expr>]
@@ -44,7 +48,7 @@ _TOKEN_RE = re.compile(
       | (?P<string>'(?:[^']|'')*')
       | (?P<qident>"(?:[^"]|"")*")
       | (?P<word>[A-Za-z_][A-Za-z0-9_$]*)
-      | (?P<op><>|!=|<=|>=|\|\||==|[-+*/%=<>(),.;&|^])
+      | (?P<op><>|!=|<=|>=|\|\||==|::|[-+*/%=<>(),.;&|^])
     )""",
     re.X,
 )
@@ -53,6 +57,15 @@ _PREC_OR, _PREC_AND, _PREC_NOT, _PREC_EQ = 5, 10, 15, 20
 _PREC_IS, _PREC_LIKE = 17, 19
 _PREC_PIPE, _PREC_CARET, _PREC_AMP, _PREC_XOR = 21, 22, 23, 24
 _PREC_PLUS, _PREC_MUL = 30, 40
+_PREC_CAST = 50   # postfix `::`: tighter than every binary operator
+
+# the type names of CAST / TRY_CAST / `::` (case-insensitive); the integer names may be followed by UNSIGNED, DOUBLE by PRECISION
+_CAST_TYPES = {"BOOLEAN": A.CastType.Boolean, "BOOL": A.CastType.Boolean, "TINYINT": A.CastType.Int8, "SMALLINT": A.CastType.Int16,
+               "INT": A.CastType.Int32, "INTEGER": A.CastType.Int32, "BIGINT": A.CastType.Int64, "REAL": A.CastType.Float32,
+               "FLOAT": A.CastType.Float32, "DOUBLE": A.CastType.Float64, "VARCHAR": A.CastType.Utf8, "TEXT": A.CastType.Utf8,
+               "STRING": A.CastType.Utf8}
+_CAST_UNSIGNED = {A.CastType.Int8: A.CastType.UInt8, A.CastType.Int16: A.CastType.UInt16, A.CastType.Int32: A.CastType.UInt32,
+                  A.CastType.Int64: A.CastType.UInt64}
 
 _BINOPS = {
     "=": (A.BinaryOperator.Eq, _PREC_EQ), "==": (A.BinaryOperator.Eq, _PREC_EQ),
@@ -191,6 +204,8 @@ class _Parser:
         infix = self._infix_words()
         if infix:
             return infix[3]
+        if k == "op" and v == "::":
+            return _PREC_CAST
         if k == "op" and v in _BINOPS:
             return _BINOPS[v][1]
         if k == "word" and v.upper() in _WORD_BINOPS:
@@ -235,6 +250,9 @@ class _Parser:
                 expr = A.Like(expr, pattern, negated, escape)
                 continue
             k, v = self.next()
+            if (k, v) == ("op", "::"):   # Expr::Cast { kind: DoubleColon }: the same as CAST
+                expr = A.Cast(expr, self._data_type(), False)
+                continue
             op = _BINOPS[v][0] if k == "op" else _WORD_BINOPS[v.upper()][0]
             right = self.parse_expr(nxt)
             expr = A.BinaryOp(expr, op, right)
@@ -269,12 +287,37 @@ class _Parser:
             # (`case + 1` and `case - 1` stay arithmetic on a column of that name)
             if up == "CASE" and (self._word_at(0) == "WHEN" or (self._starts_expr(0) and self.peek() not in (("op", "-"), ("op", "+")))):
                 return self._case()
+            if up in ("CAST", "TRY_CAST") and self.peek() == ("op", "("):
+                return self._cast(up == "TRY_CAST")
             if self.peek() == ("op", "("):
                 return self._function_call(v)
             return self._identifier_tail(A.Ident(v))
         if k == "qident":
             return self._identifier_tail(A.Ident(v, '"'))
         raise SqlParseError(f"unexpected token {v!r}")
+
+    def _cast(self, try_cast: bool) -> A.Expr:
+        """`( expr AS type )` behind CAST / TRY_CAST: sqlparser Parser::parse_cast_expr / parse_try_cast_expr"""
+        self.expect_op("(")
+        inner = self.parse_expr(0)
+        if not self.accept_word("AS"):
+            raise SqlParseError(f"expected AS in {'TRY_CAST' if try_cast else 'CAST'}, found {self.peek()[1]!r}")
+        to = self._data_type()
+        self.expect_op(")")
+        return A.Cast(inner, to, try_cast)
+
+    def _data_type(self) -> A.CastType:
+        k, v = self.next()
+        if k != "word" or v.upper() not in _CAST_TYPES:
+            raise SqlParseError(f"{v!r} is not a type CAST knows: {', '.join(sorted(_CAST_TYPES))}")
+        to = _CAST_TYPES[v.upper()]
+        if to in _CAST_UNSIGNED and self.accept_word("UNSIGNED"):
+            to = _CAST_UNSIGNED[to]
+        if v.upper() == "DOUBLE":
+            self.accept_word("PRECISION")
+        if self.peek() == ("op", "("):
+            raise SqlParseError(f"a length or precision argument of {v} is not supported")
+        return to
 
     def _case(self) -> A.Expr:
         """sqlparser Parser::parse_case_expr, behind the CASE keyword"""
@@ -659,6 +702,8 @@ def having_plan(select: Select):
             return A.InList(rewrite(e.expr), tuple(rewrite(x) for x in e.list), e.negated)
         if isinstance(e, A.Between):
             return A.Between(rewrite(e.expr), e.negated, rewrite(e.low), rewrite(e.high))
+        if isinstance(e, A.Cast):
+            return A.Cast(rewrite(e.expr), e.data_type, e.try_cast)
         if isinstance(e, A.Case):
             return A.Case(None if e.operand is None else rewrite(e.operand), tuple(rewrite(x) for x in e.conditions),
                           tuple(rewrite(x) for x in e.results), None if e.else_result is None else rewrite(e.else_result))

@@ -109,7 +109,7 @@ void* chq_ctx_stream(const chq_ctx* ctx);
  * Beyond the reference: [NOT] LIKE on Utf8 (chq_expr_like), IS [NOT] NULL on every type (chq_expr_is_null) and the scalar
  * string functions (CHQ_BINOP_STRING_CONCAT, chq_expr_function), whose results are Utf8 or Int32 columns; CASE, coalesce and
  * nullif (chq_expr_case, chq_expr_function), whose result has any of these types; BETWEEN and IN lists (chq_expr_between,
- * chq_expr_in_list). */
+ * chq_expr_in_list); explicit CAST / TRY_CAST between Boolean, the integers, the floats and Utf8 (chq_expr_cast). */
 chq_status chq_ctx_set_option(chq_ctx* ctx, const char* key, int64_t value);
 /* Counters of the last filter call: rows in, rows out, tiles, kernel launches. */
 typedef struct chq_call_stats {
@@ -215,6 +215,37 @@ chq_expr* chq_expr_in_list(chq_expr* expr, chq_expr* const* list, int n, int neg
  * `expr >= low AND expr <= high`, negated `expr < low OR expr > high`, with the values, nulls and statuses of that
  * spelled-out form; `expr` is typed once. */
 chq_expr* chq_expr_between(chq_expr* expr, int negated, chq_expr* low, chq_expr* high);
+/* The target of chq_expr_cast.  CHQ_CAST_OTHER: any other sqlparser::ast::DataType (CHQ_ERR_NOT_SUPPORTED at typing). */
+typedef enum chq_cast_type {
+  CHQ_CAST_BOOLEAN = 0, CHQ_CAST_INT8, CHQ_CAST_INT16, CHQ_CAST_INT32, CHQ_CAST_INT64, CHQ_CAST_UINT8, CHQ_CAST_UINT16,
+  CHQ_CAST_UINT32, CHQ_CAST_UINT64, CHQ_CAST_FLOAT16, CHQ_CAST_FLOAT32, CHQ_CAST_FLOAT64, CHQ_CAST_UTF8, CHQ_CAST_OTHER
+} chq_cast_type;
+/* Expr::Cast { kind: Cast | TryCast | DoubleColon, expr, data_type }: `CAST(operand AS to)`, `operand::to` (try_cast = 0) and
+ * `TRY_CAST(operand AS to)` (try_cast = 1); takes ownership of `operand`, also when it fails and returns NULL.  The reference
+ * rejects the form: these semantics are this library's own, modelled on arrow-cast 53 (CastOptions { safe: false } for CAST,
+ * safe: true for TRY_CAST) and unpinned to it.  A null row gives a null row.  A row that FAILS below ends a CAST with
+ * CHQ_ERR_ARROW_CAST (the message names the source and the target type) and becomes null under TRY_CAST.  An output column
+ * is nullable iff it holds a null.  A cast to the operand's own type is the operand itself.
+ *   integer -> integer        value preserved; fails iff it lies outside the target's range
+ *   integer -> Float16/32/64  the exact integer rounded once, to nearest even (Float16: beyond 65504 -> +-inf); never fails
+ *   float   -> integer        NaN and +-inf fail; otherwise truncated toward zero (-0.9 -> 0, also for unsigned targets;
+ *                             -0.0 -> 0); fails iff the truncated value lies outside the range
+ *   float   -> float          one rounding to nearest even, overflow -> +-inf, subnormals produced and consumed exactly; a
+ *                             NaN keeps its sign and the top payload bits that fit, quiet bit set; never fails
+ *   numeric -> Boolean        x != 0 (NaN -> true, -0.0 -> false); never fails
+ *   Boolean -> numeric        1 / 0 (1.0 / 0.0); never fails
+ *   Utf8    -> Boolean        the spellings of the cast under AND / OR (trimmed, case-folded t / true / y / yes / on / 1 ..);
+ *                             any other string fails
+ *   Utf8    -> integer        the whole row must match [+-]?[0-9]+ (`-` only for signed targets): no white space is stripped,
+ *                             any number of leading zeros, `-0` is 0, and the value must fit the target; otherwise it fails
+ *   integer -> Utf8           shortest decimal, `-` for negatives (1 to 20 bytes); never fails
+ *   Boolean -> Utf8           `true` / `false`; never fails
+ * A cast over literals only is folded on the host with the code the device runs: a failing literal CAST fails at typing
+ * wherever it stands (like `1 / 0`), a failing literal TRY_CAST is a typed null.  Lazy errors: a CAST that can fail counts as
+ * data-dependent for the rule of chq_expr_case, and reports failures on valid rows only.  A Utf8 result of more than
+ * 2^31 - 1 bytes: CHQ_ERR_ARROW_INVALID_ARGUMENT.  CHQ_ERR_NOT_SUPPORTED: Float <-> Utf8 (a correctly rounded parse and a
+ * shortest round-trip print are not built), temporal and Decimal128 operands, LargeUtf8, CHQ_CAST_OTHER. */
+chq_expr* chq_expr_cast(chq_expr* operand, chq_cast_type to, int try_cast);
 chq_expr* chq_expr_unsupported(const char* debug);                            /* any other Expr variant */
 void chq_expr_free(chq_expr* e);
 
