@@ -40,7 +40,7 @@ static_assert(CHQ_AGG_SUM - CHQ_AGG_COUNT == AGG_FN_SUM && CHQ_AGG_MIN - CHQ_AGG
 
 AggKey key_of(const Column& c) {
   AggKey k{};
-  k.validity = c.validity && c.null_count != 0 ? c.validity : nullptr;
+  k.validity = c.live_validity();
   k.bit_offset = c.offset;
   k.values = (const uint8_t*)c.values0();
   k.data = c.data;

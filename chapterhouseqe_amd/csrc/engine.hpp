@@ -130,6 +130,8 @@ struct Column {
   const void* values0() const;       // fixed: values + offset*width; utf8: offsets + offset
   int64_t bool_bit_offset() const { return offset; }
   int64_t validity_bit_offset() const { return offset; }
+  // the bitmap when it may hold nulls (null_count unknown or positive), else nullptr: what a kernel is given
+  const uint8_t* live_validity() const { return (validity && null_count != 0) ? validity : nullptr; }
 };
 
 struct Batch {

@@ -1,5 +1,5 @@
-// engine_internal.hpp -- what the engine's own translation units (arrow_io.cpp, filter.cpp, group.cpp, project.cpp) share
-// with each other and with nobody else.  The interface for the rest of the library is engine.hpp.
+// engine_internal.hpp -- what the engine's own translation units (arrow_io.cpp, filter.cpp, group.cpp, materialize.cpp,
+// project.cpp) share with each other and with nobody else.  The interface for the rest of the library is engine.hpp.
 #pragma once
 #include <algorithm>
 
@@ -91,14 +91,16 @@ void launch_tiles(Context& ctx, Params& p, int64_t rows, int64_t tile_rows, int6
 
 // ---- filter.cpp: a lowered program and its launch ------------------------------------------------------------------------
 void fill_refs(ProgramBlock& pb, const Lowered& lw, const Batch& rec, const std::vector<BufferPtr>& str_bufs);
+BufferPtr upload_literal(Context& ctx, const std::string& s);
 std::vector<BufferPtr> upload_strings(Context& ctx, const Lowered& lw);
 [[noreturn]] void throw_device_error(unsigned long long stored);
 int pick_tile_kind(const Context& ctx, const Lowered& lw, int64_t rows);
 void pick_stash(FilterParams& p, const Context& ctx, const Lowered& lw, const std::vector<Column>& cols, std::vector<int>& launch_cols, int tile_kind);
-// ---- filter.cpp: typing, and expressions that do not fit one device program ------------------------------------------------
+// ---- materialize.cpp: expressions that do not fit one device program -------------------------------------------------------
 bool lowers_alone(const TypedExpr& te, int node, const std::vector<PlanColumn>& wcols);
 void fit_to_device(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const TypedExpr& original,
                    Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te);
+// ---- filter.cpp: typing ------------------------------------------------------------------------------------------------------
 TypedExpr typed(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& expr);
 bool is_row_predicate(const TypedExpr& te);
 Column empty_like(const Column& c);

@@ -117,7 +117,7 @@ Batch join_resolved(Context& ctx, std::vector<Batch>& left, std::vector<Batch>& 
       bool any_nulls = false;
       for (int q = 0; q < sp.n_keys; ++q) {
         const Column& c = K.cols[k0 + (size_t)q];
-        sp.validity[q] = c.validity && c.null_count != 0 ? c.validity : nullptr;
+        sp.validity[q] = c.live_validity();
         sp.bit_offset[q] = c.offset;
         any_nulls |= sp.validity[q] != nullptr;
       }

@@ -73,7 +73,7 @@ JoinedGroup partition_records(Context& ctx, std::vector<Batch>& in, const chq_ta
         const Column& c = rec.cols[(size_t)cols[k0 + (size_t)q]];
         PartKey& key = hp.keys[q];
         key = PartKey{};
-        key.validity = c.validity && c.null_count != 0 ? c.validity : nullptr;
+        key.validity = c.live_validity();
         key.bit_offset = c.offset;
         key.values = (const uint8_t*)c.values0();
         key.data = c.data;

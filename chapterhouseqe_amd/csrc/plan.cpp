@@ -16,6 +16,10 @@ int dtype_width(DType t) {
   static const int w[T_NTYPES] = {0, 1, 2, 4, 8, 1, 2, 4, 8, 2, 4, 8, 0, 0};
   return t < T_NTYPES ? w[t] : 0;
 }
+const char* dtype_format(DType t) {
+  static const char* fmts[T_NTYPES] = {"b", "c", "s", "i", "l", "C", "S", "I", "L", "e", "f", "g", "u", ""};
+  return t < T_NTYPES ? fmts[t] : "";
+}
 
 static bool is_int(DType t) { return t >= T_I8 && t <= T_U64; }
 static bool is_signed(DType t) { return t >= T_I8 && t <= T_I64; }

@@ -49,6 +49,7 @@ struct Expr {
 
 const char* dtype_name(DType t);
 int dtype_width(DType t);   // bytes of a fixed-width value (0 for bool / utf8)
+const char* dtype_format(DType t);   // Arrow C format string ("" for T_FIXED_OPAQUE: its column's own)
 
 // A column as the planner sees it
 struct PlanColumn {

@@ -20,8 +20,7 @@ Column clone_device_column(Context& ctx, const Column& c) { return copy_column(c
 Column scalar_column(Context& ctx, const Scalar& s, const std::string& name) {
   Column o;
   o.name = name; o.type = s.type; o.length = 1; o.null_count = 0; o.nullable = false;
-  static const char* fmts[T_NTYPES] = {"b", "c", "s", "i", "l", "C", "S", "I", "L", "e", "f", "g", "u", ""};
-  o.format = fmts[s.type]; o.width = dtype_width(s.type);
+  o.format = dtype_format(s.type); o.width = dtype_width(s.type);
   if (s.type == T_UTF8) {
     int32_t offs[2] = {0, (int32_t)s.str.size()};
     auto ob = make_device_buffer(16, ctx.device), db = make_device_buffer(s.str.size() + 16, ctx.device);
@@ -52,11 +51,6 @@ bool subtree_can_null(const TypedExpr& t, int ni, const std::vector<PlanColumn>&
            (n.kind == Node::XCAST && n.op != 0 && cast_can_fail(n.from, n.type));   // a failing TRY_CAST row too
   n.each_child([&](int c) { r = r || subtree_can_null(t, c, cols); });   // (a string function: null where an operand is)
   return r;
-}
-
-const char* format_of(DType t) {
-  static const char* fmts[T_NTYPES] = {"b", "c", "s", "i", "l", "C", "S", "I", "L", "e", "f", "g", "u", ""};
-  return fmts[t];
 }
 
 // an expression select item's name; `*unnamed_idx` counts the UNNAMED_EXPR items so far
@@ -99,7 +93,7 @@ std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::ve
   for (size_t k = 0; k < exprs.size(); ++k) {
     const Node& root = exprs[k]->at(exprs[k]->root);
     Column& o = results[k];
-    o.type = root.type; o.format = format_of(root.type); o.width = dtype_width(root.type); o.length = nrows;
+    o.type = root.type; o.format = dtype_format(root.type); o.width = dtype_width(root.type); o.length = nrows;
     // (a Utf8 result is a string function's: fitting below turns it into a temporary column, which IS the result)
     // (.. or a CASE's, of any type)
     if (root.kind == Node::CASE && root.type == T_FIXED_OPAQUE) { o.format = pcols[(size_t)root.fmt_col].format; o.width = pcols[(size_t)root.fmt_col].width; }
@@ -428,7 +422,7 @@ bool filter_project_fused(Context& ctx, const Batch& rec, const std::vector<Plan
       o.format = c.format; o.width = c.width;
       read_once[it.copy_col] = 1;
     } else {
-      o.format = format_of(it.type); o.width = dtype_width(it.type);
+      o.format = dtype_format(it.type); o.width = dtype_width(it.type);
     }
     auto vb = make_device_buffer((size_t)nrows * o.width + 16, ctx.device);
     o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);

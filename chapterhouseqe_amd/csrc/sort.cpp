@@ -122,7 +122,7 @@ Column gather_column(Context& ctx, const Column& c, const uint32_t* perm, int64_
     return (const uint8_t*)b->ptr;
   };
   if (pad || (c.validity && c.null_count != 0)) {   // (pad: the source's bitmap, if it has one, and the padding)
-    o.validity = bits(c.validity && c.null_count != 0 ? c.validity : nullptr, c.offset, ones);
+    o.validity = bits(c.live_validity(), c.offset, ones);
     o.null_count = -1;   // set from `ones` once read back
   }
   if (c.type == T_BOOL) {

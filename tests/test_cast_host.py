@@ -429,7 +429,13 @@ def test_round_sizes_of_the_gpu_tests():
     tile = int(re.search(r"constexpr\s+int\s+STRFN_SCAN_CHUNK\s*=\s*(\d+);", strfn).group(1))
     scan_block = int(re.search(r"constexpr\s+int\s+kScanBlock\s*=\s*(\d+);", scan).group(1))
     assert G.SCAN_TILE == tile and G.SCAN_ROUND == tile * scan_block
-    assert "STRFN_SCAN_CHUNK - 1) / STRFN_SCAN_CHUNK" in open(os.path.join(CSRC, "filter.cpp")).read().split("Column evaluate_cast(")[1].split("\nvoid materialize_typed_op(")[0]
+    # (written once, in the Utf8 assembly every operator with a Utf8 result goes through)
+    host = open(os.path.join(CSRC, "materialize.cpp")).read()
+    body = lambda head: host.split("\n" + head)[1].split("\n}\n")[0]
+    formula = "STRFN_SCAN_CHUNK - 1) / STRFN_SCAN_CHUNK"
+    assert host.count(formula) == 1 and formula in body("void assemble_utf8(")
+    for caller in ("Column evaluate_cast(", "Column evaluate_strfn(", "Column evaluate_case("):
+        assert host.count(caller) == 1 and "assemble_utf8(ctx, c, " in body(caller), caller
     # the GPU tests' sizes: the scan tile and its neighbours, and the smallest count whose last word lies in the second round
     assert set(G.ROW_COUNTS) >= {0, 1, 63, 64, 65, tile - 1, tile, tile + 1}
     assert G.SECOND_ROUND_ROWS == G.GRID_ROWS + 1 and G.SECOND_ROUND_ROWS > G.SCAN_ROUND + tile

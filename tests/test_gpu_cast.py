@@ -173,6 +173,21 @@ def test_row_counts(ctx, n):
                 check_array(run(ctx, dev, cast_expr(dst, True), host), want, wvalid, dst, f"{src}->{dst} n={n} device")
 
 
+def test_zero_rows_for_every_kind_of_typed_operation(ctx):
+    """a device batch of no rows: every operator that becomes a temporary column (materialize.cpp) answers with an empty
+    column of its type and no nulls, and a Boolean one filters to no rows"""
+    host = pa.RecordBatch.from_arrays([pa.array([], pa.int32()), pa.array([], pa.utf8()), pa.array([], pa.bool_())], names=["id", "s", "b"])
+    dev = chq.DeviceRecordBatch.from_host(host, ctx)
+    for sql, typ in (("upper(s)", pa.utf8()), ("s || 'x'", pa.utf8()), ("length(s)", pa.int32()), ("s like 'a%'", pa.bool_()), ("s is null", pa.bool_()),
+                     ("s and b", pa.bool_()), ("case when b then s else 'n' end", pa.utf8()), ("case when b then id else 0 end", pa.int32()),
+                     ("cast(id as varchar)", pa.utf8()), ("cast(s as int)", pa.int32()), ("try_cast(s as boolean)", pa.bool_())):
+        arr = run(ctx, dev, parse_expr(sql), host)
+        assert arr.type == typ and len(arr) == 0 and arr.null_count == 0, (sql, arr.type, len(arr), arr.null_count)
+        if typ == pa.bool_():
+            kept = chq.filter_record(dev, empty_aliases(host), parse_expr(sql), ctx=ctx).to_host()
+            assert kept.num_rows == 0 and kept.schema.names == host.schema.names, (sql, kept.num_rows)
+
+
 def tiled(table_values, n):
     """n rows cycling through a table, as index array + the table"""
     return np.arange(n) % len(table_values)

@@ -536,3 +536,19 @@ def test_statuses_on_the_device(ctx):
     with pytest.raises(chq.ChqError) as unknown:
         chq.compute_value(dev, al, parse_expr("foo(s)"), ctx=ctx)
     assert unknown.value.code == 2 and "Function(foo)" in str(unknown.value)
+
+
+# ---- a Utf8 result past int32 offsets: refused before a byte is copied ---------------------------------------------------------------------
+def test_utf8_byte_total_refusal(ctx):
+    """forged offsets, no large allocation (tests/test_gpu_case.py has the same for CASE): two columns of two rows, each of which
+    claims 2^30 bytes in one row.  strfn_rows_kernel reads offsets only for `||`, the total (2^31) is checked on the host, and
+    the gather -- which would read the bytes -- never runs."""
+    big = 2**30
+    offs = pa.RecordBatch.from_arrays([pa.array([0, big, big], pa.int32()), pa.array([0, 0, big], pa.int32()), pa.array([1, 0, 0], pa.int32())], names=["so", "to", "c"])
+    up = chq.DeviceRecordBatch.from_host(offs, ctx)
+    data = up.column_buffer_address(2)      # 12 bytes that are never read
+    dev = chq.DeviceRecordBatch.from_device_buffers([{"name": "s", "format": "u", "values": up.column_buffer_address(0), "data": data},
+                                                     {"name": "t", "format": "u", "values": up.column_buffer_address(1), "data": data}], 2, ctx, keepalive=[up])
+    with pytest.raises(chq.ChqError) as ei:
+        chq.compute_value(dev, [[], []], parse_expr("s || t"), ctx=ctx)
+    assert ei.value.code == 22 and "int32 offsets" in str(ei.value) and str(2**31) in str(ei.value)

@@ -9,7 +9,7 @@ the same pairs rotated by 37 rows, so that every pair sits at two lane positions
 (Decimal128: 2 * 52^2 = 5 408 rows, 84 complete waves and one of 32 lanes).  The grid-stride second round of these kernels
 is tests/test_gpu_rounds.py's.
 
-Which route each test takes (filter.cpp: fit_subtree -> materialize_typed_op turns a typed operation into a Boolean
+Which route each test takes (materialize.cpp: fit_subtree -> materialize_typed_op turns a typed operation into a Boolean
 temporary column -- bits, validity, null count read back -- before the rest of the expression is lowered):
   * test_decimal128_*: Node::CMP over two T_FIXED_OPAQUE columns -> launch_cmp128.  compute_value and project_record copy the
     temporary out (evaluate_dense); filter_record / filter_project_record / filter_records run the filter kernels over it,

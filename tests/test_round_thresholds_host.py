@@ -72,8 +72,8 @@ def test_tiles_of_the_scans():
                                (source("aggregate.hip"), "agg_head_scan_kernel", "Agg")):
         assert "scan_totals_in_place<" in body_of(text, f"void {kernel}("), kernel
         assert f"{kernel}, dim3(1), dim3(k{name}Block)" in text, kernel
-    for caller in ("join.cpp", "filter.cpp"):
-        assert "launch_offsets_scan(" in source(caller), caller
+    assert "launch_offsets_scan(" in source("join.cpp")
+    assert source("materialize.cpp").count("launch_offsets_scan(") == 1   # (the one Utf8 assembly of the string functions, CASE and CAST)
     assert G.SCAN_ROUND == G.STRFN_ROUND == block * G.T
 
     # ... and the three scans of the Parquet kernels: the same loop over page counts and over the totals of blocks of
