@@ -4,15 +4,19 @@
 //   case_masks_kernel         one lane per 64 rows: the take mask of every WHEN and the remaining mask, aligned to bit 0
 //   case_and_kernel           one lane per 64 rows: a bitmap re-aligned to bit 0 and ANDed with a guard (guarded views)
 //   case_select_bool_kernel   one lane per 64 rows: a Boolean result from the masks and the branches' bitmaps
-//   case_select_fixed_kernel  one lane per row, widths 1 / 2 / 4 / 8 / 16: the value of the chosen branch only; validity word
-//                             by one ballot, null count by one atomic per wave
+//   case_select_fixed_kernel  one lane per row, widths 1 / 2 / 4 / 8 / 16: the value of the chosen branch only
 //   case_rows_kernel          one lane per row: byte length and validity of a Utf8 result (scan.hip turns them into offsets)
 //   case_gather_kernel        the bytes of every Utf8 result row from its chosen source; lane per row, or wave per row when
 //                             the wave's 64 rows hold more than CASE_WAVE_MODE_BYTES
+// The last three are on the row-wise scheme of wave_rows.h; the first three launch on its grid, a lane per word.  Every launch
+// is rows_grid(items, 256 * 32): one thread per item, `blocks > 256 * 32 ? 256 * 32 : blocks` workgroups (tests/test_gpu_case.py
+// sizes its second-pass case from this line).
 // Every load of a branch is of a row < nrows on which that branch is chosen and valid; every mask word index is below `words`.
 #include <hip/hip_runtime.h>
 
 #include "case_device.h"
+#include "typed_ops.h"   // rows_grid
+#include "wave_rows.h"
 
 namespace chq {
 namespace {
@@ -44,13 +48,6 @@ __global__ __launch_bounds__(256) void case_and_kernel(const CaseAndParams p) {
   }
 }
 
-// the nulls of one wave's rows, added by one lane: `nulls` is per lane
-__device__ __forceinline__ void add_nulls(u64* null_count, unsigned nulls) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) nulls += __shfl_xor(nulls, o, 64);
-  if ((threadIdx.x & 63) == 0 && nulls) atomicAdd(null_count, (u64)nulls);
-}
-
 __global__ __launch_bounds__(256) void case_select_bool_kernel(const CaseSelectParams p) {
   unsigned nulls = 0;
   for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < p.words; w += (int64_t)gridDim.x * 256) {
@@ -64,10 +61,9 @@ __global__ __launch_bounds__(256) void case_select_bool_kernel(const CaseSelectP
 }
 
 template <int W>
-__global__ __launch_bounds__(256) void case_select_fixed_kernel(const CaseSelectParams p) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + lane;
+__global__ __launch_bounds__(kRowsBlock) void case_select_fixed_kernel(const CaseSelectParams p) {
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id(), wave_end = wave_rows_end(p.nrows, base);
     bool valid = false;
     if (i < p.nrows) {
       const CaseBranch& b = p.br[case_choice(p.masks, p.words, p.n_when, i)];
@@ -79,20 +75,13 @@ __global__ __launch_bounds__(256) void case_select_fixed_kernel(const CaseSelect
         case_copy_value<W>(zero, i, out);
       }
     }
-    const u64 vm = __ballot(valid);
-    if (lane == 0) {
-      p.out_validity[base >> 6] = vm;
-      const int64_t rows = p.nrows - base < 64 ? p.nrows - base : 64;
-      const unsigned nulls = (unsigned)rows - (unsigned)__popcll(vm);
-      if (nulls) atomicAdd(p.null_count, (u64)nulls);
-    }
+    store_validity_word(p.out_validity, p.null_count, base, wave_end, __ballot(valid));
   }
 }
 
-__global__ __launch_bounds__(256) void case_rows_kernel(const CaseSelectParams p) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + lane;
+__global__ __launch_bounds__(kRowsBlock) void case_rows_kernel(const CaseSelectParams p) {
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id(), wave_end = wave_rows_end(p.nrows, base);
     bool valid = false;
     if (i < p.nrows) {
       const CaseBranch& b = p.br[case_choice(p.masks, p.words, p.n_when, i)];
@@ -101,22 +90,14 @@ __global__ __launch_bounds__(256) void case_rows_kernel(const CaseSelectParams p
       if (valid) case_string_range(b, i, &first, &len);
       p.out_len[i] = len;
     }
-    const u64 vm = __ballot(valid);
-    if (lane == 0) {
-      p.out_validity[base >> 6] = vm;
-      const int64_t rows = p.nrows - base < 64 ? p.nrows - base : 64;
-      const unsigned nulls = (unsigned)rows - (unsigned)__popcll(vm);
-      if (nulls) atomicAdd(p.null_count, (u64)nulls);
-    }
+    store_validity_word(p.out_validity, p.null_count, base, wave_end, __ballot(valid));
   }
 }
 
 // Rows whose output is empty (null rows among them) read nothing.  out_offsets has nrows + 1 entries.
-__global__ __launch_bounds__(256) void case_gather_kernel(const CaseSelectParams p) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + lane;
-    const int64_t wave_end = p.nrows - base < 64 ? p.nrows : base + 64;
+__global__ __launch_bounds__(kRowsBlock) void case_gather_kernel(const CaseSelectParams p) {
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id(), wave_end = wave_rows_end(p.nrows, base);
     int32_t ob = 0, n = 0;
     const uint8_t* src = nullptr;
     if (i < p.nrows) {
@@ -129,42 +110,25 @@ __global__ __launch_bounds__(256) void case_gather_kernel(const CaseSelectParams
         src = b.data + first;
       }
     }
-    if ((int64_t)p.out_offsets[wave_end] - (int64_t)p.out_offsets[base] > CASE_WAVE_MODE_BYTES) {
-      for (u64 todo = __ballot(n > 0); todo; todo &= todo - 1) {
-        const int row = __ffsll((long long)todo) - 1;
-        const uint8_t* s = (const uint8_t*)__shfl((u64)(uintptr_t)src, row);
-        uint8_t* dst = p.out_data + __shfl(ob, row);
-        const int32_t rn = __shfl(n, row);
-        for (int32_t j = lane; j < rn; j += 64) dst[j] = s[j];
-      }
-    } else {
-      uint8_t* dst = p.out_data + ob;
-      for (int32_t j = 0; j < n; ++j) dst[j] = src[j];
-    }
+    copy_rows(wave_spans_more_than(p.out_offsets, base, wave_end, CASE_WAVE_MODE_BYTES), src, p.out_data, ob, n);
   }
-}
-
-// the grid of typed_ops.hip's grid_for: one thread per item, capped; the kernels walk the rest in passes
-unsigned grid_for(int64_t items) {
-  const int64_t blocks = (items + 255) / 256;
-  return (unsigned)(blocks < 1 ? 1 : blocks > 256 * 32 ? 256 * 32 : blocks);
 }
 }  // namespace
 
 hipError_t launch_case_masks(const CaseMasksParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(case_masks_kernel, dim3(grid_for(p.words)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(case_masks_kernel, dim3(rows_grid(p.words, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_case_and(const CaseAndParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(case_and_kernel, dim3(grid_for((p.nrows + 63) / 64)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(case_and_kernel, dim3(rows_grid((p.nrows + 63) / 64, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_case_select_bool(const CaseSelectParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(case_select_bool_kernel, dim3(grid_for(p.words)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(case_select_bool_kernel, dim3(rows_grid(p.words, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_case_select_fixed(const CaseSelectParams& p, hipStream_t stream) {
-  const dim3 grid(grid_for(p.nrows)), block(256);
+  const dim3 grid(rows_grid(p.nrows, 256 * 32)), block(256);
   switch (p.width) {
     case 1: hipLaunchKernelGGL(case_select_fixed_kernel<1>, grid, block, 0, stream, p); break;
     case 2: hipLaunchKernelGGL(case_select_fixed_kernel<2>, grid, block, 0, stream, p); break;
@@ -176,11 +140,11 @@ hipError_t launch_case_select_fixed(const CaseSelectParams& p, hipStream_t strea
   return hipGetLastError();
 }
 hipError_t launch_case_rows(const CaseSelectParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(case_rows_kernel, dim3(grid_for(p.nrows)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(case_rows_kernel, dim3(rows_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_case_gather(const CaseSelectParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(case_gather_kernel, dim3(grid_for(p.nrows)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(case_gather_kernel, dim3(rows_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 }  // namespace chq

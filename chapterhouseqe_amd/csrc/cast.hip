@@ -8,19 +8,21 @@
 //   cast_len_kernel           integer / Boolean -> Utf8, step 1: the byte length of every row from the value alone.
 //   (scan.hip)                step 2: launch_offsets_scan -> Int32 offsets and the 64-bit byte total.
 //   cast_write_kernel         step 3: every lane writes its row's bytes at its offset.
-// All of them: a wave per 64 rows, rounds of a capped grid (CAST_GRID_CAP); loads and stores of consecutive rows by
-// consecutive lanes; a word of an output bitmap is its wave's ballot, stored whole by lane 0 -- nothing is written with
-// atomics.  A failing VALID row of a CAST makes lane 0 of its wave store 1 into the flag word (a plain vector store; every
-// writer writes the same value).  Null counts come from count_bits_kernel over the output validity.
+// The first three are on the row loop of wave_rows.h but not on its epilogue: nothing here is written with atomics, null counts
+// come from count_bits_kernel over the output validity, and lane 0 stores the validity word and the failure flag in one block (a
+// failing VALID row of a CAST makes it store 1 into the flag word: a plain vector store, every writer writes the same value).
+// The grid of all four is capped at CAST_GRID_CAP.
 // Every load of string data is a byte load inside [offsets[i], offsets[i + 1]) of a VALID row i < nrows.
 #include <hip/hip_runtime.h>
 
 #include "cast_device.h"
-#include "scan_device.h"   // bit_at
+#include "typed_ops.h"   // rows_grid
+#include "wave_rows.h"
 
 namespace chq {
 namespace {
 typedef unsigned long long u64;
+static_assert(CAST_BLOCK == kRowsBlock, "cast.hip runs on the row loop and the grid of wave_rows.h");
 
 enum CastClass { CC_BOOL = 0, CC_INT = 1, CC_FLOAT = 2 };
 
@@ -55,14 +57,13 @@ __device__ __forceinline__ void store_value(void* out, int64_t i, int width, uin
 
 template <int S, int D>
 __global__ __launch_bounds__(CAST_BLOCK) void cast_fixed_kernel(const CastFixedParams p) {
-  const int lane = threadIdx.x & 63;
   const int width = cast_width(p.to);
-  for (int64_t base = ((int64_t)blockIdx.x * CAST_BLOCK + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * CAST_BLOCK) {
-    const int64_t i = base + lane;
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id();
     bool valid = false, ok = false;
     uint64_t out = 0;
     if (i < p.nrows) {
-      valid = !p.validity || bit_at(p.validity, p.validity_offset + i);
+      valid = row_valid(p.validity, p.validity_offset, i);
       // (the value of a null row is read -- it lies inside the buffer -- but never judged)
       ok = cast_fixed_value(load_value<S>(p.values, p.values_offset, i, p.from), p.from, p.to, &out);
     }
@@ -70,11 +71,11 @@ __global__ __launch_bounds__(CAST_BLOCK) void cast_fixed_kernel(const CastFixedP
     if (!(valid && ok)) out = 0;
     if (D == CC_BOOL) {
       const u64 rm = __ballot(out != 0);
-      if (lane == 0) ((u64*)p.out_values)[base >> 6] = rm;
+      if (lane_id() == 0) ((u64*)p.out_values)[base >> 6] = rm;
     } else if (i < p.nrows) {
       store_value(p.out_values, i, width, out);
     }
-    if (lane == 0) {
+    if (lane_id() == 0) {
       p.out_validity[base >> 6] = vm;
       if (fm != 0 && !p.try_cast) *p.fail = 1u;
     }
@@ -82,20 +83,19 @@ __global__ __launch_bounds__(CAST_BLOCK) void cast_fixed_kernel(const CastFixedP
 }
 
 __global__ __launch_bounds__(CAST_BLOCK) void cast_parse_kernel(const CastParseParams p) {
-  const int lane = threadIdx.x & 63;
   const int width = cast_width(p.to);
-  for (int64_t base = ((int64_t)blockIdx.x * CAST_BLOCK + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * CAST_BLOCK) {
-    const int64_t i = base + lane;
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id();
     bool valid = false, ok = false;
     uint64_t out = 0;
-    if (i < p.nrows && (!p.validity || bit_at(p.validity, p.validity_offset + i))) {
+    if (i < p.nrows && row_valid(p.validity, p.validity_offset, i)) {
       valid = true;
       const int32_t b = p.offsets[i], e = p.offsets[i + 1];
       ok = cast_parse_int(p.data + b, e - b, p.to, &out);
     }
     const u64 vm = __ballot(valid && ok), fm = __ballot(valid && !ok);
     if (i < p.nrows) store_value(p.out_values, i, width, ok ? out : 0);
-    if (lane == 0) {
+    if (lane_id() == 0) {
       p.out_validity[base >> 6] = vm;
       if (fm != 0 && !p.try_cast) *p.fail = 1u;
     }
@@ -104,19 +104,18 @@ __global__ __launch_bounds__(CAST_BLOCK) void cast_parse_kernel(const CastParseP
 
 template <int S>
 __global__ __launch_bounds__(CAST_BLOCK) void cast_len_kernel(const CastPrintParams p) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = ((int64_t)blockIdx.x * CAST_BLOCK + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * CAST_BLOCK) {
-    const int64_t i = base + lane;
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id();
     bool valid = false;
     uint32_t len = 0;
-    if (i < p.nrows && (!p.validity || bit_at(p.validity, p.validity_offset + i))) {
+    if (i < p.nrows && row_valid(p.validity, p.validity_offset, i)) {
       valid = true;
       const uint64_t v = load_value<S>(p.values, p.values_offset, i, p.from);
       len = (uint32_t)(S == CC_BOOL ? cast_bool_len(v != 0) : cast_decimal_len(v, cast_is_signed(p.from)));
     }
     const u64 vm = __ballot(valid);
     if (i < p.nrows) p.out_len[i] = len;
-    if (lane == 0) p.out_validity[base >> 6] = vm;
+    if (lane_id() == 0) p.out_validity[base >> 6] = vm;
   }
 }
 
@@ -131,15 +130,11 @@ __global__ __launch_bounds__(CAST_BLOCK) void cast_write_kernel(const CastPrintP
   }
 }
 
-unsigned cast_grid(int64_t nrows) {
-  const int64_t blocks = (nrows + CAST_BLOCK - 1) / CAST_BLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > CAST_GRID_CAP ? CAST_GRID_CAP : blocks);
-}
 int class_of(int t) { return t == CT_BOOL ? CC_BOOL : cast_is_int(t) ? CC_INT : CC_FLOAT; }
 }  // namespace
 
 hipError_t launch_cast_fixed(const CastFixedParams& p, hipStream_t stream) {
-  const dim3 grid(cast_grid(p.nrows)), block(CAST_BLOCK);
+  const dim3 grid(rows_grid(p.nrows, CAST_GRID_CAP)), block(CAST_BLOCK);
 #define CHQ_CAST_CASE(S, D) \
   case (S) * 3 + (D): hipLaunchKernelGGL((cast_fixed_kernel<S, D>), grid, block, 0, stream, p); break;
   switch (class_of(p.from) * 3 + class_of(p.to)) {
@@ -152,17 +147,17 @@ hipError_t launch_cast_fixed(const CastFixedParams& p, hipStream_t stream) {
   return hipGetLastError();
 }
 hipError_t launch_cast_parse(const CastParseParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(cast_parse_kernel, dim3(cast_grid(p.nrows)), dim3(CAST_BLOCK), 0, stream, p);
+  hipLaunchKernelGGL(cast_parse_kernel, dim3(rows_grid(p.nrows, CAST_GRID_CAP)), dim3(CAST_BLOCK), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_cast_len(const CastPrintParams& p, hipStream_t stream) {
-  if (p.from == CT_BOOL) hipLaunchKernelGGL(cast_len_kernel<CC_BOOL>, dim3(cast_grid(p.nrows)), dim3(CAST_BLOCK), 0, stream, p);
-  else hipLaunchKernelGGL(cast_len_kernel<CC_INT>, dim3(cast_grid(p.nrows)), dim3(CAST_BLOCK), 0, stream, p);
+  if (p.from == CT_BOOL) hipLaunchKernelGGL(cast_len_kernel<CC_BOOL>, dim3(rows_grid(p.nrows, CAST_GRID_CAP)), dim3(CAST_BLOCK), 0, stream, p);
+  else hipLaunchKernelGGL(cast_len_kernel<CC_INT>, dim3(rows_grid(p.nrows, CAST_GRID_CAP)), dim3(CAST_BLOCK), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_cast_write(const CastPrintParams& p, hipStream_t stream) {
-  if (p.from == CT_BOOL) hipLaunchKernelGGL(cast_write_kernel<CC_BOOL>, dim3(cast_grid(p.nrows)), dim3(CAST_BLOCK), 0, stream, p);
-  else hipLaunchKernelGGL(cast_write_kernel<CC_INT>, dim3(cast_grid(p.nrows)), dim3(CAST_BLOCK), 0, stream, p);
+  if (p.from == CT_BOOL) hipLaunchKernelGGL(cast_write_kernel<CC_BOOL>, dim3(rows_grid(p.nrows, CAST_GRID_CAP)), dim3(CAST_BLOCK), 0, stream, p);
+  else hipLaunchKernelGGL(cast_write_kernel<CC_INT>, dim3(rows_grid(p.nrows, CAST_GRID_CAP)), dim3(CAST_BLOCK), 0, stream, p);
   return hipGetLastError();
 }
 }  // namespace chq

@@ -1,9 +1,7 @@
-// like.hip -- gfx950 kernel of `column [NOT] LIKE 'pattern'`.  Like the other typed operations
-// (typed_ops.hip) it writes a temporary Boolean column: one wave owns 64 consecutive rows and stores one 64-bit value word
-// and one validity word from ballots; the null count takes one atomic per wave.  The matcher is like_device.h's, the same
-// code the host folds literals with.
+// like.hip -- gfx950 kernel of `column [NOT] LIKE 'pattern'`: a temporary Boolean column on the
+// row-wise scheme of wave_rows.h.  The matcher is like_device.h's, the same code the host folds literals with.
 //
-// Two modes, picked per wave from the bytes its 64 rows span (offsets[base + 64] - offsets[base], no host decision):
+// Two modes, picked per wave from the bytes its rows span (wave_spans_more_than, no host decision):
 //   lane per row   each lane runs like_match on its own row.  Patterns whose `%` stand only at the ends (`abc%`, `%abc`,
 //                  none at all) are decided by like_ends alone, which reads the two ends and never the body.
 //   wave per row   more than LIKE_WAVE_MODE_BYTES in the wave and the pattern has pieces to search for: the wave takes its
@@ -14,7 +12,8 @@
 #include <hip/hip_runtime.h>
 
 #include "like_device.h"
-#include "scan_device.h"   // bit_at
+#include "typed_ops.h"   // rows_grid
+#include "wave_rows.h"
 
 namespace chq {
 namespace {
@@ -38,20 +37,19 @@ __device__ bool wave_search(const LikePattern& pat, const uint8_t* s, int32_t po
   return true;
 }
 
-__global__ __launch_bounds__(256) void like_kernel(const LikeParams p) {
-  const int lane = threadIdx.x & 63;
+__global__ __launch_bounds__(kRowsBlock) void like_kernel(const LikeParams p) {
+  const int lane = lane_id();
   const bool has_middle = p.pat.first_end < p.pat.last_begin;
-  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + lane;
-    const int64_t wave_end = p.nrows - base < 64 ? p.nrows : base + 64;   // (no offset of a row >= nrows is read)
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id(), wave_end = wave_rows_end(p.nrows, base);
     bool valid = false, r = false;
     int32_t b = 0, e = 0;
     if (i < p.nrows) {
-      valid = !p.validity || bit_at(p.validity, p.validity_offset + i);
+      valid = row_valid(p.validity, p.validity_offset, i);
       b = p.offsets[i]; e = p.offsets[i + 1];
     }
     const u64 vm = __ballot(valid);
-    if (has_middle && (int64_t)p.offsets[wave_end] - (int64_t)p.offsets[base] > LIKE_WAVE_MODE_BYTES) {
+    if (has_middle && wave_spans_more_than(p.offsets, base, wave_end, LIKE_WAVE_MODE_BYTES)) {
       for (u64 todo = vm; todo; todo &= todo - 1) {
         const int row = __ffsll((long long)todo) - 1;
         const int32_t rb = __shfl(b, row), re = __shfl(e, row);
@@ -64,19 +62,14 @@ __global__ __launch_bounds__(256) void like_kernel(const LikeParams p) {
       r = like_match(p.pat, p.data + b, e - b);
     }
     const u64 rm = __ballot(valid && (r != (p.negated != 0)));
-    if (lane == 0) {
-      p.out_bits[base >> 6] = rm;
-      p.out_validity[base >> 6] = vm;
-      const unsigned nulls = (unsigned)(wave_end - base) - (unsigned)__popcll(vm);
-      if (nulls) atomicAdd(p.null_count, (u64)nulls);
-    }
+    if (lane == 0) p.out_bits[base >> 6] = rm;
+    store_validity_word(p.out_validity, p.null_count, base, wave_end, vm);
   }
 }
 }  // namespace
 
 hipError_t launch_like(const LikeParams& p, hipStream_t stream) {
-  const int64_t blocks = (p.nrows + 255) / 256;
-  hipLaunchKernelGGL(like_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 256 * 32 ? 256 * 32 : blocks)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(like_kernel, dim3(rows_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 }  // namespace chq

@@ -4,18 +4,19 @@
 //   strfn_bytemap_kernel   UPPER / LOWER: a flat map over the column's byte range, oblivious of rows.  16-byte aligned loads
 //                          in the body (stores at whatever phase the output has), single bytes at the ragged ends.
 //   strfn_rebase_kernel    the offsets of a length-preserving function: the input's, rebased to 0.
-//   strfn_rows_kernel      one wave per 64 rows: LENGTH / OCTET_LENGTH values, the SUBSTRING / TRIM window of each row, the
-//                          row lengths of `||`; validity word and null count like typed_ops.hip.  Two modes like like.hip:
-//                          lane per row, or -- more than STRFN_WAVE_MODE_BYTES in the wave's 64 rows -- wave per row with a
-//                          ballot + popcount per 64-byte step.
+//   strfn_rows_kernel      LENGTH / OCTET_LENGTH values, the SUBSTRING / TRIM window of each row, the row lengths of `||`, on
+//                          the row-wise scheme of wave_rows.h.  Two modes like like.hip: lane per row, or -- more than
+//                          STRFN_WAVE_MODE_BYTES in the wave's rows -- wave per row with a ballot + popcount per 64-byte step.
 //   (scan.hip)             exclusive scan of the row lengths -> Int32 offsets and the 64-bit byte total: launch_offsets_scan.
-//   strfn_gather_kernel    the bytes of every output row from 1 source range or up to STRFN_MAX_PARTS parts; same two modes.
+//   strfn_gather_kernel    the bytes of every output row from 1 source range (copy_rows) or up to STRFN_MAX_PARTS parts (its
+//                          own loops: the parts of a row are written one behind the other before the next row); same two modes.
 // Every load of string data is a byte load inside [offsets[i], offsets[i + 1]) of a VALID row i < nrows (the byte map: inside
 // [offsets[0], offsets[nrows])): no padding is assumed, and data may be null when there are no bytes.
 #include <hip/hip_runtime.h>
 
-#include "scan_device.h"
 #include "strfn_device.h"
+#include "typed_ops.h"   // rows_grid
+#include "wave_rows.h"
 
 namespace chq {
 namespace {
@@ -101,22 +102,21 @@ __device__ void wave_trim(const uint8_t* s, int32_t n, bool left, bool right, in
   *first = b; *len = e - b;
 }
 
-__global__ __launch_bounds__(256) void strfn_rows_kernel(const StrRowsParams p) {
-  const int lane = threadIdx.x & 63;
+__global__ __launch_bounds__(kRowsBlock) void strfn_rows_kernel(const StrRowsParams p) {
+  const int lane = lane_id();
   const StrPart& a = p.part[0];
   const int fn = p.fn;
   // (SUBSTRING from the row's first byte to its end needs no data at all)
   const bool reads_data = fn == STRFN_LENGTH || fn == STRFN_TRIM || fn == STRFN_LTRIM || fn == STRFN_RTRIM ||
                           (fn == STRFN_SUBSTRING && (p.p > 1 || p.has_cnt));
-  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + lane;
-    const int64_t wave_end = p.nrows - base < 64 ? p.nrows : base + 64;   // (no offset of a row >= nrows is read)
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id(), wave_end = wave_rows_end(p.nrows, base);
     bool valid = false;
     int32_t b = 0, e = 0;
     if (i < p.nrows) {
       valid = true;
       for (int k = 0; k < p.n_parts; ++k)
-        if (p.part[k].validity && !bit_at(p.part[k].validity, p.part[k].validity_offset + i)) valid = false;
+        if (!row_valid(p.part[k].validity, p.part[k].validity_offset, i)) valid = false;
       if (a.offsets) { b = a.offsets[i]; e = a.offsets[i + 1]; }
     }
     const u64 vm = __ballot(valid);
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void strfn_rows_kernel(const StrRowsParams p) 
       }
     } else if (fn == STRFN_OCTET_LENGTH) {
       if (valid) out = e - b;
-    } else if (reads_data && (int64_t)a.offsets[wave_end] - (int64_t)a.offsets[base] > STRFN_WAVE_MODE_BYTES) {
+    } else if (reads_data && wave_spans_more_than(a.offsets, base, wave_end, STRFN_WAVE_MODE_BYTES)) {
       for (u64 todo = vm; todo; todo &= todo - 1) {
         const int row = __ffsll((long long)todo) - 1;
         const int32_t rb = __shfl(b, row), n = __shfl(e, row) - rb;
@@ -153,80 +153,61 @@ __global__ __launch_bounds__(256) void strfn_rows_kernel(const StrRowsParams p) 
       p.out_i32[i] = out;
       if (p.out_start) p.out_start[i] = start;
     }
-    if (lane == 0) {
-      p.out_validity[base >> 6] = vm;
-      const unsigned nulls = (unsigned)(wave_end - base) - (unsigned)__popcll(vm);
-      if (nulls) atomicAdd(p.null_count, (u64)nulls);
-    }
+    store_validity_word(p.out_validity, p.null_count, base, wave_end, vm);
   }
 }
 
 // ---- gather ----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void strfn_gather_kernel(const StrGatherParams p) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + lane;
-    const int64_t wave_end = p.nrows - base < 64 ? p.nrows : base + 64;
+__global__ __launch_bounds__(kRowsBlock) void strfn_gather_kernel(const StrGatherParams p) {
+  const int lane = lane_id();
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id(), wave_end = wave_rows_end(p.nrows, base);
     int32_t ob = 0, oe = 0;
     if (i < p.nrows) { ob = p.out_offsets[i]; oe = p.out_offsets[i + 1]; }
-    const bool wave_mode = (int64_t)p.out_offsets[wave_end] - (int64_t)p.out_offsets[base] > STRFN_WAVE_MODE_BYTES;
-    if (wave_mode) {
+    const bool wave_mode = wave_spans_more_than(p.out_offsets, base, wave_end, STRFN_WAVE_MODE_BYTES);
+    if (p.start) {
+      copy_rows(wave_mode, oe > ob ? p.part[0].data + p.start[i] : nullptr, p.out_data, ob, oe - ob);
+    } else if (wave_mode) {
       for (u64 todo = __ballot(oe > ob); todo; todo &= todo - 1) {
         const int row = __ffsll((long long)todo) - 1;
         const int64_t r = base + row;
         uint8_t* dst = p.out_data + __shfl(ob, row);
-        if (p.start) {
-          const uint8_t* src = p.part[0].data + p.start[r];
-          const int32_t n = __shfl(oe, row) - __shfl(ob, row);
-          for (int32_t j = lane; j < n; j += 64) dst[j] = src[j];
-        } else {
-          for (int k = 0; k < p.n_parts; ++k) {
-            const StrPart& q = p.part[k];
-            const int32_t sb = q.offsets ? q.offsets[r] : 0;
-            const int32_t n = q.offsets ? q.offsets[r + 1] - sb : q.lit_len;
-            for (int32_t j = lane; j < n; j += 64) dst[j] = q.data[sb + j];
-            dst += n;
-          }
+        for (int k = 0; k < p.n_parts; ++k) {
+          const StrPart& q = p.part[k];
+          const int32_t sb = q.offsets ? q.offsets[r] : 0;
+          const int32_t n = q.offsets ? q.offsets[r + 1] - sb : q.lit_len;
+          for (int32_t j = lane; j < n; j += 64) dst[j] = q.data[sb + j];
+          dst += n;
         }
       }
     } else if (oe > ob) {
       uint8_t* dst = p.out_data + ob;
-      if (p.start) {
-        const uint8_t* src = p.part[0].data + p.start[i];
-        for (int32_t j = 0; j < oe - ob; ++j) dst[j] = src[j];
-      } else {
-        for (int k = 0; k < p.n_parts; ++k) {
-          const StrPart& q = p.part[k];
-          const int32_t sb = q.offsets ? q.offsets[i] : 0;
-          const int32_t n = q.offsets ? q.offsets[i + 1] - sb : q.lit_len;
-          for (int32_t j = 0; j < n; ++j) dst[j] = q.data[sb + j];
-          dst += n;
-        }
+      for (int k = 0; k < p.n_parts; ++k) {
+        const StrPart& q = p.part[k];
+        const int32_t sb = q.offsets ? q.offsets[i] : 0;
+        const int32_t n = q.offsets ? q.offsets[i + 1] - sb : q.lit_len;
+        for (int32_t j = 0; j < n; ++j) dst[j] = q.data[sb + j];
+        dst += n;
       }
     }
   }
 }
-
-unsigned capped_grid(int64_t items, int64_t cap) {
-  const int64_t blocks = (items + 255) / 256;
-  return (unsigned)(blocks < 1 ? 1 : blocks > cap ? cap : blocks);
-}
 }  // namespace
 
 hipError_t launch_strfn_bytemap(const StrByteMapParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(strfn_bytemap_kernel, dim3(capped_grid(p.n / 16 + 1, 256 * 16)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(strfn_bytemap_kernel, dim3(rows_grid(p.n / 16 + 1, 256 * 16)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_strfn_rebase(const StrRebaseParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(strfn_rebase_kernel, dim3(capped_grid(p.n, 256 * 16)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(strfn_rebase_kernel, dim3(rows_grid(p.n, 256 * 16)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_strfn_rows(const StrRowsParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(strfn_rows_kernel, dim3(capped_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(strfn_rows_kernel, dim3(rows_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_strfn_gather(const StrGatherParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(strfn_gather_kernel, dim3(capped_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(strfn_gather_kernel, dim3(rows_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 }  // namespace chq

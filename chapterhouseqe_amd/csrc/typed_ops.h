@@ -4,6 +4,13 @@
 #include <stdint.h>
 
 namespace chq {
+// The launch grid of typed_ops.hip, like.hip, strfn.hip, case.hip and cast.hip: one thread per item in workgroups of 256
+// (wave_rows.h: kRowsBlock), at least one workgroup and at most cap_blocks; the kernels walk what is left in rounds.
+inline unsigned rows_grid(int64_t items, int64_t cap_blocks) {
+  const int64_t blocks = (items + 255) / 256;
+  return (unsigned)(blocks < 1 ? 1 : blocks > cap_blocks ? cap_blocks : blocks);
+}
+
 // Uniform-length Utf8 columns (keys, hashes, the reference's sample strings): utf8_uniform_kernel checks that every value
 // of a column has the length of the first one; out = {1 if some value differs, that length, offsets[0]}.
 // iota_offsets_kernel writes the offsets of n values of L bytes: 0, L, 2 L, ...

@@ -1,25 +1,23 @@
 // typed_ops.hip -- gfx950 kernels for the corners of the reference's type coverage that are not instructions of the
-// accumulator machine (device_program.h): Decimal128 comparisons, the Utf8 -> Boolean cast under AND / OR and IS [NOT] NULL.
-// Each is one pass over its input (32 B/row, the string bytes, the validity bitmap), one thread per row, one 64-bit ballot
-// per wave as output.
+// accumulator machine (device_program.h): Decimal128 comparisons, the Utf8 -> Boolean cast under AND / OR and IS [NOT] NULL,
+// on the row-wise scheme of wave_rows.h.  Each is one pass over its input (32 B/row, the string bytes, the validity bitmap).
 #include <hip/hip_runtime.h>
 
 #include "device_program.h"
-#include "scan_device.h"   // bit_at
 #include "typed_ops.h"
+#include "wave_rows.h"
 
 namespace chq {
 namespace {
 
 // arrow-ord cmp::{eq,neq,lt,lt_eq,gt,gt_eq} on i128 natives (RU/compute_value.rs:118-209 after the `left == right` arm of
 // get_common_type, :355).  Validity = both valid.
-__global__ __launch_bounds__(256) void cmp128_kernel(const Cmp128Params p) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + lane;
+__global__ __launch_bounds__(kRowsBlock) void cmp128_kernel(const Cmp128Params p) {
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id(), wave_end = wave_rows_end(p.nrows, base);
     bool r = false, valid = false;
     if (i < p.nrows) {
-      valid = (!p.a_validity || bit_at(p.a_validity, p.a_validity_offset + i)) && (!p.b_validity || bit_at(p.b_validity, p.b_validity_offset + i));
+      valid = row_valid(p.a_validity, p.a_validity_offset, i) && row_valid(p.b_validity, p.b_validity_offset, i);
       // (Arrow guarantees 8-byte alignment of the buffer only through its producer; 4-byte loads are always safe)
       const uint32_t* pa = (const uint32_t*)p.a + 4 * i;
       const uint32_t* pb = (const uint32_t*)p.b + 4 * i;
@@ -33,13 +31,8 @@ __global__ __launch_bounds__(256) void cmp128_kernel(const Cmp128Params p) {
       }
     }
     const u64 vm = __ballot(valid), rm = __ballot(r && valid);
-    if (lane == 0) {
-      p.out_bits[base >> 6] = rm;
-      p.out_validity[base >> 6] = vm;
-      const int64_t rows = p.nrows - base < 64 ? p.nrows - base : 64;
-      const unsigned nulls = (unsigned)rows - (unsigned)__popcll(vm);
-      if (nulls) atomicAdd(p.null_count, (u64)nulls);
-    }
+    if (lane_id() == 0) p.out_bits[base >> 6] = rm;
+    store_validity_word(p.out_validity, p.null_count, base, wave_end, vm);
   }
 }
 
@@ -95,39 +88,28 @@ __device__ int parse_bool(const uint8_t* p, int n) {
 #undef K5
 }
 
-__global__ __launch_bounds__(256) void utf8_to_bool_kernel(const Utf8ToBoolParams p) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + lane;
+__global__ __launch_bounds__(kRowsBlock) void utf8_to_bool_kernel(const Utf8ToBoolParams p) {
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id(), wave_end = wave_rows_end(p.nrows, base);
     int v = -1;
-    if (i < p.nrows && (!p.validity || bit_at(p.validity, p.validity_offset + i))) {
+    if (i < p.nrows && row_valid(p.validity, p.validity_offset, i)) {
       const int32_t b = p.offsets[i], e = p.offsets[i + 1];
       // a spelling is at most 5 bytes; white space around it is unbounded, so the whole value is scanned
       v = parse_bool(p.data + b, e - b);
     }
     const u64 vm = __ballot(v >= 0), rm = __ballot(v == 1);
-    if (lane == 0) {
-      p.out_bits[base >> 6] = rm;
-      p.out_validity[base >> 6] = vm;
-      const int64_t rows = p.nrows - base < 64 ? p.nrows - base : 64;
-      const unsigned nulls = (unsigned)rows - (unsigned)__popcll(vm);
-      if (nulls) atomicAdd(p.null_count, (u64)nulls);
-    }
+    if (lane_id() == 0) p.out_bits[base >> 6] = rm;
+    store_validity_word(p.out_validity, p.null_count, base, wave_end, vm);
   }
 }
 
 // IS NULL / IS NOT NULL: the result is never null, so only the value words are written
-__global__ __launch_bounds__(256) void is_null_kernel(const IsNullParams p) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) & ~63LL; base < p.nrows; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + lane;
-    bool r = false;
-    if (i < p.nrows) {
-      const bool valid = !p.validity || bit_at(p.validity, p.validity_offset + i);
-      r = valid == (p.negated != 0);
-    }
+__global__ __launch_bounds__(kRowsBlock) void is_null_kernel(const IsNullParams p) {
+  CHQ_FOR_WAVE_ROWS(base, p.nrows) {
+    const int64_t i = base + lane_id();
+    const bool r = i < p.nrows && row_valid(p.validity, p.validity_offset, i) == (p.negated != 0);
     const u64 rm = __ballot(r);
-    if (lane == 0) p.out_bits[base >> 6] = rm;
+    if (lane_id() == 0) p.out_bits[base >> 6] = rm;
   }
 }
 }  // namespace
@@ -159,20 +141,16 @@ __global__ __launch_bounds__(256) void iota_offsets_kernel(const IotaOffsetsPara
 }
 }  // namespace
 
-static int grid_for(int64_t nrows) {
-  const int64_t blocks = (nrows + 255) / 256;
-  return (int)(blocks < 1 ? 1 : blocks > 256 * 32 ? 256 * 32 : blocks);
-}
 hipError_t launch_cmp128(const Cmp128Params& p, hipStream_t stream) {
-  hipLaunchKernelGGL(cmp128_kernel, dim3(grid_for(p.nrows)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(cmp128_kernel, dim3(rows_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_is_null(const IsNullParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(is_null_kernel, dim3(grid_for(p.nrows)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(is_null_kernel, dim3(rows_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_utf8_uniform(const Utf8UniformParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(utf8_uniform_kernel, dim3(grid_for(p.nrows)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(utf8_uniform_kernel, dim3(rows_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_utf8_uniform_group(const Utf8UniformGroupParams& p, int64_t max_rows, hipStream_t stream) {
@@ -186,11 +164,11 @@ hipError_t launch_utf8_uniform_group(const Utf8UniformGroupParams& p, int64_t ma
   return hipGetLastError();
 }
 hipError_t launch_iota_offsets(const IotaOffsetsParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(iota_offsets_kernel, dim3(grid_for(p.n_plus_1)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(iota_offsets_kernel, dim3(rows_grid(p.n_plus_1, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_utf8_to_bool(const Utf8ToBoolParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(utf8_to_bool_kernel, dim3(grid_for(p.nrows)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(utf8_to_bool_kernel, dim3(rows_grid(p.nrows, 256 * 32)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 }  // namespace chq

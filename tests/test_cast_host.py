@@ -416,12 +416,19 @@ def test_round_sizes_of_the_gpu_tests():
     kernels = open(os.path.join(CSRC, "cast.hip")).read()
     const = lambda name: int(eval(re.search(r"constexpr\s+int\s+" + name + r"\s*=\s*([\d *]+);", header).group(1)))
     cap, block = const("CAST_GRID_CAP"), const("CAST_BLOCK")
-    # every launch of cast.hip goes through cast_grid: capped at CAST_GRID_CAP workgroups of CAST_BLOCK threads, a row per thread
-    assert "blocks > CAST_GRID_CAP ? CAST_GRID_CAP : blocks" in kernels
+    # every launch of cast.hip goes through rows_grid (typed_ops.h): capped at CAST_GRID_CAP workgroups of CAST_BLOCK threads, a
+    # row per thread.  The clamp and the round loop are the shared ones, written for workgroups of kRowsBlock = CAST_BLOCK threads.
+    shared, grid = (open(os.path.join(CSRC, name)).read() for name in ("wave_rows.h", "typed_ops.h"))
+    assert "static_assert(CAST_BLOCK == kRowsBlock," in kernels and f"constexpr int kRowsBlock = {block};" in shared
+    assert grid.count("inline unsigned rows_grid(int64_t items, int64_t cap_blocks) {") == 1 and f"blocks = (items + {block - 1}) / {block};" in grid
+    assert grid.count("blocks < 1 ? 1 : blocks > cap_blocks ? cap_blocks : blocks") == 1 and "blocks >" not in kernels
     launches = re.findall(r"hipLaunchKernelGGL\((.*?), (dim3\(.*?\)|grid), (dim3\(.*?\)|block), 0, stream, p\)", kernels)
-    assert len(launches) == 6 and all(g in ("dim3(cast_grid(p.nrows))", "grid") and b in ("dim3(CAST_BLOCK)", "block") for _, g, b in launches), launches
-    assert "const dim3 grid(cast_grid(p.nrows)), block(CAST_BLOCK);" in kernels
-    assert kernels.count("+= (int64_t)gridDim.x * CAST_BLOCK") == 4 and kernels.count("__launch_bounds__(CAST_BLOCK)") == 4
+    assert len(launches) == 6 == kernels.count("hipLaunchKernelGGL(")
+    assert all(g in ("dim3(rows_grid(p.nrows, CAST_GRID_CAP))", "grid") and b in ("dim3(CAST_BLOCK)", "block") for _, g, b in launches), launches
+    assert "const dim3 grid(rows_grid(p.nrows, CAST_GRID_CAP)), block(CAST_BLOCK);" in kernels
+    assert kernels.count("CHQ_FOR_WAVE_ROWS(base, p.nrows) {") == 3 and shared.count("base += (int64_t)gridDim.x * kRowsBlock)") == 1
+    assert kernels.count("gridDim") == 1 and kernels.count("+= (int64_t)gridDim.x * CAST_BLOCK") == 1   # (cast_write_kernel: a lane per row, no ballot)
+    assert kernels.count("__launch_bounds__(CAST_BLOCK)") == 4
     assert G.GRID_ROWS == cap * block
     # the offsets scan of integer -> Utf8: tiles of STRFN_SCAN_CHUNK rows, one tile total per thread of one workgroup and round
     strfn = open(os.path.join(CSRC, "strfn_device.h")).read()

@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _SRC = open(os.path.join(ROOT, "chapterhouseqe_amd", "csrc", "case.hip")).read()
 _m = re.search(r"blocks > (\d+) \* (\d+) \? \1 \* \2 : blocks", _SRC)
-GRID_ROWS = int(_m.group(1)) * int(_m.group(2)) * 256      # rows one pass of the row kernels' grid covers (case.hip: grid_for)
+GRID_ROWS = int(_m.group(1)) * int(_m.group(2)) * 256      # rows one pass of the row kernels' grid covers (case.hip: the cap of rows_grid, as its head comment quotes it)
 SCAN_TILE = int(re.search(r"STRFN_SCAN_CHUNK\s*=\s*(\d+)", open(os.path.join(ROOT, "chapterhouseqe_amd", "csrc", "strfn_device.h")).read()).group(1))
 WAVE_MODE_BYTES = int(re.search(r"CASE_WAVE_MODE_BYTES\s*=\s*(\d+)", open(os.path.join(ROOT, "chapterhouseqe_amd", "csrc", "case_device.h")).read()).group(1))
 DIV_ZERO, OVERFLOW, INVALID_ARGUMENT = 21, 20, 22

@@ -26,7 +26,7 @@ _HDR = open(os.path.join(ROOT, "chapterhouseqe_amd", "csrc", "like_device.h")).r
 # like.hip: a wave whose 64 rows hold MORE than this many string bytes walks them one at a time, 64 candidate positions per step
 WAVE_MODE_BYTES = int(re.search(r"LIKE_WAVE_MODE_BYTES\s*=\s*(\d+)", _HDR).group(1))
 STEP = 64
-GRID_ROWS = 256 * 32 * 256   # rows one pass of the launch grid covers (typed_ops.hip: grid_for; like.hip: launch_like)
+GRID_ROWS = 256 * 32 * 256   # rows one pass of the launch grid covers (typed_ops.hip, like.hip: the cap of rows_grid)
 
 # (pattern, escape): the fixed table of the CPU tier, the escape forms, and forms with several pieces to search for
 PATTERNS = [(p, None) for p in R.PATTERNS] + [("h_llo", None), ("%é_", None), ("_本%", None), ("%a_b%", None), ("%ab%b", None), ("a%\n%", None),

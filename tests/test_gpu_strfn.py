@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _HDR = open(os.path.join(ROOT, "chapterhouseqe_amd", "csrc", "strfn_device.h")).read()
 WAVE_MODE_BYTES = int(re.search(r"STRFN_WAVE_MODE_BYTES\s*=\s*(\d+)", _HDR).group(1))
 MAX_PARTS = int(re.search(r"STRFN_MAX_PARTS\s*=\s*(\d+)", _HDR).group(1))
-GRID_ROWS = 256 * 32 * 256          # rows one pass of the rows / gather grid covers (strfn.hip: capped_grid)
+GRID_ROWS = 256 * 32 * 256          # rows one pass of the rows / gather grid covers (strfn.hip: the cap of rows_grid)
 GRID_MAP_BYTES = 256 * 16 * 256 * 16  # bytes one pass of the byte map's grid covers
 
 

@@ -235,6 +235,18 @@ def test_decimal128_comparisons_on_slices(ctx, decimal_batches, offset):
             check_kept(chq.filter_record(views[1][0], AL4, parse_expr(f"x1 {op} x2"), ctx=ctx), rec, ids, f"x1 {op} x2 (host slice {offset}, {length})")
 
 
+@pytest.mark.parametrize("rows", [63, 64, 65])
+def test_decimal128_comparisons_row_counts(ctx, decimal_batches, rows):
+    """batches that end a row before, at and a row behind the first wave (one row: the slices above): the last wave's validity
+    word and null count, for an upload of its own and for a view whose validity is read from a bit offset"""
+    rec, dev, valid, _ = decimal_batches["both"]
+    sources = ((chq.DeviceRecordBatch.from_host(rec.slice(0, rows), ctx), 0, "upload"), (dev.slice(7, rows), 7, "device view at 7"))
+    for op in R.CMPS:
+        for src, off, name in sources:
+            got, _ = chq.compute_value(src, AL4, parse_expr(f"x1 {op} x2"), ctx=ctx)
+            same_bools(got, cmp_rows(op, valid)[off:off + rows], f"x1 {op} x2 ({name}, {rows} rows)")
+
+
 @pytest.mark.parametrize("nulls", ["none", "left", "both"])
 def test_decimal128_comparisons_inside_a_program(ctx, decimal_batches, nulls):
     """the Boolean temporary as an operand of the accumulator machine: `x1 < x2 and id > 0`, `x1 = x2 or flag` (flag nullable;

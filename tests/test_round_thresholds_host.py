@@ -104,29 +104,82 @@ def test_tiles_of_the_scans():
     assert G.SCAN_ROWS == G.SCAN_ROUND + G.T + 5 and G.PART_ROWS == G.PART_ROUND + G.T + 5 and G.STRFN_ROWS == G.STRFN_ROUND + G.T + 5
 
 
+# the twelve kernels on the row loop of wave_rows.h (a wave per 64 rows, rounds of the launched grid) ...
+ROW_KERNELS = {"typed_ops.hip": ("cmp128_kernel", "utf8_to_bool_kernel", "is_null_kernel"),
+               "like.hip": ("like_kernel",),
+               "strfn.hip": ("strfn_rows_kernel", "strfn_gather_kernel"),
+               "case.hip": ("case_select_fixed_kernel", "case_rows_kernel", "case_gather_kernel"),
+               "cast.hip": ("cast_fixed_kernel", "cast_parse_kernel", "cast_len_kernel")}
+# ... and every launch of the five files: kernel -> (items, cap in workgroups).  The one launch that is not rows_grid's:
+TWO_DIMENSIONAL = "utf8_uniform_group_kernel"   # grid = (batches, slices of a batch), both sized in launch_utf8_uniform_group
+LAUNCHES = {
+    "typed_ops.hip": {"cmp128_kernel": ("p.nrows", "256 * 32"), "is_null_kernel": ("p.nrows", "256 * 32"), "utf8_uniform_kernel": ("p.nrows", "256 * 32"),
+                      "iota_offsets_kernel": ("p.n_plus_1", "256 * 32"), "utf8_to_bool_kernel": ("p.nrows", "256 * 32"), TWO_DIMENSIONAL: None},
+    "like.hip": {"like_kernel": ("p.nrows", "256 * 32")},
+    "strfn.hip": {"strfn_bytemap_kernel": ("p.n / 16 + 1", "256 * 16"), "strfn_rebase_kernel": ("p.n", "256 * 16"),
+                  "strfn_rows_kernel": ("p.nrows", "256 * 32"), "strfn_gather_kernel": ("p.nrows", "256 * 32")},
+    "case.hip": {"case_masks_kernel": ("p.words", "256 * 32"), "case_and_kernel": ("(p.nrows + 63) / 64", "256 * 32"),
+                 "case_select_bool_kernel": ("p.words", "256 * 32"), "case_select_fixed_kernel": ("p.nrows", "256 * 32"),
+                 "case_rows_kernel": ("p.nrows", "256 * 32"), "case_gather_kernel": ("p.nrows", "256 * 32")},
+    "cast.hip": {"cast_fixed_kernel": ("p.nrows", "CAST_GRID_CAP"), "cast_parse_kernel": ("p.nrows", "CAST_GRID_CAP"),
+                 "cast_len_kernel": ("p.nrows", "CAST_GRID_CAP"), "cast_write_kernel": ("p.nrows", "CAST_GRID_CAP")},
+}
+
+
 def test_caps_of_the_strided_grids():
-    # typed_ops.hip: grid_for caps every launch of the file at 256 * 32 workgroups of 256 threads
-    text = source("typed_ops.hip")
-    cap = only(r"blocks > (\d+ \* \d+) \? (\d+ \* \d+) : blocks", body_of(text, "static int grid_for("))
-    assert product(cap[0]) == product(cap[1]) and G.STRIDE_ROWS == product(cap[0]) * 256
-    for kernel in ("cmp128_kernel", "is_null_kernel", "utf8_to_bool_kernel", "utf8_uniform_kernel"):
-        assert f"{kernel}, dim3(grid_for(p.nrows)), dim3(256)" in text, kernel
-        assert "+= (int64_t)gridDim.x * 256" in body_of(text, f"void {kernel}("), kernel
-    assert "iota_offsets_kernel, dim3(grid_for(p.n_plus_1)), dim3(256)" in text
+    # the round loop is written once, in wave_rows.h (a loop-head macro), and strides by the launched grid of kRowsBlock threads
+    every = {name: source(name) for name in sorted(os.listdir(CSRC)) if name.endswith((".hip", ".h")) and name != "kernels.hip"}
+    head = r"for \(int64_t base = \(\(int64_t\)blockIdx\.x \* (\w+) \+ threadIdx\.x\) & ~63LL; base < ([\w.()]+); base \+= \(int64_t\)gridDim\.x \* (\w+)\)"
+    assert [(name, found) for name, text in every.items() for found in re.findall(head, text)] == [("wave_rows.h", ("kRowsBlock", "(nrows)", "kRowsBlock"))]
+    assert sum(text.count("& ~63LL") for text in every.values()) == 1
+    rows = every["wave_rows.h"]
+    block = constant(rows, "kRowsBlock")
+    assert re.search(r"#define CHQ_FOR_WAVE_ROWS\(base, nrows\) \\\n  for \(int64_t base = [^\n]*& ~63LL;", rows)
+    assert sum(text.count("#define CHQ_FOR_WAVE_ROWS") for text in every.values()) == 1
+    cast_block = constant(every["cast_device.h"], "CAST_BLOCK")
+    assert "static_assert(CAST_BLOCK == kRowsBlock," in every["cast.hip"] and cast_block == block
+    for name, kernels in ROW_KERNELS.items():
+        for kernel in kernels:
+            body = body_of(every[name], f"void {kernel}(")
+            assert body.count("CHQ_FOR_WAVE_ROWS(base, p.nrows) {\n    const int64_t i = base + lane_id()") == 1 == body.count("CHQ_FOR_WAVE_ROWS"), kernel
+            assert "blockIdx" not in body and "gridDim" not in body and body.endswith("\n  }"), kernel   # (no loop of its own around or behind it)
+            assert re.search(r"__launch_bounds__\((kRowsBlock|CAST_BLOCK)\) void " + kernel + r"\(", every[name]), kernel
+    assert sum(len(kernels) for kernels in ROW_KERNELS.values()) == 12 == sum(text.count("CHQ_FOR_WAVE_ROWS(base, p.nrows)") for text in every.values())
 
-    # like.hip: the same cap, spelled out in launch_like
-    text = source("like.hip")
-    cap = only(r"blocks > (\d+ \* \d+) \? (\d+ \* \d+) : blocks\)\), dim3\(256\)", body_of(text, "hipError_t launch_like("))
-    assert product(cap[0]) == product(cap[1]) and G.STRIDE_ROWS == product(cap[0]) * 256
-    assert "+= (int64_t)gridDim.x * 256" in body_of(text, "void like_kernel(")
+    # the clamp is written once, in rows_grid: ceil(items / kRowsBlock) workgroups, at least 1, at most the cap the launch names
+    clamp = "blocks < 1 ? 1 : blocks > cap_blocks ? cap_blocks : blocks"
+    grid = body_of(every["typed_ops.h"], "inline unsigned rows_grid(int64_t items, int64_t cap_blocks) {")
+    assert f"return (unsigned)({clamp});" in grid and f"blocks = (items + {block - 1}) / {block};" in grid
+    assert sum(text.count(clamp) for text in every.values()) == 1
+    code = lambda text: re.sub(r"//[^\n]*", "", text)
+    assert sum(len(re.findall(r"blocks\s*>", code(text))) for name, text in every.items() if name in LAUNCHES or name == "typed_ops.h") == 1
+    # (case.hip's head comment quotes the clamp with its cap for tests/test_gpu_case.py: held to the launches below)
+    assert only(r"// .*`blocks > (\d+ \* \d+) \? \1 : blocks`", every["case.hip"]) == LAUNCHES["case.hip"]["case_rows_kernel"][1]
 
-    # strfn.hip: capped_grid(items, cap) workgroups of 256 threads; the byte map takes 16 bytes per thread
-    text = source("strfn.hip")
-    caps = {kernel: (items, product(cap)) for kernel, items, cap in
-            re.findall(r"hipLaunchKernelGGL\((\w+), dim3\(capped_grid\(([^,]+), (\d+ \* \d+)\)\), dim3\(256\)", text)}
-    assert sorted(caps) == ["strfn_bytemap_kernel", "strfn_gather_kernel", "strfn_rebase_kernel", "strfn_rows_kernel"], caps
-    assert caps["strfn_rows_kernel"] == ("p.nrows", G.STRIDE_ROWS // 256) and caps["strfn_gather_kernel"] == ("p.nrows", G.STRIDE_ROWS // 256)
-    assert caps["strfn_rebase_kernel"] == ("p.n", G.REBASE_ROWS // 256)
-    assert caps["strfn_bytemap_kernel"] == ("p.n / 16 + 1", G.BYTEMAP_BYTES // (256 * 16))
-    assert "nvec = (p.n - head) >> 4" in body_of(text, "void strfn_bytemap_kernel(")
+    # every launch of the five files takes its grid from it, with its cap spelled at the call, and workgroups of kRowsBlock threads
+    caps = {}
+    for name, expected in LAUNCHES.items():
+        text = every[name]
+        launches = re.findall(r"hipLaunchKernelGGL\(\(?(\w+)(?:<[\w, ]+>)?\)?, (dim3\(.+?\)|grid), (dim3\(\w+\)|block), 0, stream, p\)", text)
+        assert len(launches) == text.count("hipLaunchKernelGGL(") and {kernel for kernel, _, _ in launches} == set(expected), (name, launches)
+        for kernel, grid, threads in launches:
+            if grid == "grid":    # (one dim3 for the instantiations of a template)
+                grid, threads = only(r"const dim3 grid\((rows_grid\(.+?\))\), block\((\w+)\);", text)
+                grid, threads = f"dim3({grid})", f"dim3({threads})"
+            assert threads in ("dim3(256)", "dim3(CAST_BLOCK)", "dim3(kRowsBlock)") and block == 256, (kernel, threads)
+            if kernel == TWO_DIMENSIONAL:
+                assert grid == "dim3(gx, (unsigned)gy)"
+                continue
+            items, cap = expected[kernel]
+            assert grid == f"dim3(rows_grid({items}, {cap}))", (kernel, grid)
+            if cap != "CAST_GRID_CAP":   # (tests/test_cast_host.py holds that one to the sizes of the cast tests)
+                caps[kernel] = product(cap)
+
+    # the sizes of tests/test_gpu_rounds.py against those caps; the plain grid-stride loops step by the same 256 threads
+    for kernel in ("cmp128_kernel", "is_null_kernel", "utf8_to_bool_kernel", "utf8_uniform_kernel", "like_kernel", "strfn_rows_kernel", "strfn_gather_kernel"):
+        assert G.STRIDE_ROWS == caps[kernel] * block, kernel
+    assert "+= (int64_t)gridDim.x * 256" in body_of(every["typed_ops.hip"], "void utf8_uniform_kernel(")
+    assert G.REBASE_ROWS == caps["strfn_rebase_kernel"] * block and "+= (int64_t)gridDim.x * 256" in body_of(every["strfn.hip"], "void strfn_rebase_kernel(")
+    assert G.BYTEMAP_BYTES == caps["strfn_bytemap_kernel"] * block * 16   # (the byte map takes 16 bytes per thread)
+    assert "nvec = (p.n - head) >> 4" in body_of(every["strfn.hip"], "void strfn_bytemap_kernel(")
     assert G.STRIDE_N == G.STRIDE_ROWS + 64 + 1 and G.STRIDE_N > G.REBASE_ROWS and G.STRIDE_N * 9 * 0.9 > G.BYTEMAP_BYTES   # (9-byte rows, a tenth of them null)
