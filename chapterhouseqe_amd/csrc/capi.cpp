@@ -1,9 +1,8 @@
-// capi.cpp -- the extern "C" surface declared in include/chq.h.
+// capi.cpp -- the extern "C" surface declared in include/chq.h, except the expression handles (capi_expr.cpp).
 #include <algorithm>
 #include <cstring>
 #include <exception>
 #include <new>
-#include <thread>
 
 #include "engine.hpp"
 #include "parquet.hpp"
@@ -12,14 +11,15 @@
 #include "window.hpp"
 #include "join.hpp"
 #include "partition.hpp"
-#include <atomic>
 
 using namespace chq;
 
 struct chq_ctx { Context c; };
-struct chq_expr { Expr e; };
+struct chq_parquet { PqFile file; };
 
 namespace {
+
+chq_status status_of(const ChqError& e) { return e.code == CHQ_INTERNAL_PROGRAM_LIMIT ? CHQ_ERR_NOT_SUPPORTED : (chq_status)e.code; }
 
 template <typename F>
 chq_status guarded(chq_ctx* ctx, F&& f) {
@@ -29,7 +29,7 @@ chq_status guarded(chq_ctx* ctx, F&& f) {
     return CHQ_OK;
   } catch (const ChqError& e) {
     if (ctx) ctx->c.last_error = e.msg;
-    return e.code == CHQ_INTERNAL_PROGRAM_LIMIT ? CHQ_ERR_NOT_SUPPORTED : (chq_status)e.code;
+    return status_of(e);
   } catch (const std::bad_alloc&) {
     if (ctx) ctx->c.last_error = "out of host memory";
     return CHQ_ERR_OUT_OF_MEMORY;
@@ -39,30 +39,64 @@ chq_status guarded(chq_ctx* ctx, F&& f) {
   }
 }
 
-void mark_released(ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (out) { memset(out, 0, sizeof(*out)); }
-  if (out_schema) { memset(out_schema, 0, sizeof(*out_schema)); }
-}
-
-void require_out_device(int out_device) {
-  if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU)
-    throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
-}
-
-void finish(Context& c, Batch&& result_dev, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  require_out_device(out_device);
-  if (out_device == ARROW_DEVICE_ROCM) export_batch(std::move(result_dev), ARROW_DEVICE_ROCM, out, out_schema);
-  else { Batch h = to_host(c, result_dev); export_batch(std::move(h), ARROW_DEVICE_CPU, out, out_schema); }
-}
-
-void require(const void* p, const char* what) { if (!p) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null ") + what}; }
-
-// the *_record entries, handed no record (before the shared call, which takes the record in an array of one)
-chq_status null_record(chq_ctx* ctx, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+// ---- the frame of an entry that takes a context -----------------------------------------------------------------------------
+// A null context returns before the caller's structs are touched.  Then `clear` makes the outputs read as released, and
+// `body` -- the entry's checks in their documented order, then its work -- runs under `guarded`.
+template <class Clear, class Body>
+chq_status host_entry(chq_ctx* ctx, Clear&& clear, Body&& body) {
   if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  ctx->c.last_error = "null record";
-  return CHQ_ERR_INVALID_HANDLE;
+  clear();
+  return guarded(ctx, body);
+}
+// the same with the context's GPU current: every entry that may touch the device
+template <class Clear, class Body>
+chq_status entry(chq_ctx* ctx, Clear&& clear, Body&& body) {
+  return host_entry(ctx, clear, [&] { check_hip(hipSetDevice(ctx->c.device), "hipSetDevice"); body(); });
+}
+// context in, one record out
+template <class Body>
+chq_status record_entry(chq_ctx* ctx, ArrowDeviceArray* out, ArrowSchema* out_schema, Body&& body) {
+  return entry(ctx, [&] { mark_released(out, out_schema); }, body);
+}
+// context in, outs[0..n) / out_schemas[0..n) out: every output or none
+template <class Body>
+chq_status records_entry(chq_ctx* ctx, int n, ArrowDeviceArray* outs, ArrowSchema* out_schemas, Body&& body) {
+  return entry(ctx, [&] { for (int i = 0; i < n; ++i) mark_released(outs ? &outs[i] : nullptr, out_schemas ? &out_schemas[i] : nullptr); },
+               [&] {
+                 try {
+                   body();
+                 } catch (...) {   // no partial output
+                   for (int i = 0; i < n; ++i) {
+                     if (outs && outs[i].array.release) outs[i].array.release(&outs[i].array);
+                     if (out_schemas && out_schemas[i].release) out_schemas[i].release(&out_schemas[i]);
+                   }
+                   throw;
+                 }
+               });
+}
+
+// ---- the checks the entries share -------------------------------------------------------------------------------------------
+void require(const void* p, const char* what) { if (!p) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null ") + what}; }
+[[noreturn]] void invalid(const std::string& msg) { throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, msg}; }
+
+void require_out(const ArrowDeviceArray* out, const ArrowSchema* out_schema) { require(out, "output array"); require(out_schema, "output schema"); }
+void require_out_device(int out_device) {
+  if (out_device != ARROW_DEVICE_ROCM && out_device != ARROW_DEVICE_CPU) invalid("out_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM");
+}
+void require_records(int n, const ArrowDeviceArray* const* recs) {
+  if (n <= 0) invalid("at least one record batch is needed");
+  require(recs, "record array");
+}
+// `what`: "sort", "GROUP BY", "PARTITION BY", "ORDER BY", "partition", "join"
+void require_keys(int n, const void* keys, const char* what) {
+  if (n < 0) invalid(std::string("negative ") + what + " key count");
+  if (n > 0 && !keys) throw ChqError{CHQ_ERR_INVALID_HANDLE, std::string("null ") + what + " keys"};
+}
+void require_each(int n, const ArrowDeviceArray* const* recs, const char* what) { for (int i = 0; i < n; ++i) require(recs[i], what); }
+
+// the *_record entries, handed no record (before the *_records call, which takes the record in an array of one)
+chq_status null_record(chq_ctx* ctx, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  return host_entry(ctx, [&] { mark_released(out, out_schema); }, [] { require(nullptr, "record"); });
 }
 
 // the C arrays of a call as the engine takes them; a null element is CHQ_ERR_INVALID_HANDLE "null <what>"
@@ -86,16 +120,12 @@ std::vector<SortKeyArg> sort_key_args(const chq_sort_key* keys, int n, const cha
   return args;
 }
 
-// f(i) for i in [0, n) on a few host threads when the group is large: importing / exporting 10^5 Arrow structs one after
-// the other (~0.3 + 0.4 us each) used to be 93 % of a group call (round 1).  The first error, if any, is rethrown.
-template <class F>
-void for_each_parallel(int n, F&& f) {
-  if (n < 2048) { for (int i = 0; i < n; ++i) f(i); return; }
-  pool_ranges((size_t)n, 1024, [&](size_t i0, size_t i1) { for (size_t i = i0; i < i1; ++i) f((int)i); });
+std::vector<chq_select_item> select_items(const chq_select_item* fields, int n_fields) {
+  if (n_fields > 0) require(fields, "select items");
+  return std::vector<chq_select_item>(fields, fields + (n_fields > 0 ? n_fields : 0));
 }
 
-void require_each(int n, const ArrowDeviceArray* const* recs, const char* what) { for (int i = 0; i < n; ++i) require(recs[i], what); }
-
+// ---- in and out -------------------------------------------------------------------------------------------------------------
 // the batches of one group: every record is required before the first is imported
 std::vector<Batch> import_records(int n, const ArrowDeviceArray* const* recs, const ArrowSchema* schema, const char* what = "record") {
   require_each(n, recs, what);
@@ -104,148 +134,94 @@ std::vector<Batch> import_records(int n, const ArrowDeviceArray* const* recs, co
   return in;
 }
 
-// ---- the outputs of a joined group call, exported from ONE block --------------------------------------------------------
-// Every output batch of such a call is a slice of the same joined buffers (engine.hpp: JoinedGroup).  Exporting them one by
-// one (export_batch) costs ~20 allocations per batch and, worse, an atomic reference-count increment per column and batch
-// on the SAME few shared buffers from sixteen threads -- 7.5 ms for 12 500 batches, far more than the kernel.  Here the
-// Arrow structs of all batches live in a handful of arrays inside one reference-counted block that also holds the buffers:
-// exporting a batch writes ~0.6 KB of plain structs, releasing one decrements one counter.
-struct GroupBlock {
-  std::atomic<int64_t> live{0};          // exported structs whose release has not run: (1 + C) arrays + (1 + C) schemas per batch
-  std::vector<BufferPtr> buffers;
-  std::vector<std::string> names, formats;
-  std::string struct_format = "+s", empty;
-  // (plain arrays, NOT value-initialised: every element is written by the export loop, which runs on the thread pool -- zero-
-  // filling 60 MB of fresh pages on the calling thread first cost 12 ms for 100 000 batches)
-  std::unique_ptr<ArrowArray[]> child_arrays;    // [nb * C]
-  std::unique_ptr<ArrowArray*[]> child_ptrs;     // [nb * C]
-  std::unique_ptr<const void*[]> bufs;           // [nb * C * 3]
-  std::unique_ptr<const void*[]> parent_bufs;    // [nb] (the struct array's null validity)
-  std::unique_ptr<ArrowSchema[]> child_schemas;  // [nb * C]
-  std::unique_ptr<ArrowSchema*[]> schild_ptrs;   // [nb * C]
-};
-void group_drop(GroupBlock* blk) { if (blk->live.fetch_sub(1, std::memory_order_acq_rel) == 1) delete blk; }
-void group_release_child_array(ArrowArray* a) {
-  if (!a || !a->release) return;
-  auto* blk = (GroupBlock*)a->private_data;
-  a->release = nullptr; a->private_data = nullptr;
-  group_drop(blk);
+// a batch in HBM (staged when it came from the host) and its columns as the planner sees them
+struct DeviceBatch { Batch dev; std::vector<PlanColumn> pcols; };
+DeviceBatch device_batch(chq_ctx* ctx, const Batch& in, const chq_table_aliases* aliases) {
+  DeviceBatch d;
+  d.dev = to_device(ctx->c, in);
+  d.pcols = plan_columns(d.dev, aliases);
+  return d;
 }
-void group_release_array(ArrowArray* a) {
-  if (!a || !a->release) return;
-  auto* blk = (GroupBlock*)a->private_data;
-  for (int64_t i = 0; i < a->n_children; ++i) if (a->children[i] && a->children[i]->release) a->children[i]->release(a->children[i]);
-  a->release = nullptr; a->private_data = nullptr;
-  group_drop(blk);
-}
-void group_release_child_schema(ArrowSchema* s) {
-  if (!s || !s->release) return;
-  auto* blk = (GroupBlock*)s->private_data;
-  s->release = nullptr; s->private_data = nullptr;
-  group_drop(blk);
-}
-void group_release_schema(ArrowSchema* s) {
-  if (!s || !s->release) return;
-  auto* blk = (GroupBlock*)s->private_data;
-  for (int64_t i = 0; i < s->n_children; ++i) if (s->children[i] && s->children[i]->release) s->children[i]->release(s->children[i]);
-  s->release = nullptr; s->private_data = nullptr;
-  group_drop(blk);
+DeviceBatch device_batch(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, const chq_table_aliases* aliases) {
+  return device_batch(ctx, import_batch(rec, schema), aliases);
 }
 
-// `outs` / `out_schemas`: one per batch the part covers.  The block goes to the exported structs only once every one of them
-// is written; a failure before that frees it and leaves the structs released.
-void export_group(JoinedGroup&& g, int device_type, ArrowDeviceArray* outs, ArrowSchema* out_schemas) {
-  const size_t nb = g.ends.size(), C = g.joined.cols.size();
-  std::unique_ptr<GroupBlock> blk(new GroupBlock());
+void finish(Context& c, Batch&& result_dev, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  require_out_device(out_device);
+  if (out_device == ARROW_DEVICE_ROCM) export_batch(std::move(result_dev), ARROW_DEVICE_ROCM, out, out_schema);
+  else { Batch h = to_host(c, result_dev); export_batch(std::move(h), ARROW_DEVICE_CPU, out, out_schema); }
+}
+
+// The phases of a blocking operator's call -- import, run, export -- with the marks CHQ_TIMING=1 prints between them.
+template <class Import, class Run, class Export>
+void phased(const char* entry_name, const char* phase, Import&& import, Run&& run, Export&& export_result) {
+  PhaseTimer pt(entry_name);
+  auto in = import();
+  pt.mark("import");
+  auto res = run(in);
+  pt.mark(phase);
+  export_result(res);
+  pt.mark("export");
+}
+// one group in, one batch out (sort, aggregate, window)
+template <class Run>
+void blocking_call(chq_ctx* ctx, const char* entry_name, const char* phase, int n_records, const ArrowDeviceArray* const* recs,
+                   const ArrowSchema* schema, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema, Run&& run) {
+  phased(entry_name, phase, [&] { return import_records(n_records, recs, schema); }, run,
+         [&](Batch& res) { finish(ctx->c, std::move(res), out_device, out, out_schema); });
+}
+
+// ---- text results (the entries without a context) ---------------------------------------------------------------------------
+void copy_text(char* buf, size_t buf_len, const std::string& text) {
+  if (buf && buf_len) { const size_t n = std::min(buf_len - 1, text.size()); memcpy(buf, text.data(), n); buf[n] = 0; }
+}
+// `buf` receives what `f` returns, or the message of what it throws; `other`: the status of an exception that is no ChqError
+template <class F>
+chq_status text_result(char* buf, size_t buf_len, chq_status other, F&& f) {
+  std::string text;
+  chq_status st = CHQ_OK;
   try {
-    for (Column& c : g.joined.cols) {
-      blk->names.push_back(c.name); blk->formats.push_back(c.format);
-      for (BufferPtr& b : c.owned) blk->buffers.push_back(std::move(b));
-    }
-    const size_t cells = std::max<size_t>(1, nb * C);
-    blk->child_arrays.reset(new ArrowArray[cells]); blk->child_ptrs.reset(new ArrowArray*[cells]); blk->bufs.reset(new const void*[cells * 3]);
-    blk->parent_bufs.reset(new const void*[std::max<size_t>(1, nb)]); blk->child_schemas.reset(new ArrowSchema[cells]); blk->schild_ptrs.reset(new ArrowSchema*[cells]);
-    const bool host_out = device_type != ARROW_DEVICE_ROCM;
-    GroupBlock* pb = blk.get();
-    pool_ranges(nb, 1024, [&](size_t b0, size_t b1) {
-      for (size_t b = b0; b < b1; ++b) {
-        const int64_t begin = b ? g.ends[b - 1] : 0, rows = g.ends[b] - begin;
-        for (size_t i = 0; i < C; ++i) {
-          const Column& c = g.joined.cols[i];
-          const int64_t at = c.offset + begin;   // the slice's first row in the joined buffers
-          ArrowArray& ca = pb->child_arrays[b * C + i];
-          const void** cb = &pb->bufs[(b * C + i) * 3];
-          memset(&ca, 0, sizeof ca);
-          cb[0] = nullptr; cb[2] = nullptr;
-          ca.null_count = 0;
-          if (c.type == T_UTF8) { cb[1] = c.values; cb[2] = c.data; ca.offset = at; ca.n_buffers = 3; }   // a slice of the joined column
-          else if (c.type == T_BOOL || c.validity) { cb[1] = c.values; ca.offset = at; ca.n_buffers = 2; }   // (one Arrow offset serves values and validity)
-          else { cb[1] = c.values + at * c.width; ca.offset = 0; ca.n_buffers = 2; }
-          if (c.validity) {   // nulls of the slice: unknown on the device (-1), counted for a host result; an all-valid slice drops the bitmap
-            cb[0] = c.validity;
-            if (!host_out) ca.null_count = -1;
-            else {
-              int64_t nulls = 0;
-              for (int64_t r = at; r < at + rows; ++r) nulls += !((c.validity[r >> 3] >> (r & 7)) & 1);
-              ca.null_count = nulls;
-              if (nulls == 0) cb[0] = nullptr;
-            }
-          }
-          ca.length = rows; ca.buffers = cb; ca.release = group_release_child_array; ca.private_data = pb;
-          pb->child_ptrs[b * C + i] = &ca;
-          ArrowSchema& cs = pb->child_schemas[b * C + i];
-          memset(&cs, 0, sizeof cs);
-          cs.format = pb->formats[i].c_str(); cs.name = pb->names[i].c_str(); cs.flags = c.nullable ? ARROW_FLAG_NULLABLE : 0;
-          cs.release = group_release_child_schema; cs.private_data = pb;
-          pb->schild_ptrs[b * C + i] = &cs;
-        }
-        ArrowDeviceArray& o = outs[b];
-        memset(&o, 0, sizeof o);
-        pb->parent_bufs[b] = nullptr;
-        o.array.length = rows; o.array.n_buffers = 1; o.array.buffers = &pb->parent_bufs[b];
-        o.array.n_children = (int64_t)C; o.array.children = C ? &pb->child_ptrs[b * C] : nullptr;
-        o.array.release = group_release_array; o.array.private_data = pb;
-        o.device_id = device_type == ARROW_DEVICE_ROCM ? g.joined.device_id : -1; o.device_type = device_type; o.sync_event = nullptr;
-        ArrowSchema& os = out_schemas[b];
-        memset(&os, 0, sizeof os);
-        os.format = pb->struct_format.c_str(); os.name = pb->empty.c_str();
-        os.n_children = (int64_t)C; os.children = C ? &pb->schild_ptrs[b * C] : nullptr;
-        os.release = group_release_schema; os.private_data = pb;
-      }
-    });
-  } catch (...) {
-    for (size_t b = 0; b < nb; ++b) mark_released(&outs[b], &out_schemas[b]);
-    throw;
+    text = f();
+  } catch (const ChqError& e) {
+    st = status_of(e); text = e.msg;
+  } catch (const std::exception& e) {
+    st = other; text = e.what();
   }
-  blk->live.store((int64_t)(nb * (2 + 2 * C)));
-  (void)blk.release();
+  copy_text(buf, buf_len, text);
+  return st;
 }
 
-// Import of a group.  Batch 0 is imported in full.  A DEVICE-resident group then only gathers its GroupLite -- the checks of
-// import_batch on every record, but no Batch objects: the one-launch path works from the flat arrays, and building and
-// freeing 12 500 Batch objects cost ~0.6 ms of a 2.5 ms call; `gi.materialise` imports them when another path needs them.
-// Host groups are imported in full, and described by their GroupLite like any other.
-void import_group(int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema, int device, GroupInput& gi) {
-  std::vector<Batch>& in = gi.batches;
-  GroupLite& lite = gi.lite;
-  in.resize(1);
-  in[0] = import_batch(recs[0], schema);
-  lite.resize((size_t)n_records, in[0].cols.size());
-  lite.set(0, in[0], in[0], device);
-  auto import_rest = [n_records, recs, schema, &in]() {
-    if ((int)in.size() == n_records) return;
-    in.resize((size_t)n_records);
-    if (n_records > 1) for_each_parallel(n_records - 1, [&](int k) { in[(size_t)k + 1] = import_batch(recs[(size_t)k + 1], schema); });
-  };
-  if (in[0].on_device && n_records > 1) {
-    const Batch& first = in[0];
-    for_each_parallel(n_records - 1, [&](int k) { lite.set_from_arrow((size_t)k + 1, recs[(size_t)k + 1], schema, first, device); });
-    gi.materialise = import_rest;
-    return;
-  }
-  import_rest();
-  const Batch& first = in[0];
-  if (n_records > 1) for_each_parallel(n_records - 1, [&](int k) { lite.set((size_t)k + 1, in[(size_t)k + 1], first, device); });
+// ---- Parquet handles and images ---------------------------------------------------------------------------------------------
+// *out = a handle on the file `open` returns; `err`: the message when it throws
+template <class Open>
+chq_status open_parquet(chq_parquet** out, char* err, size_t err_len, Open&& open) {
+  if (!out) return CHQ_ERR_ARROW_INVALID_ARGUMENT;
+  *out = nullptr;
+  return text_result(err, err_len, CHQ_ERR_ARROW_INVALID_ARGUMENT, [&] {
+    std::unique_ptr<chq_parquet> h(new chq_parquet());
+    h->file = open();
+    *out = h.release();
+    return std::string();
+  });
+}
+
+struct ParquetImageHolder { chq::ParquetImage img; };
+void clear_image(chq_parquet_image* m) { m->data = nullptr; m->len = 0; m->release = nullptr; m->private_data = nullptr; }
+void release_parquet_image(chq_parquet_image* m) {
+  if (!m || !m->release) return;
+  delete (ParquetImageHolder*)m->private_data;
+  clear_image(m);
+}
+// context in, one Parquet image out: `write` returns the image once the entry's own checks have passed
+template <class Write>
+chq_status image_entry(chq_ctx* ctx, chq_parquet_image* out, Write&& write) {
+  return entry(ctx, [&] { if (out) clear_image(out); }, [&] {
+    require(out, "output image");
+    std::unique_ptr<ParquetImageHolder> h(new ParquetImageHolder());
+    h->img = write();
+    out->data = (const uint8_t*)h->img.bytes->ptr; out->len = h->img.len;
+    out->release = release_parquet_image; out->private_data = h.release();
+  });
 }
 
 }  // namespace
@@ -344,124 +320,12 @@ chq_status chq_ctx_set_option(chq_ctx* ctx, const char* key, int64_t value) {
   });
 }
 
-// ---- expressions ------------------------------------------------------------------------------------
-static chq_expr* new_expr(Expr::Kind k) { chq_expr* e = new (std::nothrow) chq_expr(); if (e) e->e.kind = k; return e; }
-chq_expr* chq_expr_identifier(const char* name) { chq_expr* e = new_expr(Expr::IDENT); if (e) e->e.text = name ? name : ""; return e; }
-chq_expr* chq_expr_compound_identifier(const char* const* parts, int n) {
-  chq_expr* e = new_expr(Expr::COMPOUND);
-  if (e) for (int i = 0; i < n; ++i) e->e.parts.push_back(parts[i] ? parts[i] : "");
-  return e;
-}
-chq_expr* chq_expr_number(const char* text, int is_long) { chq_expr* e = new_expr(Expr::NUMBER); if (e) { e->e.text = text ? text : ""; e->e.flag = is_long != 0; } return e; }
-chq_expr* chq_expr_boolean(int value) { chq_expr* e = new_expr(Expr::BOOLEAN); if (e) e->e.flag = value != 0; return e; }
-chq_expr* chq_expr_single_quoted_string(const char* bytes, int64_t len) {
-  chq_expr* e = new_expr(Expr::STRING);
-  if (e && bytes && len > 0) e->e.text.assign(bytes, (size_t)len);
-  return e;
-}
-chq_expr* chq_expr_unsupported_value(const char* debug) { chq_expr* e = new_expr(Expr::VALUE_OTHER); if (e) e->e.text = debug ? debug : ""; return e; }
-chq_expr* chq_expr_binary_op(chq_expr* left, chq_binary_operator op, const char* op_debug, chq_expr* right) {
-  chq_expr* e = new_expr(Expr::BINARY);
-  if (!e || !left || !right) { chq_expr_free(left); chq_expr_free(right); delete e; return nullptr; }
-  e->e.op = (int)op; e->e.text = op_debug ? op_debug : "";
-  // the wrapper structs own nothing but the Expr: move the trees in and drop the shells
-  e->e.l.reset(new Expr(std::move(left->e))); e->e.r.reset(new Expr(std::move(right->e)));
-  delete left; delete right;
-  return e;
-}
-chq_expr* chq_expr_nested(chq_expr* inner) {
-  chq_expr* e = new_expr(Expr::NESTED);
-  if (!e || !inner) { chq_expr_free(inner); delete e; return nullptr; }
-  e->e.l.reset(new Expr(std::move(inner->e)));
-  delete inner;
-  return e;
-}
-chq_expr* chq_expr_like(chq_expr* operand, const char* pattern, int64_t pattern_len, int negated, int escape) {
-  chq_expr* e = new_expr(Expr::LIKE);
-  if (!e || !operand) { chq_expr_free(operand); delete e; return nullptr; }
-  if (pattern) {   // (null: the caller's pattern was not a string literal -- typing reports it)
-    e->e.r.reset(new Expr());
-    e->e.r->kind = Expr::STRING;
-    if (pattern_len > 0) e->e.r->text.assign(pattern, (size_t)pattern_len);
-  }
-  e->e.flag = negated != 0; e->e.op = escape < 0 ? -1 : escape;
-  e->e.l.reset(new Expr(std::move(operand->e)));
-  delete operand;
-  return e;
-}
-chq_expr* chq_expr_is_null(chq_expr* operand, int negated) {
-  chq_expr* e = new_expr(Expr::ISNULL);
-  if (!e || !operand) { chq_expr_free(operand); delete e; return nullptr; }
-  e->e.flag = negated != 0;
-  e->e.l.reset(new Expr(std::move(operand->e)));
-  delete operand;
-  return e;
-}
-chq_expr* chq_expr_function(const char* name, chq_expr* const* args, int n_args) {
-  chq_expr* e = new_expr(Expr::FUNCTION);
-  bool ok = e && name && n_args >= 0 && (args || n_args == 0);
-  for (int i = 0; ok && i < n_args; ++i) ok = args[i] != nullptr;
-  if (!ok) { for (int i = 0; args && i < n_args; ++i) chq_expr_free(args[i]); delete e; return nullptr; }
-  e->e.text = name;
-  for (int i = 0; i < n_args; ++i) { e->e.args.emplace_back(new Expr(std::move(args[i]->e))); delete args[i]; }
-  return e;
-}
-// (shared by the three below) moves `n` handles into e->args; false -- and every handle freed -- when one is missing
-static bool take_children(chq_expr* e, chq_expr* const* list, int n) {
-  bool ok = e && n >= 0 && (list || n == 0);
-  for (int i = 0; ok && i < n; ++i) ok = list[i] != nullptr;
-  if (!ok) { for (int i = 0; list && i < n; ++i) chq_expr_free(list[i]); return false; }
-  for (int i = 0; i < n; ++i) { e->e.args.emplace_back(new Expr(std::move(list[i]->e))); delete list[i]; }
-  return true;
-}
-chq_expr* chq_expr_case(chq_expr* operand, chq_expr* const* conditions, chq_expr* const* results, int n_when, chq_expr* else_result) {
-  chq_expr* e = new_expr(Expr::CASE);
-  const bool ok_c = take_children(e, conditions, n_when);
-  const bool ok_r = take_children(ok_c ? e : nullptr, results, n_when);
-  if (!ok_c || !ok_r || n_when < 1) { chq_expr_free(operand); chq_expr_free(else_result); delete e; return nullptr; }
-  if (operand) { e->e.l.reset(new Expr(std::move(operand->e))); delete operand; }
-  if (else_result) { e->e.r.reset(new Expr(std::move(else_result->e))); delete else_result; }
-  return e;
-}
-chq_expr* chq_expr_in_list(chq_expr* expr, chq_expr* const* list, int n, int negated) {
-  chq_expr* e = new_expr(Expr::IN_LIST);
-  const bool ok = take_children(e, list, n);
-  if (!ok || !expr) { chq_expr_free(expr); delete e; return nullptr; }
-  e->e.flag = negated != 0;
-  e->e.l.reset(new Expr(std::move(expr->e)));
-  delete expr;
-  return e;
-}
-chq_expr* chq_expr_between(chq_expr* expr, int negated, chq_expr* low, chq_expr* high) {
-  chq_expr* e = new_expr(Expr::BETWEEN);
-  if (!e || !expr || !low || !high) { chq_expr_free(expr); chq_expr_free(low); chq_expr_free(high); delete e; return nullptr; }
-  e->e.flag = negated != 0;
-  e->e.l.reset(new Expr(std::move(expr->e)));
-  e->e.args.emplace_back(new Expr(std::move(low->e)));
-  e->e.args.emplace_back(new Expr(std::move(high->e)));
-  delete expr; delete low; delete high;
-  return e;
-}
-chq_expr* chq_expr_cast(chq_expr* operand, chq_cast_type to, int try_cast) {
-  chq_expr* e = new_expr(Expr::CAST);
-  if (!e || !operand) { chq_expr_free(operand); delete e; return nullptr; }
-  e->e.op = (int)to; e->e.flag = try_cast != 0;
-  e->e.l.reset(new Expr(std::move(operand->e)));
-  delete operand;
-  return e;
-}
-chq_expr* chq_expr_unsupported(const char* debug) { chq_expr* e = new_expr(Expr::OTHER); if (e) e->e.text = debug ? debug : ""; return e; }
-void chq_expr_free(chq_expr* e) { delete e; }
-
 // ---- the path -------------------------------------------------------------------------------------------
 chq_status chq_filter_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema,
                              const chq_table_aliases* table_aliases, const chq_expr* expr, int out_device,
                              ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(expr, "expression"); require(out, "output array"); require(out_schema, "output schema");
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+  return record_entry(ctx, out, out_schema, [&] {
+    require(expr, "expression"); require_out(out, out_schema);
     Batch in = import_batch(rec, schema);
     if (out_device == ARROW_DEVICE_CPU && !in.on_device) {   // the reference's calling pattern: small host batch in, host batch out
       Batch small;
@@ -471,65 +335,45 @@ chq_status chq_filter_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const Ar
         return;
       }
     }
-    Batch dev = to_device(ctx->c, in);
-    auto pcols = plan_columns(dev, table_aliases);
-    Batch res = filter_record(ctx->c, dev, pcols, expr->e);
+    DeviceBatch d = device_batch(ctx, in, table_aliases);
+    Batch res = filter_record(ctx->c, d.dev, d.pcols, expr->e);
     finish(ctx->c, std::move(res), out_device, out, out_schema);
   });
 }
 
 chq_status chq_plan_describe(const ArrowSchema* schema, const chq_table_aliases* table_aliases, const chq_expr* expr,
                              int64_t n_rows, int enable_minus, char* buf, size_t buf_len) {
-  std::string text;
-  chq_status st = CHQ_OK;
-  try {
-    if (!expr) throw ChqError{CHQ_ERR_INVALID_HANDLE, "null expression"};
-    text = describe_plan(schema, table_aliases, expr->e, n_rows, enable_minus != 0);
-  } catch (const ChqError& e) {
-    st = e.code == CHQ_INTERNAL_PROGRAM_LIMIT ? CHQ_ERR_NOT_SUPPORTED : (chq_status)e.code; text = e.msg;
-  } catch (const std::exception& e) {
-    st = CHQ_ERR_DEVICE; text = e.what();
-  }
-  if (buf && buf_len) { const size_t n = std::min(buf_len - 1, text.size()); memcpy(buf, text.data(), n); buf[n] = 0; }
-  return st;
+  return text_result(buf, buf_len, CHQ_ERR_DEVICE, [&] {
+    require(expr, "expression");
+    return describe_plan(schema, table_aliases, expr->e, n_rows, enable_minus != 0);
+  });
 }
 
 chq_status chq_filter_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
                               const chq_table_aliases* table_aliases, const chq_expr* expr, int out_device,
                               ArrowDeviceArray* outs, ArrowSchema* out_schemas) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  for (int i = 0; i < n_records; ++i) mark_released(outs ? &outs[i] : nullptr, out_schemas ? &out_schemas[i] : nullptr);
-  return guarded(ctx, [&] {
+  return records_entry(ctx, n_records, outs, out_schemas, [&] {
     require(expr, "expression");
-    if (n_records < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative record count"};
+    if (n_records < 0) invalid("negative record count");
     if (n_records == 0) return;
     require(recs, "record array"); require(outs, "output arrays"); require(out_schemas, "output schemas");
     require_out_device(out_device);
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_filter_records");
-    GroupInput gi;
-    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
+    GroupInput gi;   // (filled in place: gi.materialise refers to it)
+    require_each(n_records, recs, "record");
     import_group(n_records, recs, schema, ctx->c.device, gi);
     pt.mark("import");
     GroupResult res = filter_records(ctx->c, gi, table_aliases, expr->e, out_device == ARROW_DEVICE_ROCM);
     pt.mark("filter");
     if (res.batches() != (size_t)n_records)
       throw ChqError{CHQ_ERR_DEVICE, "internal error: the group result covers " + std::to_string(res.batches()) + " of " + std::to_string(n_records) + " batches"};
-    try {   // every output or none
-      size_t at = 0;
-      for (JoinedGroup& part : res.parts) {
-        const size_t n = part.ends.size();
-        export_group(std::move(part), out_device, outs + at, out_schemas + at);
-        at += n;
-      }
-      if (res.parts.empty()) for_each_parallel(n_records, [&](int i) { export_batch(std::move(res.per_batch[(size_t)i]), out_device, &outs[i], &out_schemas[i]); });
-    } catch (...) {
-      for (int i = 0; i < n_records; ++i) {
-        if (outs[i].array.release) outs[i].array.release(&outs[i].array);
-        if (out_schemas[i].release) out_schemas[i].release(&out_schemas[i]);
-      }
-      throw;
+    size_t at = 0;
+    for (JoinedGroup& part : res.parts) {
+      const size_t n = part.ends.size();
+      export_group(std::move(part), out_device, outs + at, out_schemas + at);
+      at += n;
     }
+    if (res.parts.empty()) for_each_parallel(n_records, [&](int i) { export_batch(std::move(res.per_batch[(size_t)i]), out_device, &outs[i], &out_schemas[i]); });
     pt.mark("export");
   });
 }
@@ -537,17 +381,13 @@ chq_status chq_filter_records(chq_ctx* ctx, int n_records, const ArrowDeviceArra
 chq_status chq_filter_records_coalesced(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
                                         const chq_table_aliases* table_aliases, const chq_expr* expr, int out_device,
                                         ArrowDeviceArray* out, ArrowSchema* out_schema, int64_t* rows_per_record) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(expr, "expression"); require(out, "output array"); require(out_schema, "output schema");
-    if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
-    require(recs, "record array");
+  return record_entry(ctx, out, out_schema, [&] {
+    require(expr, "expression"); require_out(out, out_schema);
+    require_records(n_records, recs);
     require_out_device(out_device);
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     PhaseTimer pt("chq_filter_records_coalesced");
-    GroupInput gi;
-    for (int i = 0; i < n_records; ++i) require(recs[i], "record");
+    GroupInput gi;   // (filled in place: gi.materialise refers to it)
+    require_each(n_records, recs, "record");
     import_group(n_records, recs, schema, ctx->c.device, gi);
     pt.mark("import");
     std::vector<int64_t> rows;
@@ -562,60 +402,37 @@ chq_status chq_filter_records_coalesced(chq_ctx* ctx, int n_records, const Arrow
 }
 
 // ---- ORDER BY (sort.cpp) ---------------------------------------------------------------------------------------------------
-namespace {
-chq_status sort_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
-                     const chq_table_aliases* table_aliases, const chq_sort_key* keys, int n_keys, int64_t limit, int out_device,
-                     ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
-    if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
-    require(recs, "record array");
-    if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative sort key count"};
-    if (n_keys > 0) require(keys, "sort keys");
+chq_status chq_sort_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                            const chq_table_aliases* table_aliases, const chq_sort_key* keys, int n_keys, int64_t limit,
+                            int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  return record_entry(ctx, out, out_schema, [&] {
+    require_out(out, out_schema);
+    require_records(n_records, recs);
+    require_keys(n_keys, keys, "sort");
     require_out_device(out_device);
     const std::vector<SortKeyArg> args = sort_key_args(keys, n_keys, "sort key column");
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    PhaseTimer pt("chq_sort_records");
-    std::vector<Batch> in = import_records(n_records, recs, schema);
-    pt.mark("import");
-    Batch res = sort_records(ctx->c, in, table_aliases, args, limit);
-    pt.mark("sort");
-    finish(ctx->c, std::move(res), out_device, out, out_schema);
-    pt.mark("export");
+    blocking_call(ctx, "chq_sort_records", "sort", n_records, recs, schema, out_device, out, out_schema,
+                  [&](std::vector<Batch>& in) { return sort_records(ctx->c, in, table_aliases, args, limit); });
   });
 }
-}  // namespace
 
 chq_status chq_sort_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, const chq_table_aliases* table_aliases,
                            const chq_sort_key* keys, int n_keys, int64_t limit, int out_device, ArrowDeviceArray* out,
                            ArrowSchema* out_schema) {
   const ArrowDeviceArray* recs[1] = {rec};
   if (!rec) return null_record(ctx, out, out_schema);
-  return sort_call(ctx, 1, recs, schema, table_aliases, keys, n_keys, limit, out_device, out, out_schema);
-}
-
-chq_status chq_sort_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
-                            const chq_table_aliases* table_aliases, const chq_sort_key* keys, int n_keys, int64_t limit,
-                            int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  return sort_call(ctx, n_records, recs, schema, table_aliases, keys, n_keys, limit, out_device, out, out_schema);
+  return chq_sort_records(ctx, 1, recs, schema, table_aliases, keys, n_keys, limit, out_device, out, out_schema);
 }
 
 // ---- GROUP BY (aggregate.cpp) ------------------------------------------------------------------------------------------------
-namespace {
-chq_status aggregate_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
-                          const chq_table_aliases* table_aliases, const chq_expr* const* keys, int n_keys, const chq_agg_item* items,
-                          int n_items, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
-    if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
-    require(recs, "record array");
-    if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative GROUP BY key count"};
-    if (n_keys > 0) require(keys, "GROUP BY keys");
-    if (n_items <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "GROUP BY needs at least one output item"};
+chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                                 const chq_table_aliases* table_aliases, const chq_expr* const* keys, int n_keys,
+                                 const chq_agg_item* items, int n_items, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  return record_entry(ctx, out, out_schema, [&] {
+    require_out(out, out_schema);
+    require_records(n_records, recs);
+    require_keys(n_keys, keys, "GROUP BY");
+    if (n_items <= 0) invalid("GROUP BY needs at least one output item");
     require(items, "output items");
     require_out_device(out_device);
     const std::vector<const Expr*> key_args = expr_args(keys, n_keys, "GROUP BY key");
@@ -627,49 +444,30 @@ chq_status aggregate_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* c
       require(items[i].name, "output column name");
       a.name = items[i].name;
     }
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    PhaseTimer pt("chq_aggregate_records");
-    std::vector<Batch> in = import_records(n_records, recs, schema);
-    pt.mark("import");
-    Batch res = aggregate_records(ctx->c, in, table_aliases, key_args, item_args);
-    pt.mark("aggregate");
-    finish(ctx->c, std::move(res), out_device, out, out_schema);
-    pt.mark("export");
+    blocking_call(ctx, "chq_aggregate_records", "aggregate", n_records, recs, schema, out_device, out, out_schema,
+                  [&](std::vector<Batch>& in) { return aggregate_records(ctx->c, in, table_aliases, key_args, item_args); });
   });
 }
-}  // namespace
 
 chq_status chq_aggregate_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, const chq_table_aliases* table_aliases,
                                 const chq_expr* const* keys, int n_keys, const chq_agg_item* items, int n_items, int out_device,
                                 ArrowDeviceArray* out, ArrowSchema* out_schema) {
   const ArrowDeviceArray* recs[1] = {rec};
   if (!rec) return null_record(ctx, out, out_schema);
-  return aggregate_call(ctx, 1, recs, schema, table_aliases, keys, n_keys, items, n_items, out_device, out, out_schema);
-}
-
-chq_status chq_aggregate_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
-                                 const chq_table_aliases* table_aliases, const chq_expr* const* keys, int n_keys,
-                                 const chq_agg_item* items, int n_items, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  return aggregate_call(ctx, n_records, recs, schema, table_aliases, keys, n_keys, items, n_items, out_device, out, out_schema);
+  return chq_aggregate_records(ctx, 1, recs, schema, table_aliases, keys, n_keys, items, n_items, out_device, out, out_schema);
 }
 
 // ---- window functions (window.cpp) -----------------------------------------------------------------------------------------
-namespace {
-chq_status window_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
-                       const chq_table_aliases* table_aliases, const chq_expr* const* partition_by, int n_partition_by,
-                       const chq_sort_key* order_by, int n_order_by, const chq_window_item* items, int n_items, int out_device,
-                       ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
-    if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
-    require(recs, "record array");
-    if (n_partition_by < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative PARTITION BY key count"};
-    if (n_partition_by > 0) require(partition_by, "PARTITION BY keys");
-    if (n_order_by < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative ORDER BY key count"};
-    if (n_order_by > 0) require(order_by, "ORDER BY keys");
-    if (n_items <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "a window call needs at least one item"};
+chq_status chq_window_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
+                              const chq_table_aliases* table_aliases, const chq_expr* const* partition_by, int n_partition_by,
+                              const chq_sort_key* order_by, int n_order_by, const chq_window_item* items, int n_items, int out_device,
+                              ArrowDeviceArray* out, ArrowSchema* out_schema) {
+  return record_entry(ctx, out, out_schema, [&] {
+    require_out(out, out_schema);
+    require_records(n_records, recs);
+    require_keys(n_partition_by, partition_by, "PARTITION BY");
+    require_keys(n_order_by, order_by, "ORDER BY");
+    if (n_items <= 0) invalid("a window call needs at least one item");
     require(items, "window items");
     require_out_device(out_device);
     const std::vector<const Expr*> part_args = expr_args(partition_by, n_partition_by, "PARTITION BY key");
@@ -682,33 +480,18 @@ chq_status window_call(chq_ctx* ctx, int n_records, const ArrowDeviceArray* cons
       require(items[i].name, "output column name");
       a.name = items[i].name;
     }
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    PhaseTimer pt("chq_window_records");
-    std::vector<Batch> in = import_records(n_records, recs, schema);
-    pt.mark("import");
-    Batch res = window_records(ctx->c, in, table_aliases, part_args, order_args, item_args);
-    pt.mark("window");
-    finish(ctx->c, std::move(res), out_device, out, out_schema);
-    pt.mark("export");
+    blocking_call(ctx, "chq_window_records", "window", n_records, recs, schema, out_device, out, out_schema,
+                  [&](std::vector<Batch>& in) { return window_records(ctx->c, in, table_aliases, part_args, order_args, item_args); });
   });
 }
-}  // namespace
 
 chq_status chq_window_record(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, const chq_table_aliases* table_aliases,
                              const chq_expr* const* partition_by, int n_partition_by, const chq_sort_key* order_by, int n_order_by,
                              const chq_window_item* items, int n_items, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
   const ArrowDeviceArray* recs[1] = {rec};
   if (!rec) return null_record(ctx, out, out_schema);
-  return window_call(ctx, 1, recs, schema, table_aliases, partition_by, n_partition_by, order_by, n_order_by, items, n_items, out_device, out,
-                     out_schema);
-}
-
-chq_status chq_window_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
-                              const chq_table_aliases* table_aliases, const chq_expr* const* partition_by, int n_partition_by,
-                              const chq_sort_key* order_by, int n_order_by, const chq_window_item* items, int n_items, int out_device,
-                              ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  return window_call(ctx, n_records, recs, schema, table_aliases, partition_by, n_partition_by, order_by, n_order_by, items, n_items,
-                     out_device, out, out_schema);
+  return chq_window_records(ctx, 1, recs, schema, table_aliases, partition_by, n_partition_by, order_by, n_order_by, items, n_items, out_device,
+                            out, out_schema);
 }
 
 // ---- JOIN (join.cpp) ---------------------------------------------------------------------------------------------------------
@@ -724,17 +507,13 @@ chq_status chq_join_records_kind(chq_ctx* ctx, int n_left, const ArrowDeviceArra
                                  const chq_table_aliases* left_aliases, int n_right, const ArrowDeviceArray* const* right,
                                  const ArrowSchema* right_schema, const chq_table_aliases* right_aliases, const chq_join_key* keys, int n_keys,
                                  int kind, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
-    if (n_left <= 0 || n_right <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch per side is needed"};
+  return record_entry(ctx, out, out_schema, [&] {
+    require_out(out, out_schema);
+    if (n_left <= 0 || n_right <= 0) invalid("at least one record batch per side is needed");
     require(left, "left record array"); require(right, "right record array");
     require(left_schema, "left schema"); require(right_schema, "right schema");
-    if (kind < CHQ_JOIN_INNER || kind > CHQ_JOIN_LEFT_ANTI)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "unknown join kind " + std::to_string(kind) + " (a chq_join_kind is expected)"};
-    if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative join key count"};
-    if (n_keys > 0) require(keys, "join keys");
+    if (kind < CHQ_JOIN_INNER || kind > CHQ_JOIN_LEFT_ANTI) invalid("unknown join kind " + std::to_string(kind) + " (a chq_join_kind is expected)");
+    require_keys(n_keys, keys, "join");
     require_out_device(out_device);
     std::vector<JoinKeyArg> args((size_t)n_keys);
     for (int k = 0; k < n_keys; ++k) {
@@ -742,16 +521,15 @@ chq_status chq_join_records_kind(chq_ctx* ctx, int n_left, const ArrowDeviceArra
       args[(size_t)k].left = &keys[k].left->e;
       args[(size_t)k].right = &keys[k].right->e;
     }
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    PhaseTimer pt("chq_join_records_kind");
-    require_each(n_left, left, "left record"); require_each(n_right, right, "right record");   // (both sides before either is imported)
-    std::vector<Batch> in_l = import_records(n_left, left, left_schema, "left record");
-    std::vector<Batch> in_r = import_records(n_right, right, right_schema, "right record");
-    pt.mark("import");
-    Batch res = join_records(ctx->c, in_l, left_aliases, in_r, right_aliases, args, kind);
-    pt.mark("join");
-    finish(ctx->c, std::move(res), out_device, out, out_schema);
-    pt.mark("export");
+    using Sides = std::pair<std::vector<Batch>, std::vector<Batch>>;
+    phased("chq_join_records_kind", "join",
+           [&] {
+             require_each(n_left, left, "left record"); require_each(n_right, right, "right record");   // (both sides before either is imported)
+             std::vector<Batch> in_l = import_records(n_left, left, left_schema, "left record");
+             return Sides(std::move(in_l), import_records(n_right, right, right_schema, "right record"));
+           },
+           [&](Sides& in) { return join_records(ctx->c, in.first, left_aliases, in.second, right_aliases, args, kind); },
+           [&](Batch& res) { finish(ctx->c, std::move(res), out_device, out, out_schema); });
   });
 }
 
@@ -759,45 +537,32 @@ chq_status chq_join_records_kind(chq_ctx* ctx, int n_left, const ArrowDeviceArra
 chq_status chq_partition_records(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
                                  const chq_table_aliases* table_aliases, const chq_expr* const* keys, int n_keys, int n_partitions,
                                  int out_device, ArrowDeviceArray* outs, ArrowSchema* out_schemas) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
   const bool p_ok = n_partitions >= 1 && n_partitions <= kPartMaxPartitions;   // (else the caller's arrays have no known length)
-  if (p_ok) for (int p = 0; p < n_partitions; ++p) mark_released(outs ? &outs[p] : nullptr, out_schemas ? &out_schemas[p] : nullptr);
-  return guarded(ctx, [&] {
-    if (n_records <= 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "at least one record batch is needed"};
-    require(recs, "record array");
-    if (n_keys < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative partition key count"};
-    if (n_keys > 0) require(keys, "partition keys");
-    if (!p_ok)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "n_partitions must be in [1, " + std::to_string(kPartMaxPartitions) + "] (" +
-                                                     std::to_string(n_partitions) + " given)"};
+  return records_entry(ctx, p_ok ? n_partitions : 0, outs, out_schemas, [&] {
+    require_records(n_records, recs);
+    require_keys(n_keys, keys, "partition");
+    if (!p_ok) invalid("n_partitions must be in [1, " + std::to_string(kPartMaxPartitions) + "] (" + std::to_string(n_partitions) + " given)");
     require(outs, "output arrays"); require(out_schemas, "output schemas");
     require_out_device(out_device);
     const std::vector<const Expr*> key_args = expr_args(keys, n_keys, "partition key");
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    PhaseTimer pt("chq_partition_records");
-    std::vector<Batch> in = import_records(n_records, recs, schema);
-    pt.mark("import");
-    JoinedGroup res = partition_records(ctx->c, in, table_aliases, key_args, n_partitions);
-    pt.mark("partition");
-    if (res.ends.size() != (size_t)n_partitions)
-      throw ChqError{CHQ_ERR_DEVICE, "internal error: " + std::to_string(res.ends.size()) + " of " + std::to_string(n_partitions) + " partitions"};
-    if (out_device == ARROW_DEVICE_CPU) res.joined = to_host(ctx->c, res.joined);
-    export_group(std::move(res), out_device, outs, out_schemas);   // every output or none
-    pt.mark("export");
+    phased("chq_partition_records", "partition", [&] { return import_records(n_records, recs, schema); },
+           [&](std::vector<Batch>& in) { return partition_records(ctx->c, in, table_aliases, key_args, n_partitions); },
+           [&](JoinedGroup& res) {
+             if (res.ends.size() != (size_t)n_partitions)
+               throw ChqError{CHQ_ERR_DEVICE, "internal error: " + std::to_string(res.ends.size()) + " of " + std::to_string(n_partitions) + " partitions"};
+             if (out_device == ARROW_DEVICE_CPU) res.joined = to_host(ctx->c, res.joined);
+             export_group(std::move(res), out_device, outs, out_schemas);   // every output or none
+           });
   });
 }
 
 chq_status chq_project_record(chq_ctx* ctx, const chq_select_item* fields, int n_fields, const ArrowDeviceArray* rec,
                               const ArrowSchema* schema, const chq_table_aliases* table_aliases, int out_device,
                               ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
-    if (n_fields > 0) require(fields, "select items");
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+  return record_entry(ctx, out, out_schema, [&] {
+    require_out(out, out_schema);
+    const std::vector<chq_select_item> items = select_items(fields, n_fields);
     Batch in = import_batch(rec, schema);
-    std::vector<chq_select_item> items(fields, fields + (n_fields > 0 ? n_fields : 0));
     if (out_device == ARROW_DEVICE_CPU && !in.on_device) {   // the materialize task's calling pattern: host in, host out
       Batch res_host;
       if (project_record_host(ctx->c, items, in, table_aliases, &res_host)) {
@@ -805,9 +570,8 @@ chq_status chq_project_record(chq_ctx* ctx, const chq_select_item* fields, int n
         return;
       }
     }
-    Batch dev = to_device(ctx->c, in);
-    auto pcols = plan_columns(dev, table_aliases);
-    Batch res = project_record(ctx->c, items, dev, pcols);
+    DeviceBatch d = device_batch(ctx, in, table_aliases);
+    Batch res = project_record(ctx->c, items, d.dev, d.pcols);
     finish(ctx->c, std::move(res), out_device, out, out_schema);
   });
 }
@@ -815,16 +579,11 @@ chq_status chq_project_record(chq_ctx* ctx, const chq_select_item* fields, int n
 chq_status chq_compute_value(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema,
                              const chq_table_aliases* table_aliases, const chq_expr* expr, int out_device,
                              ArrowDeviceArray* out, ArrowSchema* out_schema, int* out_is_scalar) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(expr, "expression"); require(out, "output array"); require(out_schema, "output schema");
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    Batch in = import_batch(rec, schema);
-    Batch dev = to_device(ctx->c, in);
-    auto pcols = plan_columns(dev, table_aliases);
+  return record_entry(ctx, out, out_schema, [&] {
+    require(expr, "expression"); require_out(out, out_schema);
+    DeviceBatch d = device_batch(ctx, rec, schema, table_aliases);
     bool sc = false;
-    Column col = compute_value(ctx->c, dev, pcols, expr->e, &sc);
+    Column col = compute_value(ctx->c, d.dev, d.pcols, expr->e, &sc);
     if (out_is_scalar) *out_is_scalar = sc ? 1 : 0;
     // reuse the batch path for the host copy
     Batch one; one.nrows = col.length; one.on_device = true; one.device_id = ctx->c.device;
@@ -839,25 +598,18 @@ chq_status chq_filter_project_record(chq_ctx* ctx, const chq_expr* predicate, co
                                      const ArrowDeviceArray* rec, const ArrowSchema* schema,
                                      const chq_table_aliases* table_aliases, int out_device, ArrowDeviceArray* out,
                                      ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(predicate, "predicate"); require(out, "output array"); require(out_schema, "output schema");
-    if (n_fields > 0) require(fields, "select items");
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
-    Batch in = import_batch(rec, schema);
-    Batch dev = to_device(ctx->c, in);
-    auto pcols = plan_columns(dev, table_aliases);
-    std::vector<chq_select_item> fused_items(fields, fields + (n_fields > 0 ? n_fields : 0));
+  return record_entry(ctx, out, out_schema, [&] {
+    require(predicate, "predicate"); require_out(out, out_schema);
+    const std::vector<chq_select_item> items = select_items(fields, n_fields);
+    DeviceBatch d = device_batch(ctx, rec, schema, table_aliases);
     Batch fused;
-    if (filter_project_fused(ctx->c, dev, pcols, predicate->e, fused_items, &fused)) {
+    if (filter_project_fused(ctx->c, d.dev, d.pcols, predicate->e, items, &fused)) {
       finish(ctx->c, std::move(fused), out_device, out, out_schema);
       return;
     }
-    Batch filtered = filter_record(ctx->c, dev, pcols, predicate->e);   // stays in HBM
+    Batch filtered = filter_record(ctx->c, d.dev, d.pcols, predicate->e);   // stays in HBM
     chq_call_stats fs = ctx->c.stats;
     auto pcols2 = plan_columns(filtered, table_aliases);
-    std::vector<chq_select_item> items(fields, fields + (n_fields > 0 ? n_fields : 0));
     Batch res = project_record(ctx->c, items, filtered, pcols2);
     fs.launches += ctx->c.stats.launches;
     ctx->c.stats = fs;
@@ -867,13 +619,10 @@ chq_status chq_filter_project_record(chq_ctx* ctx, const chq_expr* predicate, co
 
 chq_status chq_record_to_device(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, ArrowDeviceArray* out,
                                 ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+  return record_entry(ctx, out, out_schema, [&] {
+    require_out(out, out_schema);
     Batch in = import_batch(rec, schema, true);   // (staging copies bytes: every fixed width)
-    if (in.on_device) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "record is already device resident"};
+    if (in.on_device) invalid("record is already device resident");
     Batch dev = to_device(ctx->c, in);
     check_hip(hipStreamSynchronize(ctx->c.stream), "hipStreamSynchronize");
     export_batch(std::move(dev), ARROW_DEVICE_ROCM, out, out_schema);
@@ -882,10 +631,9 @@ chq_status chq_record_to_device(chq_ctx* ctx, const ArrowDeviceArray* rec, const
 
 chq_status chq_record_copy_to_peer(chq_ctx* src_ctx, chq_ctx* dst_ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema,
                                    ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!src_ctx || !dst_ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(dst_ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
+  if (!src_ctx) return CHQ_ERR_INVALID_HANDLE;
+  return host_entry(dst_ctx, [&] { mark_released(out, out_schema); }, [&] {   // (copy_to_peer makes the destination's GPU current)
+    require_out(out, out_schema);
     Batch in = import_batch(rec, schema, true);   // waits on rec->sync_event when the producer left one
     hipEvent_t ev = nullptr;
     Batch moved = copy_to_peer(src_ctx->c, dst_ctx->c, in, &ev);
@@ -904,41 +652,32 @@ void release_ipc(chq_ipc_message* m) {
 
 chq_status chq_record_to_ipc(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, int body_device,
                              chq_ipc_message* out) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  if (out) memset(out, 0, sizeof(*out));
-  return guarded(ctx, [&] {
+  return entry(ctx, [&] { if (out) memset(out, 0, sizeof(*out)); }, [&] {
     require(out, "output message");
-    if (body_device != ARROW_DEVICE_ROCM && body_device != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "body_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+    if (body_device != ARROW_DEVICE_ROCM && body_device != ARROW_DEVICE_CPU) invalid("body_device must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM");
     Batch in = import_batch(rec, schema, true);
     Batch dev = to_device(ctx->c, in);   // (a host batch is staged: the body is assembled by the device either way)
     // an unknown null count (-1, a view) stays unknown: the encoder counts it; to_device's "may have nulls" 1 would be written
     for (size_t i = 0; i < dev.cols.size(); ++i) if (in.on_device && in.cols[i].validity && in.cols[i].null_count < 0) dev.cols[i].null_count = -1;
-    auto* h = new IpcHolder();
-    try {
-      h->msg = record_to_ipc(ctx->c, dev, body_device == ARROW_DEVICE_ROCM);
-    } catch (...) { delete h; throw; }
+    std::unique_ptr<IpcHolder> h(new IpcHolder());
+    h->msg = record_to_ipc(ctx->c, dev, body_device == ARROW_DEVICE_ROCM);
     out->header = h->msg.header.data(); out->header_len = (int64_t)h->msg.header.size();
     out->body = h->msg.body->ptr; out->body_len = h->msg.body_len;
     out->body_device_type = h->msg.body_on_device ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
     out->body_device_id = h->msg.body_on_device ? ctx->c.device : -1;
     const uint8_t eos[8] = {0xff, 0xff, 0xff, 0xff, 0, 0, 0, 0};
     memcpy(out->end_of_stream, eos, 8);
-    out->release = release_ipc; out->private_data = h;
+    out->release = release_ipc; out->private_data = h.release();
   });
 }
 
 chq_status chq_record_from_ipc(chq_ctx* ctx, const uint8_t* stream, int64_t stream_len, const void* body, int64_t body_len,
                                int body_device_type, int out_device, ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema"); require(stream, "stream");
+  return record_entry(ctx, out, out_schema, [&] {
+    require_out(out, out_schema); require(stream, "stream");
     require_out_device(out_device);
     if (body && body_device_type != ARROW_DEVICE_ROCM && body_device_type != ARROW_DEVICE_CPU)
-      throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "body_device_type must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM"};
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+      invalid("body_device_type must be ARROW_DEVICE_CPU or ARROW_DEVICE_ROCM");
     Batch res = record_from_ipc(ctx->c, stream, stream_len, body, body_len, body_device_type == ARROW_DEVICE_ROCM,
                                 out_device == ARROW_DEVICE_ROCM);
     export_batch(std::move(res), out_device, out, out_schema);
@@ -946,56 +685,18 @@ chq_status chq_record_from_ipc(chq_ctx* ctx, const uint8_t* stream, int64_t stre
 }
 
 chq_status chq_ipc_describe(const uint8_t* stream, int64_t stream_len, char* buf, size_t buf_len) {
-  std::string text;
-  chq_status st = CHQ_OK;
-  try {
-    text = describe_ipc(stream, stream_len);
-  } catch (const ChqError& e) {
-    text = e.msg; st = (chq_status)e.code;
-  } catch (const std::exception& e) {
-    text = e.what(); st = CHQ_ERR_ARROW_INVALID_ARGUMENT;
-  }
-  if (buf && buf_len) { const size_t k = std::min(buf_len - 1, text.size()); memcpy(buf, text.data(), k); buf[k] = 0; }
-  return st;
+  return text_result(buf, buf_len, CHQ_ERR_ARROW_INVALID_ARGUMENT, [&] { return describe_ipc(stream, stream_len); });
 }
 
 // ---- Parquet scan -------------------------------------------------------------------------------------------------------
-struct chq_parquet { chq::PqFile file; };
-
 chq_status chq_parquet_open(const uint8_t* file, int64_t file_len, chq_parquet** out, char* err, size_t err_len) {
-  if (!out) return CHQ_ERR_ARROW_INVALID_ARGUMENT;
-  *out = nullptr;
-  std::string text;
-  chq_status st = CHQ_OK;
-  try {
-    auto* h = new chq_parquet();
-    try { h->file = parquet_open(file, file_len); } catch (...) { delete h; throw; }
-    *out = h;
-  } catch (const ChqError& e) {
-    text = e.msg; st = (chq_status)e.code;
-  } catch (const std::exception& e) {
-    text = e.what(); st = CHQ_ERR_ARROW_INVALID_ARGUMENT;
-  }
-  if (err && err_len) { const size_t k = std::min(err_len - 1, text.size()); memcpy(err, text.data(), k); err[k] = 0; }
-  return st;
+  return open_parquet(out, err, err_len, [&] { return parquet_open(file, file_len); });
 }
 chq_status chq_parquet_open_reader(int64_t file_len, chq_read_range_fn read, void* user, chq_parquet** out, char* err, size_t err_len) {
-  if (!out) return CHQ_ERR_ARROW_INVALID_ARGUMENT;
-  *out = nullptr;
-  std::string text;
-  chq_status st = CHQ_OK;
-  try {
-    if (!read) throw ChqError{CHQ_ERR_INVALID_HANDLE, "null range reader"};
-    auto* h = new chq_parquet();
-    try { h->file = parquet_open_reader(file_len, read, user); } catch (...) { delete h; throw; }
-    *out = h;
-  } catch (const ChqError& e) {
-    text = e.msg; st = (chq_status)e.code;
-  } catch (const std::exception& e) {
-    text = e.what(); st = CHQ_ERR_ARROW_INVALID_ARGUMENT;
-  }
-  if (err && err_len) { const size_t k = std::min(err_len - 1, text.size()); memcpy(err, text.data(), k); err[k] = 0; }
-  return st;
+  return open_parquet(out, err, err_len, [&] {
+    require((const void*)read, "range reader");
+    return parquet_open_reader(file_len, read, user);
+  });
 }
 void chq_parquet_close(chq_parquet* pq) { delete pq; }
 int32_t chq_parquet_num_columns(const chq_parquet* pq) { return pq ? (int32_t)pq->file.columns.size() : 0; }
@@ -1009,17 +710,15 @@ int64_t chq_parquet_row_group_num_rows(const chq_parquet* pq, int32_t row_group)
 chq_status chq_parquet_describe(const chq_parquet* pq, char* buf, size_t buf_len) {
   if (!pq) return CHQ_ERR_INVALID_HANDLE;
   const std::string text = parquet_describe(pq->file);
-  if (buf && buf_len) { const size_t k = std::min(buf_len - 1, text.size()); memcpy(buf, text.data(), k); buf[k] = 0; }
+  copy_text(buf, buf_len, text);
   return text.size() < buf_len ? CHQ_OK : CHQ_ERR_ARROW_INVALID_ARGUMENT;
 }
 chq_status chq_parquet_read_row_group(chq_ctx* ctx, const chq_parquet* pq, int32_t row_group, int out_device,
                                       ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!ctx || !pq) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
+  if (!pq) return CHQ_ERR_INVALID_HANDLE;
+  return record_entry(ctx, out, out_schema, [&] {
+    require_out(out, out_schema);
     require_out_device(out_device);
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     Batch res = parquet_read_row_group(ctx->c, pq->file, row_group);
     if (out_device == ARROW_DEVICE_CPU) res = to_host(ctx->c, res);
     export_batch(std::move(res), out_device, out, out_schema);
@@ -1033,101 +732,58 @@ chq_status chq_parquet_read_row_groups(chq_ctx* ctx, const chq_parquet* pq, int3
 
 chq_status chq_parquet_read_columns(chq_ctx* ctx, const chq_parquet* pq, int32_t first, int32_t count, const int32_t* columns,
                                     int32_t n_columns, int out_device, ArrowDeviceArray* outs, ArrowSchema* out_schemas) {
-  if (!ctx || !pq) return CHQ_ERR_INVALID_HANDLE;
-  if (outs && out_schemas) for (int32_t i = 0; i < count; ++i) mark_released(&outs[i], &out_schemas[i]);
-  return guarded(ctx, [&] {
+  if (!pq) return CHQ_ERR_INVALID_HANDLE;
+  return records_entry(ctx, outs && out_schemas ? count : 0, outs, out_schemas, [&] {   // (only a complete pair of arrays is cleared)
     if (count > 0) { require(outs, "output arrays"); require(out_schemas, "output schemas"); }
     require_out_device(out_device);
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
     if (!columns) n_columns = -1;
     std::vector<Batch> res = parquet_read_row_groups(ctx->c, pq->file, first, count, columns, n_columns);
     const chq_call_stats scan_stats = ctx->c.stats;
-    try {
-      for (size_t i = 0; i < res.size(); ++i) {
-        if (out_device == ARROW_DEVICE_CPU) res[i] = to_host(ctx->c, res[i]);
-        export_batch(std::move(res[i]), out_device, &outs[i], &out_schemas[i]);
-      }
-    } catch (...) {   // no partial output
-      for (int32_t i = 0; i < count; ++i) {
-        if (outs[i].array.release) outs[i].array.release(&outs[i].array);
-        if (out_schemas[i].release) out_schemas[i].release(&out_schemas[i]);
-      }
-      throw;
+    for (size_t i = 0; i < res.size(); ++i) {
+      if (out_device == ARROW_DEVICE_CPU) res[i] = to_host(ctx->c, res[i]);
+      export_batch(std::move(res[i]), out_device, &outs[i], &out_schemas[i]);
     }
     ctx->c.stats = scan_stats;   // (to_host does not touch them today; the scan's counters are what the call reports)
   });
 }
 
-namespace {
-struct ParquetImageHolder { chq::ParquetImage img; };
-void release_parquet_image(chq_parquet_image* m) {
-  if (!m || !m->release) return;
-  delete (ParquetImageHolder*)m->private_data;
-  m->data = nullptr; m->len = 0; m->private_data = nullptr; m->release = nullptr;
-}
-}  // namespace
-
 chq_status chq_record_to_parquet(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, chq_parquet_image* out) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  if (out) { out->data = nullptr; out->len = 0; out->release = nullptr; out->private_data = nullptr; }
-  return guarded(ctx, [&] {
-    require(out, "output image");
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+  return image_entry(ctx, out, [&] {
     Batch in = import_batch(rec, schema);
-    auto* h = new ParquetImageHolder();
-    try { h->img = record_to_parquet(ctx->c, in); } catch (...) { delete h; throw; }
-    out->data = (const uint8_t*)h->img.bytes->ptr; out->len = h->img.len;
-    out->release = release_parquet_image; out->private_data = h;
+    return record_to_parquet(ctx->c, in);
   });
 }
 
 chq_status chq_records_to_parquet(chq_ctx* ctx, int n_records, const ArrowDeviceArray* const* recs, const ArrowSchema* schema,
                                   chq_parquet_image* out) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  if (out) { out->data = nullptr; out->len = 0; out->release = nullptr; out->private_data = nullptr; }
-  return guarded(ctx, [&] {
-    require(out, "output image"); require(recs, "record batches");
-    if (n_records < 1) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "chq_records_to_parquet needs at least one record batch"};
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+  return image_entry(ctx, out, [&] {
+    require(recs, "record batches");
+    if (n_records < 1) invalid("chq_records_to_parquet needs at least one record batch");
     std::vector<Batch> in((size_t)n_records);
     std::vector<const Batch*> ptrs((size_t)n_records);
     for (int i = 0; i < n_records; ++i) { in[(size_t)i] = import_batch(recs[i], schema); ptrs[(size_t)i] = &in[(size_t)i]; }
-    auto* h = new ParquetImageHolder();
-    try { h->img = records_to_parquet(ctx->c, ptrs); } catch (...) { delete h; throw; }
-    out->data = (const uint8_t*)h->img.bytes->ptr; out->len = h->img.len;
-    out->release = release_parquet_image; out->private_data = h;
+    return records_to_parquet(ctx->c, ptrs);
   });
 }
 
 chq_status chq_record_to_host(chq_ctx* ctx, const ArrowDeviceArray* rec, const ArrowSchema* schema, ArrowDeviceArray* out,
                               ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
-    check_hip(hipSetDevice(ctx->c.device), "hipSetDevice");
+  return record_entry(ctx, out, out_schema, [&] {
+    require_out(out, out_schema);
     Batch in = import_batch(rec, schema, true);
-    if (!in.on_device) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "record is already host resident"};
+    if (!in.on_device) invalid("record is already host resident");
     for (Column& c : in.cols) if (c.validity && c.null_count < 0) c.null_count = 1;
     Batch h = to_host(ctx->c, in);
     // resolve unknown null counts on the host copy
-    for (Column& c : h.cols) {
-      if (c.validity) {
-        int64_t nulls = 0;
-        for (int64_t i = 0; i < c.length; ++i) { int64_t b = c.offset + i; nulls += !((c.validity[b >> 3] >> (b & 7)) & 1); }
-        c.null_count = nulls;
-      }
-    }
+    for (Column& c : h.cols) if (c.validity) c.null_count = count_nulls_host(c.validity, c.offset, c.length);
     export_batch(std::move(h), ARROW_DEVICE_CPU, out, out_schema);
   });
 }
 
 chq_status chq_wrap_columns(chq_ctx* ctx, const chq_column_desc* cols, int n_cols, int64_t n_rows, int device_type,
                             ArrowDeviceArray* out, ArrowSchema* out_schema) {
-  if (!ctx) return CHQ_ERR_INVALID_HANDLE;
-  mark_released(out, out_schema);
-  return guarded(ctx, [&] {
-    require(out, "output array"); require(out_schema, "output schema");
+  return host_entry(ctx, [&] { mark_released(out, out_schema); }, [&] {   // (host work only: the caller's current GPU stays)
+    require_out(out, out_schema);
     if (n_cols > 0) require(cols, "column descriptors");
     Batch b;
     b.nrows = n_rows; b.on_device = device_type == ARROW_DEVICE_ROCM; b.device_id = ctx->c.device;
@@ -1143,9 +799,9 @@ chq_status chq_wrap_columns(chq_ctx* ctx, const chq_column_desc* cols, int n_col
         Batch probe = import_batch(&da, &parent);
         c.type = probe.cols[0].type; c.width = probe.cols[0].width;
       }
-      if (n_rows > 0 && !cols[i].values) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "column '" + c.name + "' has no values buffer"};
-      if (cols[i].null_count > 0 && !cols[i].validity) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "column '" + c.name + "' reports nulls but has no validity bitmap"};
-      if (n_rows < 0 || cols[i].offset < 0) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative length or offset"};
+      if (n_rows > 0 && !cols[i].values) invalid("column '" + c.name + "' has no values buffer");
+      if (cols[i].null_count > 0 && !cols[i].validity) invalid("column '" + c.name + "' reports nulls but has no validity bitmap");
+      if (n_rows < 0 || cols[i].offset < 0) invalid("negative length or offset");
       c.nullable = cols[i].nullable != 0; c.length = n_rows; c.null_count = cols[i].validity ? cols[i].null_count : 0; c.offset = cols[i].offset;
       c.validity = (const uint8_t*)cols[i].validity; c.values = (const uint8_t*)cols[i].values; c.data = (const uint8_t*)cols[i].data;
       b.cols.push_back(std::move(c));

@@ -13,11 +13,6 @@ enum class Dir { H2D, D2H, D2D, H2H, P2P };
 Column copy_column(Context& ctx, const Column& c, Dir dir, int peer_device = -1);
 
 // ---- defined here: what the per-call host paths must be able to inline -----------------------------------------------------
-inline int64_t count_nulls_host(const uint8_t* validity, int64_t offset, int64_t n) {
-  int64_t nulls = 0;
-  for (int64_t i = 0; i < n; ++i) { int64_t b = offset + i; nulls += !((validity[b >> 3] >> (b & 7)) & 1); }
-  return nulls;
-}
 inline void add_stats(chq_call_stats& acc, const chq_call_stats& s) {
   acc.rows_in += s.rows_in; acc.rows_out += s.rows_out; acc.tiles += s.tiles; acc.launches += s.launches;
   acc.bytes_read_alg += s.bytes_read_alg; acc.bytes_written_alg += s.bytes_written_alg; acc.kernel_ns += s.kernel_ns;

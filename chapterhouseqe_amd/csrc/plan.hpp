@@ -46,6 +46,9 @@ struct Expr {
   std::unique_ptr<Expr> l, r;
   std::vector<std::unique_ptr<Expr>> args;
 };
+}  // namespace chq
+struct chq_expr { chq::Expr e; };   // the C ABI's expression handle (capi_expr.cpp builds them)
+namespace chq {
 
 const char* dtype_name(DType t);
 int dtype_width(DType t);   // bytes of a fixed-width value (0 for bool / utf8)
