@@ -84,6 +84,15 @@ void launch_tiles(Context& ctx, Params& p, int64_t rows, int64_t tile_rows, int6
   }
 }
 
+// A zero-row device column's buffers: 16 zeroed bytes of values (Utf8: offsets = {0}), for Utf8 a data buffer without bytes.
+// Queued on the stream; the caller synchronises.
+inline void give_empty_buffers(Context& ctx, Column& o) {
+  auto vb = make_device_buffer(16, ctx.device);
+  check_hip(hipMemsetAsync(vb->ptr, 0, 16, ctx.stream), "memset");
+  o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
+  if (o.type == T_UTF8) { auto db = make_device_buffer(16, ctx.device); o.data = (const uint8_t*)db->ptr; o.owned.push_back(db); }
+}
+
 // ---- filter.cpp: a lowered program and its launch ------------------------------------------------------------------------
 void fill_refs(ProgramBlock& pb, const Lowered& lw, const Batch& rec, const std::vector<BufferPtr>& str_bufs);
 BufferPtr upload_literal(Context& ctx, const std::string& s);
@@ -97,6 +106,8 @@ void fit_to_device(Context& ctx, const Batch& rec, const std::vector<PlanColumn>
                    Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te);
 // ---- filter.cpp: typing ------------------------------------------------------------------------------------------------------
 TypedExpr typed(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& expr);
+// `te` has a static error pending: a data-dependent error of its completed sub-trees (validate_roots, when there are rows), else it
+[[noreturn]] void throw_pending(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const TypedExpr& te);
 bool is_row_predicate(const TypedExpr& te);
 Column empty_like(const Column& c);
 // ---- filter.cpp: the uniform-length Utf8 rewrite -----------------------------------------------------------------------------
@@ -104,7 +115,6 @@ bool uniform_utf8_ok(bool may_hold_nulls, int64_t rows, int64_t L);
 Column uniform_to_utf8(Context& ctx, Column&& fixed, const Column& like, int64_t rows, bool on_device);
 
 // ---- project.cpp: typed trees evaluated densely over a batch, one column per expression ------------------------------------
-std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols,
-                                   const std::vector<const TypedExpr*>& exprs);
+std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const std::vector<const TypedExpr*>& exprs);
 
 }  // namespace chq

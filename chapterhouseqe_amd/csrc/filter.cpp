@@ -228,10 +228,7 @@ Batch empty_filter_result(Context& ctx, const Batch& rec) {
   out.on_device = true; out.device_id = ctx.device; out.nrows = 0;
   for (const Column& c : rec.cols) {
     Column o = empty_like(c);
-    auto vb = make_device_buffer(16, ctx.device);
-    check_hip(hipMemsetAsync(vb->ptr, 0, 16, ctx.stream), "memset");
-    o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
-    if (o.type == T_UTF8) { auto db = make_device_buffer(16, ctx.device); o.data = (const uint8_t*)db->ptr; o.owned.push_back(db); }
+    give_empty_buffers(ctx, o);
     out.cols.push_back(std::move(o));
   }
   check_hip(hipStreamSynchronize(ctx.stream), "sync");
@@ -599,20 +596,21 @@ void pick_stash(FilterParams& p, const Context& ctx, const Lowered& lw, const st
   }
 }
 
-// type_expr + the reference's error order: data-dependent errors of subtrees evaluated before a static
-// error take precedence over it
+// The reference's error order: data-dependent errors of subtrees evaluated before a static error take precedence over it
+void throw_pending(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const TypedExpr& te) {
+  if (rec.nrows > 0) {
+    std::vector<TypedExpr> subs;
+    for (int r : te.validate_roots) { TypedExpr s; s.nodes = te.nodes; s.root = r; subs.push_back(std::move(s)); }
+    std::vector<const TypedExpr*> ptrs;
+    for (auto& s : subs) ptrs.push_back(&s);
+    (void)evaluate_dense(ctx, rec, pcols, ptrs);   // throws the data-dependent error if there is one
+  }
+  throw ChqError{te.pending_code, te.pending_msg};
+}
+// type_expr in that order
 TypedExpr typed(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& expr) {
   TypedExpr te = type_expr(expr, pcols, rec.nrows, ctx.opt_enable_minus);
-  if (te.pending_code) {
-    if (rec.nrows > 0) {
-      std::vector<TypedExpr> subs;
-      for (int r : te.validate_roots) { TypedExpr s; s.nodes = te.nodes; s.root = r; subs.push_back(std::move(s)); }
-      std::vector<const TypedExpr*> ptrs;
-      for (auto& s : subs) ptrs.push_back(&s);
-      (void)evaluate_dense(ctx, rec, pcols, ptrs);   // throws the data-dependent error if there is one
-    }
-    throw ChqError{te.pending_code, te.pending_msg};
-  }
+  if (te.pending_code) throw_pending(ctx, rec, pcols, te);
   return te;
 }
 

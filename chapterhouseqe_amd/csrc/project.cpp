@@ -1,11 +1,10 @@
-// project.cpp -- dense evaluation of typed expressions, compute_value, project_record, the fused filter + project pass, the
-// host projection path and describe_plan.  Reference map: project_record = RU/record_projection.rs:16-76, compute_value =
-// RU/compute_value.rs:57-344 (RU = src/handlers/operator_handler/operators/record_utils of the reference).
+// project.cpp -- dense evaluation of typed expressions, compute_value, the select-list reader and its three consumers
+// (project_record, the fused filter + project pass, the host projection path) and describe_plan.  Reference map: project_record =
+// RU/record_projection.rs:16-76, compute_value = RU/compute_value.rs:57-344 (RU = src/handlers/operator_handler/operators/record_utils).
 #include "engine_internal.hpp"
 
 #include <cstdio>
 #include <cstring>
-#include <functional>
 
 namespace chq {
 
@@ -37,10 +36,8 @@ Column scalar_column(Context& ctx, const Scalar& s, const std::string& name) {
   return o;
 }
 
-struct ProjItem {   // one computed output of a launch
-  int out_index;     // position in the output batch
-  int null_slot;     // counter slot, -1 when the expression cannot produce nulls
-};
+// one computed output of a launch: its position in the results; its counter slot, -1 when the expression cannot produce nulls
+struct ProjItem { int out_index, null_slot; };
 
 bool subtree_can_null(const TypedExpr& t, int ni, const std::vector<PlanColumn>& cols) {
   const Node& n = t.at(ni);
@@ -63,212 +60,239 @@ std::string select_item_name(const chq_select_item& f, const Expr& e, size_t* un
   return name;
 }
 
-// the result of one compute_value call: a passthrough column, a literal-built length-1 array, or a program
-struct Evaluated {
-  enum Kind { PASSTHROUGH, SCALAR, COMPUTED } kind;
-  int col = -1;
-  Scalar value;
-  TypedExpr typed;
-  bool is_scalar = false;
+// One output column of a select list, as project_record, the single-pass kernel and the host path all take it
+struct SelectEntry {
+  // a column of `*`, a column handed through, a literal-built length-1 value, a program to run
+  enum Kind { WILDCARD, COLUMN, SCALAR, COMPUTED } kind = COMPUTED;
+  std::string name;   // of the output column
+  int col = -1;       // WILDCARD, COLUMN
+  Scalar value;       // SCALAR
+  TypedExpr typed;    // every kind but WILDCARD.  COMPUTED with pending_code set: a static error is due when the item is reached
+  bool pending() const { return typed.pending_code != 0; }
+};
+struct SelectList {
+  std::vector<SelectEntry> entries;
+  ChqError stop{0, ""};           // code != 0: an item could not be read, `entries` holds what precedes it
+  bool stop_after_earlier = true; // false: a broken item (null expr, unknown kind) is reported without evaluating anything
+  bool stopped() const { return stop.code != 0; }
+  // what the paths that only compute whole columns take: every item read, no length-1 value, no error pending
+  bool whole_columns() const {
+    for (const SelectEntry& en : entries) if (en.kind == SelectEntry::SCALAR || en.pending()) return false;
+    return !stopped();
+  }
 };
 
-Evaluated classify(Context& ctx, const Batch& rec, const Expr& e, const std::vector<PlanColumn>& pcols) {
-  Evaluated ev;
-  ev.typed = typed(ctx, rec, pcols, e);
-  const Node& root = ev.typed.at(ev.typed.root);
-  ev.is_scalar = root.is_scalar;
-  if (root.kind == Node::COL) { ev.kind = Evaluated::PASSTHROUGH; ev.col = root.col; }
-  else if (root.len1) { ev.kind = Evaluated::SCALAR; ev.value = fold_constant(ev.typed, ev.typed.root); }
-  else ev.kind = Evaluated::COMPUTED;
-  return ev;
+// a typed expression as compute_value sorts it; a literal-only one is folded here (fold_constant may throw)
+SelectEntry entry_of(TypedExpr te) {
+  SelectEntry en;
+  const Node& root = te.at(te.root);
+  if (root.kind == Node::COL) { en.kind = SelectEntry::COLUMN; en.col = root.col; }
+  else if (root.len1) { en.kind = SelectEntry::SCALAR; en.value = fold_constant(te, te.root); }
+  en.typed = std::move(te);
+  return en;
+}
+
+// THE reader of a select list (RU/record_projection.rs:16-76): kinds, `*`, typing, the three-way sort and the names, for a
+// batch of `nrows` rows with the columns `pcols`.  Host work only, and nothing is thrown: the first item that cannot be read
+// ends the list and its error is kept.
+SelectList read_select_list(const std::vector<chq_select_item>& fields, const std::vector<PlanColumn>& pcols, int64_t nrows, bool enable_minus) {
+  SelectList list;
+  auto stop = [&](ChqError why, bool after_earlier) { list.stop = std::move(why); list.stop_after_earlier = after_earlier; };
+  size_t unnamed_idx = 0;
+  for (const chq_select_item& f : fields) {
+    if (f.kind == CHQ_ITEM_WILDCARD) {   // :27-32
+      for (size_t ci = 0; ci < pcols.size(); ++ci) list.entries.push_back(SelectEntry{SelectEntry::WILDCARD, pcols[ci].name, (int)ci, {}, {}});
+      continue;
+    }
+    if (f.kind == CHQ_ITEM_QUALIFIED_WILDCARD) { stop({CHQ_ERR_PROJECT_NOT_IMPLEMENTED, "not implemented: SelectItem::QualifiedWildcard"}, true); break; }
+    if (f.kind != CHQ_ITEM_UNNAMED_EXPR && f.kind != CHQ_ITEM_EXPR_WITH_ALIAS) { stop({CHQ_ERR_INVALID_HANDLE, "unknown select item kind"}, false); break; }
+    if (!f.expr) { stop({CHQ_ERR_INVALID_HANDLE, "select item without expression"}, false); break; }
+    const Expr& e = *(const Expr*)f.expr;
+    SelectEntry en;
+    try {
+      TypedExpr te = type_expr(e, pcols, nrows, enable_minus);
+      if (te.pending_code) en.typed = std::move(te); else en = entry_of(std::move(te));
+    } catch (const ChqError& err) { stop(err, true); break; }
+    en.name = select_item_name(f, e, &unnamed_idx);
+    list.entries.push_back(std::move(en));
+  }
+  return list;
+}
+
+// the computed entries before `end`, in one evaluation
+std::vector<Column> evaluate_entries(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const SelectList& list, size_t end) {
+  std::vector<const TypedExpr*> ptrs;
+  for (size_t i = 0; i < end; ++i) if (list.entries[i].kind == SelectEntry::COMPUTED) ptrs.push_back(&list.entries[i].typed);
+  if (ptrs.empty()) return {};
+  return evaluate_dense(ctx, rec, pcols, ptrs);
+}
+
+// The list cannot be produced: entry `at` has a static error pending, or (at = entries.size()) the list stopped there.  The
+// reference evaluates the items one after the other, so what the caller gets is, strongest first:
+//   1. the data-dependent error of any EARLIER computed item (the first failing one, as evaluate_dense finds it);
+//   2. the data-dependent error of this item's own completed sub-trees (validate_roots; only when the batch has rows);
+//   3. the static error of this item.
+// A null `expr` and an unknown item kind are the exception: they are reported at once, without step 1 (QualifiedWildcard is
+// an item of the reference's like any other and takes step 1).
+[[noreturn]] void replay_stopped(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const SelectList& list, size_t at) {
+  const bool pending = at < list.entries.size();
+  if (pending || list.stop_after_earlier) (void)evaluate_entries(ctx, rec, pcols, list, at);   // 1
+  if (pending) throw_pending(ctx, rec, pcols, list.entries[at].typed);                        // 2, 3
+  throw list.stop;                                                                            // 3
+}
+
+// ---- evaluate_dense, step by step: which root may be a result, and the (still empty) column it becomes ---------------------
+Column result_column(const Node& root, const std::vector<PlanColumn>& pcols, int64_t nrows) {
+  Column o;
+  o.type = root.type; o.format = dtype_format(root.type); o.width = dtype_width(root.type); o.length = nrows;
+  // (a Utf8 result is a string function's: fitting turns it into a temporary column, which IS the result)
+  // (.. or a CASE's, of any type)
+  if (root.kind == Node::CASE && root.type == T_FIXED_OPAQUE) { o.format = pcols[(size_t)root.fmt_col].format; o.width = pcols[(size_t)root.fmt_col].width; }
+  // (.. or an explicit cast's to Utf8)
+  if (root.kind != Node::CASE && ((root.type == T_UTF8 && root.kind != Node::STRFN && root.kind != Node::XCAST) || root.type == T_FIXED_OPAQUE))
+    throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("expression result of type ") + dtype_name(root.type) + " is outside this build's scope"};
+  return o;
+}
+
+// Too large for one program even alone: sub-trees become temporary columns first (fit_to_device), then the rest is
+// evaluated like any other expression
+Column evaluate_oversized(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const TypedExpr& te) {
+  Batch work; std::vector<PlanColumn> wcols; TypedExpr fitted;
+  fit_to_device(ctx, rec, pcols, te, work, wcols, fitted);
+  if (fitted.at(fitted.root).kind == Node::COL) {   // a typed operation at the root: its temporary column is the result
+    Column c = work.cols[(size_t)fitted.at(fitted.root).col];
+    c.name.clear();
+    return c;
+  }
+  return std::move(evaluate_dense(ctx, work, wcols, {&fitted})[0]);
+}
+
+struct Packed { Lowered lw; std::vector<ProjItem> items; };
+// As many expressions from exprs[k] on as fit the program limits, for one launch; k moves past them
+Packed pack_launch(const std::vector<const TypedExpr*>& exprs, const std::vector<PlanColumn>& pcols, size_t& k) {
+  Packed pk;
+  int null_slots = 0;
+  const size_t k0 = k;
+  for (; k < exprs.size() && (int)pk.items.size() < MAX_PROJ; ++k) {
+    Lowered trial = pk.lw;
+    try {
+      lower_expr(*exprs[k], exprs[k]->root, pcols, trial);
+      if ((int)trial.prog.size() + 1 > MAX_INSTR) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "program too long"};
+    } catch (const ChqError&) { if (k == k0) throw; break; }   // (throw: does not fit even alone)
+    Instr st{}; st.op = OP_STORE; st.src_idx = (uint16_t)pk.items.size(); st.src_kind = SRC_NONE;
+    trial.prog.push_back(st);
+    pk.lw = std::move(trial);
+    const bool can_null = subtree_can_null(*exprs[k], exprs[k]->root, pcols);
+    if (can_null && null_slots >= 16) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "too many nullable outputs in one projection"};
+    pk.items.push_back(ProjItem{(int)k, can_null ? null_slots++ : -1});
+  }
+  return pk;
+}
+
+// One launch: the output buffers of pk's items, the kernel, the read-back of the error word and the null counts
+void launch_packed(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const std::vector<const TypedExpr*>& exprs,
+                   const Packed& pk, std::vector<Column>& results) {
+  const int64_t nrows = rec.nrows;
+  const std::vector<ProjItem>& items = pk.items;
+  Scratch* ds = dev_scratch(ctx);   // (looked up here: a nested evaluation may have replaced the block)
+  ProjectParams p{};
+  p.nrows = nrows; p.err = &ds->err; p.n_proj = (int32_t)items.size();
+  auto str_bufs = upload_strings(ctx, pk.lw);
+  fill_refs(p.pb, pk.lw, rec, str_bufs);
+  for (size_t i = 0; i < items.size(); ++i) {
+    Column& o = results[items[i].out_index];
+    const size_t vbytes = o.type == T_BOOL ? (size_t)((nrows + 63) / 64) * 8 + 16 : (size_t)nrows * o.width + 16;
+    auto vb = make_device_buffer(vbytes, ctx.device);
+    o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
+    ProjOut po{};
+    po.values = vb->ptr; po.type = o.type;
+    if (items[i].null_slot >= 0) {
+      auto nb = make_device_buffer((size_t)((nrows + 63) / 64) * 8 + 16, ctx.device);
+      o.validity = (const uint8_t*)nb->ptr; o.owned.push_back(nb);
+      po.validity = (u64*)nb->ptr; po.null_count = &ds->counters[items[i].null_slot];
+    }
+    p.outs[i] = po;
+  }
+  check_hip(hipMemsetAsync(ds, 0, sizeof(Scratch), ctx.stream), "memset scratch");
+  const int tile_kind = pick_tile_kind(ctx, pk.lw, nrows);
+  launch_tiles(ctx, p, nrows, kTileRows[tile_kind], (int64_t)ctx.num_cus * (tile_kind == 0 ? 2 : 8), [&](bool partial, int grid, bool tail) {
+    check_hip(launch_project(p, tile_kind, partial, grid, ctx.stream), tail ? "launch project_kernel (tail)" : "launch project_kernel");
+  });
+  const Scratch* hs = read_scratch(ctx);
+  if (hs->err != ERR_NONE) {
+    // Several expressions shared the launch and each numbers its nodes from zero, so the smallest (node, row) key may
+    // belong to a later select item.  The reference evaluates the items one after the other: do the same to find
+    // the error it would have reported.
+    if (items.size() > 1) for (const ProjItem& it : items) (void)evaluate_dense(ctx, rec, pcols, {exprs[it.out_index]});   // throws at the first failing item
+    throw_device_error(hs->err);
+  }
+  for (const ProjItem& it : items) {
+    Column& o = results[it.out_index];
+    if (it.null_slot >= 0) { o.null_count = (int64_t)hs->counters[it.null_slot]; if (o.null_count == 0) o.validity = nullptr; }
+  }
 }
 
 }  // namespace
 
 // Evaluate the expressions `exprs[k]` (typed trees) densely over `rec`; returns one column per expression.
-std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols,
-                                   const std::vector<const TypedExpr*>& exprs) {
-  const int64_t nrows = rec.nrows;
-  std::vector<Column> results(exprs.size());
-  for (size_t k = 0; k < exprs.size(); ++k) {
-    const Node& root = exprs[k]->at(exprs[k]->root);
-    Column& o = results[k];
-    o.type = root.type; o.format = dtype_format(root.type); o.width = dtype_width(root.type); o.length = nrows;
-    // (a Utf8 result is a string function's: fitting below turns it into a temporary column, which IS the result)
-    // (.. or a CASE's, of any type)
-    if (root.kind == Node::CASE && root.type == T_FIXED_OPAQUE) { o.format = pcols[(size_t)root.fmt_col].format; o.width = pcols[(size_t)root.fmt_col].width; }
-    // (.. or an explicit cast's to Utf8)
-    if (root.kind != Node::CASE && ((root.type == T_UTF8 && root.kind != Node::STRFN && root.kind != Node::XCAST) || root.type == T_FIXED_OPAQUE))
-      throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("expression result of type ") + dtype_name(root.type) + " is outside this build's scope"};
-  }
-  if (nrows == 0) {
-    for (Column& o : results) {
-      auto vb = make_device_buffer(16, ctx.device);
-      o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
-      if (o.type != T_UTF8) continue;
-      auto db = make_device_buffer(16, ctx.device);   // offsets = {0}, no bytes
-      check_hip(hipMemsetAsync(vb->ptr, 0, 16, ctx.stream), "memset");
-      o.data = (const uint8_t*)db->ptr; o.data_bytes = 0; o.owned.push_back(db);
-    }
+std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const std::vector<const TypedExpr*>& exprs) {
+  std::vector<Column> results;
+  for (const TypedExpr* te : exprs) results.push_back(result_column(te->at(te->root), pcols, rec.nrows));
+  if (rec.nrows == 0) {
+    for (Column& o : results) { give_empty_buffers(ctx, o); if (o.type == T_UTF8) o.data_bytes = 0; }
     check_hip(hipStreamSynchronize(ctx.stream), "sync");
     return results;
   }
   ensure_scratch(ctx, 1);
-  size_t k = 0;
-  while (k < exprs.size()) {
-    if (!lowers_alone(*exprs[k], exprs[k]->root, pcols)) {
-      // too large for one program even alone: sub-trees become temporary columns first (fit_to_device), then the
-      // rest is evaluated like any other expression
-      Batch work; std::vector<PlanColumn> wcols; TypedExpr fitted;
-      fit_to_device(ctx, rec, pcols, *exprs[k], work, wcols, fitted);
-      if (fitted.at(fitted.root).kind == Node::COL) {   // a typed operation at the root: its temporary column is the result
-        results[k] = work.cols[(size_t)fitted.at(fitted.root).col];
-        results[k].name.clear();
-        ++k;
-        continue;
-      }
-      std::vector<const TypedExpr*> one{&fitted};
-      Column c = std::move(evaluate_dense(ctx, work, wcols, one)[0]);
-      results[k] = std::move(c);
-      ++k;
-      continue;
-    }
-    // pack as many expressions as fit the program limits into one launch
-    Scratch* ds = dev_scratch(ctx);   // (looked up here: a nested call above may have replaced the block)
-    Lowered lw;
-    std::vector<ProjItem> items;
-    int null_slots = 0;
-    size_t k0 = k;
-    for (; k < exprs.size() && (int)items.size() < MAX_PROJ; ++k) {
-      Lowered trial = lw;
-      try {
-        lower_expr(*exprs[k], exprs[k]->root, pcols, trial);
-        if ((int)trial.prog.size() + 1 > MAX_INSTR) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "program too long"};
-      } catch (const ChqError& e) {
-        if (k == k0) throw;   // does not fit even alone
-        break;
-      }
-      Instr st{}; st.op = OP_STORE; st.src_idx = (uint16_t)items.size(); st.src_kind = SRC_NONE;
-      trial.prog.push_back(st);
-      lw = std::move(trial);
-      const bool can_null = subtree_can_null(*exprs[k], exprs[k]->root, pcols);
-      if (can_null && null_slots >= 16) throw ChqError{CHQ_ERR_NOT_SUPPORTED, "too many nullable outputs in one projection"};
-      items.push_back(ProjItem{(int)k, can_null ? null_slots++ : -1});
-    }
-    ProjectParams p{};
-    p.nrows = nrows; p.err = &ds->err; p.n_proj = (int32_t)items.size();
-    auto str_bufs = upload_strings(ctx, lw);
-    fill_refs(p.pb, lw, rec, str_bufs);
-    for (size_t i = 0; i < items.size(); ++i) {
-      Column& o = results[items[i].out_index];
-      const size_t vbytes = o.type == T_BOOL ? (size_t)((nrows + 63) / 64) * 8 + 16 : (size_t)nrows * o.width + 16;
-      auto vb = make_device_buffer(vbytes, ctx.device);
-      o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
-      ProjOut po{};
-      po.values = vb->ptr; po.type = o.type;
-      if (items[i].null_slot >= 0) {
-        auto nb = make_device_buffer((size_t)((nrows + 63) / 64) * 8 + 16, ctx.device);
-        o.validity = (const uint8_t*)nb->ptr; o.owned.push_back(nb);
-        po.validity = (u64*)nb->ptr; po.null_count = &ds->counters[items[i].null_slot];
-      }
-      p.outs[i] = po;
-    }
-    check_hip(hipMemsetAsync(ds, 0, sizeof(Scratch), ctx.stream), "memset scratch");
-    const int tile_kind = pick_tile_kind(ctx, lw, nrows);
-    launch_tiles(ctx, p, nrows, kTileRows[tile_kind], (int64_t)ctx.num_cus * (tile_kind == 0 ? 2 : 8), [&](bool partial, int grid, bool tail) {
-      check_hip(launch_project(p, tile_kind, partial, grid, ctx.stream), tail ? "launch project_kernel (tail)" : "launch project_kernel");
-    });
-    const Scratch* hs = read_scratch(ctx);
-    if (hs->err != ERR_NONE) {
-      // Several expressions shared the launch and each numbers its nodes from zero, so the smallest (node, row) key may
-      // belong to a later select item.  The reference evaluates the items one after the other: do the same to find
-      // the error it would have reported.
-      if (items.size() > 1) {
-        for (const ProjItem& it : items) {
-          std::vector<const TypedExpr*> one{exprs[it.out_index]};
-          (void)evaluate_dense(ctx, rec, pcols, one);   // throws at the first failing item
-        }
-      }
-      throw_device_error(hs->err);
-    }
-    for (const ProjItem& it : items) {
-      Column& o = results[it.out_index];
-      if (it.null_slot >= 0) { o.null_count = (int64_t)hs->counters[it.null_slot]; if (o.null_count == 0) o.validity = nullptr; }
-    }
+  for (size_t k = 0; k < exprs.size();) {
+    if (!lowers_alone(*exprs[k], exprs[k]->root, pcols)) { results[k] = evaluate_oversized(ctx, rec, pcols, *exprs[k]); ++k; continue; }
+    const Packed pk = pack_launch(exprs, pcols, k);
+    launch_packed(ctx, rec, pcols, exprs, pk, results);
   }
   return results;
 }
 
 Column compute_value(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& expr, bool* is_scalar) {
   ctx.stats = chq_call_stats{};
-  Evaluated ev = classify(ctx, rec, expr, pcols);
-  if (is_scalar) *is_scalar = ev.is_scalar;
+  const SelectEntry en = entry_of(typed(ctx, rec, pcols, expr));
+  if (is_scalar) *is_scalar = en.typed.at(en.typed.root).is_scalar;
   Column out;
-  switch (ev.kind) {
-    case Evaluated::PASSTHROUGH: out = clone_device_column(ctx, rec.cols[ev.col]); check_hip(hipStreamSynchronize(ctx.stream), "sync"); break;
-    case Evaluated::SCALAR: out = scalar_column(ctx, ev.value, ""); break;
-    default: { std::vector<const TypedExpr*> v{&ev.typed}; out = std::move(evaluate_dense(ctx, rec, pcols, v)[0]); } break;
+  switch (en.kind) {
+    case SelectEntry::COLUMN: out = clone_device_column(ctx, rec.cols[en.col]); check_hip(hipStreamSynchronize(ctx.stream), "sync"); break;
+    case SelectEntry::SCALAR: out = scalar_column(ctx, en.value, ""); break;
+    default: out = std::move(evaluate_dense(ctx, rec, pcols, {&en.typed})[0]); break;
   }
   out.nullable = out.null_count > 0;
   return out;
 }
 
-Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, const Batch& rec,
-                     const std::vector<PlanColumn>& pcols) {
+Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, const Batch& rec, const std::vector<PlanColumn>& pcols) {
   ctx.stats = chq_call_stats{};
   Batch out;
   out.on_device = true; out.device_id = ctx.device;
-  std::vector<Evaluated> evs;            // computed items, evaluated together after the walk
-  std::vector<int> computed_slot;        // output column index of each computed item
-  std::vector<size_t> passthrough_slot;  // output column index of each identifier item
-  size_t unnamed_idx = 0;
-  auto evaluate_items = [&]() -> std::vector<Column> {   // the computed items so far, in one evaluation
-    if (evs.empty()) return {};
-    std::vector<const TypedExpr*> ptrs;
-    for (auto& ev : evs) ptrs.push_back(&ev.typed);
-    return evaluate_dense(ctx, rec, pcols, ptrs);
-  };
-  for (const chq_select_item& f : fields) {
-    switch (f.kind) {
-      case CHQ_ITEM_WILDCARD:   // RU/record_projection.rs:27-32
-        for (const Column& c : rec.cols) out.cols.push_back(clone_device_column(ctx, c));
-        break;
-      case CHQ_ITEM_QUALIFIED_WILDCARD:
-        (void)evaluate_items();
-        throw ChqError{CHQ_ERR_PROJECT_NOT_IMPLEMENTED, "not implemented: SelectItem::QualifiedWildcard"};
-      case CHQ_ITEM_UNNAMED_EXPR:
-      case CHQ_ITEM_EXPR_WITH_ALIAS: {
-        if (!f.expr) throw ChqError{CHQ_ERR_INVALID_HANDLE, "select item without expression"};
-        const Expr& e = *(const Expr*)f.expr;
-        Evaluated ev;
-        try {
-          ev = classify(ctx, rec, e, pcols);
-        } catch (const ChqError&) {
-          (void)evaluate_items();   // the reference evaluates the items in order: errors of earlier computed items come first
-          throw;
-        }
-        const std::string name = select_item_name(f, e, &unnamed_idx);
-        Column col;
-        if (ev.kind == Evaluated::PASSTHROUGH) { col = clone_device_column(ctx, rec.cols[ev.col]); passthrough_slot.push_back(out.cols.size()); }
-        else if (ev.kind == Evaluated::SCALAR) col = scalar_column(ctx, ev.value, name);
-        else { computed_slot.push_back((int)out.cols.size()); evs.push_back(std::move(ev)); }
-        col.name = name;
-        out.cols.push_back(std::move(col));
-      } break;
-      default: throw ChqError{CHQ_ERR_INVALID_HANDLE, "unknown select item kind"};
-    }
+  const SelectList list = read_select_list(fields, pcols, rec.nrows, ctx.opt_enable_minus);
+  size_t bad = 0;   // the first item that cannot be produced
+  while (bad < list.entries.size() && !list.entries[bad].pending()) ++bad;
+  if (bad < list.entries.size() || list.stopped()) replay_stopped(ctx, rec, pcols, list, bad);
+  const size_t n_out = list.entries.size();   // (one entry per output column)
+  auto kind = [&](size_t k) { return list.entries[k].kind; };
+  for (const SelectEntry& en : list.entries) {   // the computed items stay empty until all are evaluated together
+    Column col;
+    if (en.kind == SelectEntry::SCALAR) col = scalar_column(ctx, en.value, en.name);
+    else if (en.kind != SelectEntry::COMPUTED) col = clone_device_column(ctx, rec.cols[en.col]);
+    out.cols.push_back(std::move(col));
   }
-  std::vector<Column> cols = evaluate_items();
-  for (size_t i = 0; i < cols.size(); ++i) {
-    std::string name = out.cols[computed_slot[i]].name;
-    out.cols[computed_slot[i]] = std::move(cols[i]);
-    out.cols[computed_slot[i]].name = name;
+  std::vector<Column> cols = evaluate_entries(ctx, rec, pcols, list, n_out);
+  for (size_t k = 0, next = 0; k < n_out; ++k) {
+    if (kind(k) == SelectEntry::COMPUTED) out.cols[k] = std::move(cols[next++]);
+    out.cols[k].name = list.entries[k].name;
   }
   // an identifier over a view keeps the view's bitmap with its null count unknown (imported as "may have nulls"): count the
   // window's nulls, so that its nullability is the reference's null_count > 0 below
   std::vector<size_t> counted;
-  for (size_t k : passthrough_slot) {
+  for (size_t k = 0; k < n_out; ++k) {
     Column& c = out.cols[k];
+    if (kind(k) != SelectEntry::COLUMN) continue;
     if (c.validity && c.null_count != 0 && c.length == 0) { c.null_count = 0; c.validity = nullptr; }
     else if (c.validity && c.null_count != 0) counted.push_back(k);
   }
@@ -291,14 +315,8 @@ Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, c
   }
   // Field nullability: wildcard fields keep the schema flag; computed / identifier fields use
   // Array::is_nullable() = null_count > 0 (RU/record_projection.rs:45-47, 51-53, 62-66)
-  {
-    size_t k = 0;
-    for (const chq_select_item& f : fields) {
-      if (f.kind == CHQ_ITEM_WILDCARD) { k += rec.cols.size(); continue; }
-      out.cols[k].nullable = out.cols[k].null_count > 0;
-      ++k;
-    }
-  }
+  for (size_t k = 0; k < out.cols.size(); ++k)
+    if (kind(k) != SelectEntry::WILDCARD) out.cols[k].nullable = out.cols[k].null_count > 0;
   // RecordBatch::try_new (RU/record_projection.rs:72-73)
   if (out.cols.empty()) throw ChqError{CHQ_ERR_ARROW_INVALID_ARGUMENT, "must either specify a row count or at least one column"};
   const int64_t len = out.cols[0].length;
@@ -316,83 +334,84 @@ Batch project_record(Context& ctx, const std::vector<chq_select_item>& fields, c
 // Returns false when the call is outside the fused kernel's scope or when the device flagged any error -- the caller
 // then runs the two reference steps, which produce the reference's result or error exactly.
 // =================================================================================================
-bool filter_project_fused(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& pred,
-                          const std::vector<chq_select_item>& fields, Batch* result) {
-  const int64_t nrows = rec.nrows;
-  if (ctx.opt_fuse == 0 || nrows < 2 || fields.empty()) return false;
+namespace {
+struct FusedPlan {
+  struct Item { std::string name; bool nullable; int copy_col; int store_slot; DType type; };
+  std::vector<Item> items;   // the output columns: a copy of an input column or a store slot of the select items' program
+  Lowered lwp, lwq;          // the predicate; the computed select items, one OP_STORE each
+  int n_computed = 0;
+};
+
+// Eligibility: a row predicate and a list of whole columns, over plain columns only, within the kernel's limits
+bool plan_fused(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& pred, const std::vector<chq_select_item>& fields, FusedPlan& fp) {
   auto plain = [&](int ci) {   // fixed-width, no nulls
     const Column& c = rec.cols[ci];
     return c.type != T_BOOL && c.type != T_UTF8 && c.width > 0 && !(c.validity && c.null_count != 0);
   };
-  struct Item { std::string name; bool nullable; int copy_col; int store_slot; DType type; };
-  std::vector<Item> items;
-  std::vector<TypedExpr> computed;
-  Lowered lwp, lwq;
-  try {
-    TypedExpr tp = type_expr(pred, pcols, nrows, ctx.opt_enable_minus);
-    if (!is_row_predicate(tp)) return false;
-    lower_expr(tp, tp.root, pcols, lwp);
-    if (!lwp.strs.empty()) return false;
-    for (int ci : lwp.refs) if (!plain(ci)) return false;
-
-    size_t unnamed_idx = 0;
-    for (const chq_select_item& f : fields) {
-      if (f.kind == CHQ_ITEM_WILDCARD) {
-        for (size_t ci = 0; ci < rec.cols.size(); ++ci) {
-          if (!plain((int)ci)) return false;
-          items.push_back(Item{rec.cols[ci].name, rec.cols[ci].nullable, (int)ci, -1, rec.cols[ci].type});
-        }
-        continue;
-      }
-      if ((f.kind != CHQ_ITEM_UNNAMED_EXPR && f.kind != CHQ_ITEM_EXPR_WITH_ALIAS) || !f.expr) return false;
-      const Expr& e = *(const Expr*)f.expr;
-      TypedExpr te = type_expr(e, pcols, nrows, ctx.opt_enable_minus);
-      if (te.pending_code) return false;
-      const Node& root = te.at(te.root);
-      if (root.len1) return false;   // a literal-built column: RecordBatch::try_new decides on the filtered length
-      const std::string name = select_item_name(f, e, &unnamed_idx);
-      if (root.kind == Node::COL) {
-        if (!plain(root.col)) return false;
-        items.push_back(Item{name, false, root.col, -1, rec.cols[root.col].type});
-        continue;
-      }
-      if (root.type == T_BOOL || root.type == T_UTF8 || root.type == T_F16 || root.type == T_FIXED_OPAQUE) return false;
-      if ((int)computed.size() >= MAX_PROJ) return false;
-      lower_expr(te, te.root, pcols, lwq);
-      Instr st{}; st.op = OP_STORE; st.src_idx = (uint16_t)computed.size(); st.src_kind = SRC_NONE;
-      lwq.prog.push_back(st);
-      if ((int)lwq.prog.size() > MAX_INSTR || !lwq.strs.empty()) return false;
-      items.push_back(Item{name, false, -1, (int)computed.size(), root.type});
-      computed.push_back(std::move(te));
-    }
-    for (int ci : lwq.refs) if (!plain(ci)) return false;
-  } catch (const ChqError&) {
-    return false;   // static errors are the two-step path's to report, in the reference's order
-  }
   int n_copy = 0;
-  for (const Item& it : items) n_copy += it.copy_col >= 0;
-  if (n_copy > MAX_FUSED_COPY) return false;
-  if (ctx.opt_fuse == 1 && nrows > (1 << 18)) {
-    // (small batches are latency-bound: one launch and one synchronisation always beat two of each)
-    // Worth it?  The single pass is instruction-bound (interpreter + compacting stores in one kernel) while the two
-    // steps run near the HBM roofline, so it only pays when it moves clearly fewer bytes: the filter step copies the
-    // WHOLE table, the single pass touches only what the predicate and the select items need.  Selectivity is not
-    // known yet; 0.5 is assumed.  (Measured: 8-column table, 3 columns used: 3.2 ms vs 7.4 ms; config 3, 5 columns,
-    // 4 used: 12.9 ms vs 12.4 ms.)
-    double w_table = 0, w_pred = 0, w_proj = 0, w_out = 0;
-    std::vector<char> in_pred(rec.cols.size(), 0), in_proj(rec.cols.size(), 0);
-    for (const Column& c : rec.cols) w_table += c.width > 0 ? c.width : 16;
-    for (int ci : lwp.refs) if (!in_pred[ci]) { in_pred[ci] = 1; w_pred += rec.cols[ci].width; }
-    for (int ci : lwq.refs) if (!in_proj[ci]) { in_proj[ci] = 1; w_proj += rec.cols[ci].width; }
-    for (const Item& it : items) {
-      if (it.copy_col >= 0 && !in_proj[it.copy_col]) { in_proj[it.copy_col] = 1; w_proj += rec.cols[it.copy_col].width; }
-      w_out += it.copy_col >= 0 ? rec.cols[it.copy_col].width : dtype_width(it.type);
+  try {
+    TypedExpr tp = type_expr(pred, pcols, rec.nrows, ctx.opt_enable_minus);
+    if (!is_row_predicate(tp)) return false;
+    lower_expr(tp, tp.root, pcols, fp.lwp);
+    if (!fp.lwp.strs.empty()) return false;
+    for (int ci : fp.lwp.refs) if (!plain(ci)) return false;
+    // (static errors are the two steps' to report, in the reference's order; a literal-built column's length too: try_new's)
+    const SelectList list = read_select_list(fields, pcols, rec.nrows, ctx.opt_enable_minus);
+    if (!list.whole_columns()) return false;
+    for (const SelectEntry& en : list.entries) {
+      if (en.kind != SelectEntry::COMPUTED) {
+        if (!plain(en.col) || ++n_copy > MAX_FUSED_COPY) return false;
+        fp.items.push_back({en.name, en.kind == SelectEntry::WILDCARD && rec.cols[en.col].nullable, en.col, -1, rec.cols[en.col].type});
+        continue;
+      }
+      const Node& root = en.typed.at(en.typed.root);
+      if (root.type == T_BOOL || root.type == T_UTF8 || root.type == T_F16 || root.type == T_FIXED_OPAQUE) return false;
+      if (fp.n_computed >= MAX_PROJ) return false;
+      lower_expr(en.typed, en.typed.root, pcols, fp.lwq);
+      Instr st{}; st.op = OP_STORE; st.src_idx = (uint16_t)fp.n_computed; st.src_kind = SRC_NONE;
+      fp.lwq.prog.push_back(st);
+      if ((int)fp.lwq.prog.size() > MAX_INSTR || !fp.lwq.strs.empty()) return false;
+      fp.items.push_back({en.name, false, -1, fp.n_computed++, root.type});
     }
-    const double two_steps = w_table + 0.5 * w_table + 0.5 * (w_proj + w_out);
-    const double one_pass = w_pred + w_proj + 0.5 * w_out;
-    if (two_steps < 2.0 * one_pass) return false;
+    for (int ci : fp.lwq.refs) if (!plain(ci)) return false;
+  } catch (const ChqError&) {
+    return false;   // the predicate does not type, or something does not lower: the two steps decide
   }
+  return true;
+}
 
+// Worth it?  The single pass is instruction-bound (interpreter + compacting stores in one kernel) while the two
+// steps run near the HBM roofline, so it only pays when it moves clearly fewer bytes: the filter step copies the
+// WHOLE table, the single pass touches only what the predicate and the select items need.  Selectivity is not
+// known yet; 0.5 is assumed.  (Measured: 8-column table, 3 columns used: 3.2 ms vs 7.4 ms; config 3, 5 columns,
+// 4 used: 12.9 ms vs 12.4 ms.)
+bool single_pass_pays(const Batch& rec, const FusedPlan& fp) {
+  double w_table = 0, w_pred = 0, w_proj = 0, w_out = 0;
+  std::vector<char> in_pred(rec.cols.size(), 0), in_proj(rec.cols.size(), 0);
+  for (const Column& c : rec.cols) w_table += c.width > 0 ? c.width : 16;
+  for (int ci : fp.lwp.refs) if (!in_pred[ci]) { in_pred[ci] = 1; w_pred += rec.cols[ci].width; }
+  for (int ci : fp.lwq.refs) if (!in_proj[ci]) { in_proj[ci] = 1; w_proj += rec.cols[ci].width; }
+  for (const FusedPlan::Item& it : fp.items) {
+    if (it.copy_col >= 0 && !in_proj[it.copy_col]) { in_proj[it.copy_col] = 1; w_proj += rec.cols[it.copy_col].width; }
+    w_out += it.copy_col >= 0 ? rec.cols[it.copy_col].width : dtype_width(it.type);
+  }
+  const double two_steps = w_table + 0.5 * w_table + 0.5 * (w_proj + w_out);
+  const double one_pass = w_pred + w_proj + 0.5 * w_out;
+  return two_steps >= 2.0 * one_pass;
+}
+}  // namespace
+
+bool filter_project_fused(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const Expr& pred,
+                          const std::vector<chq_select_item>& fields, Batch* result) {
+  const int64_t nrows = rec.nrows;
+  if (ctx.opt_fuse == 0 || nrows < 2 || fields.empty()) return false;
+  FusedPlan fp;
+  if (!plan_fused(ctx, rec, pcols, pred, fields, fp)) return false;
+  // (small batches are latency-bound: one launch and one synchronisation always beat two of each)
+  if (ctx.opt_fuse == 1 && nrows > (1 << 18) && !single_pass_pays(rec, fp)) return false;
+  const Lowered &lwp = fp.lwp, &lwq = fp.lwq;
+
+  // The launch.  (The tile kind is this kernel's own rule, not pick_tile_kind's.)
   const int tile_kind = (lwp.wide || lwq.wide || lwp.num_temps > 0 || lwq.num_temps > 0) ? 2
                         : (ctx.opt_tile_kind == 0 || ctx.opt_tile_kind == 1) ? (int)ctx.opt_tile_kind
                         : (nrows >= (1 << 18) ? 0 : 1);
@@ -409,26 +428,22 @@ bool filter_project_fused(Context& ctx, const Batch& rec, const std::vector<Plan
   bind_scratch(p, ctx);
   fill_refs(p.pred, lwp, rec, {});
   fill_refs(p.proj, lwq, rec, {});
-  p.n_proj = (int32_t)computed.size();
+  p.n_proj = fp.n_computed;
   std::vector<char> read_once(rec.cols.size(), 0);
   for (int ci : lwp.refs) read_once[ci] = 1;
   for (int ci : lwq.refs) read_once[ci] = 1;
   int64_t out_width = 0;
-  for (const Item& it : items) {
+  for (const FusedPlan::Item& it : fp.items) {
+    const Column* c = it.copy_col >= 0 ? &rec.cols[it.copy_col] : nullptr;
     Column o;
     o.name = it.name; o.nullable = it.nullable; o.type = it.type;
-    if (it.copy_col >= 0) {
-      const Column& c = rec.cols[it.copy_col];
-      o.format = c.format; o.width = c.width;
-      read_once[it.copy_col] = 1;
-    } else {
-      o.format = dtype_format(it.type); o.width = dtype_width(it.type);
-    }
+    o.format = c ? c->format : dtype_format(it.type); o.width = c ? c->width : dtype_width(it.type);
     auto vb = make_device_buffer((size_t)nrows * o.width + 16, ctx.device);
     o.values = (const uint8_t*)vb->ptr; o.owned.push_back(vb);
-    if (it.copy_col >= 0) {
+    if (c) {
+      read_once[it.copy_col] = 1;
       OutCol& oc = p.copies[p.n_copy++];
-      oc.in = rec.cols[it.copy_col].values0(); oc.out = vb->ptr; oc.width = (uint32_t)o.width;
+      oc.in = c->values0(); oc.out = vb->ptr; oc.width = (uint32_t)o.width;
     } else {
       ProjOut& po = p.outs[it.store_slot];
       po.values = vb->ptr; po.type = (uint8_t)it.type;
@@ -468,64 +483,45 @@ bool project_record_host(Context& ctx, const std::vector<chq_select_item>& field
   Batch host = rec;   // shallow: null counts resolved below
   for (Column& c : host.cols) if (c.validity && c.null_count < 0) c.null_count = count_nulls_host(c.validity, c.offset, c.length);
   const std::vector<PlanColumn> pcols = plan_columns(host, aliases);
-  struct Item { int copy_col; int computed; std::string name; bool keep_schema_flag; };
-  std::vector<Item> items;
-  std::vector<TypedExpr> computed;
-  try {
-    size_t unnamed_idx = 0;
-    for (const chq_select_item& f : fields) {
-      if (f.kind == CHQ_ITEM_WILDCARD) {
-        for (size_t ci = 0; ci < host.cols.size(); ++ci) items.push_back(Item{(int)ci, -1, host.cols[ci].name, true});
-        continue;
-      }
-      if ((f.kind != CHQ_ITEM_UNNAMED_EXPR && f.kind != CHQ_ITEM_EXPR_WITH_ALIAS) || !f.expr) return false;
-      const Expr& e = *(const Expr*)f.expr;
-      TypedExpr te = type_expr(e, pcols, nrows, ctx.opt_enable_minus);
-      if (te.pending_code) return false;
-      const Node& root = te.at(te.root);
-      if (root.len1) return false;
-      const std::string name = select_item_name(f, e, &unnamed_idx);
-      if (root.kind == Node::COL) { items.push_back(Item{root.col, -1, name, false}); continue; }
-      items.push_back(Item{-1, (int)computed.size(), name, false});
-      computed.push_back(std::move(te));
-    }
-  } catch (const ChqError&) {
-    return false;
+  const SelectList list = read_select_list(fields, pcols, nrows, ctx.opt_enable_minus);
+  if (!list.whole_columns()) return false;
+  std::vector<const TypedExpr*> computed;
+  for (const SelectEntry& en : list.entries) {
+    if (en.kind == SelectEntry::COMPUTED) computed.push_back(&en.typed);
+    // (a `*` column keeps its schema flag.)  RecordBatch::try_new would refuse: let the general path say so
+    if (en.kind == SelectEntry::WILDCARD && !host.cols[en.col].nullable && host.cols[en.col].null_count > 0) return false;
   }
-  for (const Item& it : items)   // RecordBatch::try_new would refuse: let the general path say so
-    if (it.copy_col >= 0 && it.keep_schema_flag && !host.cols[it.copy_col].nullable && host.cols[it.copy_col].null_count > 0) return false;
 
   ctx.stats = chq_call_stats{};
   ctx.stats.rows_in = nrows; ctx.stats.rows_out = nrows;
   std::vector<Column> results;
   if (!computed.empty()) {
     std::vector<char> needed(host.cols.size(), 0);
-    for (const TypedExpr& te : computed) for (const Node& n : te.nodes) if (n.kind == Node::COL) needed[n.col] = 1;
+    for (const TypedExpr* te : computed) for (const Node& n : te->nodes) if (n.kind == Node::COL) needed[n.col] = 1;
     Batch dev;
     dev.nrows = nrows; dev.on_device = true; dev.device_id = ctx.device;
     for (size_t ci = 0; ci < host.cols.size(); ++ci) {
       if (needed[ci]) dev.cols.push_back(copy_column(ctx, host.cols[ci], Dir::H2D));
       else { Column ph = empty_like(host.cols[ci]); ph.length = nrows; dev.cols.push_back(std::move(ph)); }   // never dereferenced
     }
-    std::vector<const TypedExpr*> ptrs;
-    for (const TypedExpr& te : computed) ptrs.push_back(&te);
-    std::vector<Column> dcols = evaluate_dense(ctx, dev, pcols, ptrs);
+    std::vector<Column> dcols = evaluate_dense(ctx, dev, pcols, computed);
     for (Column& c : dcols) results.push_back(copy_column(ctx, c, Dir::D2H));
     check_hip(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize");
   }
   Batch out;
   out.on_device = false; out.device_id = -1; out.nrows = nrows;
-  for (const Item& it : items) {
+  size_t next_result = 0;
+  for (const SelectEntry& en : list.entries) {
     Column c;
-    if (it.copy_col >= 0) {
-      c = copy_column(ctx, host.cols[it.copy_col], Dir::H2H);
-      c.nullable = it.keep_schema_flag ? host.cols[it.copy_col].nullable : c.null_count > 0;
+    if (en.kind != SelectEntry::COMPUTED) {
+      c = copy_column(ctx, host.cols[en.col], Dir::H2H);
+      c.nullable = en.kind == SelectEntry::WILDCARD ? host.cols[en.col].nullable : c.null_count > 0;
       if (c.validity && c.null_count == 0) c.validity = nullptr;
     } else {
-      c = std::move(results[(size_t)it.computed]);
+      c = std::move(results[next_result++]);
       c.nullable = c.null_count > 0;
     }
-    c.name = it.name;
+    c.name = en.name;
     out.cols.push_back(std::move(c));
   }
   if (out.cols.empty()) return false;
@@ -536,6 +532,14 @@ bool project_record_host(Context& ctx, const std::vector<chq_select_item>& field
 // =================================================================================================
 // describe_plan: the host half of a call (typing, coercion, constant folding, lowering) without a GPU
 // =================================================================================================
+// f(index, node) for every node of `kind` in the tree under `ni`, operands first
+template <class F>
+static void each_of_kind(const TypedExpr& te, int ni, Node::Kind kind, const F& f) {
+  const Node& n = te.at(ni);
+  n.each_child([&](int c) { each_of_kind(te, c, kind, f); });
+  if (n.kind == kind) f(ni, n);
+}
+
 std::string describe_plan(const ArrowSchema* schema, const chq_table_aliases* aliases, const Expr& expr, int64_t nrows,
                           bool enable_minus) {
   if (!schema || !schema->format || strcmp(schema->format, "+s") != 0)
@@ -578,33 +582,21 @@ std::string describe_plan(const ArrowSchema* schema, const chq_table_aliases* al
     out += "split " + e.msg + "\n";
     // the string functions of the tree, operands first: one line each, with the parts of a flattened `||` chain
     static const char* kStrFn[] = {"upper", "lower", "length", "octet_length", "substring", "trim", "ltrim", "rtrim", "concat"};
-    std::function<void(int)> walk = [&](int ni) {
-      const Node& n = te.at(ni);
-      n.each_child(walk);
-      if (n.kind != Node::STRFN) return;
+    each_of_kind(te, te.root, Node::STRFN, [&](int, const Node& n) {
       out += std::string("strfn ") + kStrFn[n.op];
       if (n.op == STRFN_CONCAT) out += " parts=" + std::to_string(n.parts.size());
       if (n.op == STRFN_SUBSTRING) out += " from=" + std::to_string(n.sub_p) + (n.sub_has_cnt ? " for=" + std::to_string(n.sub_cnt) : "");
       out += "\n";
-    };
-    walk(te.root);
+    });
     // the CASEs of the tree, operands first: WHENs, ELSE, result type, operands evaluated under a guard
-    std::function<void(int)> cases = [&](int ni) {
-      const Node& n = te.at(ni);
-      n.each_child(cases);
-      if (n.kind != Node::CASE) return;
+    each_of_kind(te, te.root, Node::CASE, [&](int ni, const Node& n) {
       out += "case whens=" + std::to_string(n.op) + " else=" + (n.case_else ? "1" : "0") + " type=" + dtype_name(n.type) +
              " guarded=" + std::to_string(case_guarded_parts(te, ni, nullptr)) + "\n";
-    };
-    cases(te.root);
+    });
     // the explicit casts of the tree, operands first
-    std::function<void(int)> casts = [&](int ni) {
-      const Node& n = te.at(ni);
-      n.each_child(casts);
-      if (n.kind != Node::XCAST) return;
+    each_of_kind(te, te.root, Node::XCAST, [&](int, const Node& n) {
       out += std::string("cast ") + dtype_name(n.from) + " -> " + dtype_name(n.type) + (n.op ? " try" : "") + "\n";
-    };
-    casts(te.root);
+    });
     return out;
   }
   out += "program wide=" + std::to_string((int)lw.wide) + " num_temps=" + std::to_string(lw.num_temps) + " refs=";
