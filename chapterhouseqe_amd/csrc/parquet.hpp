@@ -116,4 +116,54 @@ ParquetImage record_to_parquet(Context& ctx, const Batch& rec);
 // several batches of one schema -> one file, one row group per batch
 ParquetImage records_to_parquet(Context& ctx, const std::vector<const Batch*>& recs);
 
+// ---- the writer's file layout (parquet_layout.cpp) --------------------------------------------------------------------
+// Pure host arithmetic between the device encode and the assembly of parquet_write.cpp: page cuts, level runs, Thrift page
+// headers, chunk offsets, statistics bytes and the footer, over plain structs and offsets (no pointers, no HIP), so that
+// tests/parquet_layout_main.cpp runs it without a GPU.
+constexpr int PW_LAYOUT_BLOCK_ROWS = 4096;   // = PW_BLOCK_ROWS of parquet_device.h: page boundaries are multiples of it
+
+// What the device produced for one column chunk.
+struct PwChunk {
+  std::string name;
+  int physical = PQ_INT32;      // PqType: BOOLEAN (bit-packed), INT32 / INT64 / FLOAT / DOUBLE (4 or 8 bytes a value), BYTE_ARRAY (Utf8)
+  bool optional = false;
+  int64_t rows = 0;
+  int64_t stream_bytes = 0;     // the PLAIN value stream: non-null values only, without gaps
+  bool has_levels = false;      // a level bitmap exists: ceil(rows / 8) bytes, the validity bits from bit 0
+  std::vector<unsigned long long> prefix;   // bytes of the stream in front of every 4096-row block (empty where pages are cut by arithmetic)
+  int64_t null_count = 0;
+  bool has_minmax = false;
+  std::string min_value, max_value;   // Statistics.min_value / max_value: PLAIN encoding of the value (Utf8: the bytes)
+};
+
+// One data page: `head` from the host, then a slice of the chunk's level bitmap, then a slice of its value stream.
+struct PwPage {
+  int64_t rows = 0;
+  std::vector<uint8_t> head;    // Thrift PageHeader + the host part of the level section ([u32 length][run header])
+  int64_t levels_at = 0, levels_bytes = 0;
+  int64_t stream_at = 0, stream_bytes = 0;
+  int64_t total() const { return (int64_t)head.size() + levels_bytes + stream_bytes; }
+};
+struct PwChunkLayout {
+  std::vector<PwPage> pages;
+  int64_t at = 0, bytes = 0;    // file offset of the first page header (set by parquet_layout_group), length of the chunk
+};
+// One row group of the file: a batch's chunks and where they lie.
+struct PwGroup {
+  int64_t rows = 0;
+  std::vector<PwChunk> chunks;
+  std::vector<PwChunkLayout> layout;
+};
+
+// Rows per page of a row group: `opt_page_rows` rounded down to a multiple of 4096, at least 4096, widened so that a chunk
+// has at most 64 pages.
+int64_t parquet_write_page_rows(int64_t opt_page_rows, int64_t rows);
+PwChunkLayout parquet_layout_chunk(const PwChunk& c, int64_t page_rows);
+// Lays out every chunk of `g` one behind the other from file offset `at` (advanced past the last page).
+void parquet_layout_group(PwGroup& g, int64_t page_rows, int64_t& at);
+// FileMetaData: the schema of the first group, every group's chunks.
+std::vector<uint8_t> parquet_write_footer(const std::vector<PwGroup>& groups);
+// min_value / max_value of a fixed-width or Boolean chunk from the order-preserving int64 keys of pw_stats_kernel.
+void parquet_statistics_bytes(int64_t min_key, int64_t max_key, PwChunk& c);
+
 }  // namespace chq
