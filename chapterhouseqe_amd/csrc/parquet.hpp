@@ -20,6 +20,8 @@
 #include <string>
 #include <vector>
 
+#include "parquet_jobs.h"
+
 namespace chq {
 
 enum PqType : int { PQ_BOOLEAN = 0, PQ_INT32 = 1, PQ_INT64 = 2, PQ_INT96 = 3, PQ_FLOAT = 4, PQ_DOUBLE = 5, PQ_BYTE_ARRAY = 6, PQ_FIXED_LEN_BYTE_ARRAY = 7 };
@@ -115,6 +117,56 @@ struct ParquetImage {
 ParquetImage record_to_parquet(Context& ctx, const Batch& rec);
 // several batches of one schema -> one file, one row group per batch
 ParquetImage records_to_parquet(Context& ctx, const std::vector<const Batch*>& recs);
+
+// ---- the scan's host plans (parquet_scan_plan.cpp) -----------------------------------------------------------------------
+// Pure host arithmetic in front of the uploads and launches of parquet_scan.cpp: what a column is, where every page of its
+// chunk lies (the chunk itself, or the uncompressed image of a compressed one), the inflate jobs, the cut of a call into waves
+// and of a wave's jobs into launch chains -- every "malformed" / "unsupported" decision of a scan that the host can make.
+// Plain structs and offsets (no device pointers, no HIP): tests/parquet_scan_plan_main.cpp runs it without a GPU.
+struct PqColumnClass {
+  const char* format = nullptr;   // Arrow format string
+  int width = 0;                  // fixed-width types
+  bool byte_array = false, boolean = false, optional = false, compressed = false;
+  bool has_levels = false;        // definition levels are decoded (optional column whose statistics do not rule nulls out)
+  int64_t first = 0, csize = 0;   // the chunk's bytes in the file (0, 0 for a row group without rows)
+};
+// Refuses what the scan does not decode (repeated, logical / converted / physical type, codec) and a chunk that cannot be
+// (values != rows, outside the file, 4 GiB).
+PqColumnClass parquet_classify_column(const PqColumnSchema& cs, const PqColumnChunk& cc, int64_t rows, int64_t file_size);
+
+struct PqColumnPlan {
+  std::vector<PqPageDesc> descs;                          // one per data page; offsets into the chunk or its image
+  std::vector<int32_t> plain_list, dict_list, rle_list;   // the data pages by encoding: a partition of `descs`
+  std::vector<uint32_t> h_nonnull, h_base;                // per page: values and first value, if the column has no levels
+  uint32_t dict_at = 0, dict_len = 0, dict_count = 0;     // dictionary page payload
+  int64_t image_bytes = 0;                                // compressed chunk: size of the uncompressed image
+  std::vector<PqCodecJob> jobs;                           // compressed chunk: its inflate jobs, pointer fields null
+  bool dict_walked = false;                               // uncompressed Utf8 dictionary: walked here, on the host
+  std::vector<uint32_t> h_src, h_len;                     // ... position and length of every entry
+};
+// `pages`: the chunk's page headers; `chunk_bytes`: its k.csize bytes (only read where the chunk is uncompressed).
+PqColumnPlan parquet_plan_column(const PqColumnClass& k, const PqColumnSchema& cs, const std::vector<PqPage>& pages, int64_t rows,
+                                 const uint8_t* chunk_bytes);
+
+// A call's row groups in waves of at most 1 GiB of selected chunk bytes (at least one row group): `bytes` per row group ->
+// the boundaries 0 = c[0] < c[1] < ... = bytes.size().
+std::vector<int> parquet_wave_cuts(const std::vector<int64_t>& bytes);
+// The compressed pages of a wave of n row groups are inflated in 1, 2 or 3 parts of consecutive row groups ...
+size_t parquet_inflate_parts(size_t n);
+// ... and part `part` ends behind row group j of the wave
+inline bool parquet_part_ends(size_t j, size_t n_parts, size_t n, size_t part) { return (j + 1) * n_parts / n != part; }
+
+// One chain of inflate launches: SEG, INDEX (+ RESOLVE), BLOCK (+ whole-page), FINISH jobs, in that order on one stream.
+struct PqChain {
+  std::vector<PqCodecJob> seg, index, blocks, finish;
+  size_t words = 0;   // of the chain's index table; the jobs' `index` is a byte offset into it until the table exists
+  std::vector<PqCodecJob> flat() const;   // seg, index, blocks, finish
+};
+// An indexed page: its INDEX (or SEG + RESOLVE), BLOCK and FINISH jobs.
+void parquet_chain_add_page(PqChain& ch, const PqCodecJob& j, bool segments, bool force_fallback);
+// Routes a part's jobs by the option `snappy_blocks`: whole-page jobs and the indexed pages below 512 KiB of compressed
+// bytes into `part`, the larger ones into the wave's `large` chain.
+void parquet_route_jobs(const PqCodecJob* jobs, size_t n, int64_t snappy_blocks, PqChain& part, PqChain& large);
 
 // ---- the writer's file layout (parquet_layout.cpp) --------------------------------------------------------------------
 // Pure host arithmetic between the device encode and the assembly of parquet_write.cpp: page cuts, level runs, Thrift page

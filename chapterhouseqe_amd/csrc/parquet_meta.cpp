@@ -7,7 +7,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "engine.hpp"
+#include "plan.hpp"   // ChqError
 
 namespace chq {
 namespace {

@@ -10,7 +10,7 @@ tests can compare the scan with pyarrow's reader on the same bytes.
   encode / decode     element scripts <-> raw snappy streams (every tag, every literal header width, padded preambles)
   canonical / respell the elements of the compressor's stream, and re-spellings of them that produce the same bytes
   repack              a snappy Parquet file whose pages are re-compressed by a callback (Thrift compact protocol in Python)
-  Plan                the scan planner's numbers (parquet_scan.cpp): which path a page takes, its segment bounds
+  Plan                the scan planner's numbers (parquet_scan_plan.cpp): which path a page takes, its segment bounds
 """
 from __future__ import annotations
 
@@ -282,7 +282,7 @@ def grow(elems, k: int, lo: int = 0, hi: Optional[int] = None) -> list:
     return out
 
 
-# ---- the scan planner's numbers (parquet_scan.cpp, parquet_codec.hip) ----------------------------------------------------
+# ---- the scan planner's numbers (parquet_scan_plan.cpp, parquet_codec.hip) ----------------------------------------------------
 SEGMENTS = 16            # PQ_SNAPPY_SEGMENTS
 LEAD = 2048              # PQ_SNAPPY_LEAD
 BLOCK = 65536            # output bytes per BLOCK job and of the LDS ring

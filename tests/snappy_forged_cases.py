@@ -2,7 +2,7 @@
 asserts that its stream has the shape it is named for, so the CPU tier (tests/test_snappy_forge.py) proves the shapes and
 that pyarrow reads the files; the GPU tier compares the scan with pyarrow on them.
 
-The kernel paths (csrc/parquet_codec.hip, planned by csrc/parquet_scan.cpp) a page can take, by option snappy_blocks:
+The kernel paths (csrc/parquet_codec.hip, planned by csrc/parquet_scan_plan.cpp) a page can take, by option snappy_blocks:
   0  one wave inflates the whole page (SNAPPY job)
   1  default: pages of 3 * 64 KiB of output and more are walked (INDEX, or SEG + RESOLVE for 64 KiB and more of input),
      inflated one wave per 64 KiB block (BLOCK) and finished (FINISH: redoes the page if a block gave up)

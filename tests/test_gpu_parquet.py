@@ -647,3 +647,40 @@ def test_scan_on_a_context_that_borrows_torchs_default_stream():
     img = chq.record_to_parquet(got[0], ctx=c)
     assert pq.read_table(io.BytesIO(img)).to_batches()[0].equals(want.read_row_group(0).to_batches()[0])
     c.close()
+
+
+@pytest.mark.parametrize("codec,row_groups", [("none", 2), ("snappy", 2), ("snappy", 6)])
+def test_an_error_behind_queued_work_leaves_the_context_usable(ctx, codec, row_groups):
+    """the last row group of one call has a defect the host finds (tests/parquet_plan_files.py: a V2 level section larger than
+    its page) after the uploads of the row groups in front of it are queued -- and, with six snappy row groups, after the
+    inflate launches of the first three: the call returns that error once everything in flight has drained, and the next
+    call on the same context reads row group 0 like pyarrow"""
+    from tests.parquet_plan_files import LEVELS_PAST_PAGE, levels_past_page
+    t, raw = levels_past_page(codec, row_groups)
+    want = pq.ParquetFile(io.BytesIO(write_bytes(t, compression=codec, row_group_size=300))).read_row_group(0).to_batches()[0]
+    for f in (chq.ParquetFile(raw), chq.ParquetFile(None, reader=lambda off, ln: raw[off:off + ln], size=len(raw))):
+        with pytest.raises(chq.ChqError) as e:
+            f.read_row_groups(ctx=ctx)
+        assert (e.value.code, e.value.message) == LEVELS_PAST_PAGE[codec]
+        got = f.read_row_groups(0, 1, ctx=ctx)
+        assert len(got) == 1 and got[0].to_host().equals(want)
+        f.close()
+
+
+@pytest.mark.parametrize("row_groups", [6, 12])
+def test_snappy_row_groups_across_the_inflate_parts(ctx, row_groups):
+    """six row groups in one call are inflated in two parts, twelve in three (parquet_scan_plan.cpp: parquet_inflate_parts);
+    the columns of every part wait for their own part's inflate launches"""
+    n = 300 * row_groups
+    rng = np.random.default_rng(row_groups)
+    t = pa.table([pa.array(rng.integers(-2**62, 2**62, n)), pa.array(["text %d" % v * (v % 5) for v in rng.integers(0, 500, n)], mask=rng.random(n) < 0.2)],
+                 schema=pa.schema([pa.field("k", pa.int64(), nullable=False), pa.field("s", pa.utf8())]))
+    raw = write_bytes(t, compression="snappy", row_group_size=300)
+    want = pq.ParquetFile(io.BytesIO(raw))
+    assert want.metadata.num_row_groups == row_groups and want.metadata.row_group(0).column(1).compression == "SNAPPY"
+    f = chq.ParquetFile(raw)
+    got = f.read_row_groups(ctx=ctx)
+    assert len(got) == row_groups
+    for g, b in enumerate(got):
+        assert b.to_host().equals(want.read_row_group(g).to_batches()[0]), g
+    f.close()

@@ -142,7 +142,7 @@ def test_repack_reproduces_pyarrows_files(kw):
 
 
 def test_planner_model():
-    """the numbers of parquet_scan.cpp the builders aim at"""
+    """the numbers of parquet_scan_plan.cpp the builders aim at"""
     B = F.BLOCK
     assert not F.Plan(10**6, 3 * B - 1).indexed and F.Plan(10**6, 3 * B).indexed and not F.Plan(10**6, 3 * B, 0).indexed
     assert F.Plan(65535, 3 * B).n_seg == 1 and F.Plan(65536, 3 * B).n_seg == 2 and F.Plan(65536, 3 * B, 3).n_seg == 1
