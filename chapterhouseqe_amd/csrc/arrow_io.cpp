@@ -320,6 +320,48 @@ void export_group(JoinedGroup&& g, int device_type, ArrowDeviceArray* outs, Arro
   (void)blk.release();
 }
 
+// ---- GroupLite: the per-batch facts of a group (group_plan.hpp) -------------------------------------------------------------
+// `set` reads an imported batch, `set_from_arrow` the Arrow structs of a device batch (the checks of import_batch, but no
+// Batch object).  Both run per batch on the pool's threads and allocate nothing.  They must agree on: the residency bits,
+// GL_SHORT below 2 rows, GL_SCHEMA_DIFFERS for anything the group paths cannot take (the full import then decides and
+// reports), and per column what `put_column` stores.
+void GroupLite::set(size_t b, const Batch& r, const Batch& first, int device) {
+  rows[b] = r.nrows;
+  uint8_t f = 0;
+  if (!r.on_device) f |= GL_ON_HOST;
+  if (r.on_device && r.device_id == device) f |= GL_ON_DEVICE;
+  if (r.nrows < 2) f |= GL_SHORT;
+  if (r.cols.size() != ncols) { flags[b] = (uint8_t)(f | GL_SCHEMA_DIFFERS); return; }
+  for (size_t i = 0; i < ncols; ++i) {
+    const Column& c = r.cols[i];
+    const Column& c0 = first.cols[i];
+    if (c.type != c0.type || c.width != c0.width || c.format != c0.format) f |= GL_SCHEMA_DIFFERS;
+    f |= put_column(b * ncols + i, GroupCol{c.type, c.width}, !r.on_device, c.validity, c.null_count, c.length, c.values, c.data, c.offset);
+  }
+  flags[b] = f;
+}
+
+void GroupLite::set_from_arrow(size_t b, const ArrowDeviceArray* rec, const ArrowSchema* schema, const Batch& first, int device) {
+  const ArrowArray& a = rec->array;
+  if (a.offset != 0 || a.n_children != schema->n_children || (size_t)a.n_children != ncols || rec->device_type != ARROW_DEVICE_ROCM || rec->sync_event) {
+    flags[b] = GL_SCHEMA_DIFFERS;   // (anything unusual: the full import decides -- and reports)
+    return;
+  }
+  rows[b] = a.length;
+  uint8_t f = 0;
+  if ((int)rec->device_id == device) f |= GL_ON_DEVICE;
+  if (a.length < 2) f |= GL_SHORT;
+  for (size_t i = 0; i < ncols; ++i) {
+    const ArrowArray* ca = a.children[i];
+    if (!ca || ca->length < a.length || ca->offset < 0 || ca->n_buffers < 2 || !ca->buffers || !ca->buffers[1] ||
+        (ca->null_count > 0 && !ca->buffers[0])) { f |= GL_SCHEMA_DIFFERS; continue; }
+    const Column& c0 = first.cols[i];
+    const uint8_t* bytes = c0.type == T_UTF8 && ca->n_buffers > 2 ? (const uint8_t*)ca->buffers[2] : nullptr;
+    f |= put_column(b * ncols + i, GroupCol{c0.type, c0.width}, false, (const uint8_t*)ca->buffers[0], ca->null_count, a.length, (const uint8_t*)ca->buffers[1], bytes, ca->offset);
+  }
+  flags[b] = f;
+}
+
 // Import of a group.  Batch 0 is imported in full.  A DEVICE-resident group then only gathers its GroupLite -- the checks of
 // import_batch on every record, but no Batch objects: the one-launch path works from the flat arrays, and building and
 // freeing 12 500 Batch objects cost ~0.6 ms of a 2.5 ms call; `gi.materialise` imports them when another path needs them.

@@ -18,6 +18,7 @@
 #include "strfn_device.h"
 #include "cast_device.h"
 #include "plan.hpp"
+#include "group_plan.hpp"
 
 namespace chq {
 
@@ -232,12 +233,7 @@ void export_batch(Batch&& b, int device_type, ArrowDeviceArray* out, ArrowSchema
 void export_single_column(Column&& c, bool on_device, int device_id, ArrowDeviceArray* out, ArrowSchema* out_schema);
 // the caller's output structs read as released (either may be null)
 void mark_released(ArrowDeviceArray* out, ArrowSchema* out_schema);
-// cleared bits among bits [offset, offset + n) of a host bitmap (inline: the per-call host paths use it)
-inline int64_t count_nulls_host(const uint8_t* validity, int64_t offset, int64_t n) {
-  int64_t nulls = 0;
-  for (int64_t i = 0; i < n; ++i) { int64_t b = offset + i; nulls += !((validity[b >> 3] >> (b & 7)) & 1); }
-  return nulls;
-}
+// (count_nulls_host: group_plan.hpp)
 
 Batch to_device(Context& ctx, const Batch& b);   // stage host batch into HBM (no-op view when already there)
 Batch to_host(Context& ctx, const Batch& b);
@@ -255,26 +251,7 @@ Batch filter_record(Context& ctx, const Batch& rec_dev, const std::vector<PlanCo
 // synchronisation).  False = outside its scope or an error was flagged: take the general path.
 bool filter_record_small_host(Context& ctx, const Batch& rec_host, const chq_table_aliases* aliases, const Expr& expr, Batch* result);
 bool filter_record_large_host(Context& ctx, const Batch& rec_host, const chq_table_aliases* aliases, const Expr& expr, Batch* result);
-// Per-batch facts of a group in flat arrays, gathered while the batches are imported (capi.cpp: the Arrow structs of 10^4
-// batches are ~10^5 dependent cache misses, taken once, on the pool's threads).  Later passes of a group call -- eligibility,
-// row totals, pointer tables -- read these arrays instead of walking the Batch objects again.
-struct GroupLite {
-  size_t ncols = 0;
-  std::vector<int64_t> rows;               // [nb]
-  std::vector<const uint8_t*> values0;     // [nb * ncols] Column::values0() (Boolean: the bitmap)
-  std::vector<const uint8_t*> data;        // [nb * ncols] Utf8 bytes
-  std::vector<const uint8_t*> validity;    // [nb * ncols] validity bitmap, null when the column has no nulls in that batch
-  std::vector<int64_t> offset;             // [nb * ncols] Arrow slice offset: bit position of row 0 in the bitmaps
-  std::vector<uint8_t> flags;              // [nb] GL_*
-  // GL_NULLS: a validity bitmap that may clear a bit (device batch: bitmap present and null_count != 0; host batch: nulls
-  // counted, by the producer or here).  GL_ON_DEVICE: in this context's GPU memory.  GL_ON_HOST: in host memory.
-  enum : uint8_t { GL_NULLS = 1, GL_NO_UTF8_DATA = 2, GL_SCHEMA_DIFFERS = 4, GL_ON_DEVICE = 8, GL_SHORT = 16, GL_ON_HOST = 32 };
-  void resize(size_t nb, size_t nc) { ncols = nc; rows.assign(nb, 0); values0.assign(nb * nc, nullptr); data.assign(nb * nc, nullptr); validity.assign(nb * nc, nullptr); offset.assign(nb * nc, 0); flags.assign(nb, 0); }
-  // the facts of batch b from an imported batch / straight from the Arrow structs of a device batch (no Batch object)
-  void set(size_t b, const Batch& r, const Batch& first, int device);
-  void set_from_arrow(size_t b, const ArrowDeviceArray* rec, const ArrowSchema* schema, const Batch& first, int device);
-  GroupLite slice(size_t b0, size_t b1) const;   // the facts of batches [b0, b1)
-};
+// GroupLite, the per-batch facts of a group in flat arrays: group_plan.hpp
 // The joined result of a group call, or of consecutive batches of it: ONE batch holding every surviving row in input order
 // (columns as the producing path built them, buffers kept alive by Column::owned) and the exclusive end row of every input
 // batch it covers.  chq_filter_records cuts it into per-batch Arrow structs from one block (export_group);

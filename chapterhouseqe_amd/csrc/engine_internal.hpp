@@ -1,5 +1,5 @@
-// engine_internal.hpp -- what the engine's own translation units (arrow_io.cpp, filter.cpp, group.cpp, materialize.cpp,
-// project.cpp) share with each other and with nobody else.  The interface for the rest of the library is engine.hpp.
+// engine_internal.hpp -- what the engine's own translation units (arrow_io.cpp, filter.cpp, group.cpp, group_concat.cpp,
+// materialize.cpp, project.cpp) share with each other and with nobody else.  The interface for the rest of the library is engine.hpp.
 #pragma once
 #include <algorithm>
 
@@ -18,8 +18,7 @@ inline void add_stats(chq_call_stats& acc, const chq_call_stats& s) {
   acc.bytes_read_alg += s.bytes_read_alg; acc.bytes_written_alg += s.bytes_written_alg; acc.kernel_ns += s.kernel_ns;
 }
 
-constexpr int64_t kTileRows[3] = {1024 * 16, 256 * 8, 256 * 8};
-constexpr int kGridPerCu[3] = {1, 4, 4};
+constexpr int kGridPerCu[3] = {1, 4, 4};   // (kTileRows: group_plan.hpp)
 
 struct Scratch {   // header of ctx.small (device) and layout of ctx.pinned (host mirror)
   uint32_t ticket; uint32_t pad0;      // --- [0, kPerPass): re-cleared before every pass of a multi-pass filter
@@ -113,6 +112,30 @@ Column empty_like(const Column& c);
 // ---- filter.cpp: the uniform-length Utf8 rewrite -----------------------------------------------------------------------------
 bool uniform_utf8_ok(bool may_hold_nulls, int64_t rows, int64_t L);
 Column uniform_to_utf8(Context& ctx, Column&& fixed, const Column& like, int64_t rows, bool on_device);
+
+// ---- group_concat.cpp: the batches of a group joined into one -----------------------------------------------------------------
+// f(begin, end) over [0, n) on a few host threads when there is enough to copy (one thread moves ~10 GB/s, the PCIe
+// link 55 GB/s: packing a group single-threaded would be the slowest step of a host-resident call)
+template <class F>
+void parallel_ranges(size_t n, size_t bytes, F&& f) {
+  if (bytes < ((size_t)8 << 20) || n < 2) { f((size_t)0, n); return; }
+  const size_t T = std::min<size_t>(std::min<size_t>(8, pool_width()), n);
+  pool_ranges(n, (n + T - 1) / T, [&](size_t i0, size_t i1) { f(i0, i1); });
+}
+inline void ensure_pinned_table(Context& ctx, size_t bytes) {
+  ctx.pinned_tbl.reserve(bytes, bytes + bytes / 4 + 4096, "hipHostMalloc (group table)");
+}
+Batch concat_host_batches(const std::vector<Batch>& recs, size_t b0, size_t b1);
+Batch concat_device_batches(Context& ctx, const std::vector<Batch>& recs, size_t b0, size_t b1, const std::vector<std::vector<int64_t>>& utf8_bytes);
+struct Utf8Sizes {   // the size gather of a group, in flight between device_utf8_bytes_issue and _finish
+  std::vector<int> cols;
+  size_t nb = 0;
+  BufferPtr d_tbl;
+  int32_t* h_ends = nullptr;   // [cols][2 nb] in ctx.pinned_sizes
+};
+Utf8Sizes device_utf8_bytes_issue(Context& ctx, const GroupLite& lite, const std::vector<int>& utf8_cols);
+std::vector<std::vector<int64_t>> device_utf8_bytes_finish(Context& ctx, const Utf8Sizes& z);
+std::vector<std::vector<int64_t>> device_utf8_bytes(Context& ctx, const GroupLite& lite, const std::vector<int>& utf8_cols);
 
 // ---- project.cpp: typed trees evaluated densely over a batch, one column per expression ------------------------------------
 std::vector<Column> evaluate_dense(Context& ctx, const Batch& rec, const std::vector<PlanColumn>& pcols, const std::vector<const TypedExpr*>& exprs);

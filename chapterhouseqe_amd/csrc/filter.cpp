@@ -519,7 +519,7 @@ bool plain_host_columns(const Batch& rec, int64_t* row_bytes = nullptr) {
 }  // namespace
 
 // =================================================================================================
-// shared with group.cpp and project.cpp (engine_internal.hpp)
+// shared with group.cpp, group_concat.cpp and project.cpp (engine_internal.hpp)
 // =================================================================================================
 void fill_refs(ProgramBlock& pb, const Lowered& lw, const Batch& rec, const std::vector<BufferPtr>& str_bufs) {
   pb.n_instr = (int32_t)lw.prog.size();

@@ -59,7 +59,7 @@ void fill_null_counts(std::vector<Column>& cols, int64_t rows, const std::vector
 Batch sort_records(Context& ctx, std::vector<Batch>& in, const chq_table_aliases* aliases, const std::vector<SortKeyArg>& keys,
                    int64_t limit);
 
-// group.cpp: the batches of a group joined into ONE device batch by the concat kernels (a single batch: its device view).
+// group_concat.cpp: the batches of a group joined into ONE device batch by the concat kernels (a single batch: its device view).
 // A Utf8 column whose joined bytes pass int32 offsets is CHQ_ERR_ARROW_INVALID_ARGUMENT, naming the column.
 Batch join_group(Context& ctx, const std::vector<Batch>& recs);
 

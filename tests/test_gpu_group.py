@@ -622,3 +622,52 @@ def test_groups_of_uniform_length_strings_run_as_plain_groups(nulls):
             if big.num_rows:
                 assert batches_identical(big.to_host(), whole[0], check_nullable=False), sql
     c.close()
+
+
+def test_tiles_and_launches_are_those_of_the_host_plan():
+    """ties the CPU tier (tests/test_group_plan_host.py) to the path that runs: for six small device groups `tiles` and
+    `launches` of one filter_records call are what the independent model of the plans (tests/group_plan_reference.py)
+    predicts, and the outputs are those of the per-batch loop"""
+    from . import group_plan_reference as R
+
+    def with_nulls(rec, col, seed):
+        cols = list(rec.columns)
+        cols[col] = pa.array(cols[col].to_numpy(), mask=np.random.default_rng(seed).random(rec.num_rows) < 0.2)
+        return pa.RecordBatch.from_arrays(cols, names=rec.schema.names)
+
+    def strings(n, seed):
+        r = np.random.default_rng(seed)
+        return pa.record_batch({"id": pa.array(r.integers(0, 1000, n).astype(np.int32)),
+                                "s": pa.array(["w" * int(l) + str(i % 7) for i, l in enumerate(r.integers(0, 20, n))]),
+                                "value2": pa.array((r.random(n) * 40 - 10).astype(np.float32))})
+
+    def fixed(sizes, seed):
+        return [fixed_batch(n, seed + i, with_wide=False) for i, n in enumerate(sizes)]
+
+    nullable = fixed([1024] * 3, 940)
+    nullable[1] = with_nulls(nullable[1], 1, 5)
+    cases = [   # name, batches, schema, columns with nulls, options; and what the rules give, worked out by hand
+        ("uniform 1025 x 3", fixed([1025] * 3, 900), "fffff", (), {}, {"tiles": 3, "launches": 2}),           # 2 large waves would idle 37 %: small tiles
+        ("ragged", fixed([2, 16385, 513], 910), "fffff", (), {}, {"tiles": 1 + 9 + 1, "launches": 2}),
+        ("1024 x 5, tile_kind 1", fixed([1024] * 5, 920), "fffff", (), {"tile_kind": 1}, {"tiles": 3, "launches": 1}),   # 10 waves of 512 rows
+        ("a nullable column", nullable, "fffff", (1,), {}, {"tiles": 1, "launches": 2}),                                   # + one bitmap compaction
+        ("a short Utf8 column", [strings(2000, 930 + i) for i in range(4)], "fuf", (), {}, {"tiles": 1, "launches": 1}),
+        ("group_mode 1", fixed([3000] * 4, 950), "fffff", (), {"group_mode": 1}, {"tiles": 8, "launches": 2}),
+    ]
+    e = parse_expr("value2 > 10.0")
+    for name, recs, schema, null_cols, options, by_hand in cases:
+        c = chq.Context(0)
+        for k, v in options.items():
+            c.set_option(k, v)
+        want = R.predict_launch([r.num_rows for r in recs], schema, null_cols, options.get("tile_kind", -1), options.get("group_mode", 0))
+        assert want == by_hand, (name, want)
+        al = empty_aliases(recs[0])
+        devs = [chq.DeviceRecordBatch.from_host(r, c) for r in recs]
+        got = chq.filter_records(devs, al, e, ctx=c)
+        st = c.last_stats()
+        assert {"tiles": st["tiles"], "launches": st["launches"]} == want, (name, st, want)
+        assert st["rows_in"] == sum(r.num_rows for r in recs) and st["rows_out"] == sum(g.num_rows for g in got), (name, st)
+        for i, (g, d) in enumerate(zip(got, devs)):
+            one = chq.filter_record(d, al, e, ctx=c).to_host()
+            assert batches_identical(g.to_host(), one), f"{name}: batch {i}:\n{explain_diff(g.to_host(), one)}"
+        c.close()

@@ -39,7 +39,7 @@ the same comparison.  The Utf8 comparison (strcmp_op) is checked on a table of b
 Columns holding bytes that are not UTF-8 (80 and ff alone) are staged as they are: neither pyarrow's from_buffers nor the
 library validates them, so they take part in the column-against-column forms.
 
-Batch groups (filter_records; group.cpp: plan_group / filter_group) are proved by `launches` and `tiles` together, because a
+Batch groups (filter_records; group_plan.cpp: plan_group, group.cpp: filter_group) are proved by `launches` and `tiles` together, because a
 joined group and a one-launch group can launch equally often:
     one launch over the batches as they lie (`group_fold` = 1, joined span <= 24 x rows): launches and tiles equal those of the
         same group without its string column -- the same group table, the strings fold into the same launch (+ 0)

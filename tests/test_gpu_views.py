@@ -202,7 +202,7 @@ def test_group_path_sweep_on_views(opts):
 # ---- evidence that the paths ran -------------------------------------------------------------------------------------
 def test_uniform_group_path_runs_on_views():
     """bitmap-free uniform strings in views take the uniform-length group path: its stats differ from the fold path's by
-    exactly its offsets pass and its fixed-width reads (bytes_read_alg, group.cpp: (rows + batches) x 4 per column, L per
+    exactly its offsets pass and its fixed-width reads (bytes_read_alg, group.cpp, uniform_group: (rows + batches) x 4 per column, L per
     row) against the fold's 8 per row and the kept bytes; the writes agree"""
     rec = host_parent("k4+k16")
     lens = [4, 16]
