@@ -103,7 +103,7 @@ EXPORTED_SYMBOLS = [
     "chq_abi_version", "chq_status_name", "chq_ctx_create", "chq_ctx_destroy", "chq_ctx_last_error", "chq_ctx_stream",
     "chq_ctx_set_option", "chq_ctx_last_stats", "chq_expr_identifier", "chq_expr_compound_identifier", "chq_expr_number",
     "chq_expr_boolean", "chq_expr_single_quoted_string", "chq_expr_unsupported_value", "chq_expr_binary_op",
-    "chq_expr_nested", "chq_expr_like", "chq_expr_is_null", "chq_expr_function", "chq_expr_case", "chq_expr_in_list", "chq_expr_between", "chq_expr_cast", "chq_expr_unsupported", "chq_expr_free", "chq_filter_record", "chq_filter_records", "chq_filter_records_coalesced", "chq_plan_describe", "chq_project_record",
+    "chq_expr_nested", "chq_expr_like", "chq_expr_is_null", "chq_expr_function", "chq_expr_case", "chq_expr_in_list", "chq_expr_between", "chq_expr_cast", "chq_expr_typed_string", "chq_expr_unsupported", "chq_expr_free", "chq_filter_record", "chq_filter_records", "chq_filter_records_coalesced", "chq_plan_describe", "chq_project_record",
     "chq_compute_value", "chq_filter_project_record", "chq_record_to_device", "chq_record_to_host", "chq_wrap_columns",
     "chq_record_copy_to_peer", "chq_record_to_ipc", "chq_record_from_ipc", "chq_ipc_describe",
     "chq_parquet_open", "chq_parquet_open_reader", "chq_parquet_num_columns", "chq_parquet_column_name", "chq_parquet_read_columns",
@@ -175,6 +175,7 @@ def lib():
         "chq_expr_case": (vp, [vp, C.POINTER(vp), C.POINTER(vp), ci, vp]),
         "chq_expr_in_list": (vp, [vp, C.POINTER(vp), ci, ci]), "chq_expr_between": (vp, [vp, ci, vp, vp]),
         "chq_expr_cast": (vp, [vp, ci, ci]),
+        "chq_expr_typed_string": (vp, [ci, cp, i64]),
         "chq_expr_unsupported": (vp, [cp]), "chq_expr_free": (None, [vp]),
         "chq_filter_record": (ci, [vp, PDA, PS, PTA, vp, ci, PDA, PS]),
         "chq_filter_records": (ci, [vp, ci, C.POINTER(PDA), PS, PTA, vp, ci, PDA, PS]),

@@ -51,7 +51,7 @@ chq_status host_entry(chq_ctx* ctx, Clear&& clear, Body&& body) {
 // the same with the context's GPU current: every entry that may touch the device
 template <class Clear, class Body>
 chq_status entry(chq_ctx* ctx, Clear&& clear, Body&& body) {
-  return host_entry(ctx, clear, [&] { check_hip(hipSetDevice(ctx->c.device), "hipSetDevice"); body(); });
+  return host_entry(ctx, clear, [&] { ctx->c.typed_stats = chq_call_stats{}; check_hip(hipSetDevice(ctx->c.device), "hipSetDevice"); body(); });
 }
 // context in, one record out
 template <class Body>
@@ -289,7 +289,15 @@ chq_status chq_ctx_create(int device_id, void* hip_stream, chq_ctx** out) {
 void chq_ctx_destroy(chq_ctx* ctx) { delete ctx; }
 const char* chq_ctx_last_error(const chq_ctx* ctx) { return ctx ? ctx->c.last_error.c_str() : "null context"; }
 void* chq_ctx_stream(const chq_ctx* ctx) { return ctx ? (void*)ctx->c.stream : nullptr; }
-void chq_ctx_last_stats(const chq_ctx* ctx, chq_call_stats* out) { if (ctx && out) *out = ctx->c.stats; }
+void chq_ctx_last_stats(const chq_ctx* ctx, chq_call_stats* out) {
+  if (!ctx || !out) return;
+  *out = ctx->c.stats;
+  // (the temporal kernels of the call's expressions: counted apart, see Context::typed_stats)
+  out->launches += ctx->c.typed_stats.launches;
+  out->bytes_read_alg += ctx->c.typed_stats.bytes_read_alg;
+  out->bytes_written_alg += ctx->c.typed_stats.bytes_written_alg;
+  out->kernel_ns += ctx->c.typed_stats.kernel_ns;
+}
 
 chq_status chq_ctx_set_option(chq_ctx* ctx, const char* key, int64_t value) {
   if (!ctx || !key) return CHQ_ERR_INVALID_HANDLE;

@@ -124,5 +124,10 @@ chq_expr* chq_expr_cast(chq_expr* operand, chq_cast_type to, int try_cast) {
   if (e) { e->e.op = (int)to; e->e.flag = try_cast != 0; }
   return e;
 }
+chq_expr* chq_expr_typed_string(chq_typed_string_kind kind, const char* bytes, int64_t len) {
+  chq_expr* e = new_expr(Expr::TYPED_STRING);
+  if (e) { e->e.op = (int)kind; if (bytes && len > 0) e->e.text.assign(bytes, (size_t)len); }
+  return e;
+}
 
 }  // extern "C"

@@ -50,6 +50,9 @@ hipError_t launch_cast_fixed(const CastFixedParams& p, hipStream_t stream);
 hipError_t launch_cast_parse(const CastParseParams& p, hipStream_t stream);
 hipError_t launch_cast_len(const CastPrintParams& p, hipStream_t stream);
 hipError_t launch_cast_write(const CastPrintParams& p, hipStream_t stream);
+// temporal.hip
+hipError_t launch_temporal_part(const TemporalParams& p, hipStream_t stream);
+hipError_t launch_temporal_trunc(const TemporalParams& p, hipStream_t stream);
 hipError_t launch_utf8_uniform(const Utf8UniformParams& p, hipStream_t stream);
 hipError_t launch_iota_offsets(const IotaOffsetsParams& p, hipStream_t stream);
 hipError_t launch_count_bits(const uint8_t* in, int64_t bit_offset, int64_t nbits, unsigned long long* out, hipStream_t stream);
@@ -169,6 +172,9 @@ struct Context {
   int num_cus = 0;
   std::string last_error;
   chq_call_stats stats{};
+  // launches and algorithmic bytes of the temporal kernels (temporal.hip) since the current C ABI entry began: they run while an
+  // expression is fitted, before the operator resets `stats`, so they are kept apart and added by chq_ctx_last_stats
+  chq_call_stats typed_stats{};
   // options
   int64_t opt_tile_kind = -1;       // -1 auto
   bool opt_enable_minus = false;

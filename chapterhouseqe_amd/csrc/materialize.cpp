@@ -1,6 +1,7 @@
 // materialize.cpp -- expressions that do not fit one device program: sub-trees evaluated into temporary columns until the
 // rest fits (fit_to_device), and the operators that are never device-program instructions and always become one -- LIKE,
-// IS NULL, Decimal128 comparisons, Utf8 -> Boolean, the scalar string functions, CASE, CAST / TRY_CAST.  filter.cpp and
+// IS NULL, Decimal128 comparisons, Utf8 -> Boolean, the scalar string functions, CASE, CAST / TRY_CAST, EXTRACT / date_part and
+// date_trunc.  filter.cpp and
 // project.cpp (evaluate_dense) both come here.
 #include "engine_internal.hpp"
 
@@ -110,6 +111,7 @@ bool is_typed_op(const TypedExpr& te, int node) {
   const Node& n = te.nodes[node];
   return (n.kind == Node::CMP && n.from == T_FIXED_OPAQUE) || (n.kind == Node::TOBOOL && n.from == T_UTF8) ||
          n.kind == Node::LIKE || n.kind == Node::ISNULL || n.kind == Node::STRFN || n.kind == Node::CASE || n.kind == Node::XCAST ||
+         n.kind == Node::TPART || n.kind == Node::TTRUNC ||
          (n.kind == Node::CONST && n.cval.null);   // `'maybe' AND ..` folded to NULL, next to a column of a one-row batch
 }
 void fit_subtree(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict, bool is_root);
@@ -468,6 +470,38 @@ Column evaluate_cast(Context& ctx, const Batch& work, const TypedExpr& te, const
   return c;
 }
 
+// ---- EXTRACT / date_part, date_trunc (temporal.hip) ------------------------------------------------
+// The temporary column of TPART / TTRUNC node `n`, whose operand is a column of `work`: an Int32 column, or one of the operand's
+// own DataType.  No row fails; the rows the null rule of temporal_device.h makes null are counted by the kernel.
+Column evaluate_temporal(Context& ctx, const Batch& work, const TypedExpr& te, const Node& n) {
+  const int64_t nrows = work.nrows;
+  const Column& sc = work.cols[(size_t)te.nodes[n.l].col];
+  const bool part = n.kind == Node::TPART;
+  Column c = part ? result_column(T_I32, "i", 4, nrows) : result_column(T_FIXED_OPAQUE, sc.format, sc.width, nrows);
+  if (nrows == 0) return zero_row_result(ctx, std::move(c));
+  auto valid = bitmap_buffer(ctx, nrows);
+  auto count = zeroed_counters(ctx);
+  auto vb = make_device_buffer((size_t)nrows * (size_t)c.width + 16, ctx.device);
+  TemporalParams p{};
+  p.values = sc.values; p.values_offset = sc.offset; p.validity = sc.live_validity(); p.validity_offset = sc.offset;
+  p.nrows = nrows; p.kind = n.tkind; p.op = n.op;
+  p.out_values = vb->ptr; p.out_validity = (u64*)valid->ptr; p.null_count = (u64*)count->ptr;
+  kernel_span_begin(ctx);
+  check_hip(part ? launch_temporal_part(p, ctx.stream) : launch_temporal_trunc(p, ctx.stream), part ? "launch temporal_part_kernel" : "launch temporal_trunc_kernel");
+  kernel_span_end(ctx);
+  u64 nulls = 0;
+  check_hip(hipMemcpyAsync(&nulls, count->ptr, 8, hipMemcpyDeviceToHost, ctx.stream), "read null count");
+  check_hip(hipStreamSynchronize(ctx.stream), "sync");
+  // (a call's counters: the values read and written once, the validity words in and out)
+  ++ctx.typed_stats.launches;
+  ctx.typed_stats.kernel_ns += kernel_span_ns(ctx);   // (0 unless `time_kernels` is set)
+  ctx.typed_stats.bytes_read_alg += nrows * sc.width + (p.validity ? (nrows + 7) / 8 : 0);
+  ctx.typed_stats.bytes_written_alg += nrows * c.width + (nrows + 7) / 8;
+  c.values = (const uint8_t*)vb->ptr; c.owned = {vb};
+  finish_nulls(c, (int64_t)nulls, valid);
+  return c;
+}
+
 // A typed operation becomes a temporary column in three steps: its operands as columns, its own kernels, the replacement.
 void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wcols, TypedExpr& te, int node, bool strict) {
   const Node::Kind kind = te.nodes[node].kind;
@@ -479,7 +513,7 @@ void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wc
     const bool is_concat = kind == Node::STRFN && te.nodes[node].op == STRFN_CONCAT;
     std::vector<int> operands;
     if (is_concat) operands = te.nodes[node].parts;
-    else if (kind == Node::ISNULL || kind == Node::LIKE || kind == Node::TOBOOL || kind == Node::XCAST || kind == Node::STRFN) operands.push_back(te.nodes[node].l);
+    else if (kind == Node::ISNULL || kind == Node::LIKE || kind == Node::TOBOOL || kind == Node::XCAST || kind == Node::STRFN || kind == Node::TPART || kind == Node::TTRUNC) operands.push_back(te.nodes[node].l);
     for (int l : operands) {
       fit_subtree(ctx, work, wcols, te, l, strict, false);
       if (te.nodes[l].kind != Node::COL && !(is_concat && te.nodes[l].kind == Node::CONST)) materialize_node(ctx, work, wcols, te, l);
@@ -489,6 +523,7 @@ void materialize_typed_op(Context& ctx, Batch& work, std::vector<PlanColumn>& wc
   Column c = kind == Node::CASE    ? evaluate_case(ctx, work, wcols, te, node, strict)
              : kind == Node::STRFN ? evaluate_strfn(ctx, work, te, n)
              : kind == Node::XCAST ? evaluate_cast(ctx, work, te, n)
+             : kind == Node::TPART || kind == Node::TTRUNC ? evaluate_temporal(ctx, work, te, n)
                                    : evaluate_bool_op(ctx, work, te, n);
   replace_by_column(work, wcols, te, node, std::move(c));
 }

@@ -70,6 +70,26 @@ DType opaque_compare_class(const PlanColumn& c) {
   if (f.rfind("d:", 0) == 0 && c.width == 16) return T_FIXED_OPAQUE;
   return T_NTYPES;
 }
+// ---- temporal kinds (temporal_device.h) ----------------------------------------------------------------
+const char* const kTemporalFieldNames[TF_NFIELDS] = {"year", "quarter", "month", "week", "day", "doy", "dow", "hour", "minute", "second"};
+const char* const kTemporalUnitNames[TU_NUNITS] = {"year", "quarter", "month", "week", "day", "hour", "minute", "second"};
+int temporal_kind_of(const std::string& f, std::string* zone) {
+  if (zone) zone->clear();
+  if (f == "tdD") return TK_DATE32;
+  if (f == "tdm") return TK_DATE64;
+  if (f == "tts") return TK_TIME32_S;
+  if (f == "ttm") return TK_TIME32_MS;
+  if (f == "ttu") return TK_TIME64_US;
+  if (f == "ttn") return TK_TIME64_NS;
+  if (f.size() >= 4 && f.compare(0, 2, "ts") == 0 && f[3] == ':') {
+    if (zone) *zone = f.substr(4);
+    switch (f[2]) { case 's': return TK_TS_S; case 'm': return TK_TS_MS; case 'u': return TK_TS_US; case 'n': return TK_TS_NS; default: return -1; }
+  }
+  return -1;
+}
+// there is no zone database: a Timestamp column is read as UTC wall-clock time, which only these zones make true
+static bool zone_is_utc(const std::string& z) { return z.empty() || z == "UTC" || z == "+00:00"; }
+
 // "d:p,s" and "d:p,s,128" name the same DataType
 static std::string canonical_format(const std::string& f) {
   if (f.rfind("d:", 0) == 0 && f.size() > 4 && f.compare(f.size() - 4, 4, ",128") == 0) return f.substr(0, f.size() - 4);
@@ -326,6 +346,7 @@ struct Typer {
   bool enable_minus;
   TypedExpr t;
   int order = 0;
+  std::vector<std::pair<int, int>> retyped;   // read_as: a date_trunc node -> its one integer-typed copy
 
   int push(Node n) {
     n.ref_order = order < 250 ? order : 250;
@@ -374,9 +395,26 @@ struct Typer {
     return maybe_fold((int)t.nodes.size() - 1);
   }
 
+  // A DATE / TIMESTAMP literal has no Arrow type of its own: only a comparison -- and BETWEEN and IN, which are comparisons --
+  // takes one (build_any), next to the temporal operand whose DataType it adopts (binary()).  Everywhere else it is refused here.
   int build(const Expr& e) {
+    const int ni = build_any(e);
+    if (t.nodes[ni].tlit)
+      fail(CHQ_ERR_NOT_SUPPORTED, "a DATE / TIMESTAMP literal stands only beside a Date or Timestamp operand of a comparison, BETWEEN or IN: '" + t.nodes[ni].cval.str + "'");
+    return ni;
+  }
+  int build_any(const Expr& e) {
     switch (e.kind) {
-      case Expr::NESTED: return build(*e.l);
+      case Expr::NESTED: return build_any(*e.l);
+      case Expr::TYPED_STRING: {
+        if (e.op != CHQ_TYPED_STRING_DATE && e.op != CHQ_TYPED_STRING_TIMESTAMP) fail(CHQ_ERR_NOT_SUPPORTED, "a typed string of this kind is outside this build's scope");
+        TemporalLiteral lit;
+        if (!temporal_parse_literal(e.op, e.text.data(), (int64_t)e.text.size(), &lit))
+          fail(CHQ_ERR_ARROW_CAST, std::string("Cast error: '") + e.text + "' is not a " + (e.op == CHQ_TYPED_STRING_DATE ? "DATE (YYYY-MM-DD)" : "TIMESTAMP (YYYY-MM-DD HH:MM[:SS[.f]])") + " literal");
+        Node n{}; n.kind = Node::CONST; n.type = T_FIXED_OPAQUE; n.is_scalar = true; n.len1 = true; n.tlit = e.op + 1;
+        n.cval.type = T_FIXED_OPAQUE; n.cval.str = e.text; n.tval = lit;
+        return push(n);
+      }
       case Expr::NUMBER: {
         if (e.flag) fail(CHQ_ERR_VALUE_TYPE_NOT_IMPLEMENTED, "value type not implemented: Number(\"" + e.text + "\", true)");
         if (e.text.find('.') != std::string::npos) {
@@ -416,8 +454,8 @@ struct Typer {
         fail(CHQ_ERR_IDENTIFIER_NOT_FOUND, "identifier not found: \"" + joined + "\"");
       }
       case Expr::BINARY: {
-        int l = build(*e.l);
-        int r = build(*e.r);
+        int l = build_any(*e.l);
+        int r = build_any(*e.r);
         return binary(e, l, r);
       }
       case Expr::LIKE: {
@@ -477,7 +515,7 @@ struct Typer {
       }
       case Expr::BETWEEN: {   // x >= lo AND x <= hi / x < lo OR x > hi, x typed once
         if (e.args.size() != 2 || !e.l) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "BETWEEN needs an operand, a low and a high bound");
-        const int x = build(*e.l), lo = build(*e.args[0]), hi = build(*e.args[1]);
+        const int x = build_any(*e.l), lo = build_any(*e.args[0]), hi = build_any(*e.args[1]);
         Expr a; a.kind = Expr::BINARY; a.op = e.flag ? CHQ_BINOP_LT : CHQ_BINOP_GTEQ; a.text = e.flag ? "Lt" : "GtEq";
         Expr b; b.kind = Expr::BINARY; b.op = e.flag ? CHQ_BINOP_GT : CHQ_BINOP_LTEQ; b.text = e.flag ? "Gt" : "LtEq";
         Expr j; j.kind = Expr::BINARY; j.op = e.flag ? CHQ_BINOP_OR : CHQ_BINOP_AND; j.text = e.flag ? "Or" : "And";
@@ -492,15 +530,15 @@ struct Typer {
         for (const auto& a : e.args) {
           const Expr* q = a.get();
           while (q->kind == Expr::NESTED) q = q->l.get();
-          if (q->kind != Expr::NUMBER && q->kind != Expr::BOOLEAN && q->kind != Expr::STRING && q->kind != Expr::VALUE_OTHER)
+          if (q->kind != Expr::NUMBER && q->kind != Expr::BOOLEAN && q->kind != Expr::STRING && q->kind != Expr::VALUE_OTHER && q->kind != Expr::TYPED_STRING)
             fail(CHQ_ERR_NOT_SUPPORTED, "every item of an IN list must be a literal");
         }
-        const int x = build(*e.l);
+        const int x = build_any(*e.l);
         Expr c; c.kind = Expr::BINARY; c.op = e.flag ? CHQ_BINOP_NOTEQ : CHQ_BINOP_EQ; c.text = e.flag ? "NotEq" : "Eq";
         Expr j; j.kind = Expr::BINARY; j.op = e.flag ? CHQ_BINOP_AND : CHQ_BINOP_OR; j.text = e.flag ? "And" : "Or";
         int acc = -1;
         for (const auto& a : e.args) {
-          const int item = build(*a);
+          const int item = build_any(*a);
           const int one = binary(c, x, item);
           acc = acc < 0 ? one : binary(j, acc, one);
         }
@@ -540,6 +578,7 @@ struct Typer {
       const int nul = push(z);
       return case_node({c}, {nul}, a, e.text.c_str());
     }
+    if (!strcasecmp(e.text.c_str(), "date_part") || !strcasecmp(e.text.c_str(), "date_trunc")) return temporal_function(e);
     int fn = -1; size_t lo = 0, hi = 0;
     for (const auto& f : kFns) if (!strcasecmp(e.text.c_str(), f.name)) { fn = f.fn; lo = f.min_args; hi = f.max_args; }
     // (an unknown name: what every call answered before there were functions)
@@ -565,6 +604,74 @@ struct Typer {
       if (n.sub_has_cnt && n.sub_cnt < 0) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, "negative substring length not allowed: " + std::to_string(n.sub_cnt));
     }
     return maybe_fold(push(n));
+  }
+
+  // date_part('field', e) -- what EXTRACT(field FROM e) arrives as -- and date_trunc('unit', e): e is a Date32 / Date64 /
+  // Timestamp column (date_part: or a Time32 / Time64 one, for the clock fields) or a date_trunc of one.
+  int temporal_function(const Expr& e) {
+    const bool part = !strcasecmp(e.text.c_str(), "date_part");
+    if (e.args.size() != 2) fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, e.text + " takes 2 arguments, found " + std::to_string(e.args.size()));
+    const Expr* fe = e.args[0].get();
+    while (fe->kind == Expr::NESTED) fe = fe->l.get();
+    int op = -1;
+    if (fe->kind == Expr::STRING) {
+      const int count = part ? (int)TF_NFIELDS : (int)TU_NUNITS;
+      for (int k = 0; k < count; ++k) if (!strcasecmp(fe->text.c_str(), part ? kTemporalFieldNames[k] : kTemporalUnitNames[k])) op = k;
+    }
+    if (op < 0)
+      fail(CHQ_ERR_NOT_SUPPORTED, std::string("the ") + (part ? "field" : "unit") + " of " + e.text + " must be a string literal naming one of " +
+                                      (part ? "year, quarter, month, week, day, doy, dow, hour, minute, second" : "year, quarter, month, week, day, hour, minute, second"));
+    const int l = build(*e.args[1]);
+    const Node& ln = t.nodes[l];
+    if (ln.type != T_FIXED_OPAQUE)
+      fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, e.text + " needs a Date32, Date64" + (part ? ", Timestamp, Time32 or Time64" : " or Timestamp") + " operand, found " + dtype_name(ln.type));
+    if (ln.kind != Node::COL && ln.kind != Node::TTRUNC)
+      fail(CHQ_ERR_NOT_SUPPORTED, e.text + " of the temporal result of CASE, coalesce or nullif is outside this build's scope");
+    const int fc = opaque_col(ln);
+    std::string zone;
+    const int kind = temporal_kind_of(cols[fc].format, &zone);
+    if (kind < 0 || (!part && temporal_is_time(kind)))
+      fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, e.text + " needs a Date32, Date64" + (part ? ", Timestamp, Time32 or Time64" : " or Timestamp") + " operand, found a '" + cols[fc].format + "' column");
+    if (!zone_is_utc(zone))
+      fail(CHQ_ERR_NOT_SUPPORTED, e.text + " of a Timestamp in time zone '" + zone + "' is outside this build's scope: there is no zone database (UTC and +00:00 are read as they are)");
+    if (temporal_is_time(kind) && op < TF_HOUR)
+      fail(CHQ_ERR_ARROW_INVALID_ARGUMENT, std::string("a '") + cols[fc].format + "' column has no " + kTemporalFieldNames[op] + ": a Time has hour, minute and second");
+    Node n{}; n.kind = part ? Node::TPART : Node::TTRUNC; n.op = op; n.tkind = kind; n.l = l; n.from = T_FIXED_OPAQUE;
+    n.type = part ? T_I32 : T_FIXED_OPAQUE; n.fmt_col = part ? -1 : fc;
+    n.is_scalar = ln.is_scalar; n.len1 = ln.len1;
+    return push(n);
+  }
+
+  // A DATE / TIMESTAMP literal next to the temporal operand `other` of a comparison becomes an Int32 / Int64 constant in
+  // `other`'s unit; its fmt_col makes it a value of `other`'s DataType for the rules that follow.
+  void resolve_literal(int lit, int other) {
+    Node& n = t.nodes[lit];
+    const Node& o = t.nodes[other];
+    const std::string& text = n.cval.str;
+    const int lk = n.tlit - 1;
+    const char* lname = lk == TEMPORAL_LIT_DATE ? "DATE" : "TIMESTAMP";
+    if (o.tlit) fail(CHQ_ERR_NOT_SUPPORTED, "a comparison of two DATE / TIMESTAMP literals is outside this build's scope");
+    if (o.type != T_FIXED_OPAQUE)   // what `date_column < 5` answers
+      fail(CHQ_ERR_UNSUPPORTED_TYPE_COERSION, std::string("unsupported type coersion for operation between types ") + dtype_name(T_FIXED_OPAQUE) + " and " + dtype_name(o.type));
+    if (o.kind != Node::COL && o.kind != Node::TTRUNC)
+      fail(CHQ_ERR_NOT_SUPPORTED, "an operator on the temporal / decimal result of CASE, coalesce or nullif is outside this build's scope");
+    const int fc = opaque_col(o);
+    std::string zone;
+    const int kind = temporal_kind_of(cols[fc].format, &zone);
+    if (kind < 0 || temporal_is_time(kind))
+      fail(CHQ_ERR_NOT_SUPPORTED, std::string("a ") + lname + " literal beside a '" + cols[fc].format + "' operand is outside this build's scope");
+    if (lk == TEMPORAL_LIT_TIMESTAMP && (kind == TK_DATE32 || kind == TK_DATE64))
+      fail(CHQ_ERR_NOT_SUPPORTED, "a TIMESTAMP literal beside a Date32 / Date64 operand is outside this build's scope: write a DATE literal");
+    if (!zone_is_utc(zone))
+      fail(CHQ_ERR_NOT_SUPPORTED, std::string("a ") + lname + " literal beside a Timestamp in time zone '" + zone + "' is outside this build's scope: there is no zone database");
+    int64_t raw = 0;
+    switch (temporal_literal_raw(n.tval, kind, &raw)) {
+      case 1: fail(CHQ_ERR_ARROW_CAST, std::string("Cast error: ") + lname + " '" + text + "' holds fraction digits finer than the unit of '" + cols[fc].format + "'");
+      case 2: fail(CHQ_ERR_ARROW_CAST, std::string("Cast error: ") + lname + " '" + text + "' does not fit the Int64 of '" + cols[fc].format + "'");
+      default: break;
+    }
+    n.tlit = 0; n.fmt_col = fc;
+    n.cval = scalar_bits(opaque_compare_class(cols[fc]), (uint64_t)raw);
   }
 
   // the batch column whose format a T_FIXED_OPAQUE value has: a column's own, a CASE's fmt_col
@@ -627,10 +734,28 @@ struct Typer {
     return maybe_fold(push(n));
   }
 
+  // An opaque operand of a comparison read as Int32 / Int64: a copy of its node with that type.  A date_trunc is copied once,
+  // however many comparisons read it (BETWEEN and IN type their operand once and compare it several times): every one of them
+  // refers to the one copy, so the engine evaluates it once and the others find its temporary column.
+  int read_as(int ni, DType cls) {
+    const bool shared = t.nodes[ni].kind == Node::TTRUNC;
+    if (shared) for (const auto& done : retyped) if (done.first == ni) return done.second;
+    Node a = t.nodes[ni]; a.type = cls;
+    t.nodes.push_back(a);
+    const int copy = (int)t.nodes.size() - 1;
+    if (shared) retyped.emplace_back(ni, copy);
+    return copy;
+  }
+
   // length of a datum: 1 for literal-built arrays, nrows for everything else
   bool same_len(const Node& a, const Node& b) const { return a.len1 == b.len1 || nrows == 1; }
 
   int binary(const Expr& e, int l, int r) {
+    if (t.nodes[l].tlit || t.nodes[r].tlit) {
+      const bool cmp = e.op == CHQ_BINOP_EQ || e.op == CHQ_BINOP_NOTEQ || e.op == CHQ_BINOP_GT || e.op == CHQ_BINOP_GTEQ || e.op == CHQ_BINOP_LT || e.op == CHQ_BINOP_LTEQ;
+      if (!cmp) fail(CHQ_ERR_NOT_SUPPORTED, "a DATE / TIMESTAMP literal under an operator other than a comparison is outside this build's scope");
+      if (t.nodes[l].tlit) resolve_literal(l, r); else resolve_literal(r, l);
+    }
     if (e.op == CHQ_BINOP_AND || e.op == CHQ_BINOP_OR) {
       // RU/compute_value.rs:71-116: both sides cast to Boolean, then compute::and / compute::or on
       // &BooleanArray (no scalar broadcast), result flagged non-scalar
@@ -664,10 +789,13 @@ struct Typer {
     DType lt = t.nodes[l].type, rt = t.nodes[r].type, ct;
     // (a temporal / decimal value is always a plain column: no literal and no operator produces one)
     // (.. or, since CASE, a CASE over such columns, whose temporary column no operator reads yet)
-    if ((lt == T_FIXED_OPAQUE && t.nodes[l].kind != Node::COL) || (rt == T_FIXED_OPAQUE && t.nodes[r].kind != Node::COL))
+    // (.. or, since date_trunc and the temporal literals, a date_trunc -- whose temporary column IS read, as Int32 / Int64 -- or
+    // a literal that has taken its neighbour's unit)
+    const auto plain = [&](int ni) { const Node& q = t.nodes[ni]; return q.kind == Node::COL || q.kind == Node::TTRUNC || (q.kind == Node::CONST && q.fmt_col >= 0 && !q.cval.null); };
+    if ((lt == T_FIXED_OPAQUE && !plain(l)) || (rt == T_FIXED_OPAQUE && !plain(r)))
       fail(CHQ_ERR_NOT_SUPPORTED, "an operator on the temporal / decimal result of CASE, coalesce or nullif is outside this build's scope");
     const bool both_opaque = lt == T_FIXED_OPAQUE && rt == T_FIXED_OPAQUE;
-    const bool same_opaque = both_opaque && canonical_format(cols[t.nodes[l].col].format) == canonical_format(cols[t.nodes[r].col].format);
+    const bool same_opaque = both_opaque && canonical_format(cols[opaque_col(t.nodes[l])].format) == canonical_format(cols[opaque_col(t.nodes[r])].format);
     if (!common_type(lt, rt, &ct) || (both_opaque && !same_opaque))
       fail(CHQ_ERR_UNSUPPORTED_TYPE_COERSION, std::string("unsupported type coersion for operation between types ") +
                                                   dtype_name(lt) + " and " + dtype_name(lt));
@@ -680,7 +808,7 @@ struct Typer {
       if (ct == T_FIXED_OPAQUE) {
         // arrow-arith 53 arithmetic_op: decimals and Duration +/- have arithmetic (not built here); dates and timestamps
         // only subtract; everything else is "Invalid arithmetic operation" like any non-numeric type
-        const std::string& f = cols[ln.col].format;
+        const std::string& f = cols[opaque_col(ln)].format;
         const bool sub = aop == OP_SUB, addsub = aop == OP_ADD || sub;
         if (f.rfind("d:", 0) == 0 || (f.rfind("tD", 0) == 0 && addsub) || ((f.rfind("td", 0) == 0 || f.rfind("ts", 0) == 0) && sub))
           fail(CHQ_ERR_NOT_SUPPORTED, "arithmetic on '" + f + "' columns is outside this build's scope");
@@ -692,13 +820,12 @@ struct Typer {
         fail(CHQ_ERR_ARROW_COMPUTE, "Cannot perform a binary operation on arrays of different length");
     } else {
       if (ct == T_FIXED_OPAQUE) {
-        const DType cls = opaque_compare_class(cols[ln.col]);
+        const DType cls = opaque_compare_class(cols[opaque_col(ln)]);
         if (cls == T_NTYPES)
-          fail(CHQ_ERR_NOT_SUPPORTED, "comparison of '" + cols[ln.col].format + "' columns is outside this build's scope");
+          fail(CHQ_ERR_NOT_SUPPORTED, "comparison of '" + cols[opaque_col(ln)].format + "' columns is outside this build's scope");
         if (cls != T_FIXED_OPAQUE) {   // the raw values ARE Int32 / Int64: the same columns, read as integers
-          Node a = ln, b = rn; a.type = cls; b.type = cls;
-          t.nodes.push_back(a); l = (int)t.nodes.size() - 1;
-          t.nodes.push_back(b); r = (int)t.nodes.size() - 1;
+          l = read_as(l, cls);
+          r = read_as(r, cls);
           ct = cls;
         }
       }
@@ -830,6 +957,7 @@ struct Gen {
       case Node::STRFN: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "a string function runs as its own kernel");
       case Node::CASE: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "CASE runs as its own kernel");
       case Node::XCAST: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "an explicit cast runs as its own kernel");
+      case Node::TPART: case Node::TTRUNC: fail(CHQ_INTERNAL_PROGRAM_LIMIT, "a temporal function runs as its own kernel");
       case Node::CMP:
         if (n.from == T_UTF8) { gen_strcmp(n); return; }
         if (n.from == T_FIXED_OPAQUE) fail(CHQ_INTERNAL_PROGRAM_LIMIT, "Decimal128 comparison runs as its own kernel");

@@ -19,6 +19,7 @@
 #include "strfn_device.h"
 #include "case_device.h"
 #include "cast_device.h"
+#include "temporal_device.h"
 
 namespace chq {
 
@@ -38,7 +39,8 @@ struct Expr {
   // "Function(name)").  CASE: l = the operand of a simple CASE or null, args = the n conditions (simple CASE: the values)
   // followed by the n results, r = the ELSE or null.  IN_LIST: l = the operand, args = the list, flag = NOT IN.  BETWEEN:
   // l = the operand, args = {low, high}, flag = NOT BETWEEN.  CAST: l = the operand, op = the chq_cast_type, flag = TRY_CAST.
-  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER, LIKE, ISNULL, FUNCTION, CASE, IN_LIST, BETWEEN, CAST } kind;
+  // TYPED_STRING (`DATE '..'`, `TIMESTAMP '..'`): op = the chq_typed_string_kind, text = the string.
+  enum Kind { NESTED, BINARY, NUMBER, BOOLEAN, STRING, VALUE_OTHER, IDENT, COMPOUND, OTHER, LIKE, ISNULL, FUNCTION, CASE, IN_LIST, BETWEEN, CAST, TYPED_STRING } kind;
   int op = 0;             // chq_binary_operator
   std::string text;       // number text / identifier / string bytes / debug text
   bool flag = false;      // is_long / boolean value / negated
@@ -77,6 +79,10 @@ int utf8_to_bool(const uint8_t* bytes, int64_t len);
 // how a temporal / decimal column compares with another of the SAME DataType: as I32 / I64 values, as 128-bit integers
 // (T_FIXED_OPAQUE returned, width 16), or not at all in this build (T_NTYPES)
 DType opaque_compare_class(const PlanColumn& c);
+// the TemporalKind of an Arrow format string (Date32 / Date64 / Timestamp / Time32 / Time64), or -1; *zone = a Timestamp's time zone
+int temporal_kind_of(const std::string& format, std::string* zone);
+extern const char* const kTemporalFieldNames[TF_NFIELDS];
+extern const char* const kTemporalUnitNames[TU_NUNITS];
 
 struct Node {
   // (a CMP whose `from` is T_FIXED_OPAQUE compares two Decimal128 columns, a TOBOOL whose `from` is T_UTF8 parses a Utf8
@@ -90,8 +96,13 @@ struct Node {
   // A result may be a CONST whose cval is null, of any type (nullif).  fmt_col: the batch column whose Arrow format a
   // T_FIXED_OPAQUE result has (a COL's is its own).  XCAST is an explicit CAST / TRY_CAST (l = the operand, `from` its type,
   // `type` the target, op = 1 for TRY_CAST): cast.hip writes a temporary column of the target type.  CAST stays the implicit
-  // widening of the coercion table, an instruction of the device program.)
-  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL, LIKE, ISNULL, STRFN, CASE, XCAST } kind;
+  // widening of the coercion table, an instruction of the device program.  TPART is EXTRACT / date_part (l = the temporal
+  // operand, a column or a TTRUNC; op = the TemporalField; tkind = the operand's TemporalKind; the result is Int32), TTRUNC is
+  // date_trunc (op = the TemporalUnit; the result is T_FIXED_OPAQUE with the operand's format, fmt_col): temporal.hip writes a
+  // temporary column.  A CONST with `tlit` set is a DATE / TIMESTAMP literal that has not met its temporal neighbour yet (tlit =
+  // chq_typed_string_kind + 1, cval.str = the string); binary() turns it into an Int32 / Int64 CONST of the neighbour's unit,
+  // fmt_col = the neighbour's column, and nothing else accepts one.)
+  enum Kind { COL, CONST, ARITH, CMP, ANDOR, CAST, TOBOOL, LIKE, ISNULL, STRFN, CASE, XCAST, TPART, TTRUNC } kind;
   DType type;
   bool is_scalar;   // ArrayDatum.is_scalar
   bool len1;        // array length is 1 regardless of the batch (built from literals only)
@@ -104,7 +115,10 @@ struct Node {
   std::shared_ptr<const LikePattern> like;   // LIKE
   std::vector<int> parts;                    // STRFN_CONCAT, CASE
   bool case_else = false;                    // CASE
-  int fmt_col = -1;                          // CASE of T_FIXED_OPAQUE
+  int fmt_col = -1;                          // CASE / TTRUNC / temporal literal of T_FIXED_OPAQUE
+  int tkind = 0;                             // TPART, TTRUNC: TemporalKind of the operand
+  int tlit = 0;                              // CONST: an unresolved DATE / TIMESTAMP literal
+  TemporalLiteral tval{};                    // .. as it was parsed where it stands
   int32_t sub_p = 0, sub_cnt = 0;            // STRFN_SUBSTRING: FROM sub_p [FOR sub_cnt]
   bool sub_has_cnt = false;
   // every operand: l, r and the parts

@@ -45,7 +45,8 @@ bool subtree_can_null(const TypedExpr& t, int ni, const std::vector<PlanColumn>&
   if (n.kind == Node::CONST) return n.cval.null;
   if (n.kind == Node::ISNULL) return false;   // IS [NOT] NULL is never null
   bool r = (n.kind == Node::TOBOOL && n.from == T_UTF8) ||   // a bad spelling is NULL
-           (n.kind == Node::XCAST && n.op != 0 && cast_can_fail(n.from, n.type));   // a failing TRY_CAST row too
+           (n.kind == Node::XCAST && n.op != 0 && cast_can_fail(n.from, n.type)) ||   // a failing TRY_CAST row too
+           n.kind == Node::TPART || n.kind == Node::TTRUNC;   // a date outside the year range
   n.each_child([&](int c) { r = r || subtree_can_null(t, c, cols); });   // (a string function: null where an operand is)
   return r;
 }
@@ -147,9 +148,10 @@ Column result_column(const Node& root, const std::vector<PlanColumn>& pcols, int
   o.type = root.type; o.format = dtype_format(root.type); o.width = dtype_width(root.type); o.length = nrows;
   // (a Utf8 result is a string function's: fitting turns it into a temporary column, which IS the result)
   // (.. or a CASE's, of any type)
-  if (root.kind == Node::CASE && root.type == T_FIXED_OPAQUE) { o.format = pcols[(size_t)root.fmt_col].format; o.width = pcols[(size_t)root.fmt_col].width; }
+  // (.. or a date_trunc's, of its operand's DataType)
+  if ((root.kind == Node::CASE || root.kind == Node::TTRUNC) && root.type == T_FIXED_OPAQUE) { o.format = pcols[(size_t)root.fmt_col].format; o.width = pcols[(size_t)root.fmt_col].width; }
   // (.. or an explicit cast's to Utf8)
-  if (root.kind != Node::CASE && ((root.type == T_UTF8 && root.kind != Node::STRFN && root.kind != Node::XCAST) || root.type == T_FIXED_OPAQUE))
+  if (root.kind != Node::CASE && root.kind != Node::TTRUNC && ((root.type == T_UTF8 && root.kind != Node::STRFN && root.kind != Node::XCAST) || root.type == T_FIXED_OPAQUE))
     throw ChqError{CHQ_ERR_NOT_SUPPORTED, std::string("expression result of type ") + dtype_name(root.type) + " is outside this build's scope"};
   return o;
 }
@@ -532,12 +534,20 @@ bool project_record_host(Context& ctx, const std::vector<chq_select_item>& field
 // =================================================================================================
 // describe_plan: the host half of a call (typing, coercion, constant folding, lowering) without a GPU
 // =================================================================================================
-// f(index, node) for every node of `kind` in the tree under `ni`, operands first
+// f(index, node) for every node of `kind` in the tree under `ni`, operands first; a node that several operators read (the
+// operand of BETWEEN and IN) once, where it is first met
+template <class F>
+static void each_of_kind(const TypedExpr& te, int ni, Node::Kind kind, const F& f, std::vector<char>& seen) {
+  if (seen[(size_t)ni]) return;
+  seen[(size_t)ni] = 1;
+  const Node& n = te.at(ni);
+  n.each_child([&](int c) { each_of_kind(te, c, kind, f, seen); });
+  if (n.kind == kind) f(ni, n);
+}
 template <class F>
 static void each_of_kind(const TypedExpr& te, int ni, Node::Kind kind, const F& f) {
-  const Node& n = te.at(ni);
-  n.each_child([&](int c) { each_of_kind(te, c, kind, f); });
-  if (n.kind == kind) f(ni, n);
+  std::vector<char> seen(te.nodes.size(), 0);
+  each_of_kind(te, ni, kind, f, seen);
 }
 
 std::string describe_plan(const ArrowSchema* schema, const chq_table_aliases* aliases, const Expr& expr, int64_t nrows,
@@ -596,6 +606,13 @@ std::string describe_plan(const ArrowSchema* schema, const chq_table_aliases* al
     // the explicit casts of the tree, operands first
     each_of_kind(te, te.root, Node::XCAST, [&](int, const Node& n) {
       out += std::string("cast ") + dtype_name(n.from) + " -> " + dtype_name(n.type) + (n.op ? " try" : "") + "\n";
+    });
+    // the temporal functions of the tree, operands first: the operand's kind; a date_trunc keeps its operand's Arrow format
+    each_of_kind(te, te.root, Node::TPART, [&](int, const Node& n) {
+      out += std::string("temporal part ") + kTemporalFieldNames[n.op] + " kind=" + std::to_string(n.tkind) + "\n";
+    });
+    each_of_kind(te, te.root, Node::TTRUNC, [&](int, const Node& n) {
+      out += std::string("temporal trunc ") + kTemporalUnitNames[n.op] + " kind=" + std::to_string(n.tkind) + " format=" + cols[(size_t)n.fmt_col].format + "\n";
     });
     return out;
   }

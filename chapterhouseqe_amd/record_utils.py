@@ -28,7 +28,7 @@ _OPS = {A.BinaryOperator.And: 0, A.BinaryOperator.Or: 1, A.BinaryOperator.Plus: 
 _OP_OTHER = 13
 # the scalar string functions the library evaluates (include/chq.h: chq_expr_function); every other call stays unsupported
 _SCALAR_FUNCTIONS = {"upper", "lower", "length", "char_length", "character_length", "octet_length", "substring", "substr",
-                     "trim", "ltrim", "rtrim", "coalesce", "nullif"}
+                     "trim", "ltrim", "rtrim", "coalesce", "nullif", "date_part", "date_trunc"}
 
 
 class ChqError(Exception):
@@ -343,6 +343,18 @@ def _expr_to_c(e: A.Expr):
             raise
         arr = (C.c_void_p * max(1, len(built)))(*built)
         return lib.chq_expr_function(e.name.encode(), arr, len(built))
+    if isinstance(e, A.TypedString):
+        b = e.value.encode()
+        return lib.chq_expr_typed_string(int(e.data_type), b, len(b))
+    if isinstance(e, A.Extract):   # sent as date_part('field', expr)
+        f = e.field.encode()
+        arr = (C.c_void_p * 2)(lib.chq_expr_single_quoted_string(f, len(f)), None)
+        try:
+            arr[1] = _expr_to_c(e.expr)
+        except BaseException:
+            lib.chq_expr_free(arr[0])
+            raise
+        return lib.chq_expr_function(b"date_part", arr, 2)
     if isinstance(e, A.Cast):
         return lib.chq_expr_cast(_expr_to_c(e.expr), int(e.data_type), int(e.try_cast))
     if isinstance(e, (A.Case, A.InList, A.Between)):

@@ -181,6 +181,32 @@ class Cast(Expr):
         return None
 
 
+class TypedStringType(enum.IntEnum):
+    """the data type of a TypedString (include/chq.h: chq_typed_string_kind)"""
+    Date = 0
+    Timestamp = 1
+
+
+@dataclass(frozen=True)
+class TypedString(Expr):
+    """Expr::TypedString { data_type, value }: `DATE '2024-03-01'`, `TIMESTAMP '2024-03-01 00:00:00'`"""
+    data_type: TypedStringType
+    value: str
+
+
+@dataclass(frozen=True)
+class Extract(Expr):
+    """Expr::Extract { field, expr }: `EXTRACT(field FROM expr)`; `field` as written.  It reaches the library as
+    `date_part('field', expr)`."""
+    field: str
+    expr: Expr
+
+    @property
+    def args(self):
+        """None, like `Cast.args`: `extract(year from ts)` parsed as a call without a plain argument list before"""
+        return None
+
+
 @dataclass(frozen=True)
 class UnsupportedExpr(Expr):
     """UnaryOp, Function, Subquery, ... -- compute_value.rs:338-342 rejects them."""

@@ -18,6 +18,9 @@ sample queries (reference: sample_queries/simple.sql) to be written as SQL text.
   `like`, `not`, `is` and `escape` are operators only where these forms continue (`like` / `not like` in front of something
   that can start an expression, `is` in front of `null` / `not null`, `escape` behind a pattern and in front of a string);
   anywhere else they stay ordinary words, e.g. aliases.  Prefix `not <expr>` stays an UnsupportedExpr.
+    date '<string>' | timestamp '<string>'                   -> TypedString (the keyword counts only in front of a string
+                                                                literal; anywhere else `date` and `timestamp` are ordinary words)
+    extract ( <field> from <expr> )                          -> Extract (sent to the library as date_part('<field>', <expr>))
     cast ( <expr> as <type> ) | try_cast ( <expr> as <type> ) | <expr> :: <type>   -> Cast
   `cast` / `try_cast` open the form only in front of `(`; `::` binds tighter than any binary operator.  <type> is one of
   boolean | bool | tinyint | smallint | int | integer | bigint (each integer name optionally followed by `unsigned`) | real |
@@ -289,6 +292,13 @@ class _Parser:
                 return self._case()
             if up in ("CAST", "TRY_CAST") and self.peek() == ("op", "("):
                 return self._cast(up == "TRY_CAST")
+            # Expr::TypedString: the keyword counts only in front of a string literal; elsewhere `date` / `timestamp` are words
+            if up in ("DATE", "TIMESTAMP") and self.peek()[0] == "string":
+                return A.TypedString(A.TypedStringType.Date if up == "DATE" else A.TypedStringType.Timestamp, self.next()[1])
+            if up == "EXTRACT" and self.peek() == ("op", "("):
+                ex = self._extract()
+                if ex is not None:
+                    return ex
             if self.peek() == ("op", "("):
                 return self._function_call(v)
             return self._identifier_tail(A.Ident(v))
@@ -305,6 +315,19 @@ class _Parser:
         to = self._data_type()
         self.expect_op(")")
         return A.Cast(inner, to, try_cast)
+
+    def _extract(self) -> Optional[A.Expr]:
+        """`( field FROM expr )` behind EXTRACT: sqlparser Parser::parse_extract_expr.  `field` is a word or a string literal.
+        Anything else between the parentheses: None, and the text parses as a call like before."""
+        start = self.i
+        self.expect_op("(")
+        k, field = self.next()
+        if k in ("word", "string") and self.accept_word("FROM"):
+            inner = self.parse_expr(0)
+            self.expect_op(")")
+            return A.Extract(field, inner)
+        self.i = start
+        return None
 
     def _data_type(self) -> A.CastType:
         k, v = self.next()
@@ -704,6 +727,8 @@ def having_plan(select: Select):
             return A.Between(rewrite(e.expr), e.negated, rewrite(e.low), rewrite(e.high))
         if isinstance(e, A.Cast):
             return A.Cast(rewrite(e.expr), e.data_type, e.try_cast)
+        if isinstance(e, A.Extract):
+            return A.Extract(e.field, rewrite(e.expr))
         if isinstance(e, A.Case):
             return A.Case(None if e.operand is None else rewrite(e.operand), tuple(rewrite(x) for x in e.conditions),
                           tuple(rewrite(x) for x in e.results), None if e.else_result is None else rewrite(e.else_result))

@@ -109,7 +109,9 @@ void* chq_ctx_stream(const chq_ctx* ctx);
  * Beyond the reference: [NOT] LIKE on Utf8 (chq_expr_like), IS [NOT] NULL on every type (chq_expr_is_null) and the scalar
  * string functions (CHQ_BINOP_STRING_CONCAT, chq_expr_function), whose results are Utf8 or Int32 columns; CASE, coalesce and
  * nullif (chq_expr_case, chq_expr_function), whose result has any of these types; BETWEEN and IN lists (chq_expr_between,
- * chq_expr_in_list); explicit CAST / TRY_CAST between Boolean, the integers, the floats and Utf8 (chq_expr_cast). */
+ * chq_expr_in_list); explicit CAST / TRY_CAST between Boolean, the integers, the floats and Utf8 (chq_expr_cast); DATE /
+ * TIMESTAMP literals beside Date / Timestamp operands (chq_expr_typed_string), EXTRACT / date_part and date_trunc
+ * (chq_expr_function). */
 chq_status chq_ctx_set_option(chq_ctx* ctx, const char* key, int64_t value);
 /* Counters of the last filter call: rows in, rows out, tiles, kernel launches. */
 typedef struct chq_call_stats {
@@ -246,6 +248,36 @@ typedef enum chq_cast_type {
  * 2^31 - 1 bytes: CHQ_ERR_ARROW_INVALID_ARGUMENT.  CHQ_ERR_NOT_SUPPORTED: Float <-> Utf8 (a correctly rounded parse and a
  * shortest round-trip print are not built), temporal and Decimal128 operands, LargeUtf8, CHQ_CAST_OTHER. */
 chq_expr* chq_expr_cast(chq_expr* operand, chq_cast_type to, int try_cast);
+/* The data type of chq_expr_typed_string. */
+typedef enum chq_typed_string_kind { CHQ_TYPED_STRING_DATE = 0, CHQ_TYPED_STRING_TIMESTAMP = 1 } chq_typed_string_kind;
+/* Expr::TypedString { data_type, value }: `DATE '2024-03-01'`, `TIMESTAMP '2024-03-01 12:30:00.5'`.  The reference rejects the
+ * form: these semantics are this library's own.
+ *   DATE is YYYY-MM-DD; TIMESTAMP is YYYY-MM-DD, a space or `T`, HH:MM[:SS[.f{1,9}]].  Years 0001 - 9999, a day of the proleptic
+ *   Gregorian calendar, hours 00 - 23, minutes and seconds 00 - 59, no zone suffix, no white space around it; anything else is
+ *   CHQ_ERR_ARROW_CAST at typing, the message quoting the literal.
+ *   The literal has no Arrow type of its own.  It stands beside a Date32 / Date64 / Timestamp operand of a comparison (either
+ *   order; BETWEEN and IN lists are comparisons) and takes that operand's DataType: a DATE is days beside Date32, milliseconds
+ *   beside Date64, midnight in the unit beside Timestamp(unit); a TIMESTAMP is admitted beside Timestamp(unit) only
+ *   (CHQ_ERR_NOT_SUPPORTED beside a Date).  A Timestamp with a time zone is admitted for `UTC` and `+00:00`, the literal is then
+ *   UTC; any other zone is CHQ_ERR_NOT_SUPPORTED (there is no zone database).  Fraction digits finer than the unit, and a value
+ *   that does not fit the unit's Int64 (`TIMESTAMP '2300-01-01 00:00:00'` beside nanoseconds), are CHQ_ERR_ARROW_CAST.  The
+ *   comparison then is the integer comparison of the raw values.
+ *   Beside a non-temporal operand: CHQ_ERR_UNSUPPORTED_TYPE_COERSION, as for `date_column < 5`.  Alone, beside another literal,
+ *   under any other operator, as a function argument or CASE branch, beside Time32 / Time64 / Duration / Decimal128:
+ *   CHQ_ERR_NOT_SUPPORTED.
+ * The temporal functions come through chq_expr_function, names and fields case-insensitive:
+ *   date_part('field', e) -> Int32   what EXTRACT(field FROM e) is sent as.  field: year, quarter, month, week (ISO 8601), day,
+ *                                    doy, dow (Sunday = 0), hour, minute, second (whole seconds)
+ *   date_trunc('unit', e)            of e's own DataType (unit and zone kept).  unit: year, quarter, month, week (Monday), day,
+ *                                    hour, minute, second; on Date32 the units below day are the identity
+ *   e is a Date32 / Date64 (read as milliseconds) / Timestamp (no zone, `UTC`, `+00:00`) column or a date_trunc of one;
+ *   date_part also takes Time32 / Time64 columns, for hour / minute / second.  The value is split by FLOOR division into days
+ *   since 1970-01-01 and a time of day (-1 s is 1969-12-31 23:59:59); the calendar is the proleptic Gregorian one.  No row
+ *   fails: a row whose date lies outside years -262143 .. 262142, a Time outside one day, and a truncation that does not fit the
+ *   raw integer come out null.  Statuses: a field / unit that is not a string literal or not in the list, and any other zone,
+ *   CHQ_ERR_NOT_SUPPORTED; any other operand type, and a date field of a Time, CHQ_ERR_ARROW_INVALID_ARGUMENT.  A date_trunc
+ *   result compares with a literal or a value of the same DataType; chq_ctx_last_stats counts the launches and bytes. */
+chq_expr* chq_expr_typed_string(chq_typed_string_kind kind, const char* bytes, int64_t len);
 chq_expr* chq_expr_unsupported(const char* debug);                            /* any other Expr variant */
 void chq_expr_free(chq_expr* e);
 

@@ -173,6 +173,8 @@ extern "C" {
     pub fn chq_expr_between(expr: *mut chq_expr, negated: c_int, low: *mut chq_expr, high: *mut chq_expr) -> *mut chq_expr;
     /// `to`: chq_cast_type (0 Boolean, 1..4 Int8..Int64, 5..8 UInt8..UInt64, 9 Float16, 10 Float32, 11 Float64, 12 Utf8, 13 other)
     pub fn chq_expr_cast(operand: *mut chq_expr, to: c_int, try_cast: c_int) -> *mut chq_expr;
+    /// Expr::TypedString; `kind`: chq_typed_string_kind (0 DATE, 1 TIMESTAMP)
+    pub fn chq_expr_typed_string(kind: c_int, bytes: *const c_char, len: i64) -> *mut chq_expr;
     pub fn chq_expr_unsupported(debug: *const c_char) -> *mut chq_expr;
     pub fn chq_expr_free(e: *mut chq_expr);
 
